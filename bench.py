@@ -8,7 +8,16 @@ environment) this file is a rank.  Started plainly with --gpus N > 1 it is the L
 process, relays rank 0's JSON line and exits with the child's code.  A world size different from --gpus is an error, never a
 silent 1-GPU run.  Every rank runs the same per-GPU workload (weak scaling).
 
-Two legs, both in the ONE JSON line rank 0 prints:
+A plain run measures the headline only: set-up, W warm-up steps, the K timed steps of the leg that carries `value` (the rollout, or the
+train step with --mode train), the outputs of its last step when --dump-outputs DIR is given, and the line.  Everything else below (the
+additional train and precision legs, `roofline`, `cpu_baseline`) runs with --full.
+
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR
+writes what the timed path returned in its last timed step as DIR/<name>.npy (float32; a fixed, seeded sample of an array larger than
+DUMP_SAMPLE elements, named <name>_sample): the rollout's loss, psnr_all, gen_images and gen_states, and after a train step also the
+updated parameters (`params`, the flat buffer).  Inputs and initial weights are seeded, so two builds compare output for output.
+
+Legs of a --full run, all in the ONE JSON line rank 0 prints:
   value / ms_per_step : the rollout, Model.__call__ forward, feed-self (predict_model.py:126-128).  It shards over the batch with
                         no data-path collective (SURVEY.md 8e "inference rollout: replicas only").
   train               : optimizer.update (train_model.py:950) = forward + BPTT backward + gradient all-reduce over RCCL, overlapped
@@ -75,6 +84,11 @@ def build_parser():
                     help="preset of a BASELINE.json config, numbered from 1 as VERDICT / DESIGN do (config N = `configs[N-1]`; per-GPU batch 32 throughout): 2 = the default "
                          "(CDNA 64x64 T=10 fp32 rollout), 3 = --precision bf16 --mode train (at --gpus 8: global batch 256), 4 = --model STP, "
                          "5 = --size 128 --seq-len 20.  Explicit flags given after it still win.")
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline leg, run every other leg: the train legs (rollout mode), the bf16x6 / fp16x3 legs, roofline '
+                         'and cpu_baseline (each still switched off by its --no-* flag).  Off: the run measures `value` only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed as DIR/<name>.npy (rank 0; GPU runs)')
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--batch', type=int, default=32, help='sequences per GPU (config 2: 32)')
@@ -277,6 +291,21 @@ def timed(step, steps, warmup, sync, barrier):
     return time.perf_counter() - t0, out
 
 
+DUMP_SAMPLE = 6 * 1024 * 1024      # elements: at most two arrays reach it (gen_images, params), 48 MB of float32 in all
+
+
+def dump_outputs(outdir, arrays, np):
+    """--dump-outputs: name -> device tensor, written as float32 .npy files.  An array larger than DUMP_SAMPLE elements is written as a
+    sample of DUMP_SAMPLE elements of its flattened form at indices drawn from a fixed seed (`<name>_sample.npy`)."""
+    os.makedirs(outdir, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy().astype(np.float32)
+        if a.size > DUMP_SAMPLE:
+            idx = np.sort(np.random.RandomState(0).randint(0, a.size, DUMP_SAMPLE))
+            a, name = a.reshape(-1)[idx], name + '_sample'
+        np.save(os.path.join(outdir, name + '.npy'), a)
+
+
 CONFIG_PRESETS = {      # BASELINE.json `configs[i]` -> the flags that select it (per-GPU batch 32; config 3 / 5 are quoted at 8 GPUs: --gpus 8)
     2: ([], '1xMI355X: batch=32, 64x64x3, 10-frame CDNA, action-conditioned, fp32'),
     3: (['--precision', 'bf16', '--mode', 'train'], '8xMI355X DP: global batch=256, 64x64x3, 10-frame CDNA, RCCL all-reduce over xGMI, bf16'),
@@ -419,6 +448,8 @@ def _inject(leg, where, rank):
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     args = parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit('bench.py: --steps must be at least 1 and --warmup at least 0')
     env_world = os.environ.get('WORLD_SIZE')
     if env_world is None and args.gpus > 1:
         sys.exit(launch_ranks(args, argv))
@@ -543,14 +574,16 @@ def main(argv=None):
         actions = torch.from_numpy((0.1 * rs.standard_normal((T, B, 5))).astype(np.float32)).to(dev)
         states = torch.from_numpy((0.1 * rs.standard_normal((T, B, 5))).astype(np.float32)).to(dev)
     do_rollout = args.mode == 'rollout'
-    do_train = args.mode == 'train' or not args.no_train
+    full = args.full            # without it only the leg that carries `value` runs
+    do_train = args.mode == 'train' or (full and not args.no_train)
     train_mode = args.mode == 'train'
     fp32_run = args.precision == 'fp32'
     split_modes = (('bf16x6', '3 bf16 pieces, 6 bf16 MFMAs per product'),
                    ('fp16x3', '2 fp16 pieces (weights packed times a per-tensor power of two), 3 fp16 MFMAs per product'))
-    do_split = do_rollout and not dry and fp32_run and not args.no_bf16x6 and world == 1     # (additional objects of the 1-GPU line only)
+    do_split = full and do_rollout and not dry and fp32_run and not args.no_bf16x6 and world == 1     # (additional objects of the 1-GPU line only)
     do_bf16_train = do_train and not train_mode and fp32_run and not args.no_bf16_train and (not dry or world > 1)
     do_x6_train = do_train and not train_mode and fp32_run and not dry and not args.no_bf16x6 and world == 1
+    dump = args.dump_outputs if (args.dump_outputs and rank == 0 and not dry) else None
     # the legs of this run, least risky first: the replicas' rollout (no data-path collective), the fp32 train step (one all-reduce per gradient
     # group), the bf16 train step (all-to-all + all-gather per group), then the passes that only rank 0 measures
     if do_rollout:
@@ -563,9 +596,9 @@ def main(argv=None):
             run.planned.append('train_bf16')
         if do_x6_train:
             run.planned += ['train_' + m for m, _ in split_modes]
-    if not args.no_roofline and not dry:
+    if full and not args.no_roofline and not dry:
         run.planned.append('roofline')
-    if world == 1 and not args.no_cpu_baseline and not dry:
+    if full and world == 1 and not args.no_cpu_baseline and not dry:
         run.planned.append('cpu_baseline')
 
     def base_line(elapsed, loss_val):
@@ -627,8 +660,12 @@ def main(argv=None):
             def rollout_body(step):
                 w0 = time.perf_counter()
                 elapsed, loss = timed(step, args.steps, args.warmup, sync, barrier)
-                st['elapsed'] = elapsed = max_over_ranks(elapsed)
                 st['t_ref'] = max(0.05, time.perf_counter() - w0)
+                if dump:
+                    m = st['model']
+                    dump_outputs(dump, {'loss': m.loss, 'psnr_all': m.psnr_all, 'gen_images': torch.stack(m.gen_images),
+                                        'gen_states': torch.stack(m.gen_states)}, np)
+                st['elapsed'] = elapsed = max_over_ranks(elapsed)
                 st['rollout_step'] = step
                 base_line(elapsed, 0.0 if dry else float(loss))
                 return elapsed
@@ -719,6 +756,9 @@ def main(argv=None):
                     return op.update(tm, [images, actions, states], 0)                  # schedsamp_k = -1: feed-self, deterministic
             probed = dp.prepare(tm, probe=True) if dp is not None else []   # one untimed collective of each kind this schedule uses
             t_with, tloss = timed(train_step, args.steps, args.warmup, sync, barrier)
+            if dump and train_mode:                      # the leg that carries `value`, before any later pass moves the parameters
+                dump_outputs(dump, {'loss': tloss, 'psnr_all': tm.psnr_all, 'gen_images': torch.stack(tm.gen_images),
+                                    'gen_states': torch.stack(tm.gen_states), 'params': tm._flat_params}, np)
             t_with = max_over_ranks(t_with)
             algo = dp.last_algo if dp is not None else None
             payload_bytes = dp.last_payload_bytes if dp is not None else None

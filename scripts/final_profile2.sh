@@ -6,8 +6,8 @@ tag=${1:-cur}
 out=gpurun_out/prof2_$tag
 mkdir -p $out
 export TMPDIR=/tmp
-NB="--no-cpu-baseline"
-for c in 3 4 5; do python3 bench.py --config $c > $out/config${c}_bench.json 2> $out/config${c}_bench.err || echo "config $c failed"; tail -c 400 $out/config${c}_bench.json; echo; done
+NB="--full --no-cpu-baseline"
+for c in 3 4 5; do python3 bench.py --config $c --full > $out/config${c}_bench.json 2> $out/config${c}_bench.err || echo "config $c failed"; tail -c 400 $out/config${c}_bench.json; echo; done
 for prec in fp32 bf16; do
     python3 bench.py --mode train --precision $prec --steps 10 --warmup 3 $NB --no-roofline > $out/train_${prec}_two_streams.json 2> $out/train_${prec}_two_streams.err
     PIVP_SIDE_STREAM=0 python3 bench.py --mode train --precision $prec --steps 10 --warmup 3 $NB --no-roofline > $out/train_${prec}_one_stream.json 2> $out/train_${prec}_one_stream.err
@@ -25,7 +25,7 @@ import subprocess
 print(subprocess.run([sys.executable,'scripts/train_standalone_table.py','$out/train_${prec}_one_stream_kernel_stats.csv','13',str(a),str(b)],capture_output=True,text=True).stdout)" | tee $out/train_standalone_table_$prec.md
 done
 d=$out/c3
-rocprofv3 --kernel-trace --stats --output-format csv -d $d -o c3 -- python3 bench.py --config 3 --no-roofline > $out/config3_prof.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $d -o c3 -- python3 bench.py --config 3 --full --no-roofline > $out/config3_prof.log 2>&1
 f=$(find $d -name "c3_kernel_stats.csv" | head -n 1); [ -n "$f" ] && cp "$f" $out/config3_kernel_stats.csv
 tr=$(find $d -name "c3_kernel_trace.csv" | head -n 1)
 [ -n "$tr" ] && { python3 scripts/queue_breakdown.py "$tr" > $out/config3_queues.txt 2>&1; python3 scripts/launch_count.py "$tr" > $out/config3_launches.txt 2>&1; python3 scripts/overlap_report.py "$tr" > $out/config3_overlap.txt 2>&1; }

@@ -7,8 +7,8 @@ tag=${1:-cur}
 out=gpurun_out/prof_$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-NB="--no-cpu-baseline"
-python3 bench.py > $out/bench.json 2> $out/bench.err                                   # the driver's command: rollout + train leg + cpu baseline
+NB="--full --no-cpu-baseline"                 # every line keeps the legs besides the headline (train, roofline, precision modes)
+python3 bench.py --full > $out/bench.json 2> $out/bench.err                            # every leg: rollout + train legs + roofline + cpu baseline
 python3 bench.py --mode train --steps 10 --warmup 3 $NB > $out/bench_train.json 2> $out/bench_train.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/kt -o rollout -- python3 bench.py --steps 7 --warmup 2 $NB --no-train --no-bf16x6 > $out/kt.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/train -o train -- python3 bench.py --mode train --steps 4 --warmup 1 $NB --no-roofline > $out/train.log 2>&1

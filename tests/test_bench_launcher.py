@@ -16,7 +16,7 @@ def _env(**kw):
 
 
 def test_bench_launches_its_own_ranks():
-    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--dry', '--steps', '2', '--warmup', '1'],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--dry', '--full', '--steps', '2', '--warmup', '1'],
                        env=_env(), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{')]
@@ -45,7 +45,7 @@ def test_bench_refuses_a_world_of_the_wrong_size():
 
 
 def test_bench_single_rank_dry_reports_both_legs():
-    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--dry', '--steps', '2', '--warmup', '1'],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--dry', '--full', '--steps', '2', '--warmup', '1'],
                        env=_env(), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-2000:]
     out = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith('{')][0])
@@ -55,7 +55,7 @@ def test_bench_single_rank_dry_reports_both_legs():
 def test_eight_ranks_dry():
     """The driver's largest run (--gpus 8): launcher, rendezvous on a port torchrun picks, 8 ranks' bookkeeping, the overlapped
     all-reduce over 8 gloo ranks and the one JSON line.  Host logic only (stub kernels)."""
-    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '8', '--dry', '--steps', '2', '--warmup', '1'],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '8', '--dry', '--full', '--steps', '2', '--warmup', '1'],
                        env=_env(), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{')]
@@ -91,7 +91,7 @@ def _line(p):
 
 
 def _run(extra_env, launcher='own', timeout=300):
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--dry', '--steps', '2', '--warmup', '1']
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--dry', '--full', '--steps', '2', '--warmup', '1']
     if launcher == 'outer':          # the driver's way: bench.py is a rank under somebody else's torchrun
         cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
                '--master-port', '29641'] + cmd[1:]
@@ -175,3 +175,43 @@ def test_a_stale_parent_does_not_spend_the_budget_before_the_first_leg():
                 os.environ.pop(k, None)
             else:
                 os.environ[k] = v
+
+
+def test_a_plain_run_measures_the_headline_only():
+    """Without --full the run is set-up, warm-up, the K timed steps of the `value` leg and the line: no train, precision, roofline or CPU leg."""
+    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--dry', '--steps', '3', '--warmup', '1'],
+                       env=_env(), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-2000:]
+    out = _line(p)
+    assert out['steps'] == 3 and out['warmup'] == 1 and out['ms_per_step'] > 0 and out['incomplete'] == []
+    for key in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+        assert key in out
+    assert not [k for k in out if k.startswith('train') or k.startswith('rollout_')]
+    assert out['roofline'] is None and out['cpu_baseline'] is None
+
+
+def test_bench_refuses_zero_steps():
+    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--dry', '--steps', '0', '--warmup', '1'],
+                       env=_env(), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+    assert p.returncode != 0 and '--steps' in p.stderr
+    assert not [ln for ln in p.stdout.splitlines() if ln.startswith('{')]
+
+
+def test_dump_outputs_writes_float32_and_samples_large_arrays(tmp_path):
+    """--dump-outputs: every array as float32 .npy; one above DUMP_SAMPLE elements as a fixed, seeded sample of that many elements."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+    import bench
+    big = torch.arange(bench.DUMP_SAMPLE + 1000, dtype=torch.float32)
+    arrays = {'loss': torch.tensor(0.25), 'gen_states': torch.ones(9, 2, 5, dtype=torch.float64), 'gen_images': big}
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), arrays, np)
+    assert sorted(os.listdir(tmp_path / 'a')) == ['gen_images_sample.npy', 'gen_states.npy', 'loss.npy']
+    loss = np.load(tmp_path / 'a' / 'loss.npy')
+    assert loss.dtype == np.float32 and float(loss) == 0.25
+    st = np.load(tmp_path / 'a' / 'gen_states.npy')
+    assert st.dtype == np.float32 and st.shape == (9, 2, 5)
+    s1, s2 = np.load(tmp_path / 'a' / 'gen_images_sample.npy'), np.load(tmp_path / 'b' / 'gen_images_sample.npy')
+    assert s1.dtype == np.float32 and s1.shape == (bench.DUMP_SAMPLE,) and np.array_equal(s1, s2)
+    assert np.all(np.diff(s1) >= 0) and s1.max() > bench.DUMP_SAMPLE // 2       # sorted indices drawn over the whole array

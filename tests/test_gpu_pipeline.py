@@ -127,7 +127,7 @@ def test_bench_two_ranks_rehearsal_on_one_gpu(pivp):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK')}
     p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--backend', 'gloo', '--share-gpu', '--batch', '4',
-                        '--steps', '2', '--warmup', '1', '--no-cpu-baseline'], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                        '--steps', '2', '--warmup', '1', '--full', '--no-cpu-baseline'], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                        text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     out = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith('{')][-1])
@@ -138,3 +138,27 @@ def test_bench_two_ranks_rehearsal_on_one_gpu(pivp):
     assert np.isfinite(tr['loss']) and np.isfinite(out['config']['loss'])
     assert tr['allreduce_algo'] == 'allreduce' and out['train_bf16']['allreduce_algo'] == 'rs_ag'      # fp32 payload: ring; bf16 payload: all-links, fp32 local sum
     assert set(out['train_bf16']['allreduce_algo_ms_per_step']) == {'allreduce', 'rs_ag'}
+
+
+def test_bench_dump_outputs_is_the_last_timed_step(pivp, tmp_path):
+    """`bench.py --steps K --warmup W --dump-outputs DIR`: the plain run's last timed rollout as float32 .npy files; the loss in the line is
+    the dumped one, and a second run with the same arguments computes the same frames (seeded inputs and weights)."""
+    import json, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK')}
+    outs = []
+    for d in ('a', 'b'):
+        p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--batch', '4', '--steps', '3', '--warmup', '1',
+                            '--dump-outputs', str(tmp_path / d)], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+        assert p.returncode == 0, p.stderr[-3000:]
+        outs.append(json.loads([ln for ln in p.stdout.splitlines() if ln.startswith('{')][-1]))
+    out = outs[0]
+    assert out['steps'] == 3 and out['ms_per_step'] > 0 and 'train' not in out
+    files = {f: np.load(tmp_path / 'a' / f) for f in sorted(os.listdir(tmp_path / 'a'))}
+    assert sorted(files) == ['gen_images.npy', 'gen_states.npy', 'loss.npy', 'psnr_all.npy']
+    assert all(a.dtype == np.float32 for a in files.values())
+    assert files['gen_images.npy'].shape == (9, 4, 3, 64, 64) and files['gen_states.npy'].shape == (9, 4, 5)
+    assert np.isfinite(files['gen_images.npy']).all()
+    assert float(files['loss.npy']) == np.float32(out['config']['loss'])
+    other = np.load(tmp_path / 'b' / 'gen_images.npy')
+    assert np.abs(other - files['gen_images.npy']).max() < 1e-5
