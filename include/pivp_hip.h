@@ -105,6 +105,20 @@ int pivp_plan_set_param(pivp_plan_t* plan, int idx, const float* dptr);
  * workspace bound, a mode that needs deeper rings than the bound layout holds is refused with PIVP_ERR_STATE (nothing changes); modes that fit switch in place. */
 int pivp_plan_set_precision(pivp_plan_t* plan, int precision);
 int pivp_plan_get_precision(const pivp_plan_t* plan);
+/* Deterministic training (on = 1; default 0).  A training step -- pivp_rollout_forward, pivp_rollout_backward, the optimizer's elementwise update -- then gives
+ * the same bits every time for the same inputs, parameters, optimizer state, plan shape, precision, PIVP_WGRAD_BATCH and GPU model, whatever the side-stream
+ * schedule (PIVP_SIDE_STREAM), the process or the workspace address: no float atomics are reached, and every sum runs in an order fixed by the problem shape.
+ * The ConvLSTM data gradients never split K; the ConvLSTM weight gradients take the fp32 slot form (partial slots summed once per sweep, in every precision
+ * mode); the bias, head, enc0 and enc3 / state-predictor gradients go through per-block rows summed in order behind each launch.  Served: PIVP_PRECISION_F32,
+ * _BF16 and _BF16X3 (the ConvLSTM weight gradients then in fp32: deterministic BF16 is not default BF16's arithmetic there); CDNA, STP and DNA; shapes
+ * whose ConvLSTM maps are powers of two at least 8 wide.  Anything else returns PIVP_ERR_BADARG and the plan is unchanged (BF16X6, FP16X3 included); pivp_plan_set_precision refuses those modes while the switch is on.  Gradient groups, pivp_plan_group_wait and
+ * the callback keep their meaning: a group is final after its reductions.
+ * ORDER: pivp_plan_set_precision -> pivp_plan_set_deterministic -> pivp_plan_workspace_bytes -> pivp_plan_set_workspace.  On adds workspace (the slots and
+ * rows above), so pivp_plan_workspace_bytes grows with this call while no workspace is bound; turning it on with a workspace bound that was sized without it
+ * returns PIVP_ERR_STATE.  A data-parallel run is deterministic only if its collective is.  Added in ABI 17 without a version change: backward
+ * compatible, nothing else moved. */
+int pivp_plan_set_deterministic(pivp_plan_t* plan, int on);
+int pivp_plan_get_deterministic(const pivp_plan_t* plan);
 /* The precision modes re-pack the ConvLSTM weights (bf16 / split pieces) at the start of every rollout, because the parameters may have changed.  With
  * constant weights (serving) pivp_plan_set_pack_cache(plan, 1) keeps the packs; the caller then calls pivp_plan_params_changed after EVERY modification of a
  * parameter tensor.  The Python Model does both by itself (torch's in-place version counter + its own optimizer steps). */

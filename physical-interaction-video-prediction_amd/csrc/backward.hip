@@ -144,6 +144,36 @@ int bias_grad(const float* dy, int ld, int N, int M, float* db, hipStream_t s) {
     return PIVP_LAUNCH_STATUS();
 }
 
+// Deterministic sweeps: dst += the rows of `part` in ascending order (pivp_kernels.h, DetSegs).  One thread per (group, element); the row loop
+// keeps eight loads in flight.
+__global__ __launch_bounds__(256) void det_rows_reduce_kernel(const float* __restrict__ part, int rows, int groups, int n, const DetSegs segs) {
+    const int i = blockIdx.x * 256 + threadIdx.x, g = blockIdx.y;
+    if (i >= n || g >= groups) return;
+    const float* src = part + (size_t)g * rows * n + i;
+    float acc = 0.f;
+    int r = 0;
+    for (; r + 8 <= rows; r += 8) {
+        float v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = src[(size_t)(r + u) * n];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) acc += v[u];
+    }
+    for (; r < rows; ++r) acc += src[(size_t)r * n];
+    if (groups > 1) { segs.dst[0][(size_t)g * n + i] += acc; return; }
+    int k = 0, lo = 0;
+    while (k + 1 < segs.nseg && i >= lo + segs.n[k]) { lo += segs.n[k]; ++k; }
+    segs.dst[k][i - lo] += acc;
+}
+
+int det_rows_reduce(const float* part, int rows, int groups, const DetSegs& segs, hipStream_t s) {
+    PIVP_CHECK_ARG(part && rows > 0 && groups > 0 && segs.nseg >= 1 && segs.nseg <= 5 && (groups == 1 || segs.nseg == 1));
+    int n = 0;
+    for (int k = 0; k < segs.nseg; ++k) { PIVP_CHECK_ARG(segs.dst[k] && segs.n[k] > 0); n += segs.n[k]; }
+    hipLaunchKernelGGL(det_rows_reduce_kernel, dim3((n + 255) / 256, groups), dim3(256), 0, s, part, rows, groups, n, segs);
+    return PIVP_LAUNCH_STATUS();
+}
+
 // dy[pix][c] *= (y[pix][c] > 0)   (backward of the ReLU fused into a producer, TM:697-700)
 __global__ __launch_bounds__(256) void relu_mask_kernel(float* __restrict__ dy, int lddy, const float* __restrict__ y, int ldy,
                                                         int C, long npix, const float* __restrict__ add, int ldadd) {

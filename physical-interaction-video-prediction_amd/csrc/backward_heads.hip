@@ -455,7 +455,8 @@ constexpr int HB_DP = 129;       // pitch of the [output][pixel] tile: lanes tha
 __global__ __launch_bounds__(256) void heads_bwd_kernel(const float* __restrict__ e6, const float* __restrict__ wm, const float* __restrict__ we,
                                                         const float* __restrict__ dpm, const float* __restrict__ dpe,
                                                         float* __restrict__ de6, float* __restrict__ dwm, float* __restrict__ dbm,
-                                                        float* __restrict__ dwe, float* __restrict__ dbe, int total_px, int HW, int NP, int NE) {
+                                                        float* __restrict__ dwe, float* __restrict__ dbe, int total_px, int HW, int NP, int NE,
+                                                        float* __restrict__ part) {
     PIVP_SET_MAIN_PRIO();
     __shared__ __attribute__((aligned(16))) float xt[HB_PX * 68];        // [pixel][64 + 4]; reused for the block reduction of dW
     __shared__ float dpt[HB_MAXOUT * HB_DP];                              // [output][pixel]
@@ -564,6 +565,17 @@ __global__ __launch_bounds__(256) void heads_bwd_kernel(const float* __restrict_
 #pragma unroll
         for (int r = 0; r < 16; ++r) red[((wave * 2 + t) * 32 + (r & 3) + 8 * (r >> 2) + 4 * half) * 33 + l31] = dwacc[t][r];
     __syncthreads();
+    if (part) {      // deterministic sweeps: this block's row [dwm | dwe | dbm | dbe] of the partial sums, det_rows_reduce adds the rows in order
+        float* row = part + (size_t)blockIdx.x * 65 * NO;
+        for (int e = tid; e < 64 * NO; e += 256) {
+            const int k = e / NO, o = e - k * NO;
+            const int idx = ((k >> 5) * 32 + (k & 31)) * 33 + o;
+            const float v = (red[idx] + red[2 * 32 * 33 + idx]) + (red[4 * 32 * 33 + idx] + red[6 * 32 * 33 + idx]);
+            row[o < NP ? k * NP + o : 64 * NP + k * NE + (o - NP)] = v;
+        }
+        if ((tid & 7) == 0 && (tid >> 3) < NO) row[64 * NO + (tid >> 3)] = dbacc;
+        return;
+    }
     for (int e = tid; e < 64 * NO; e += 256) {
         const int k = e / NO, o = e - k * NO;
         const int idx = ((k >> 5) * 32 + (k & 31)) * 33 + o;
@@ -572,12 +584,21 @@ __global__ __launch_bounds__(256) void heads_bwd_kernel(const float* __restrict_
     }
     if ((tid & 7) == 0 && (tid >> 3) < NO) { const int o = tid >> 3; if (o < NP) atomicAdd(dbm + o, dbacc); else atomicAdd(dbe + (o - NP), dbacc); }
 }
+long long heads_bwd_det_floats(int B, int HW, int NP, int NE) {
+    return (long long)((B * HW + HB_PX * HB_SUB - 1) / (HB_PX * HB_SUB)) * 65 * (NP + NE);
+}
 int heads_bwd(const float* e6, const float* wm, const float* we, const float* dpm, const float* dpe, float* de6,
-              float* dwm, float* dbm, float* dwe, float* dbe, int B, int HW, int NP, int NE, hipStream_t s) {
+              float* dwm, float* dbm, float* dwe, float* dbe, int B, int HW, int NP, int NE, hipStream_t s, float* det_part) {
     PIVP_CHECK_ARG(e6 && wm && we && dpm && dpe && de6 && dwm && dbm && dwe && dbe && B > 0 && HW > 0 && NP + NE <= HB_MAXOUT);
-    const int total = B * HW;
-    hipLaunchKernelGGL(heads_bwd_kernel, dim3((total + HB_PX * HB_SUB - 1) / (HB_PX * HB_SUB)), dim3(256), 0, s, e6, wm, we, dpm, dpe, de6, dwm, dbm, dwe, dbe,
-                       total, HW, NP, NE);
+    const int total = B * HW, blocks = (total + HB_PX * HB_SUB - 1) / (HB_PX * HB_SUB);
+    hipLaunchKernelGGL(heads_bwd_kernel, dim3(blocks), dim3(256), 0, s, e6, wm, we, dpm, dpe, de6, dwm, dbm, dwe, dbe,
+                       total, HW, NP, NE, det_part);
+    if (det_part) {
+        const int rc = PIVP_LAUNCH_STATUS();
+        if (rc != PIVP_OK) return rc;
+        DetSegs sg{{dwm, dwe, dbm, dbe, nullptr}, {64 * NP, 64 * NE, NP, NE, 0}, 4};
+        return det_rows_reduce(det_part, blocks, 1, sg, s);
+    }
     return PIVP_LAUNCH_STATUS();
 }
 
@@ -588,7 +609,7 @@ int heads_bwd(const float* e6, const float* wm, const float* we, const float* dp
 //   d x[b][kk] = sum_o Wt[kk][o] dv[b][o];  dWt[kk][o] += sum_b x[b][kk] dv[b][o];  db[o] += sum_b dv[b][o]
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void cdna_kernels_bwd_dv_kernel(const float* __restrict__ vpre, const float* __restrict__ dkpart, int ntiles,
-                                                                  float* __restrict__ dv, float* __restrict__ db, int NM) {
+                                                                  float* __restrict__ dv, float* __restrict__ db, int NM, float* __restrict__ part) {
     PIVP_SET_MAIN_PRIO();
     __shared__ float u[256], dk[256];
     const int b = blockIdx.x, o = threadIdx.x, nout = NM * 25, nused = (NM - 1) * 25;
@@ -609,7 +630,8 @@ __global__ __launch_bounds__(256) void cdna_kernels_bwd_dv_kernel(const float* _
         for (int i = 0; i < 25; ++i) dot = fmaf(dk[g + i], u[g + i], dot);
         const float du = (d - dot / S) / S;
         out = (vpre[(size_t)b * 256 + o] - 1e-12f > 0.f) ? du : 0.f;
-        atomicAdd(db + o, out);
+        if (part) part[(size_t)b * nout + o] = out;      // deterministic sweeps: row b, summed over the samples in order by det_rows_reduce
+        else atomicAdd(db + o, out);
     }
     dv[(size_t)b * 256 + o] = out;
 }
@@ -686,9 +708,16 @@ __global__ __launch_bounds__(256) void skinny_linear_bwd_w_kernel(const float* _
 }
 
 int cdna_kernels_bwd(const float* hidden5, const float* wt, const float* vpre, const float* dkpart, int ntiles, float* dv,
-                     float* dhidden5, int accum_dx, float* dwt, float* db, int B, int K, int NM, hipStream_t s, const SideFork* fork) {
+                     float* dhidden5, int accum_dx, float* dwt, float* db, int B, int K, int NM, hipStream_t s, const SideFork* fork, float* det_part) {
     PIVP_CHECK_ARG(hidden5 && wt && vpre && dkpart && dv && dhidden5 && dwt && db && B > 0 && K > 0 && NM >= 1 && NM * 25 <= 256);
-    hipLaunchKernelGGL(cdna_kernels_bwd_dv_kernel, dim3(B), dim3(256), 0, s, vpre, dkpart, ntiles, dv, db, NM);
+    hipLaunchKernelGGL(cdna_kernels_bwd_dv_kernel, dim3(B), dim3(256), 0, s, vpre, dkpart, ntiles, dv, db, NM, det_part);
+    if (det_part) {
+        const int rc = PIVP_LAUNCH_STATUS();
+        if (rc != PIVP_OK) return rc;
+        DetSegs sg{{db, nullptr, nullptr, nullptr, nullptr}, {NM * 25, 0, 0, 0, 0}, 1};
+        const int rr = det_rows_reduce(det_part, B, 1, sg, s);
+        if (rr != PIVP_OK) return rr;
+    }
     hipLaunchKernelGGL(skinny_linear_bwd_x_kernel, dim3((K + 31) / 32, (B + 31) / 32), dim3(256), 0, s, wt, dv, dhidden5, B, K, accum_dx);
     hipStream_t sw = s;      // the weight gradient needs dv only: on the fork's stream it runs beside the rest of the sweep
     if (fork && fork->side) {
@@ -712,6 +741,12 @@ int cdna_kernels_bwd(const float* hidden5, const float* wt, const float* vpre, c
 // ------------------------------------------------------------------------------------------
 // threads per block: one pixel per thread on 8 x 64 tiles, two waves per SIMD (256 threads: 224 us per launch at B = 32)
 constexpr int CBS_NT = 512;
+// Deterministic sweeps (dacc != null): the scattered d prev contributions are added as 64-bit integers in units of 2^-48 -- in the block's LDS window
+// and, outside it, in a global accumulator -- and integer addition is exact, so the sums do not depend on the order in which the lanes, waves and
+// blocks arrive.  stp_dprev_finish adds the accumulator into d prev once per launch (one float rounding per element) and clears it.  Range +-2^15:
+// d prev is the gradient of a mean over the frame's elements, many orders of magnitude below it.
+constexpr double CBS_FIX = 281474976710656.0;      // 2^48
+__device__ __forceinline__ unsigned long long cbs_fix(float v) { return (unsigned long long)__double2ll_rn((double)v * CBS_FIX); }
 constexpr int CBS_R = 12;        // rows above / below the tile held in the LDS window of d prev
 // `whole` (feed-self sweeps on frames whose three planes fit in LDS: 48 KB at 64 x 64): a block's window of d prev is the WHOLE frame, so
 // every scattered bilinear weight is an LDS atomic whatever theta is (with the +-12-row window a random-init theta, far from the identity,
@@ -723,7 +758,7 @@ __global__ __launch_bounds__(CBS_NT) void composite_bwd_stp_kernel(const float* 
                                                                 const float* __restrict__ layer0, const float* __restrict__ theta,
                                                                 const float* __restrict__ go, float* __restrict__ dmk, float* __restrict__ dz,
                                                                 float* __restrict__ dthpart, float* __restrict__ dprev,
-                                                                int H, int W, int NM, int stp_zero, int whole) {
+                                                                int H, int W, int NM, int stp_zero, int whole, unsigned long long* __restrict__ dacc) {
     PIVP_SET_MAIN_PRIO();
     extern __shared__ __attribute__((aligned(16))) float sm[];
     __shared__ float red[CBS_NT / 64][6];
@@ -737,7 +772,10 @@ __global__ __launch_bounds__(CBS_NT) void composite_bwd_stp_kernel(const float* 
     float* gmx = lg + NP * win_max;              // [NP][G]
     float* ginv = gmx + NP * G_max;              // [NP][G]
     float* dwin = ginv + NP * G_max;             // [3][WR][W]  this block's window of d prev (feed-self only)
-    if (dprev)
+    unsigned long long* const dwin64 = reinterpret_cast<unsigned long long*>(sm + ((NP * win_max + 2 * NP * G_max + 1) & ~1));   // ... as integers (dacc)
+    if (dprev && dacc)
+        for (int i = tid; i < 3 * WR * W; i += CBS_NT) dwin64[i] = 0ull;
+    else if (dprev)
         for (int i = tid; i < 3 * WR * W; i += CBS_NT) dwin[i] = 0.f;
     const float* lgb = logits + (size_t)b * NP * HW;
     const unsigned magic = 0xFFFFFFFFu / (unsigned)NP + 1u;        // exact x / NP for x * NP < 2^32 (as in composite_bwd_cdna_kernel)
@@ -812,7 +850,22 @@ __global__ __launch_bounds__(CBS_NT) void composite_bwd_stp_kernel(const float* 
             const float dw = g * msum;                                   // d loss / d warp[c](p)
             du = fmaf(dw, (1.f - wv1) * (nb[0][1] - nb[0][0]) + wv1 * (nb[1][1] - nb[1][0]), du);
             dvv = fmaf(dw, (1.f - wu1) * (nb[1][0] - nb[0][0]) + wu1 * (nb[1][1] - nb[0][1]), dvv);
-            if (dprev) {
+            if (dprev && dacc) {      // deterministic: the same scatter in fixed point (whole == 0: a +-CBS_R-row window)
+                unsigned long long* dq = dacc + ((size_t)b * 3 + c) * HW;
+                unsigned long long* dwc = dwin64 + c * WR * W;
+                atomicAdd(dwc + (y - wy0) * W + x, cbs_fix(mk0 * g));
+#pragma unroll
+                for (int a = 0; a < 2; ++a)
+#pragma unroll
+                    for (int e = 0; e < 2; ++e) {
+                        const int uu = iu + e, vv = iv + a;
+                        if ((unsigned)uu < (unsigned)W && (unsigned)vv < (unsigned)H) {
+                            const unsigned long long val = cbs_fix(dw * (a ? wv1 : 1.f - wv1) * (e ? wu1 : 1.f - wu1));
+                            if ((unsigned)(vv - wy0) < (unsigned)WR) atomicAdd(dwc + (vv - wy0) * W + uu, val);
+                            else atomicAdd(dq + vv * W + uu, val);
+                        }
+                    }
+            } else if (dprev) {
                 // scatter into the block's LDS window of d prev (rows wy0 .. wy0 + WR - 1: the tile's own rows +- CBS_R, where a near-identity
                 // warp lands); targets outside it go straight to memory.  Straight global atomics for everything cost 215 of this kernel's
                 // 231 us: neighbouring pixels' bilinear footprints overlap, so the lanes of one instruction hit the same addresses.
@@ -843,7 +896,13 @@ __global__ __launch_bounds__(CBS_NT) void composite_bwd_stp_kernel(const float* 
     for (int j = 0; j < 6; ++j) dth[j] = wave_sum(dth[j]);
     if ((tid & 63) == 0) for (int j = 0; j < 6; ++j) red[tid >> 6][j] = dth[j];
     __syncthreads();
-    if (dprev && !whole)   // the window's touched elements, one atomic each (other tiles' windows overlap this one)
+    if (dprev && dacc)     // the window into the integer accumulator (other tiles' windows overlap this one)
+        for (int i = tid; i < 3 * WR * W; i += CBS_NT) {
+            const unsigned long long v = dwin64[i];
+            const int c = i / (WR * W), rem = i - c * (WR * W), r = rem / W, xx = rem - r * W, yy = wy0 + r;
+            if (v != 0ull && (unsigned)yy < (unsigned)H) atomicAdd(dacc + ((size_t)b * 3 + c) * HW + yy * W + xx, v);
+        }
+    else if (dprev && !whole)   // the window's touched elements, one atomic each (other tiles' windows overlap this one)
         for (int i = tid; i < 3 * WR * W; i += CBS_NT) {
             const float v = dwin[i];
             const int c = i / (WR * W), rem = i - c * (WR * W), r = rem / W, xx = rem - r * W, yy = wy0 + r;
@@ -864,16 +923,27 @@ __global__ __launch_bounds__(CBS_NT) void composite_bwd_stp_kernel(const float* 
     }
 }
 
+// d prev += the integer accumulator (units of 2^-48), which is cleared for the next launch
+__global__ __launch_bounds__(256) void stp_dprev_finish_kernel(unsigned long long* __restrict__ acc, float* __restrict__ dprev, long n) {
+    PIVP_SET_MAIN_PRIO();
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        const long long v = (long long)acc[i];
+        if (v) { dprev[i] += (float)((double)v * (1.0 / CBS_FIX)); acc[i] = 0ull; }
+    }
+}
+
 int composite_bwd_stp(const float* prev, const float* logits, const float* layer0, const float* theta, const float* go,
-                      float* dmk, float* dz, float* dthpart, float* dprev, int B, int H, int W, int NM, int stp_zero, hipStream_t s) {
+                      float* dmk, float* dz, float* dthpart, float* dprev, int B, int H, int W, int NM, int stp_zero, hipStream_t s,
+                      unsigned long long* det_acc) {
     PIVP_CHECK_ARG(prev && logits && layer0 && theta && go && dmk && dz && dthpart && B > 0 && H > 1 && W > 1 && NM >= 2 && NM <= 10);
     const int CB_TR = composite_bwd_rows(W);
     const int NP = NM + 1, np = CB_TR * W, win = np + 2 * (NP - 1), G = np / NP + 2;
     constexpr int whole_on = 8;      // at most this many blocks per sample, each with the whole frame's d prev in LDS (B = 32: 29.3 / 29.3 / 28.6 / 28.2 / 28.0 ms per STP
                                      // train step for one block per tile with a +-12-row window / 1 / 2 / 4 / 8)
     const size_t lds_head = sizeof(float) * ((size_t)NP * win + 2 * NP * G);
-    const int whole = (whole_on > 0 && dprev && lds_head + sizeof(float) * 3 * (size_t)H * W <= 96 * 1024) ? 1 : 0;
-    const size_t lds = lds_head + sizeof(float) * 3 * (size_t)(whole ? H : CB_TR + 2 * CBS_R) * W;
+    const int whole = (!det_acc && whole_on > 0 && dprev && lds_head + sizeof(float) * 3 * (size_t)H * W <= 96 * 1024) ? 1 : 0;
+    const size_t wn = 3 * (size_t)(whole ? H : CB_TR + 2 * CBS_R) * W;
+    const size_t lds = lds_head + (det_acc ? 8 + sizeof(unsigned long long) * wn : sizeof(float) * wn);     // (+8: the integer window's alignment)
     PIVP_CHECK_ARG(lds <= 150 * 1024);
     const int ntiles = composite_bwd_tiles(H, W);
     int per_sample = ntiles;
@@ -885,11 +955,17 @@ int composite_bwd_stp(const float* prev, const float* logits, const float* layer
     if (CB_TR == 8) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&composite_bwd_stp_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         hipLaunchKernelGGL(composite_bwd_stp_kernel<8>, grid, dim3(CBS_NT), lds, s, prev, logits, layer0, theta, go, dmk,
-                           dz, dthpart, dprev, H, W, NM, stp_zero, whole);
+                           dz, dthpart, dprev, H, W, NM, stp_zero, whole, dprev ? det_acc : nullptr);
     } else {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&composite_bwd_stp_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         hipLaunchKernelGGL(composite_bwd_stp_kernel<4>, grid, dim3(CBS_NT), lds, s, prev, logits, layer0, theta, go, dmk,
-                           dz, dthpart, dprev, H, W, NM, stp_zero, whole);
+                           dz, dthpart, dprev, H, W, NM, stp_zero, whole, dprev ? det_acc : nullptr);
+    }
+    if (dprev && det_acc) {
+        const int rc = PIVP_LAUNCH_STATUS();
+        if (rc != PIVP_OK) return rc;
+        const long n = (long)B * 3 * H * W;
+        hipLaunchKernelGGL(stp_dprev_finish_kernel, dim3((unsigned)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024)), dim3(256), 0, s, det_acc, dprev, n);
     }
     return PIVP_LAUNCH_STATUS();
 }
@@ -898,7 +974,7 @@ int composite_bwd_stp(const float* prev, const float* logits, const float* layer
 //   d theta = sum of the tile partials; dW2 += d theta (x) s1; db2 += d theta; dv = (W2^T d theta) [s1 > 0]; db1 += dv
 __global__ __launch_bounds__(128) void stp_params_bwd_kernel(const float* __restrict__ dthpart, int ntiles, const float* __restrict__ s1,
                                                              const float* __restrict__ w2, float* __restrict__ dw2, float* __restrict__ db2,
-                                                             float* __restrict__ db1, float* __restrict__ dv) {
+                                                             float* __restrict__ db1, float* __restrict__ dv, float* __restrict__ part) {
     PIVP_SET_MAIN_PRIO();
     __shared__ float dth[6];
     const int b = blockIdx.x, o = threadIdx.x;
@@ -906,7 +982,8 @@ __global__ __launch_bounds__(128) void stp_params_bwd_kernel(const float* __rest
         float a = 0.f;
         for (int t = 0; t < ntiles; ++t) a += dthpart[((size_t)b * ntiles + t) * 8 + o];
         dth[o] = a;
-        atomicAdd(db2 + o, a);
+        if (part) part[(size_t)b * 706 + o] = a;      // deterministic sweeps: row b = [db2 | dw2 | db1], summed over the samples by det_rows_reduce
+        else atomicAdd(db2 + o, a);
     }
     __syncthreads();
     float out = 0.f;
@@ -914,18 +991,30 @@ __global__ __launch_bounds__(128) void stp_params_bwd_kernel(const float* __rest
         const float sv = s1[(size_t)b * 256 + o];
         float d = 0.f;
 #pragma unroll
-        for (int j = 0; j < 6; ++j) { d = fmaf(w2[j * 100 + o], dth[j], d); atomicAdd(dw2 + j * 100 + o, dth[j] * sv); }
+        for (int j = 0; j < 6; ++j) {
+            d = fmaf(w2[j * 100 + o], dth[j], d);
+            if (part) part[(size_t)b * 706 + 6 + j * 100 + o] = dth[j] * sv;
+            else atomicAdd(dw2 + j * 100 + o, dth[j] * sv);
+        }
         out = sv > 0.f ? d : 0.f;
-        atomicAdd(db1 + o, out);
+        if (part) part[(size_t)b * 706 + 606 + o] = out;
+        else atomicAdd(db1 + o, out);
     }
     dv[(size_t)b * 256 + o] = out;
     dv[(size_t)b * 256 + 128 + o] = 0.f;
 }
 
 int stp_params_bwd(const float* hidden5, const float* wt1, const float* s1, const float* w2, const float* dthpart, int ntiles, float* dv,
-                   float* dhidden5, float* dwt1, float* db1, float* dw2, float* db2, int B, int K, hipStream_t s) {
+                   float* dhidden5, float* dwt1, float* db1, float* dw2, float* db2, int B, int K, hipStream_t s, float* det_part) {
     PIVP_CHECK_ARG(hidden5 && wt1 && s1 && w2 && dthpart && dv && dhidden5 && dwt1 && db1 && dw2 && db2 && B > 0 && K > 0);
-    hipLaunchKernelGGL(stp_params_bwd_kernel, dim3(B), dim3(128), 0, s, dthpart, ntiles, s1, w2, dw2, db2, db1, dv);
+    hipLaunchKernelGGL(stp_params_bwd_kernel, dim3(B), dim3(128), 0, s, dthpart, ntiles, s1, w2, dw2, db2, db1, dv, det_part);
+    if (det_part) {
+        int rc = PIVP_LAUNCH_STATUS();
+        if (rc != PIVP_OK) return rc;
+        DetSegs sg{{db2, dw2, db1, nullptr, nullptr}, {6, 600, 100, 0, 0}, 3};
+        rc = det_rows_reduce(det_part, B, 1, sg, s);
+        if (rc != PIVP_OK) return rc;
+    }
     hipLaunchKernelGGL(skinny_linear_bwd_x_kernel, dim3((K + 31) / 32, (B + 31) / 32), dim3(256), 0, s, wt1, dv, dhidden5, B, K, 0);
     hipLaunchKernelGGL(skinny_linear_bwd_w_kernel, dim3((K + 7) / 8), dim3(256), 0, s, hidden5, dv, dwt1, B, K);
     return PIVP_LAUNCH_STATUS();
@@ -944,7 +1033,7 @@ __global__ __launch_bounds__(256) void enc3_state_bwd_kernel(const float* __rest
                                                              const float* __restrict__ dsnew, float* __restrict__ de2,
                                                              float* __restrict__ dw3, float* __restrict__ db3, float* __restrict__ dwcs,
                                                              float* __restrict__ dbcs, float* __restrict__ dstate_prev,
-                                                             int HW8, int use_state, int mask_e2) {
+                                                             int HW8, int use_state, int mask_e2, float* __restrict__ part) {
     PIVP_SET_MAIN_PRIO();
     __shared__ float xt[64 * 65];
     __shared__ float dt[64 * 65];
@@ -982,11 +1071,16 @@ __global__ __launch_bounds__(256) void enc3_state_bwd_kernel(const float* __rest
     // blockIdx.z = quarter q: 16 of the tile's 64 pixels for d e2 and 16 of the 64 input channels for dW (every quarter stages the whole
     // tile: 48 KB from L2).  One block per (tile, sample) ran 2 x 64 iterations of 16 FMAs on 32 of 256 CUs: 41 us for 17 MFLOP.
     const int q = blockIdx.z;
+    // deterministic sweeps (part != null): the (tile, sample) pair's row [dw3 | db3 | dwcs | dbcs] and its five d state_prev values, stored instead of
+    // added (enc3_state_bwd_det_floats); every element of the row is written by one of the pair's four quarters
+    const int cin3 = use_state ? 74 : 64, rowlen = cin3 * 64 + 64 + 55;
+    float* const row = part ? part + ((size_t)b * gridDim.x + tile) * rowlen : nullptr;
+    float* const dsrow = part ? part + (size_t)gridDim.y * gridDim.x * rowlen + ((size_t)b * gridDim.x + tile) * 5 : nullptr;
     if (tid < 64) {
         float c = 0.f;
         for (int p = 0; p < 64; ++p) c += dt[p * 65 + tid];
         colsum[tid] = c;
-        if (q == 0) atomicAdd(db3 + tid, c);
+        if (q == 0) { if (row) row[cin3 * 64 + tid] = c; else atomicAdd(db3 + tid, c); }
     }
     {   // d e2[p][ci] = sum_co w3[ci][co] dpre[p][co]: thread (p = 16 q + tid/16, 4 ci)
         const int p = q * 16 + (tid >> 4), cg = (tid & 15) * 4;
@@ -1010,22 +1104,32 @@ __global__ __launch_bounds__(256) void enc3_state_bwd_kernel(const float* __rest
 #pragma unroll
             for (int i = 0; i < 4; ++i) acc[i] = fmaf(xv, dt[p * 65 + cg + i], acc[i]);
         }
+        if (row) {      // (rows of rowlen floats: not 16-B aligned)
 #pragma unroll
-        for (int i = 0; i < 4; ++i) atomicAdd(dw3 + ci * 64 + cg + i, acc[i]);
+            for (int i = 0; i < 4; ++i) row[ci * 64 + cg + i] = acc[i];
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) atomicAdd(dw3 + ci * 64 + cg + i, acc[i]);
+        }
     }
     if (q != 0) return;      // the state predictor and the smeared action/state rows: once per (tile, sample)
     __syncthreads();
     if (use_state && tid < 64) {
 #pragma unroll
-        for (int j = 0; j < 10; ++j) atomicAdd(dw3 + (64 + j) * 64 + tid, sa[j] * colsum[tid]);
+        for (int j = 0; j < 10; ++j) { if (row) row[(64 + j) * 64 + tid] = sa[j] * colsum[tid]; else atomicAdd(dw3 + (64 + j) * 64 + tid, sa[j] * colsum[tid]); }
     }
     if (tid < 10) {
         float v = 0.f;
         if (use_state) for (int co = 0; co < 64; ++co) v = fmaf(w3[(64 + tid) * 64 + co], colsum[co], v);
         if (tile == 0) for (int o = 0; o < 5; ++o) v = fmaf(wcs[o * 10 + tid], dsnew[b * 5 + o], v);
-        if (tid >= 5) atomicAdd(dstate_prev + b * 5 + tid - 5, v);
+        if (tid >= 5) { if (dsrow) dsrow[tid - 5] = v; else atomicAdd(dstate_prev + b * 5 + tid - 5, v); }
     }
-    if (tile == 0 && tid >= 64 && tid < 64 + 50) {
+    if (row && tid >= 64 && tid < 64 + 50) {      // (the state predictor's rows: sample b's value in tile 0's row, zeros in the others)
+        const int o = (tid - 64) / 10, j = (tid - 64) % 10;
+        row[cin3 * 64 + 64 + o * 10 + j] = tile == 0 ? dsnew[b * 5 + o] * sa[j] : 0.f;
+        if (j == 0) row[cin3 * 64 + 64 + 50 + o] = tile == 0 ? dsnew[b * 5 + o] : 0.f;
+    }
+    if (!row && tile == 0 && tid >= 64 && tid < 64 + 50) {
         const int o = (tid - 64) / 10, j = (tid - 64) % 10;
         atomicAdd(dwcs + o * 10 + j, dsnew[b * 5 + o] * sa[j]);
         if (j == 0) atomicAdd(dbcs + o, dsnew[b * 5 + o]);
@@ -1033,11 +1137,26 @@ __global__ __launch_bounds__(256) void enc3_state_bwd_kernel(const float* __rest
 }
 int enc3_state_bwd(const float* e2, const float* e3, const float* de3, int ldd3, const float* action, const float* state, const float* w3,
                    const float* wcs, const float* dsnew, float* de2, float* dw3, float* db3, float* dwcs, float* dbcs,
-                   float* dstate_prev, int B, int HW8, int use_state, hipStream_t s, int mask_e2) {
+                   float* dstate_prev, int B, int HW8, int use_state, hipStream_t s, int mask_e2, float* det_part) {
     PIVP_CHECK_ARG(e2 && e3 && de3 && action && state && w3 && wcs && dsnew && de2 && dw3 && db3 && dwcs && dbcs && dstate_prev && B > 0 && HW8 > 0);
-    hipLaunchKernelGGL(enc3_state_bwd_kernel, dim3((HW8 + 63) / 64, B, 4), dim3(256), 0, s, e2, e3, de3, ldd3, action, state, w3, wcs, dsnew, de2,
-                       dw3, db3, dwcs, dbcs, dstate_prev, HW8, use_state, mask_e2);
+    const int tiles = (HW8 + 63) / 64;
+    hipLaunchKernelGGL(enc3_state_bwd_kernel, dim3(tiles, B, 4), dim3(256), 0, s, e2, e3, de3, ldd3, action, state, w3, wcs, dsnew, de2,
+                       dw3, db3, dwcs, dbcs, dstate_prev, HW8, use_state, mask_e2, det_part);
+    if (det_part) {      // the weights over all (sample, tile) rows; d state_prev per sample over its tiles (inside the timestep: the next step reads it)
+        int rc = PIVP_LAUNCH_STATUS();
+        if (rc != PIVP_OK) return rc;
+        const int cin3 = use_state ? 74 : 64, rowlen = cin3 * 64 + 64 + 55;
+        DetSegs w{{dw3, db3, dwcs, dbcs, nullptr}, {cin3 * 64, 64, 50, 5, 0}, 4};
+        rc = det_rows_reduce(det_part, B * tiles, 1, w, s);
+        if (rc != PIVP_OK) return rc;
+        DetSegs ds{{dstate_prev, nullptr, nullptr, nullptr, nullptr}, {5, 0, 0, 0, 0}, 1};
+        return det_rows_reduce(det_part + (size_t)B * tiles * rowlen, tiles, B, ds, s);
+    }
     return PIVP_LAUNCH_STATUS();
+}
+long long enc3_state_bwd_det_floats(int B, int HW8, int use_state) {
+    const long long rows = (long long)B * ((HW8 + 63) / 64);
+    return rows * ((use_state ? 74 : 64) * 64 + 64 + 55) + rows * 5;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1045,7 +1164,7 @@ int enc3_state_bwd(const float* e2, const float* e3, const float* de3, int ldd3,
 // (feed-self) d img[c](y,x) = sum over taps with matching parity.
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void enc0_wgrad_kernel(const float* __restrict__ img, const float* __restrict__ d, float* __restrict__ dw,
-                                                         float* __restrict__ db, int B, int H, int W) {
+                                                         float* __restrict__ db, int B, int H, int W, float* __restrict__ part) {
     __shared__ float pt[64 * 76];
     __shared__ float dtl[64 * 33];
     const int H2 = H >> 1, W2 = W >> 1, total = B * H2 * W2, tid = threadIdx.x;
@@ -1079,6 +1198,13 @@ __global__ __launch_bounds__(256) void enc0_wgrad_kernel(const float* __restrict
             for (int i = 0; i < 10; ++i) { const int k = kg + 8 * i; if (k < 75) acc[i] = fmaf(pt[p * 76 + k], dv, acc[i]); }
             if (kg == 0) bacc += dv;
         }
+    }
+    if (part) {      // deterministic sweeps: this block's row [dw | db], det_rows_reduce adds the rows in order
+        float* row = part + (size_t)blockIdx.x * (75 * 32 + 32);
+#pragma unroll
+        for (int i = 0; i < 10; ++i) { const int k = kg + 8 * i; if (k < 75) row[k * 32 + co] = acc[i]; }
+        if (kg == 0) row[75 * 32 + co] = bacc;
+        return;
     }
 #pragma unroll
     for (int i = 0; i < 10; ++i) { const int k = kg + 8 * i; if (k < 75) atomicAdd(dw + k * 32 + co, acc[i]); }
@@ -1146,7 +1272,7 @@ __global__ __launch_bounds__(256) void enc0_dgrad_kernel(const float* __restrict
 }
 
 int enc0_bwd(const float* img, const float* w, const float* d, float* dw, float* db, float* dimg, int dimg_accum, int B, int H, int W,
-             hipStream_t s, const SideFork* fork) {
+             hipStream_t s, const SideFork* fork, float* det_part) {
     PIVP_CHECK_ARG(img && w && d && dw && db && B > 0 && H > 0 && W > 0);
     PIVP_CHECK_ARG(!dimg || (H % 2 == 0 && W % 2 == 0));       // the parity-class data gradient: checked before anything is enqueued
     hipStream_t sw = s;
@@ -1156,13 +1282,26 @@ int enc0_bwd(const float* img, const float* w, const float* d, float* dw, float*
     }
     const int total = B * (H / 2) * (W / 2);
     int blocks = (total + 63) / 64; if (blocks > 512) blocks = 512;
-    hipLaunchKernelGGL(enc0_wgrad_kernel, dim3(blocks), dim3(256), 0, sw, img, d, dw, db, B, H, W);
+    hipLaunchKernelGGL(enc0_wgrad_kernel, dim3(blocks), dim3(256), 0, sw, img, d, dw, db, B, H, W, det_part);
+    if (det_part) {
+        const int rc = PIVP_LAUNCH_STATUS();
+        if (rc != PIVP_OK) return rc;
+        DetSegs sg{{dw, db, nullptr, nullptr, nullptr}, {75 * 32, 32, 0, 0, 0}, 2};
+        const int rr = det_rows_reduce(det_part, blocks, 1, sg, sw);
+        if (rr != PIVP_OK) return rr;
+    }
     if (fork && fork->side && hipEventRecord(fork->done, fork->side) != hipSuccess) return PIVP_ERR_LAUNCH;
     if (dimg) {
         const long tp = (long)B * (H / 2) * (W / 2);           // pixels per parity class, 64 per block
         hipLaunchKernelGGL(enc0_dgrad_kernel, dim3((unsigned)((tp + 63) / 64), 4), dim3(256), 0, s, d, w, dimg, dimg_accum, B, H, W);
     }
     return PIVP_LAUNCH_STATUS();
+}
+
+long long enc0_bwd_det_floats(int B, int H, int W) {
+    const int total = B * (H / 2) * (W / 2);
+    int blocks = (total + 63) / 64; if (blocks > 512) blocks = 512;
+    return (long long)blocks * (75 * 32 + 32);
 }
 
 // out[i] = a[i] + b[i] over n floats with row strides (sum of two gradient contributions into one buffer)

@@ -735,7 +735,8 @@ int igemm_lstm(const IgemmDesc& d, hipStream_t stream, int variant, int* ln_npar
 // rows, 5 splits: 123.6), lstm5 64x64 / 8 91.4 (5: 97.0), lstm6 128x96 / 4 159.7 (128x64 / 5: 182.1), lstm7 64x128 unsplit 210.6.
 // Returns false when the descriptor is not such a conv.  ks == 1: plain stores, the destination need not be zeroed.
 static bool dgrad_choice(const IgemmDesc& d, int& bt, int& bks) {
-    if (!(d.ksplit_ok && !d.deconv && !d.bias && !d.relu && !d.accum && d.ksize * d.ksize * ((d.c0 + d.c1) / 32) > 40)) return false;
+    if (!((d.ksplit_ok || d.no_ksplit) && !d.deconv && !d.bias && !d.relu && !d.accum && d.ksize * d.ksize * ((d.c0 + d.c1) / 32) > 40)) return false;
+    const int ks_max = d.no_ksplit ? 1 : 10;      // deterministic sweeps: the best unsplit grid (plain stores, no atomics)
     const int nt = d.N / 32;
     struct Tile { int wm, wn, ntb; double eff; int resident; };
     static const Tile tiles[] = {{2, 2, 2, 0.80, 4}, {4, 1, 1, 0.70, 3}, {4, 1, 2, 0.90, 2}, {4, 1, 3, 0.95, 2}, {4, 1, 4, 1.00, 1}, {2, 2, 4, 0.95, 2}, {1, 4, 4, 0.80, 3}};
@@ -752,7 +753,7 @@ static bool dgrad_choice(const IgemmDesc& d, int& bt, int& bks) {
         if (nt % tiles[t].ntb) continue;
         const int bm = 32 * tiles[t].wm, bn = 32 * tiles[t].ntb;
         const long mb = (d.M + bm - 1) / bm, nb = d.N / bn;
-        for (int ks = 1; ks <= 10 && ks * 8 <= nchunks; ++ks) {          // >= 8 chunks per split
+        for (int ks = 1; ks <= ks_max && ks * 8 <= nchunks; ++ks) {      // >= 8 chunks per split
             const long blocks = mb * nb * ks;
             const long per_cu = (blocks + cus - 1) / cus;
             const int res = (int)(per_cu < tiles[t].resident ? per_cu : tiles[t].resident);

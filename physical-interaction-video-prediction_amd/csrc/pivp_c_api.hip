@@ -207,17 +207,19 @@ static int conv_s1_desc(IgemmDesc& d, const float* x, int cin, int ldx, const fl
     return PIVP_OK;
 }
 // true when run_conv_s1 with these arguments adds K-split partial sums into `out` (B * H * W * ldo floats to be zeroed first)
-bool conv_s1_splits_k(int cin, int cout, int ldo, int ksize, int B, int H, int W, int wN) {
+bool conv_s1_splits_k(int cin, int cout, int ldo, int ksize, int B, int H, int W, int wN, int no_split) {
+    if (no_split) return false;
     IgemmDesc d;
     static float dummy;
     if (conv_s1_desc(d, &dummy, cin, cin, &dummy, &dummy, cout, ldo, ksize, B, H, W, 0, wN) != PIVP_OK) return false;
     return d.ksplit_ok && igemm_conv_ksplit(d) > 1;
 }
 int run_conv_s1(const float* x, int cin, int ldx, const float* w, float* out, int cout, int ldo, int ksize, int B, int H, int W,
-                hipStream_t s, int accum, int wN, int dest_zeroed) {
+                hipStream_t s, int accum, int wN, int dest_zeroed, int no_split) {
     IgemmDesc d;
     int rc = conv_s1_desc(d, x, cin, ldx, w, out, cout, ldo, ksize, B, H, W, accum, wN);
     if (rc != PIVP_OK) return rc;
+    if (no_split && d.ksplit_ok) { d.ksplit_ok = 0; d.no_ksplit = 1; }      // deterministic sweeps: an unsplit grid, plain stores
     if (d.ksplit_ok && !dest_zeroed && igemm_conv_ksplit(d) > 1 &&
         hipMemsetAsync(out, 0, (size_t)B * H * W * ldo * 4, s) != hipSuccess) return PIVP_ERR_LAUNCH;
     return igemm_conv(d, s);
@@ -236,17 +238,19 @@ static int conv5x5_bf16_desc(IgemmDesc& d, const float* x, int cin, int ldx, flo
     if (!accum && ldo == cout) d.ksplit_ok = 1;     // contiguous fresh output: the K-split path may be used; it needs a zeroed destination
     return PIVP_OK;
 }
-bool conv5x5_bf16_splits_k(int cin, int cout, int ldo, int B, int H, int W, int planes) {
+bool conv5x5_bf16_splits_k(int cin, int cout, int ldo, int B, int H, int W, int planes, int no_split) {
+    if (no_split) return false;
     IgemmDesc d;
     static float dummy;
     if (conv5x5_bf16_desc(d, &dummy, cin, cin, &dummy, cout, ldo, 0, B, H, W) != PIVP_OK) return false;
     return d.ksplit_ok && conv5x5_bf16_ksplit(d, planes) > 1;
 }
 int run_conv5x5_bf16(const float* x, int cin, int ldx, const unsigned short* wb, float* out, int cout, int ldo, int accum,
-                     int B, int H, int W, hipStream_t s, int planes, int dest_zeroed, const float* ascale_part, const EpSpec* ep) {
+                     int B, int H, int W, hipStream_t s, int planes, int dest_zeroed, const float* ascale_part, const EpSpec* ep, int no_split) {
     IgemmDesc d;
     int rc = conv5x5_bf16_desc(d, x, cin, ldx, out, cout, ldo, accum, B, H, W);
     if (rc != PIVP_OK) return rc;
+    if (no_split) d.ksplit_ok = 0;      // deterministic sweeps: one block per output tile over the whole K (no atomics)
     d.wscale_part = ascale_part;
     if (ep && ep->applied) *ep->applied = 0;
     if (ep && ep->src && ep->mode && !(d.ksplit_ok && conv5x5_bf16_ksplit(d, planes) > 1)) {
@@ -262,7 +266,7 @@ int run_conv5x5_bf16(const float* x, int cin, int ldx, const unsigned short* wb,
 int run_wgrad(int mode, const float* x0, int c0, int ld0, const float* x1, int c1, int ld1, int wcin, const float* dy, int ldy, int N,
               float* dw, int B, int Hx, int Wx, int Hy, int Wy, int ksize, int pad, int stride, hipStream_t s, float* db,
               int* bias_done, int bf16, int tcount, long long ts_x0, long long ts_x1, long long ts_dy, float* part, WgradDesc* desc_out,
-              const float* dy_absmax, int dy_absmax_stride, int form, int part_overwrite) {
+              const float* dy_absmax, int dy_absmax_stride, int form, int part_overwrite, int slot_ntw, int slot_j) {
     WgradDesc d;
     memset(&d, 0, sizeof(d));
     d.x0 = x0; d.c0 = c0; d.ld0 = ld0; d.x1 = x1; d.c1 = x1 ? c1 : 0; d.ld1 = ld1; d.cin = c0 + (x1 ? c1 : 0); d.wcin = wcin;
@@ -279,6 +283,7 @@ int run_wgrad(int mode, const float* x0, int c0, int ld0, const float* x1, int c
     d.dy_absmax = dy_absmax; d.dy_absmax_stride = dy_absmax_stride;
     d.pieces = bf16 == 3 ? 3 : 0;       // (bf16: 1 = operands rounded to bf16; 3 = three bf16 pieces per operand, fp32-grade)
     d.form = form;
+    d.slot_ntw = slot_ntw; d.slot_j = slot_j;
     if (desc_out) *desc_out = d;
     if (bf16 || dy_absmax) {   // bf16 precision mode (5x5 ConvLSTM case only): operands rounded to bf16, fp32 accumulation; db summed on the side in fp32
         if (bias_done) *bias_done = db != nullptr;
@@ -305,12 +310,13 @@ int run_convlstm_backward(const float* x, int cx, int ldx, const float* h_prev, 
                           const float* c_old, const float* c_new, const float* dh_a, int lda, const float* dh_b, int ldb,
                           float* dc, int dc_valid, float* dG, float* wt, float* d_in, float* dW, float* db,
                           int B, int H, int W, hipStream_t s, int wt_ready, unsigned short* wt_bf16, int bf16_planes, const SideFork* fork,
-                          const LnFuse* ln, int dx_only, float* dg_absmax, const EpSpec* ep) {
+                          const LnFuse* ln, int dx_only, float* dg_absmax, const EpSpec* ep, int det) {
     const int M = B * H * W, cin = cx + C, N = 4 * C;
     if (wt_bf16 && bf16_planes == -2 && !dg_absmax) return PIVP_ERR_BADARG;
-    // a K-split data gradient adds into d_in: the gate kernel clears it on the side (one launch less than a memset per cell and timestep)
-    const bool zero = wt_bf16 ? conv5x5_bf16_splits_k(N, cin, cin, B, H, W, bf16_planes)
-                              : (dx_only ? conv_s1_splits_k(N, cx, cin, 5, B, H, W, cin) : conv_s1_splits_k(N, cin, cin, 5, B, H, W, 0));
+    // a K-split data gradient adds into d_in: the gate kernel clears it on the side (one launch less than a memset per cell and timestep).
+    // det (deterministic sweeps): never split, so that every element of d_in is one block's plain store.
+    const bool zero = wt_bf16 ? conv5x5_bf16_splits_k(N, cin, cin, B, H, W, bf16_planes, det)
+                              : (dx_only ? conv_s1_splits_k(N, cx, cin, 5, B, H, W, cin, det) : conv_s1_splits_k(N, cin, cin, 5, B, H, W, 0, det));
     int rc = lstm_gates_bwd(gates, c_old, c_new, dh_a, lda, dh_b, ldb, dc, dc_valid, dG, M, C, s, B, ln, zero ? d_in : nullptr, (long long)M * cin);
     if (rc != PIVP_OK) return rc;
     if (dg_absmax) {      // fp16 pieces: dG's power-of-two scale from its largest |value| (gradients lie far below fp16's normal range); in front of the
@@ -333,12 +339,12 @@ int run_convlstm_backward(const float* x, int cx, int ldx, const float* h_prev, 
             rc = pack_lstm_bf16(wt, wt_bf16, N, cin, s, conv5x5_bf16_rows(cin), bf16_planes, 1);      // fragment-major plain pack, every map width
             if (rc != PIVP_OK) return rc;
         }
-        rc = run_conv5x5_bf16(dG, N, N, wt_bf16, d_in, cin, cin, 0, B, H, W, s, bf16_planes, zero, dg_absmax, ep);
+        rc = run_conv5x5_bf16(dG, N, N, wt_bf16, d_in, cin, cin, 0, B, H, W, s, bf16_planes, zero, dg_absmax, ep, det);
     } else {
         if (ep && ep->applied) *ep->applied = 0;      // (the fp32 data-gradient kernels have no such hook)
         // d[x,h] = conv5x5(dG, W^T flipped); dx_only: the x columns alone (the pack's first cx of cin; the h columns of d_in stay unwritten)
-        rc = dx_only ? run_conv_s1(dG, N, N, wt, d_in, cx, cin, 5, B, H, W, s, 0, cin, zero)
-                     : run_conv_s1(dG, N, N, wt, d_in, cin, cin, 5, B, H, W, s, 0, 0, zero);
+        rc = dx_only ? run_conv_s1(dG, N, N, wt, d_in, cx, cin, 5, B, H, W, s, 0, cin, zero, det)
+                     : run_conv_s1(dG, N, N, wt, d_in, cin, cin, 5, B, H, W, s, 0, 0, zero, det);
     }
     if (rc != PIVP_OK) return rc;
     if (!dW) return PIVP_OK;   // the caller batches this layer's weight gradient over several timesteps itself (pivp_plan.hip)
@@ -414,6 +420,15 @@ long long conv_backward_part_floats(int mode, int cin, int cout, int B, int Hin,
     d.Hg = mode ? Hin : Hout; d.Wg = mode ? Win : Wout; d.M = B * d.Hg * d.Wg;
     return igemm_wgrad_part_floats(d);
 }
+bool conv_backward_fixed_order(int mode, int cin, int cout, int B, int Hin, int Win) {
+    const int Hout = mode ? 2 * Hin : Hin / 2, Wout = mode ? 2 * Win : Win / 2;
+    WgradDesc d;
+    memset(&d, 0, sizeof(d));
+    d.c0 = cin; d.ld0 = cin; d.cin = cin; d.wcin = cin; d.N = cout; d.ldy = cout; d.B = B; d.Hx = Hin; d.Wx = Win; d.Hy = Hout; d.Wy = Wout;
+    d.deconv = mode; d.ksize = 3; d.pad = 1; d.stride = 2;
+    d.Hg = mode ? Hin : Hout; d.Wg = mode ? Win : Wout; d.M = B * d.Hg * d.Wg;
+    return wgrad3x3s2_ok(d);
+}
 // descriptor of a ConvLSTM weight gradient's ONE-timestep geometry (what the partial buffer's size and the reduction depend on)
 static void lstm_wgrad_geom(WgradDesc& d, int cx, int C, int B, int H, int W) {
     memset(&d, 0, sizeof(d));
@@ -422,20 +437,20 @@ static void lstm_wgrad_geom(WgradDesc& d, int cx, int C, int B, int H, int W) {
     d.ksize = 5; d.pad = 2; d.stride = 1;
 }
 // (the sweep's t = 0 has no h operand: its launch differentiates the x rows only -- fewer tiles, another partition of the same buffer, reduced on its own)
-long long lstm_wgrad_part_floats(int cx, int C, int B, int H, int W, int form) {
+long long lstm_wgrad_part_floats(int cx, int C, int B, int H, int W, int slot_ntw, int slot_j) {
     WgradDesc d;
     lstm_wgrad_geom(d, cx, C, B, H, W);
-    d.form = form;
+    d.slot_ntw = slot_ntw; d.slot_j = slot_j;
     if (!wgrad5x5p_ok(d)) return 0;
     const long long full = wgrad5x5p_part_floats(d);
     d.c1 = 0; d.cin = cx;
     const long long xonly = wgrad5x5p_part_floats(d);
     return full > xonly ? full : xonly;
 }
-int lstm_wgrad_reduce(int cx, int C, int has_h, float* part, float* dW, float* db, int B, int H, int W, hipStream_t s, int form) {
+int lstm_wgrad_reduce(int cx, int C, int has_h, float* part, float* dW, float* db, int B, int H, int W, hipStream_t s, int slot_ntw, int slot_j) {
     WgradDesc d;
     lstm_wgrad_geom(d, cx, C, B, H, W);
-    d.form = form;
+    d.slot_ntw = slot_ntw; d.slot_j = slot_j;
     if (!has_h) { d.c1 = 0; d.cin = cx; }
     d.part = part; d.dw = dW; d.db = db;
     return igemm_wgrad_reduce(d, s);
@@ -549,7 +564,7 @@ extern "C" int pivp_wgrad5x5_f32_batch(const float* x, int cx, int ldx, const fl
     if (!x || !dG || !dW || tcount < 1 || form < 0 || form > 2 || (part && lstm_wgrad_part_floats(cx, C, B, H, W, form) <= 0)) return PIVP_ERR_BADARG;
     int bias_done = 0;
     int rc = run_wgrad(0, x, cx, ldx, h_prev, C, C, cx + C, dG, 4 * C, 4 * C, dW, B, H, W, H, W, 5, 2, 1, (hipStream_t)stream, db, &bias_done, 0,
-                       tcount, ts_x, ts_h, ts_dG, part, nullptr, nullptr, 0, form, overwrite ? 1 : 0);
+                       tcount, ts_x, ts_h, ts_dG, part, nullptr, nullptr, 0, form, overwrite ? 1 : 0, form);      // (form: the wave form without part, the slot form's columns per wave with it)
     if (rc != PIVP_OK) return rc;
     if (db && !bias_done)
         for (int j = 0; j < tcount; ++j) {
@@ -571,7 +586,7 @@ extern "C" int pivp_wgrad5x5_f32_partition(int cx, int C, int has_h, int B, int 
     if (cx <= 0 || C <= 0 || B <= 0 || H <= 0 || W <= 0 || form < 0 || form > 2 || !geom8 || !nsegs || !nslots) return PIVP_ERR_BADARG;
     WgradDesc d;
     lstm_wgrad_geom(d, cx, C, B, H, W);
-    d.form = form;
+    d.slot_ntw = form;
     if (!has_h) { d.c1 = 0; d.cin = cx; }
     if (!wgrad5x5p_ok(d)) return PIVP_ERR_BADARG;
     return wgrad5x5p_partition(d, geom8, segs, seg_cap, nsegs, slots, slot_cap, nslots);

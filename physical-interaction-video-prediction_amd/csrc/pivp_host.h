@@ -42,9 +42,10 @@ int run_deconv3x3s2_ln(const float* h_raw, int c_ln, const float* x1, int c1, in
                        const float* wscale_part = nullptr, const MotionRider* rider = nullptr);
 int run_conv_s1(const float* x, int cin, int ldx, const float* w, float* out, int cout, int ldo, int ksize, int B, int H, int W,
                 hipStream_t s, int accum = 0, int wN = 0,    // wN: columns of the weight pack when only its first `cout` are wanted
-                int dest_zeroed = 0);                        // 1: the caller has cleared `out` (see conv_s1_splits_k)
-bool conv_s1_splits_k(int cin, int cout, int ldo, int ksize, int B, int H, int W, int wN);
-bool conv5x5_bf16_splits_k(int cin, int cout, int ldo, int B, int H, int W, int planes = 1);
+                int dest_zeroed = 0,                         // 1: the caller has cleared `out` (see conv_s1_splits_k)
+                int no_split = 0);                           // 1: never split K (deterministic sweeps: no atomics into `out`)
+bool conv_s1_splits_k(int cin, int cout, int ldo, int ksize, int B, int H, int W, int wN, int no_split = 0);
+bool conv5x5_bf16_splits_k(int cin, int cout, int ldo, int B, int H, int W, int planes = 1, int no_split = 0);
 // IgemmDesc::ep_*: a second tensor met in the plain 5x5 bf16 convolution's epilogue (mode 1 ReLU mask, 2 add) on its first `cols` output columns.
 // *applied (host) tells the caller whether the launch took it (unsplit grid) or the separate pass is still the caller's to run.
 struct EpSpec { const float* src; int ld, cols, mode; int* applied; };
@@ -55,7 +56,8 @@ int run_wgrad(int mode, const float* x0, int c0, int ld0, const float* x1, int c
               float* part = nullptr, WgradDesc* desc_out = nullptr,    // part: WgradDesc::part; desc_out: the descriptor that was launched
               const float* dy_absmax = nullptr, int dy_absmax_stride = 0,    // two fp16 pieces per operand (WgradDesc::dy_absmax; 5x5 ConvLSTM case only)
               int form = 0,                                                   // WgradDesc::form (bf16 operands, a batch of timesteps: four- / eight-wave blocks)
-              int part_overwrite = 0);                                        // WgradDesc::part_overwrite
+              int part_overwrite = 0,                                         // WgradDesc::part_overwrite
+              int slot_ntw = 0, int slot_j = 0);                              // WgradDesc::slot_ntw / slot_j (the fp32 slot form's partition)
 int run_convlstm_backward(const float* x, int cx, int ldx, const float* h_prev, int C, const float* w, const float* gates,
                           const float* c_old, const float* c_new, const float* dh_a, int lda, const float* dh_b, int ldb,
                           float* dc, int dc_valid, float* dG, float* wt, float* d_in, float* dW, float* db,
@@ -63,12 +65,13 @@ int run_convlstm_backward(const float* x, int cx, int ldx, const float* h_prev, 
                           const SideFork* fork = nullptr, const LnFuse* ln = nullptr,    // ln: dh_a is formed from the LayerNorm behind the cell
                           int dx_only = 0,    // 1: d h_{t-1} is not needed (the sweep's last timestep): only the cx columns of d_in are computed
                           float* dg_absmax = nullptr,         // 66 floats: receives dG's partial maxima (absmax_partials), the scale of the fp16-piece data gradient
-                          const EpSpec* ep = nullptr);        // the data gradient's epilogue hook (bf16 / split-precision data gradients on unsplit grids)
+                          const EpSpec* ep = nullptr,         // the data gradient's epilogue hook (bf16 / split-precision data gradients on unsplit grids)
                                                               // (bf16_planes == -2 needs it) and of the fp16-piece weight gradient (WgradDesc::dy_absmax)
+                          int det = 0);                       // deterministic sweeps: unsplit data gradients (the caller passes dW = null)
 int run_conv5x5_bf16(const float* x, int cin, int ldx, const unsigned short* wb, float* out, int cout, int ldo, int accum,
                      int B, int H, int W, hipStream_t s, int planes = 1, int dest_zeroed = 0,
                      const float* ascale_part = nullptr,      // planes == -2: absmax_partials(x) (the activations' power-of-two scale)
-                     const EpSpec* ep = nullptr);
+                     const EpSpec* ep = nullptr, int no_split = 0);
 int run_conv_backward(int mode, const float* x, int cin, int ldx, const float* w, float* dy, int cout, int ldy, const float* y, int ldyy,
                       float* wt, float* dx, int lddx, int accum_dx, float* dW, float* db, int B, int Hin, int Win, hipStream_t s,
                       int wt_ready = 0, const SideFork* fork = nullptr, float* part = nullptr, WgradDesc* desc_out = nullptr,
@@ -78,10 +81,12 @@ int run_conv_backward(int mode, const float* x, int cin, int ldx, const float* w
                                                                         // LDS reads, 2 MFMAs per 32-pixel chunk -- was built and is slower: profiles/r05/NOTES.md)
 // floats of WgradDesc::part a conv3x3s2 (mode 0) / deconv3x3s2 (mode 1) weight gradient of these sizes needs
 long long conv_backward_part_floats(int mode, int cin, int cout, int B, int Hin, int Win);
+bool conv_backward_fixed_order(int mode, int cin, int cout, int B, int Hin, int Win);      // the partial-plane form with its column sums (wgrad3x3s2) serves it
 // the fp32 ConvLSTM weight gradient's partial slots (csrc/wgrad5x5p.hip): floats of WgradDesc::part (0: the shape is not served), and the reduction
 // (has_h = 0: of launches without an h operand -- the sweep's t = 0 --, which cut the x rows' tiles their own way: reduce before switching)
-long long lstm_wgrad_part_floats(int cx, int C, int B, int H, int W, int form = 0);      // form: WgradDesc::form (0 by shape, 1 / 2 = 32 / 64 columns per wave)
-int lstm_wgrad_reduce(int cx, int C, int has_h, float* part, float* dW, float* db, int B, int H, int W, hipStream_t s, int form = 0);
+// slot_ntw / slot_j: WgradDesc::slot_ntw (0 by shape, 1 / 2 = 32 / 64 columns per wave) and WgradDesc::slot_j (0 = by the CU count, > 0 fixed)
+long long lstm_wgrad_part_floats(int cx, int C, int B, int H, int W, int slot_ntw = 0, int slot_j = 0);
+int lstm_wgrad_reduce(int cx, int C, int has_h, float* part, float* dW, float* db, int B, int H, int W, hipStream_t s, int slot_ntw = 0, int slot_j = 0);
 int run_layernorm(const float* x, const float* g, const float* b, float* out, float* partials, int B, int n, int C,
                   int ldo, float eps, int relu, hipStream_t s, float* stat_out = nullptr, int fused_nparts = 0);
 // run-time wave priority of the main stream's kernels (pivp_common.h): every translation unit with such kernels, on stream s

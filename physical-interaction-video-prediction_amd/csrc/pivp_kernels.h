@@ -30,6 +30,7 @@ struct IgemmDesc {
     float* out; int ldo; int relu;
     int accum;                           // 1: out += result (gradient accumulation)
     int ksplit_ok;                       // 1: `out` is pre-zeroed and may be produced by K-split blocks with atomic adds
+    int no_ksplit;                       // 1 (deterministic sweeps): the long-K data gradient picks its tile among unsplit grids only (no atomics)
     // ConvLSTM epilogue
     const float* cstate_in; float* cstate_out; float* hout; int C;
     float* gates_out;                    // optional [M][4C]: tanh(j), sigma(i), sigma(f+1), sigma(o) for the backward pass
@@ -110,6 +111,9 @@ struct WgradDesc {
     int pieces;                          // wgrad5x5_bf16 only: 3 = three bf16 pieces per operand, six MFMAs per product (the bf16x6 mode's weight gradient)
     int form;                            // wgrad5x5_bf16, plain bf16 operands, a batch of timesteps: 0 = by size (four-wave blocks that co-reside with the main stream's
                                          // kernels for maps of up to 32 x 32 x 32 pixels per timestep, else eight-wave blocks), 1 = four-wave, 2 = eight-wave
+    // wgrad5x5p (the fp32 slot form) only -- its partition, which the batch launches, the slot buffer's size and the reduction must agree on:
+    int slot_ntw;                        // 32-column MFMA tiles per wave: 0 = by shape (1), 1, 2 (needs N % 64 == 0)
+    int slot_j;                          // blocks per XCD: 0 = two per CU of this device (the CU count decides the order of the sums), > 0 = this many
 };
 int igemm_wgrad(const WgradDesc& d, hipStream_t s, int* bias_done = nullptr);
 long long igemm_wgrad_part_floats(const WgradDesc& d);    // 0 when the ConvLSTM fast path would take this descriptor
@@ -245,6 +249,12 @@ int lstm_gates_bwd(const float* gates, const float* c_old, const float* c_new, c
                    const LnFuse* ln = nullptr,
                    float* zero = nullptr, long long zero_floats = 0);
 int bias_grad(const float* dy, int ld, int N, int M, float* db, hipStream_t s);
+// Deterministic sweeps: a kernel that would add its blocks' partial sums into a gradient with atomics instead STORES block r's sums in row r of
+// `part` ([groups][rows][n] floats; every block writes every element of its row), and det_rows_reduce adds the rows into the destinations in
+// ascending row order -- a function of the problem shape alone.  Row element i goes to the segment that holds it (segments in order, lengths
+// summing to n); with groups > 1 there is one segment, and group g's sum goes to dst[g * n + i].
+struct DetSegs { float* dst[5]; int n[5]; int nseg; };
+int det_rows_reduce(const float* part, int rows, int groups, const DetSegs& segs, hipStream_t s);
 int relu_mask(float* dy, int lddy, const float* y, int ldy, int C, long npix, hipStream_t s,
               const float* add = nullptr, int ldadd = 0);   // add: dy = (dy + add) masked -- a second gradient path into the same activation
 int ln_bwd_slices(int n);
@@ -267,22 +277,31 @@ int composite_bwd_tiles(int H, int W);
 int composite_bwd_cdna(const float* prev, const float* logits, const float* layer0, const float* kerns, const float* go,
                        float* dmk, float* dz, float* dkpart, float* dprev, int dprev_accum, int B, int H, int W, int NM, hipStream_t s);
 int composite_bwd_stp(const float* prev, const float* logits, const float* layer0, const float* theta, const float* go,
-                      float* dmk, float* dz, float* dthpart, float* dprev, int B, int H, int W, int NM, int stp_zero, hipStream_t s);
+                      float* dmk, float* dz, float* dthpart, float* dprev, int B, int H, int W, int NM, int stp_zero, hipStream_t s,
+                      unsigned long long* det_acc = nullptr);     // det_acc (B x 3 x H x W, zero): d prev through exact integer sums (deterministic sweeps)
 int stp_params_bwd(const float* hidden5, const float* wt1, const float* s1, const float* w2, const float* dthpart, int ntiles, float* dv,
-                   float* dhidden5, float* dwt1, float* db1, float* dw2, float* db2, int B, int K, hipStream_t s);
+                   float* dhidden5, float* dwt1, float* db1, float* dw2, float* db2, int B, int K, hipStream_t s,
+                   float* det_part = nullptr);      // det_part (B x 706 floats): per-sample rows + det_rows_reduce instead of atomics
 int composite_bwd_dna(const float* prev, const float* logits, const float* e7, const float* go, float* dmk, float* dz,
                       float* dprev, int dprev_accum, int B, int H, int W, hipStream_t s);
 int mask_softmax_bwd(const float* logits, float* dmk, int B, int HW, int NP, hipStream_t s);
 int heads_bwd(const float* e6, const float* wm, const float* we, const float* dpm, const float* dpe, float* de6,
-              float* dwm, float* dbm, float* dwe, float* dbe, int B, int HW, int NP, int NE, hipStream_t s);
+              float* dwm, float* dbm, float* dwe, float* dbe, int B, int HW, int NP, int NE, hipStream_t s,
+              float* det_part = nullptr);      // det_part (heads_bwd_det_floats): per-block rows + det_rows_reduce instead of atomics
+long long heads_bwd_det_floats(int B, int HW, int NP, int NE);
 int cdna_kernels_bwd(const float* hidden5, const float* wt, const float* vpre, const float* dkpart, int ntiles, float* dv,
-                     float* dhidden5, int accum_dx, float* dwt, float* db, int B, int K, int NM, hipStream_t s, const SideFork* fork = nullptr);   // fork: where the WEIGHT-gradient kernel runs (behind dv)
+                     float* dhidden5, int accum_dx, float* dwt, float* db, int B, int K, int NM, hipStream_t s, const SideFork* fork = nullptr,   // fork: where the WEIGHT-gradient kernel runs (behind dv)
+                     float* det_part = nullptr);      // det_part (B x 256 floats): the bias gradient through per-sample rows + det_rows_reduce
 int enc3_state_bwd(const float* e2, const float* e3, const float* de3, int ldd3, const float* action, const float* state, const float* w3,
                    const float* wcs, const float* dsnew, float* de2, float* dw3, float* db3, float* dwcs, float* dbcs,
                    float* dstate_prev, int B, int HW8, int use_state, hipStream_t s,
-                   int mask_e2 = 0);   // 1: de2 is masked by (e2 > 0), i.e. it is the gradient in front of enc2's ReLU
+                   int mask_e2 = 0,    // 1: de2 is masked by (e2 > 0), i.e. it is the gradient in front of enc2's ReLU
+                   float* det_part = nullptr);      // det_part (enc3_state_bwd_det_floats): per-block rows + det_rows_reduce instead of atomics
+long long enc3_state_bwd_det_floats(int B, int HW8, int use_state);
 int enc0_bwd(const float* img, const float* w, const float* d, float* dw, float* db, float* dimg, int dimg_accum, int B, int H, int W,
-             hipStream_t s, const SideFork* fork = nullptr);   // fork: where the weight / bias gradient kernel runs
+             hipStream_t s, const SideFork* fork = nullptr,   // fork: where the weight / bias gradient kernel runs
+             float* det_part = nullptr);      // det_part (enc0_bwd_det_floats): per-block rows + det_rows_reduce instead of atomics
+long long enc0_bwd_det_floats(int B, int H, int W);
 int add_strided(float* dst, int ldd, const float* src, int lds_, int C, long npix, hipStream_t s);
 
 // planar NCHW <-> NHWC helpers for taps (conv_res) and tests

@@ -48,6 +48,9 @@ static int ln_partial_cap(int HW) {
 // (PIVP_WGRAD_BATCH=1), the dG rings then simply double-buffer; the batched path stays for larger per-GPU batches and is tested
 // (tests/test_gpu_train.py).  Timestep 0 is always its own batch (its h_{-1} = 0 half is skipped).
 constexpr size_t ENC_RING_BYTES_MAX = (size_t)2 << 30;   // the five stride-2 3x3 layers' dY rings together (pivp_plan::eg_cap is cut to fit)
+// Deterministic sweeps: the fp32 slot form of the ConvLSTM weight gradients with this many blocks per XCD whatever the device reports (WgradDesc::slot_j;
+// two per CU on a 256-CU MI355X), so that the order of its sums follows the problem shape alone -- not the CU count of a partition mode
+constexpr int DET_SLOT_J = 64;
 constexpr int WG_BATCH_MAX = 8;   // most timesteps one ConvLSTM weight-gradient launch can take (dG ring slots per ring: pivp_plan::wg_cap <= this)
 
 struct Slab {
@@ -76,6 +79,10 @@ struct Grads {   // gradient workspace (single copy, reused by every timestep of
     size_t wg_part[5], wg_part_floats;   // per-block partial weight gradients of enc6, enc5, enc4, enc2, enc1 (WgradDesc::part), one contiguous region
     size_t wtb_lstm[7];             // ... and their bf16 packs (bf16 precision mode)
     size_t dg_absmax;               // fp16-piece data gradients: the partial maxima of the dG in front of the launch (absmax_partials; stream-ordered, one buffer)
+    // deterministic sweeps only (pivp_plan_set_deterministic; 0 otherwise): the ConvLSTM weight gradients' segment slots (wgrad5x5p, one region per cell,
+    // summed once per sweep), and the per-block rows of the output side's small gradients (heads_bwd, the CDNA generator's bias, enc3 + state
+    // predictor, enc0, the STP regressor), summed in order behind each launch; STP's d prev as exact 64-bit integer sums (det_stp_acc)
+    size_t lstm_part[7], det_heads, det_dv, det_enc3, det_enc0, det_stp, det_stp_acc;
 };
 
 }  // namespace
@@ -106,6 +113,8 @@ struct pivp_plan {
                                       // backward sweep and every other op of that mode are the fp32 ones)
     int main_prio = -1;               // pivp_plan_set_main_priority: -1 = on unless a gradient listener is registered (data parallelism), 0 / 1 = as said
     int bf16_all = 0;                 // precision mode BF16: also the ConvLSTM gradients and the enc5 / enc6 transposed convs
+    int det = 0;                      // pivp_plan_set_deterministic: fixed-order forms of every sum of the sweep (no float atomics)
+    bool lstm_started[7] = {};        // deterministic sweeps: the cell's weight-gradient slots hold this sweep's sums (before: stored, not added)
     pivp_grad_group_cb grad_cb = nullptr; void* grad_cb_user = nullptr;   // gradient-group-final notifications (t = 0 sweep)
     int loss_nparts;
     int last_steps;
@@ -245,6 +254,17 @@ static void plan_layout(pivp_plan* p) {
             g.wt_enc[i] = (i == 0 || i == 3) ? 0 : carve((size_t)encw[i]);
         }
         g.dg_absmax = carve((size_t)7 * 2 * p->wg_cap * 72);     // dG's partial maxima per (cell, ring, slot): the fp16-piece gradients' scales
+        for (int i = 0; i < 7; ++i) g.lstm_part[i] = 0;
+        g.det_heads = g.det_dv = g.det_enc3 = g.det_enc0 = g.det_stp = g.det_stp_acc = 0;
+        if (p->det) {      // (pivp_plan_set_deterministic has checked that every cell's shape is served)
+            const int hh[7] = {p->H2, p->H2, p->H4, p->H4, p->H8, p->H4, p->H2}, wv[7] = {p->W2, p->W2, p->W4, p->W4, p->W8, p->W4, p->W2};
+            for (int i = 0; i < 7; ++i) g.lstm_part[i] = carve((size_t)lstm_wgrad_part_floats(kLstm[i].cx, kLstm[i].C, B, hh[i], wv[i], 0, DET_SLOT_J));
+            g.det_heads = carve((size_t)heads_bwd_det_floats(B, (int)HW, p->NP, p->NE));
+            g.det_dv = carve((size_t)B * 256);
+            g.det_enc3 = carve((size_t)enc3_state_bwd_det_floats(B, (int)HW8, cfg->use_state));
+            g.det_enc0 = carve((size_t)enc0_bwd_det_floats(B, H, W));
+            if (cfg->model_type == PIVP_MODEL_STP) { g.det_stp = carve((size_t)B * 706); g.det_stp_acc = carve((size_t)B * 3 * HW * 2); }   // (64-bit integers)
+        }
         g.go = carve((size_t)(T - 1) * B * 3 * HW);
         g.dmk = carve((size_t)B * p->NP * HW); g.dz = carve((size_t)B * p->NE * HW);
         g.dkpart = carve((size_t)B * composite_bwd_tiles(H, W) * 256);
@@ -370,8 +390,10 @@ extern "C" int pivp_plan_set_grad(pivp_plan_t* plan, int idx, float* dptr) {
 // PIVP_PRECISION_BF16 = operands
 // rounded to bf16, fp32 accumulation / gates / state (csrc/convlstm_bf16.hip), and in the backward sweep their data and weight gradients
 // (csrc/convlstm_bf16.hip <NCH, false>, csrc/wgrad_bf16.hip).  Everything else stays fp32, as do the parameters, the gradients and Adam.  Refused when a layer's map does not fit the bf16 kernel's tiles (8-wide maps need an even batch).
+static bool det_supported(const pivp_plan* p, int precision);
 extern "C" int pivp_plan_set_precision(pivp_plan_t* plan, int precision) {
     if (!plan || precision < PIVP_PRECISION_F32 || precision > PIVP_PRECISION_FP16X3) return PIVP_ERR_BADARG;
+    if (plan->det && !det_supported(plan, precision)) return PIVP_ERR_BADARG;      // a deterministic plan keeps to the modes its sweep serves
     if (precision == PIVP_PRECISION_BF16 || precision == PIVP_PRECISION_BF16X3) {   // (BF16X6: a layer its tile does not serve runs the fp32 kernel)
         const int hs[7] = {plan->H2, plan->H2, plan->H4, plan->H4, plan->H8, plan->H4, plan->H2};
         const int wsz[7] = {plan->W2, plan->W2, plan->W4, plan->W4, plan->W8, plan->W4, plan->W2};
@@ -404,6 +426,34 @@ extern "C" int pivp_plan_set_precision(pivp_plan_t* plan, int precision) {
     if (!plan->ws) plan_layout(plan);
     return PIVP_OK;
 }
+// Deterministic training (include/pivp_hip.h): every sum of the forward and the backward sweep in an order fixed by the problem shape.  Served:
+// precision F32, BF16 and BF16X3 (the ConvLSTM weight gradients then take the fp32 slot form, wgrad5x5p), models CDNA, STP and DNA, and shapes whose
+// cells fit wgrad5x5p and whose stride-2 3x3 layers fit wgrad3x3s2 (both with their column sums: no bias_grad launch is needed).
+static bool det_supported(const pivp_plan* p, int precision) {
+    if (precision != PIVP_PRECISION_F32 && precision != PIVP_PRECISION_BF16 && precision != PIVP_PRECISION_BF16X3) return false;
+    const int B = p->cfg.batch;
+    const int hh[7] = {p->H2, p->H2, p->H4, p->H4, p->H8, p->H4, p->H2}, wv[7] = {p->W2, p->W2, p->W4, p->W4, p->W8, p->W4, p->W2};
+    for (int i = 0; i < 7; ++i) if (lstm_wgrad_part_floats(kLstm[i].cx, kLstm[i].C, B, hh[i], wv[i], 0, DET_SLOT_J) <= 0) return false;
+    const int mode[5] = {1, 1, 1, 0, 0}, ci[5] = {64, 96, 128, 64, 32};
+    const int hin[5] = {p->H2, p->H4, p->H8, p->H4, p->H2}, win[5] = {p->W2, p->W4, p->W8, p->W4, p->W2};
+    for (int k = 0; k < 5; ++k) if (!conv_backward_fixed_order(mode[k], ci[k], ci[k], B, hin[k], win[k])) return false;
+    return true;
+}
+extern "C" int pivp_plan_set_deterministic(pivp_plan_t* plan, int on) {
+    if (!plan) return PIVP_ERR_BADARG;
+    const int want = on ? 1 : 0;
+    if (want == plan->det) return PIVP_OK;
+    if (want && !det_supported(plan, plan->precision)) return PIVP_ERR_BADARG;
+    if (plan->ws) {      // a bound workspace keeps its layout: switching on needs the slots it was sized with
+        if (want && plan->has_grads && plan->g.det_heads == 0) return PIVP_ERR_STATE;
+        plan->det = want;
+        return PIVP_OK;
+    }
+    plan->det = want;
+    plan_layout(plan);
+    return PIVP_OK;
+}
+extern "C" int pivp_plan_get_deterministic(const pivp_plan_t* plan) { return plan ? plan->det : PIVP_ERR_BADARG; }
 // Inference with constant weights: keep the bf16 / fp16 weight packs across rollouts (on = 1) instead of rebuilding them at the start of each.  The
 // caller then owes pivp_plan_params_changed after EVERY modification of a parameter tensor (optimizer step, checkpoint load, host write); set_param,
 // set_precision and set_workspace invalidate by themselves.  Default off.
@@ -895,7 +945,7 @@ static int backward_step(pivp_plan* p, int t, const float* prev, bool prev_has_g
                                  wg_flush ? fork_of(i, f) : nullptr, &lf[i],    // dW = null: only the fork's `ready` (behind the gate math) is used
                                  t == 0 ? 1 : 0,
                                  (p->bwd_planes == -2 || p->x3_wgrad) ? ws + g.dg_absmax + ((size_t)(i * 2 + wg_ring) * p->wg_cap + wg_slot) * 72 : nullptr,    // t = 0: nobody reads d h_{-1}
-                                 ep));
+                                 ep, p->det));
         if (t == 0) RC(ln_finish(i + 1));       // the sweep's last timestep: the norm's partial parameter planes (written by the gate kernel) become its gradient
         if (!wg_flush) return PIVP_OK;
         // weight + bias gradient of the whole batch: timestep j of it reads slab (first - j) and ring slot j; on the side stream it
@@ -903,12 +953,28 @@ static int backward_step(pivp_plan* p, int t, const float* prev, bool prev_has_g
         hipStream_t sw = p->side ? p->side_of(i) : s;
         const int cnt = wg_slot + 1;
         int bias_done = 0;
+        if (p->det) {
+            // deterministic sweeps: the fp32 slot form (wgrad5x5p) in every precision mode -- each launch adds into the cell's slots (the sweep's first
+            // stores), the slots are summed in a fixed order once: t = 0 has no h operand and cuts the slots another way, so the batches with h are
+            // reduced in front of it and its own launch behind it
+            // (the slot form takes every shape pivp_plan_set_deterministic admits, and it sums the columns of dG itself: bias_done is always set)
+            float* part = ws + g.lstm_part[i];
+            if (t == 0 && p->lstm_started[i])
+                RC(lstm_wgrad_reduce(L.cx, L.C, 1, part, G(p, p->i_lstm_w[i]), G(p, p->i_lstm_b[i]), B, hh, wwid, sw, 0, DET_SLOT_J));
+            RC(run_wgrad(0, p->wg_x[i], L.cx, ldx, p->wg_h[i], L.C, L.C, cin, ring, N, N, G(p, p->i_lstm_w[i]), B, hh, wwid, hh, wwid, 5, 2, 1, sw,
+                         G(p, p->i_lstm_b[i]), &bias_done, 0, cnt, -slab_bytes, -slab_bytes, (long long)dG1 * 4, part, nullptr, nullptr, 0, 0,
+                         (t == 0 || !p->lstm_started[i]) ? 1 : 0, 0, DET_SLOT_J));
+            if (t == 0)
+                RC(lstm_wgrad_reduce(L.cx, L.C, p->wg_h[i] ? 1 : 0, part, G(p, p->i_lstm_w[i]), G(p, p->i_lstm_b[i]), B, hh, wwid, sw, 0, DET_SLOT_J));
+            else p->lstm_started[i] = true;
+        } else
         RC(run_wgrad(0, p->wg_x[i], L.cx, ldx, p->wg_h[i], L.C, L.C, cin, ring, N, N, G(p, p->i_lstm_w[i]), B, hh, wwid, hh, wwid, 5, 2, 1, sw,
                      G(p, p->i_lstm_b[i]), &bias_done, p->bf16_all ? 1 : (p->x6_wgrad && (wwid % 16 == 0 || B % 2 == 0)) ? 3 : 0, cnt, -slab_bytes, -slab_bytes,
                      (long long)dG1 * 4, nullptr, nullptr,
                      // (fp16 pieces; an 8-wide map with an odd batch does not fit that kernel's two-image tiles: the fp32 kernel takes the batch)
                      (p->x3_wgrad && (wwid % 16 == 0 || B % 2 == 0)) ? ws + g.dg_absmax + (size_t)(i * 2 + wg_ring) * p->wg_cap * 72 : nullptr, 72,
                      (long)B * c.height * c.width > 32L * 64 * 64 ? 2 : 0));      // (frames above 64 x 64 x 32: the eight-wave weight gradient on every layer, WgradDesc::form)
+        if (!bias_done && p->det) return PIVP_ERR_STATE;      // (unreachable: see above)
         if (!bias_done)
             for (int j = 0; j < cnt; ++j) RC(bias_grad(ring + (size_t)j * dG1, N, N, B * hh * wwid, G(p, p->i_lstm_b[i]), sw));
         if (p->side && hipEventRecord(p->ev_ring_done[i][wg_ring], p->side_of(i)) != hipSuccess) return PIVP_ERR_LAUNCH;
@@ -949,6 +1015,7 @@ static int backward_step(pivp_plan* p, int t, const float* prev, bool prev_has_g
         RC(run_wgrad(E.mode, p->enc_x0[k], E.c, E.ldx, nullptr, 0, 0, E.c, dy0, E.ldy, E.c, G(p, p->i_enc_w[E.layer]), B, E.Hin, E.Win, Hout, Wout, 3, 1, 2, sw,
                      G(p, p->i_enc_b[E.layer]), &bias_done, 0, cnt, -slab_bytes, 0, dy_step, ws + g.wg_part[k], &p->enc_desc[k], nullptr, 0, 0,
                      p->enc_started[k] ? 0 : 1));
+        if (!bias_done && p->det) return PIVP_ERR_STATE;      // (unreachable: set_deterministic admits only shapes wgrad3x3s2 serves, column sums included)
         if (!bias_done)
             for (int j = 0; j < cnt; ++j) RC(bias_grad(dy0 + (size_t)j * (dy_step / 4), E.ldy, E.c, B * Hout * Wout, G(p, p->i_enc_b[E.layer]), sw));
         if (p->side && hipEventRecord(p->ev_done[7 + k][eg_ring], sw) != hipSuccess) return PIVP_ERR_LAUNCH;
@@ -962,21 +1029,22 @@ static int backward_step(pivp_plan* p, int t, const float* prev, bool prev_has_g
                                   prev_has_grad ? go_prev : nullptr, 1, B, H, W, c.num_masks, s));
         else if (c.model_type == PIVP_MODEL_STP)
             RC(composite_bwd_stp(prev, ws + S.logits, ws + S.layer0, ws + S.theta, go, ws + g.dmk, ws + g.dz, ws + g.dkpart,
-                                 prev_has_grad ? go_prev : nullptr, B, H, W, c.num_masks, c.stp_zero_border, s));
+                                 prev_has_grad ? go_prev : nullptr, B, H, W, c.num_masks, c.stp_zero_border, s,
+                                 p->det ? reinterpret_cast<unsigned long long*>(ws + g.det_stp_acc) : nullptr));
         else
             RC(composite_bwd_dna(prev, ws + S.logits, ws + S.enc7, go, ws + g.dmk, ws + g.dz, prev_has_grad ? go_prev : nullptr, 1,
                                  B, H, W, s));
         RC(mask_softmax_bwd(ws + S.logits, ws + g.dmk, B, HW, p->NP, s));
         RC(heads_bwd(ws + S.e6, P(p, p->i_masks_w), P(p, p->i_enc7_w), ws + g.dmk, ws + g.dz, ws + g.e6, G(p, p->i_masks_w),
-                     G(p, p->i_masks_b), G(p, p->i_enc7_w), G(p, p->i_enc7_b), B, HW, p->NP, p->NE, s));
+                     G(p, p->i_masks_b), G(p, p->i_enc7_w), G(p, p->i_enc7_b), B, HW, p->NP, p->NE, s, p->det ? ws + g.det_heads : nullptr));
         RC(join(13));      // d v (the kernel generator's weight gradient reads it)
         if (c.model_type == PIVP_MODEL_CDNA)
             RC(cdna_kernels_bwd(ws + S.n5, P(p, p->i_head_w), ws + S.vpre, ws + g.dkpart, composite_bwd_tiles(H, W), ws + g.dv[par], ws + g.n5, 0,
-                                G(p, p->i_head_w), G(p, p->i_head_b), B, p->K5, c.num_masks, s, fork_of(13, fe)));
+                                G(p, p->i_head_w), G(p, p->i_head_b), B, p->K5, c.num_masks, s, fork_of(13, fe), p->det ? ws + g.det_dv : nullptr));
         else if (c.model_type == PIVP_MODEL_STP)
             RC(stp_params_bwd(ws + S.n5, P(p, p->i_head_w), ws + S.vpre, P(p, p->i_head2_w), ws + g.dkpart, composite_bwd_tiles(H, W),
                               ws + g.dv[par], ws + g.n5, G(p, p->i_head_w), G(p, p->i_head_b), G(p, p->i_head2_w), G(p, p->i_head2_b),
-                              B, p->K5, s));
+                              B, p->K5, s, p->det ? ws + g.det_stp : nullptr));
         else if (hipMemsetAsync(ws + g.n5, 0, (size_t)px8 * 128 * 4, s) != hipSuccess) return PIVP_ERR_LAUNCH;   // DNA: no hidden5 head
         // group 6 (TM:601), reversed: norm_enc6 (+relu) <- enc6 deconv <- [hidden7 | enc0]
         RC(join(7));       // d e6raw
@@ -1050,7 +1118,7 @@ static int backward_step(pivp_plan* p, int t, const float* prev, bool prev_has_g
     RC(enc3_state_bwd(ws + S.e2, ws + S.e3, DIN(4, true), 192, action, state_prev, P(p, p->i_enc_w[3]), P(p, p->i_cs_w),
                       ws + g.dstate + (size_t)t * B * 5, d_e2, G(p, p->i_enc_w[3]), G(p, p->i_enc_b[3]), G(p, p->i_cs_w),
                       G(p, p->i_cs_b), t > 0 ? ws + g.dstate + (size_t)(t - 1) * B * 5 : ws + g.dstate + (size_t)(c.seq_len - 1) * B * 5,
-                      B, p->H8 * p->W8, c.use_state, s, 1));      // d e2 comes out masked by enc2's ReLU
+                      B, p->H8 * p->W8, c.use_state, s, 1, p->det ? ws + g.det_enc3 : nullptr));      // d e2 comes out masked by enc2's ReLU
     // group 2 (TM:597): enc2 conv (ReLU) <- hidden4 <- lstm4 <- hidden3 <- lstm3 <- enc1
     enc_add(3, ws + S.n4);
     RC(run_conv_backward(0, ws + S.n4, 64, 64, P(p, p->i_enc_w[2]), d_e2, 64, 64, nullptr, 0, ws + g.wt_enc[2], ws + g.n4, 64, 0,
@@ -1076,7 +1144,7 @@ static int backward_step(pivp_plan* p, int t, const float* prev, bool prev_has_g
     RC(join(12));          // d e0raw
     RC(lnb(0, ep_ok0 ? DIN(0, true) : ws + g.cat7 + 32, 64, ws + S.cat7 + 32, 64, ws + S.e0raw, ws + g.e0raw[par], n2, 32, 1));
     RC(enc0_bwd(prev, P(p, p->i_enc_w[0]), ws + g.e0raw[par], G(p, p->i_enc_w[0]), G(p, p->i_enc_b[0]), prev_has_grad ? go_prev : nullptr, 1,
-                B, H, W, s, fork_of(12, fe)));
+                B, H, W, s, fork_of(12, fe), p->det ? ws + g.det_enc0 : nullptr));
     RC(done(5));
     return PIVP_OK;
 }
@@ -1138,6 +1206,9 @@ static int rollout_backward_sweep(pivp_plan_t* plan, const float* images, const 
     if (hipMemsetAsync(ws + g.ln_ppart[0], 0, g.ln_ppart_floats * 4, s) != hipSuccess) return PIVP_ERR_LAUNCH;
     for (int j = 0; j < 9; ++j) plan->ln_touched[j] = false;
     for (int k = 0; k < 5; ++k) { plan->enc_desc_valid[k] = false; plan->enc_cnt[k] = 0; plan->enc_started[k] = false; }
+    for (int i = 0; i < 7; ++i) plan->lstm_started[i] = false;
+    if (plan->det && g.det_stp_acc &&      // STP's integer d prev accumulator starts at zero (each launch's finish clears what it used)
+        hipMemsetAsync(ws + g.det_stp_acc, 0, (size_t)B * 3 * c.height * c.width * 8, s) != hipSuccess) return PIVP_ERR_LAUNCH;
     // d loss / d gen_states[t] for every t (zero before ctx-1), later accumulated with the state recurrence
     if (hipMemsetAsync(ws + g.dstate, 0, (size_t)T * B * 5 * 4, s) != hipSuccess) return PIVP_ERR_LAUNCH;
     // (gen_states[t] against states[t + 1], t = ctx-1 .. T-2: contiguous in t, one launch; likewise the frames' loss terms below -- 16 launches per sweep before)

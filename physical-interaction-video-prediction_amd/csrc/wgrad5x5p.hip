@@ -6,17 +6,19 @@
 // runs the 5 taps kx of the row against the same dG fragments on v_mfma_f32_32x32x2_f32 (rows = ci, columns = n, k = pixels); the four waves
 // of a block share the tile over interleaved chunks and meet through LDS at the end.  What round 6 changes around that unit:
 //   * staging by LDS-DMA (global_load_lds_dwordx4 per 1 KiB piece, issued from inline asm so that hipcc's vmcnt(0)-before-every-LDS-read does
-//     not drain the pipeline): no staging registers, no ds_write; NTW = 1: four 5-KiB buffers per wave = three chunks in flight behind a counted
-//     vmcnt, NTW = 2 (64 columns per wave, 0.7 x the staged bytes and DMAs per MFMA; 160 accumulator registers fit two waves per SIMD now that the
-//     staging registers are gone): two 7-KiB buffers; out-of-image strip pixels read a 16-byte zero word;
-//   * the grid is G = 2 blocks per CU, always, and the (tile, chunk) work is dealt to them in equal contiguous ranges (a block whose range crosses
+//     not drain the pipeline): no staging registers, no ds_write; NTW = 1: three 5-KiB buffers per wave (60 KiB per block) = two chunks in flight
+//     behind a counted vmcnt, NTW = 2 (64 columns per wave, 0.7 x the staged bytes and DMAs per MFMA; 160 accumulator registers fit two waves per SIMD
+//     now that the staging registers are gone): two 7-KiB buffers (56 KiB); out-of-image strip pixels read a 16-byte zero word;
+//   * the grid is G = 2 blocks per CU (WgradDesc::slot_j = 0), or a fixed number of blocks per XCD (slot_j > 0: the deterministic sweep, whose order
+//     of the sums then does not follow the CU count), and the (tile, chunk) work is dealt to them in equal contiguous ranges (a block whose range crosses
 //     a tile boundary runs two or more SEGMENTS, each with its own block reduction): no partially filled last round (the tile x split grid of
 //     round 2 filled 480 of 512 slots on every layer of the model), and the blocks of one XCD (linear id mod 8) work on one part of the pixels
 //     and one part of the tiles, so that what an XCD streams it streams through its own L2;
 //   * no atomics: a segment's result is added (or, for a sweep's first launch, stored) into the segment's own slot of a partial buffer with plain
 //     loads issued before the K loop; wgrad5x5p_reduce sums the slots of a tile in a fixed order into the packed gradient.  The partition is a
 //     function of one timestep's geometry alone, so every launch of a sweep, the buffer and the reduction agree, and the result is bit-identical
-//     from sweep to sweep.  The bias gradient (column sums of dG) rides along in the slots' tails.
+//     from sweep to sweep.  The bias gradient (column sums of dG) rides along in the slots' tails: the tiles that carry it always write their tails
+//     (zeros for a launch without db), so a reduction with db never reads a tail no launch wrote.
 // Measured (profiles/r06/NOTES.md 1; scripts/bench_lstm_backward.py, B = 32, us per launch, round-2 kernel -> this one): lstm1/2 117 -> 116, lstm3 89 -> 90,
 // lstm4 116 -> 115, lstm5 89 -> 90, lstm6 166 -> 167, lstm7 221 -> 218: 0.746 -> 0.740 of the fp32 MFMA peak over the seven cells -- no faster.  The stamps
 // say why: the clock holds 2.38 GHz in both kernels (not the limiter), prologue + epilogue shrank to 2 us and the grid is full, but the K loop itself runs
@@ -25,7 +27,8 @@
 // 32 x 32 x 5-tap wave tile costs; the 64-column tile (NTW = 2, 0.7 x both) needs 256 VGPRs with 45 spilled to keep two waves per SIMD and two LDS buffers:
 // 4-17 % slower on every cell.  In the backward sweep the slots cost 0.7 ms per train step (27.3 -> 28.0 ms): 42 MB of slot traffic per launch stream through
 // HBM beside the main stream's memory-bound kernels, where the round-2 kernel's atomics hit a gradient that stays in L2.  So the SWEEP keeps the round-2 kernel
-// (pivp_plan.hip), and this one is the bit-reproducible form behind pivp_wgrad5x5_f32_batch (part != NULL).
+// (pivp_plan.hip), and this one is the bit-reproducible form behind pivp_wgrad5x5_f32_batch (part != NULL) and the deterministic sweep
+// (pivp_plan_set_deterministic: every precision mode's ConvLSTM weight gradients, one reduction per cell and sweep).
 #include <type_traits>
 
 #include "pivp_kernels.h"
@@ -48,7 +51,7 @@ constexpr int WP_IT = 32 * 33;             // one 32 x 32 tile image of the bloc
 constexpr int WP_IMG = 5 * WP_IT;
 constexpr int wp_nbuf(int ntw) { return ntw == 1 ? 3 : 2; }                       // LDS buffers per wave
 constexpr int wp_buf(int ntw) { return (2 * ntw + 3) * 256; }                      // floats per buffer: the dG tile's 2 NTW pieces, then the strip's three
-constexpr int wp_lds_floats(int ntw) { return 4 * wp_nbuf(ntw) * wp_buf(ntw); }   // 80 KiB / 56 KiB: two blocks per CU
+constexpr int wp_lds_floats(int ntw) { return 4 * wp_nbuf(ntw) * wp_buf(ntw); }   // 60 KiB / 56 KiB: two blocks per CU
 constexpr int wp_slot(int ntw) { return 5 * ntw * 1024 + 64; }                    // floats per segment slot: [t][kx][n][ci] + the bias tail (32 NTW used)
 static_assert(2 * WP_IMG + 4 * 64 <= wp_lds_floats(1) && 2 * WP_IMG + 4 * 64 <= wp_lds_floats(2), "the block reduction's images live in the staging buffers");
 
@@ -112,15 +115,15 @@ inline bool wp_ok_shape(const WgradDesc& d) {
     return true;
 }
 inline int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
-// d.form: 0 = by shape, 1 / 2 = 32 / 64 columns per wave (64 needs N % 64 == 0)
+// d.slot_ntw: 0 = by shape, 1 / 2 = 32 / 64 columns per wave (64 needs N % 64 == 0)
 inline int wp_ntw(const WgradDesc& d) {
     if (d.N % 64) return 1;
-    if (d.form == 1 || d.form == 2) return d.form;
+    if (d.slot_ntw == 1 || d.slot_ntw == 2) return d.slot_ntw;
     return 1;
 }
 inline WpGeom wp_geom(const WgradDesc& d) {
     WpGeom g;
-    g.J = (2 * pivp_cu_count()) / 8;
+    g.J = d.slot_j > 0 ? d.slot_j : (2 * pivp_cu_count()) / 8;
     if (g.J < 1) g.J = 1;
     g.NTW = wp_ntw(d);
     g.T = 5 * (d.cin / 32) * (d.N / (32 * g.NTW));
@@ -309,7 +312,6 @@ __global__ __launch_bounds__(256, 2) void wgrad5x5p_kernel(const WgradDesc d, co
             __builtin_amdgcn_sched_barrier(0);
             mfmas(0);
             if constexpr (STEADY) wp_wait_vm<(DEPTH - 1) * NPIECE>();      // the chunks behind it + 1 may still be in flight
-            else if (DEPTH >= 3 && it + 3 == n_my) wp_wait_vm<NPIECE>();      // (three buffers ahead: it + 2 is the last chunk)
             else wp_wait_vm<0>();
             __builtin_amdgcn_sched_barrier(0);
             if (more) read_step(std::integral_constant<int, 0>{}, 0, (it + 1) % NBUF);
@@ -323,8 +325,7 @@ __global__ __launch_bounds__(256, 2) void wgrad5x5p_kernel(const WgradDesc d, co
             // prologue: up to DEPTH chunks in flight, the first one landed, its first operands read
             const int npro = n_my < DEPTH ? n_my : DEPTH;
             for (int c = 0; c < npro; ++c) { prep(); pieces_all(c); }
-            if (npro == 3) wp_wait_vm<2 * NPIECE>();
-            else if (npro == 2) wp_wait_vm<NPIECE>();
+            if (npro == 2) wp_wait_vm<NPIECE>();      // (npro <= DEPTH <= 2)
             else wp_wait_vm<0>();
             if (n_my > DEPTH) prep();                   // chunk DEPTH: issued during chunk 0
             read_step(std::integral_constant<int, 0>{}, 0, 0);
@@ -389,9 +390,9 @@ __global__ __launch_bounds__(256, 2) void wgrad5x5p_kernel(const WgradDesc d, co
             }
             if (t + 1 < NTW) __syncthreads();          // the next 32 columns' images overwrite these
         }
-        if (bias_tile && tid < YP) {
+        if (ky == 2 && cb == 0 && tid < YP) {      // the tail of every bias-carrying tile is written, with or without db
             float* const q = slot + 5 * NTW * 1024 + tid;
-            const float v = (bred[tid] + bred[YP + tid]) + (bred[2 * YP + tid] + bred[3 * YP + tid]);
+            const float v = bias_tile ? (bred[tid] + bred[YP + tid]) + (bred[2 * YP + tid] + bred[3 * YP + tid]) : 0.f;
             *q = d.part_overwrite ? v : *q + v;
         }
         __syncthreads();                               // the next segment's DMAs overwrite the images

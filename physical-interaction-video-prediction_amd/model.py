@@ -133,11 +133,22 @@ class _Plan(object):
 
 
 class Model(object):
-    """MI355X drop-in for the reference's `Model` (TM:478-764)."""
+    """MI355X drop-in for the reference's `Model` (TM:478-764).
+
+    deterministic=True: a training step (forward, `backward()`, `Adam.update`) gives the same bits every time for the same inputs, parameters,
+    optimizer state, plan shape, precision, PIVP_WGRAD_BATCH and GPU model -- whatever the side-stream schedule, the process or the workspace
+    address (include/pivp_hip.h, pivp_plan_set_deterministic).  Served with precision 'fp32', 'bf16' and 'bf16x3', for CDNA, STP and DNA;
+    other combinations raise ValueError.  Under the switch the ConvLSTM weight gradients are computed in fp32 in every precision mode, so
+    deterministic 'bf16' differs from default 'bf16' there (it is the more precise of the two) and its step is slower (README).  A data-parallel
+    run is deterministic only if its collective is: `algo='rs_ag'` sums the shards in rank order, the RCCL ring is not guaranteed to
+    (DESIGN.md 6)."""
+
+    DETERMINISTIC_PRECISIONS = ('fp32', 'bf16', 'bf16x3')
 
     def __init__(self, num_masks, is_cdna=True, is_dna=False, is_stp=False, use_state=True,
                  scheduled_sampling_k=-1, num_frame_before_prediction=2, prefix=None,
-                 device='cuda:0', ln_eps=1e-6, stp_border='clamp', keep_activations=False, precision='fp32', main_priority=None):
+                 device='cuda:0', ln_eps=1e-6, stp_border='clamp', keep_activations=False, precision='fp32', main_priority=None,
+                 deterministic=False):
         if is_cdna:                      # TM:531-542, precedence cdna > stp > dna
             self.model_type = 'CDNA'
         elif is_stp:
@@ -173,6 +184,12 @@ class Model(object):
         if precision not in ('fp32', 'bf16', 'bf16x3', 'bf16x6', 'fp16x3'):
             raise ValueError("precision must be 'fp32', 'bf16', 'bf16x3', 'bf16x6' or 'fp16x3'")
         self.precision = precision
+        if not isinstance(deterministic, bool):
+            raise ValueError('deterministic must be a bool, not %r' % (deterministic,))
+        if deterministic and precision not in self.DETERMINISTIC_PRECISIONS:
+            raise ValueError("deterministic=True is not served with precision=%r (only %s)"
+                             % (precision, ', '.join(map(repr, self.DETERMINISTIC_PRECISIONS))))
+        self.deterministic = deterministic
         self.main_priority = main_priority     # None / False / True: include/pivp_hip.h, pivp_plan_set_main_priority
         self._ref_pending = None       # reference-layout arrays loaded before the first call
         self._params = None            # name -> view into _flat_params (internal layout)
@@ -330,6 +347,10 @@ class Model(object):
             if self.precision != 'fp32':
                 _lib.check(lib.pivp_plan_set_precision(plan.h, {'bf16': 1, 'bf16x3': 2, 'bf16x6': 3, 'fp16x3': 4}[self.precision]),
                            'pivp_plan_set_precision(%s)' % self.precision)
+            if self.deterministic:      # before the workspace is sized: the fixed-order forms add slots to it
+                if lib.pivp_plan_set_deterministic(plan.h, 1) != 0:
+                    raise ValueError('deterministic=True is not served for precision=%r, model %s at B=%d, %dx%d'
+                                     % (self.precision, self.model_type, B, H, W))
             nbytes = lib.pivp_plan_workspace_bytes(plan.h)
             plan.workspace = torch.empty(nbytes // 4 + 64, dtype=torch.float32, device=self.device)
             base = plan.workspace.data_ptr()

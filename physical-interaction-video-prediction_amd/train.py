@@ -49,6 +49,9 @@ def build_parser():
     p.add_argument('--validation_interval', type=int, default=200)
     p.add_argument('--save_interval', type=int, default=50)
     p.add_argument('--debug', type=int, default=0)
+    # 1: bit-reproducible training (Model(deterministic=True)) and host RNGs seeded with 0 -- shuffle, scheduled sampling, initial weights --
+    # so that two runs over the same data write identical training-N / state-N arrays
+    p.add_argument('--deterministic', type=int, default=0, choices=(0, 1))
     return p
 
 
@@ -80,14 +83,15 @@ def main(argv=None):
     logger.info('Data set contain %d, %d will be use for training and %d will be use for validation', len(images), len(tr_i), len(va_i))
     model = Model(num_masks=args.num_masks, is_cdna=args.model_type == 'CDNA', is_dna=args.model_type == 'DNA',
                   is_stp=args.model_type == 'STP', use_state=args.use_state, scheduled_sampling_k=args.schedsamp_k,
-                  num_frame_before_prediction=args.context_frames, prefix='train', device=device, keep_activations=True)
+                  num_frame_before_prediction=args.context_frames, prefix='train', device=device, keep_activations=True,
+                  deterministic=bool(args.deterministic))
     optimizer = Adam(alpha=args.learning_rate).setup(model, data_parallel=dp)
     if args.pretrained_model:
         load_npz(args.pretrained_model, model)
     per_rank = args.batch_size // world
     if per_rank * world != args.batch_size:
         raise SystemExit('--batch_size must be divisible by the number of ranks')
-    np.random.seed(0 if world > 1 else None)      # identical shuffles on every rank; each takes its shard of the batch
+    np.random.seed(0 if world > 1 or args.deterministic else None)      # identical shuffles on every rank; each takes its shard of the batch
     if world > 1:                                 # ... but its own scheduled-sampling draws (rank-offset stream)
         model.sampling_rng = np.random.RandomState(1 + rank)
     train_iter = ds.SerialIterator(ds.group_examples(tr_i, tr_a, tr_s), args.batch_size, repeat=True, shuffle=True)
