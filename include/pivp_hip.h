@@ -147,6 +147,21 @@ int pivp_rollout_forward(pivp_plan_t* plan, const float* images, const float* ac
                          const unsigned char* gt_select, float* gen_images, float* gen_states, float* results,
                          void* stream);
 
+/* Open-loop rollout for planning (Finn & Levine 2017, visual MPC): the same timesteps as pivp_rollout_forward with gt_select = NULL -- feed-self
+ * after the context, frames bit-identical to it on the same context -- but no ground truth beyond the context frames and no loss.
+ *   context_images [ctx][B][3][H][W]; actions [T-1][B][5]; state0 [B][5]   (ctx = context_frames, T = seq_len of the plan)
+ *   track_in [B][P][H*W] or NULL (then track_planes must be 0 and track_out is ignored): non-negative planes given on frame track_frame = f,
+ *             0 <= f <= ctx-1, 1 <= P <= 8.  Step t >= f advects them with pivp_pixel_track behind the step's head, whose softmaxed masks are
+ *             then written at EVERY step t >= f; with P = 0 they are kept for the last step only, as in pivp_rollout_forward.
+ *   gen_images [T-1][B][3][H][W]; gen_states [T-1][B][5]; track_out [T-1-f][B][P][H*W]: the RAW planes on predicted frames f+1 .. T-1
+ *             (the map is linear, so normalising is the caller's choice).  Caller-owned memory: the workspace is the one of pivp_rollout_forward.
+ * Every precision mode is served (the tracking kernel is fp32 in all of them).  Bad P / f / null pointers: PIVP_ERR_BADARG, nothing launched.
+ * pivp_rollout_backward after this call returns PIVP_ERR_STATE; pivp_get_tap keeps working.  Added in ABI 17 without a version change, like
+ * pivp_plan_set_deterministic: backward compatible, nothing else moved. */
+int pivp_rollout_predict(pivp_plan_t* plan, const float* context_images, const float* actions, const float* state0,
+                         const float* track_in, int track_planes, int track_frame,
+                         float* gen_images, float* gen_states, float* track_out, void* stream);
+
 /* Wave priority of the caller-stream kernels of pivp_rollout_backward (s_setprio 3 against the side stream's weight-gradient waves: the single-GPU train
  * step gains 1.5 %).  mode -1 (default): on unless a gradient listener is registered (pivp_plan_set_grad_callback: a data-parallel rank, whose collective's
  * waves must not be starved); 0 / 1: off / on.  The switch is one word per device and process, rewritten on the call's stream when the wanted value
@@ -450,6 +465,14 @@ int pivp_stp_params(const float* hidden5, const float* wt1, const float* b1, con
 int pivp_composite(const float* prev, const float* mask_logits, const float* layer0, const float* aux, float* out,
                    float* masks_out, int B, int H, int W, int num_masks, int model_type, int stp_zero_border,
                    void* stream);
+
+/* One step of designated-pixel tracking: the linear map "previous frame -> next frame" of the step's compositing (TM:720-728) applied to P planes
+ * [B][P][H*W] instead of the RGB frame, with the synthesised layer sigmoid(enc7) := 0 (pixels painted from scratch carry no mass; DNA has no such
+ * layer).  masks: the SOFTMAXED masks [B][num_masks+1][H*W] (masks_out of pivp_composite / pivp_frame_head); aux as pivp_composite (DNA: the enc7
+ * planes).  Equal to pivp_composite(prev = planes, layer0 = 0) per plane up to rounding.  1 <= P <= 8, planes_out != planes_in, geometry limits of
+ * pivp_composite; anything else PIVP_ERR_BADARG.  fp32, fixed summation order, no atomics. */
+int pivp_pixel_track(const float* planes_in, const float* masks, const float* aux, float* planes_out,
+                     int B, int P, int H, int W, int num_masks, int model_type, int stp_zero_border, void* stream);
 
 /* The output side of one timestep in ONE launch: relu(norm_enc6(raw enc6)) (TM:601) -> mask logits + enc7 (TM:718-719, TM:315-317 /
  * 454-455 / 387-388) -> the motion head's finisher on the K-slice partial sums of its Linear (TM:321-329 CDNA kernels / TM:458-468 STP

@@ -44,6 +44,7 @@ SIGNATURES = {
     'pivp_plan_set_workspace': (_i, [_vp, _vp, _ll]),
     'pivp_reset_state': (_i, [_vp, _vp]),
     'pivp_rollout_forward': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'pivp_rollout_predict': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     'pivp_plan_set_grad': (_i, [_vp, _i, _vp]),
     'pivp_rollout_backward': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'pivp_plan_set_profiling': (_i, [_vp, _i]),
@@ -122,6 +123,7 @@ SIGNATURES = {
     'pivp_motion_partials': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     'pivp_frame_head': (_i, [_c.POINTER(PivpFrameHeadArgs), _vp]),
     'pivp_composite': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    'pivp_pixel_track': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     'pivp_resize_images': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _vp]),
     'pivp_select_frames': (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),
     'pivp_wgrad5x5_f32_part_floats': (_ll, [_i, _i, _i, _i, _i, _i]),

@@ -927,6 +927,10 @@ extern "C" int pivp_composite(const float* prev, const float* mask_logits, const
     return composite(prev, mask_logits, layer0, aux, out, masks_out, B, H, W, num_masks, model_type, stp_zero_border,
                      (hipStream_t)stream);
 }
+extern "C" int pivp_pixel_track(const float* planes_in, const float* masks, const float* aux, float* planes_out,
+                                int B, int P, int H, int W, int num_masks, int model_type, int stp_zero_border, void* stream) {
+    return pixel_track(planes_in, masks, aux, planes_out, B, P, H, W, num_masks, model_type, stp_zero_border, (hipStream_t)stream);
+}
 extern "C" int pivp_resize_images(const float* in, float* out, int planes, int Hin, int Win, int Hout, int Wout, float scale, void* stream) {
     return resize_bilinear(in, out, planes, Hin, Win, Hout, Wout, scale, (hipStream_t)stream);
 }

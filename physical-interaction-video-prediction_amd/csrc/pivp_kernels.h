@@ -205,6 +205,11 @@ int composite(const float* prev, const float* mask_logits, const float* layer0, 
               float* out, float* masks_out, int B, int H, int W, int num_masks, int mode, int stp_zero_border,
               hipStream_t s);
 
+// One step of designated-pixel tracking (csrc/pixel_track.hip): the step's compositing map applied to P planes, synthesised layer := 0.
+// masks: SOFTMAXED [B][NM+1][HW]; aux as composite's.  1 <= P <= 8; geometry limits of composite.
+int pixel_track(const float* planes_in, const float* masks, const float* aux, float* planes_out, int B, int P, int H, int W,
+                int num_masks, int mode, int stp_zero_border, hipStream_t s);
+
 // One launch for the output side of a timestep (csrc/frame_head.hip): norm_enc6 + ReLU + the 1x1 heads + the motion head's finisher +
 // flat softmax + transform + compositing; bit-identical to heads_1x1 + cdna_kernels / stp_params + composite.
 struct FrameHeadArgs {

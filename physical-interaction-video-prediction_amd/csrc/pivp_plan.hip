@@ -119,6 +119,8 @@ struct pivp_plan {
     int loss_nparts;
     int last_steps;
     bool last_sched;                  // last forward used scheduled sampling (frames detached, TM:669-670)
+    bool last_predict = false;        // last rollout was pivp_rollout_predict: nothing to back-propagate
+    bool masks_every_step = false;    // pivp_rollout_predict with tracked planes: the head writes its softmaxed masks at every step
     bool prof_on = false;
     std::vector<hipEvent_t> prof_ev;
     std::vector<int> prof_layer;
@@ -714,7 +716,7 @@ static int run_step(pivp_plan* p, int t, const float* prev, const float* action,
         a.e6raw = ws + S.e6raw; a.ln_part = lnp; a.ln_nparts = np; a.gamma = P(p, p->i_ln_g[8]); a.beta = P(p, p->i_ln_b[8]); a.eps = eps;
         a.wm = P(p, p->i_masks_w); a.bm = P(p, p->i_masks_b); a.we = P(p, p->i_enc7_w); a.be = P(p, p->i_enc7_b);
         a.prev = prev; a.out = gen_out; a.enc7 = ws + S.enc7;
-        a.masks_out = t == c.seq_len - 2 ? ws + p->o_masks : nullptr;
+        a.masks_out = (t == c.seq_len - 2 || p->masks_every_step) ? ws + p->o_masks : nullptr;
         a.stat_out = ws + S.lnstat + (size_t)8 * B * 2;
         if (train) { a.logits_out = ws + S.logits; a.layer0_out = ws + S.layer0; a.y_out = ws + S.e6; }
         a.B = B; a.H = H; a.W = W; a.NM = c.num_masks; a.stp_zero = c.stp_zero_border;
@@ -759,16 +761,8 @@ static const float* step_input(pivp_plan* plan, int t, const float* images, cons
     return plan->ws + plan->slabs[t % plan->nslabs].prevsel;
 }
 
-extern "C" int pivp_rollout_forward(pivp_plan_t* plan, const float* images, const float* actions, const float* states,
-                                    const unsigned char* gt_select, float* gen_images, float* gen_states, float* results,
-                                    void* stream) {
-    if (!plan || !images || !actions || !states || !gen_images || !gen_states || !results) return PIVP_ERR_BADARG;
-    if (!plan->ws) return PIVP_ERR_STATE;
-    for (const ParamInfo& pi : plan->params) if (!pi.ptr) return PIVP_ERR_STATE;
-    hipStream_t s = (hipStream_t)stream;
-    const pivp_config_t& c = plan->cfg;
-    const int B = c.batch, T = c.seq_len, ctx = c.context_frames;
-    const size_t fr = (size_t)B * 3 * c.height * c.width;
+// in front of a rollout's first timestep (pivp_rollout_forward and pivp_rollout_predict)
+static int rollout_prepare_packs(pivp_plan* plan, hipStream_t s) {
     // The precision modes' weight packs: rebuilt at the start of every rollout (the parameters may have changed since the last call: optimizer step,
     // checkpoint load) unless the caller keeps them -- pivp_plan_set_pack_cache(plan, 1) -- and reports every change with pivp_plan_params_changed.
     const bool repack = !(plan->pack_cache && plan->packs_valid);
@@ -787,6 +781,20 @@ extern "C" int pivp_rollout_forward(pivp_plan_t* plan, const float* images, cons
                               kLstm[i].cx + kLstm[i].C, 4 * kLstm[i].C, s, 0, plan->lstm_planes,
                               0));
     plan->packs_valid = 1;
+    return PIVP_OK;
+}
+
+extern "C" int pivp_rollout_forward(pivp_plan_t* plan, const float* images, const float* actions, const float* states,
+                                    const unsigned char* gt_select, float* gen_images, float* gen_states, float* results,
+                                    void* stream) {
+    if (!plan || !images || !actions || !states || !gen_images || !gen_states || !results) return PIVP_ERR_BADARG;
+    if (!plan->ws) return PIVP_ERR_STATE;
+    for (const ParamInfo& pi : plan->params) if (!pi.ptr) return PIVP_ERR_STATE;
+    hipStream_t s = (hipStream_t)stream;
+    const pivp_config_t& c = plan->cfg;
+    const int B = c.batch, T = c.seq_len, ctx = c.context_frames;
+    const size_t fr = (size_t)B * 3 * c.height * c.width;
+    RC(rollout_prepare_packs(plan, s));
     for (int t = 0; t < T - 1; ++t) {
         if (t >= ctx && gt_select)                                     // TM:667-670
             RC(run_select_frames(images + t * fr, gen_images + (t - 1) * fr, gt_select + (size_t)t * B,
@@ -797,6 +805,7 @@ extern "C" int pivp_rollout_forward(pivp_plan_t* plan, const float* images, cons
     }
     plan->last_steps = T - 1;
     plan->last_sched = gt_select != nullptr;
+    plan->last_predict = false;
     // loss (TM:737-759): frames ctx..T-1 vs gen[ctx-1..T-2]
     const int nf = T - ctx;
     float* lp = plan->ws + plan->o_losspart;
@@ -812,6 +821,44 @@ extern "C" int pivp_rollout_forward(pivp_plan_t* plan, const float* images, cons
     }
     RC(loss_finalize(lp, plan->loss_nparts, nf, (int)fr, states + (size_t)ctx * B * 5, gen_states + (size_t)(ctx - 1) * B * 5,
                      B * 5, (float)(T - ctx), results, s));
+    return PIVP_OK;
+}
+
+// Open-loop rollout (include/pivp_hip.h): the timesteps of pivp_rollout_forward in feed-self mode, no loss; optionally P tracked planes advected
+// behind every step's head into caller-owned memory.
+extern "C" int pivp_rollout_predict(pivp_plan_t* plan, const float* context_images, const float* actions, const float* state0,
+                                    const float* track_in, int track_planes, int track_frame,
+                                    float* gen_images, float* gen_states, float* track_out, void* stream) {
+    if (!plan || !context_images || !actions || !state0 || !gen_images || !gen_states) return PIVP_ERR_BADARG;
+    const pivp_config_t& c = plan->cfg;
+    const int B = c.batch, T = c.seq_len, ctx = c.context_frames, P = track_planes, f = track_frame;
+    if (ctx < 1 || T - 1 < ctx) return PIVP_ERR_BADARG;
+    if (track_in ? (P < 1 || P > 8 || !track_out || f < 0 || f > ctx - 1) : P != 0) return PIVP_ERR_BADARG;
+    if (!plan->ws) return PIVP_ERR_STATE;
+    for (const ParamInfo& pi : plan->params) if (!pi.ptr) return PIVP_ERR_STATE;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t fr = (size_t)B * 3 * c.height * c.width;
+    const size_t pl = (size_t)B * P * c.height * c.width;
+    RC(rollout_prepare_packs(plan, s));
+    plan->last_steps = 0;                    // an error below leaves nothing to tap or back-propagate
+    plan->last_predict = true;
+    int rc = PIVP_OK;
+    for (int t = 0; t < T - 1 && rc == PIVP_OK; ++t) {
+        plan->masks_every_step = P > 0 && t >= f;
+        const float* prev = t < ctx ? context_images + t * fr : gen_images + (t - 1) * fr;      // TM:663-666
+        const float* st_prev = t == 0 ? state0 : gen_states + (size_t)(t - 1) * B * 5;
+        rc = run_step(plan, t, prev, actions + (size_t)t * B * 5, st_prev, gen_images + t * fr, gen_states + (size_t)t * B * 5, s);
+        if (rc == PIVP_OK && P > 0 && t >= f) {
+            const Slab& S = plan->slabs[t % plan->nslabs];
+            const float* aux = plan->ws + (c.model_type == PIVP_MODEL_CDNA ? S.kerns : c.model_type == PIVP_MODEL_STP ? S.theta : S.enc7);
+            rc = pixel_track(t == f ? track_in : track_out + (size_t)(t - f - 1) * pl, plan->ws + plan->o_masks, aux,
+                             track_out + (size_t)(t - f) * pl, B, P, c.height, c.width, c.num_masks, c.model_type, c.stp_zero_border, s);
+        }
+    }
+    plan->masks_every_step = false;
+    if (rc != PIVP_OK) return rc;
+    plan->last_steps = T - 1;
+    plan->last_sched = false;
     return PIVP_OK;
 }
 
@@ -1179,6 +1226,7 @@ static int rollout_backward_sweep(pivp_plan_t* plan, const float* images, const 
                                   const unsigned char* gt_select, const float* gen_images, const float* gen_states, void* stream) {
     if (!plan || !images || !actions || !states || !gen_images || !gen_states) return PIVP_ERR_BADARG;
     if (!plan->ws || !plan->has_grads || plan->last_steps != plan->cfg.seq_len - 1) return PIVP_ERR_STATE;
+    if (plan->last_predict) return PIVP_ERR_STATE;      // pivp_rollout_predict keeps no loss to differentiate
     if ((gt_select != nullptr) != plan->last_sched) return PIVP_ERR_STATE;
     for (const ParamInfo& pi : plan->params) if (!pi.ptr || !pi.grad) return PIVP_ERR_STATE;
     hipStream_t s = (hipStream_t)stream;

@@ -207,6 +207,9 @@ class Model(object):
         self.loss = 0.0
         self.psnr_all = 0.0
         self.gen_images = []
+        self._imagined = False         # the last rollout was imagine(): taps exist, a loss does not
+        self.pixel_distrib = None      # imagine(designated=...): (T-1-f, B, P, H, W) tracked planes on the predicted frames
+        self.pixel_mass = None         # ... and their raw sums (T-1-f, B, P)
 
     # ---- parameters ---------------------------------------------------------------------
     def _shapes(self):
@@ -329,8 +332,9 @@ class Model(object):
             if self._grads is not None:
                 _lib.check(lib.pivp_plan_set_grad(plan.h, i, self._grads[name].data_ptr()), 'pivp_plan_set_grad(%s)' % name)
 
-    def _plan_for(self, B, T, H, W):
-        key = (B, T, H, W, self.keep_activations)
+    def _plan_for(self, B, T, H, W, keep_activations=None):
+        keep = self.keep_activations if keep_activations is None else bool(keep_activations)
+        key = (B, T, H, W, keep)
         plan = self._plans.get(key)
         if plan is None:
             lib = self._require_gpu()
@@ -338,7 +342,7 @@ class Model(object):
                                   model_type={'CDNA': 0, 'STP': 1, 'DNA': 2}[self.model_type],
                                   use_state=1 if self.use_state else 0,
                                   context_frames=self.num_frame_before_prediction,
-                                  keep_activations=1 if self.keep_activations else 0,
+                                  keep_activations=1 if keep else 0,
                                   ln_eps=self.ln_eps, stp_zero_border=1 if self.stp_border == 'zeros' else 0)
             plan = _Plan(lib, cfg)
             _lib.check(lib.pivp_plan_set_pack_cache(plan.h, 1), 'pivp_plan_set_pack_cache')
@@ -374,6 +378,7 @@ class Model(object):
         self.loss = 0.0
         self.psnr_all = 0.0
         self._results = None
+        self._imagined = False
         if self._active is not None:
             self._reset_plan(self._active)
 
@@ -437,12 +442,112 @@ class Model(object):
             self._gen = gen
             self._gen_states = gen_states
             self._results = results
+            self._imagined = False
             self._nf = nf
             self.gen_images = [gen[t] for t in range(T - 1)]
             self.gen_states = [gen_states[t] for t in range(T - 1)]
             self.loss = results[0]
             self.psnr_all = results[1]
         return self.loss
+
+    # ---- planning surface (no counterpart in the reference: Finn & Levine 2017 roll this model forward under candidate actions) -------
+    MAX_TRACK_PLANES = 8
+
+    @staticmethod
+    def _host_shape(a):
+        """Shape of an argument as `_as_device` would see it, without touching a device."""
+        if torch.is_tensor(a):
+            return tuple(a.shape)
+        if isinstance(a, (list, tuple)) and len(a) and torch.is_tensor(a[0]):
+            return (len(a),) + tuple(a[0].shape)
+        return tuple(np.shape(a))
+
+    def _check_imagine_args(self, context_images, actions, state, designated, designated_frame):
+        """-> (ctx, T, B, H, W, P, f); every complaint is a ValueError raised before the GPU or the library is needed."""
+        ctx = int(self.num_frame_before_prediction)
+        si, sa, ss = self._host_shape(context_images), self._host_shape(actions), self._host_shape(state)
+        if len(si) != 5 or si[2] != 3:
+            raise ValueError('context_images must be time-major (ctx, B, 3, H, W), got shape %s' % (si,))
+        if ctx < 1 or si[0] != ctx:
+            raise ValueError('context_images holds %d frames, the model was built with num_frame_before_prediction=%d' % (si[0], ctx))
+        _, B, _, H, W = si
+        if B < 1 or H < 1 or W < 1:
+            raise ValueError('context_images is empty: shape %s' % (si,))
+        if len(sa) != 3 or sa[1] != B or sa[2] != 5:
+            raise ValueError('actions must be (T-1, %d, 5), got shape %s' % (B, sa))
+        if sa[0] < ctx:
+            raise ValueError('actions cover %d steps; at least the %d context steps are needed (T - 1 >= ctx)' % (sa[0], ctx))
+        if ss != (B, 5):
+            raise ValueError('state must be (%d, 5): the robot state of frame 0, got shape %s' % (B, ss))
+        T = sa[0] + 1
+        P, f = 0, ctx - 1
+        if designated is None:
+            if designated_frame is not None:
+                raise ValueError('designated_frame given without designated planes')
+        else:
+            sd = self._host_shape(designated)
+            if len(sd) != 4 or sd[0] != B or sd[2:] != (H, W):
+                raise ValueError('designated must be (%d, P, %d, %d), got shape %s' % (B, H, W, sd))
+            P = sd[1]
+            if not 1 <= P <= self.MAX_TRACK_PLANES:
+                raise ValueError('designated holds %d planes per sample; 1 to %d are served' % (P, self.MAX_TRACK_PLANES))
+            if designated_frame is not None:
+                if isinstance(designated_frame, bool) or int(designated_frame) != designated_frame:
+                    raise ValueError('designated_frame must be an integer frame index, not %r' % (designated_frame,))
+                f = int(designated_frame)
+            if not 0 <= f <= ctx - 1:
+                raise ValueError('designated_frame %d is not an observed frame (0 .. %d)' % (f, ctx - 1))
+        return ctx, T, B, H, W, P, f
+
+    def imagine(self, context_images, actions, state, designated=None, designated_frame=None, normalize=False):
+        """Open-loop prediction for planning: roll the model forward from `context_images` (ctx, B, 3, H, W) -- the observed frames --, the robot
+        `state` (B, 5) of frame 0 and candidate `actions` (T-1, B, 5), feeding its own predictions back after the context.  No ground truth beyond
+        the context, no loss: `loss` / `psnr_all` are left alone, `summaries` is [] and `backward()` raises until the model is called again.  Always
+        feed-self (ignores config.train and scheduled sampling) and always on an inference plan.  Sets `gen_images` / `gen_states` as `__call__`
+        does and returns the frames as one tensor (T-1, B, 3, H, W): bit-identical to a feed-self `__call__` on the same context.
+
+        designated: (B, P, H, W) non-negative planes (1 <= P <= 8; `planning.one_hot_planes`) given on frame `designated_frame` (0 .. ctx-1, default
+        the last observed one).  Every step from that frame on moves them exactly as it moves the frame's pixels -- the step's transforms and
+        compositing masks are a linear map, applied here to the planes with the synthesised layer set to zero (painted-from-scratch pixels carry
+        no mass) -- giving the predicted distribution of the designated pixels: `pixel_distrib` (T-1-f, B, P, H, W), entry i on predicted frame
+        f+1+i, and `pixel_mass` (T-1-f, B, P), always the raw plane sums.  normalize=True divides each plane by its sum; the raw mass is
+        informative (how much of the pixel the model explains by motion), so this is optional."""
+        ctx, T, B, H, W, P, f = self._check_imagine_args(context_images, actions, state, designated, designated_frame)
+        with torch.cuda.device(self.device) if torch.cuda.is_available() else contextlib.nullcontext():
+            self._require_gpu()
+            images = self._as_device(context_images, ())
+            actions = self._as_device(actions, (5,))
+            state = self._as_device(state, (5,))
+            planes = self._as_device(designated, ()) if P else None
+            self._ensure_params(H, W)
+            plan = self._plan_for(B, T, H, W, keep_activations=False)
+            self._active = plan
+            gen = torch.empty((T - 1, B, 3, H, W), dtype=torch.float32, device=self.device)
+            gen_states = torch.empty((T - 1, B, 5), dtype=torch.float32, device=self.device)
+            track = torch.empty((T - 1 - f, B, P, H, W), dtype=torch.float32, device=self.device) if P else None
+            pkey = (self._flat_params.data_ptr(), self._flat_params._version, getattr(self, '_params_epoch', 0))
+            if getattr(plan, 'packed_key', None) != pkey:
+                _lib.check(plan.lib.pivp_plan_params_changed(plan.h), 'pivp_plan_params_changed')
+                plan.packed_key = pkey
+            _lib.check(plan.lib.pivp_rollout_predict(plan.h, images.data_ptr(), actions.data_ptr(), state.data_ptr(),
+                                                     planes.data_ptr() if P else None, P, f, gen.data_ptr(), gen_states.data_ptr(),
+                                                     track.data_ptr() if P else None, self._stream()), 'pivp_rollout_predict')
+            self._inputs = (images, actions, state, planes)   # keep alive until the stream has consumed them
+            self._gt_mask = None
+            self._gen = gen
+            self._gen_states = gen_states
+            self._results = None
+            self._imagined = True
+            self.gen_images = [gen[t] for t in range(T - 1)]
+            self.gen_states = [gen_states[t] for t in range(T - 1)]
+            if P:
+                mass = track.sum(dim=(3, 4))
+                self.pixel_mass = mass
+                self.pixel_distrib = track / mass[..., None, None] if normalize else track
+            else:
+                self.pixel_mass = None
+                self.pixel_distrib = None
+        return gen
 
     # ---- training surface (Chainer: model.cleargrads(); loss.backward(); TM:950 via optimizer.update) -------
     def cleargrads(self):
@@ -539,7 +644,7 @@ class Model(object):
     def tap(self, name, step=None):
         """Activation of a timestep, planar NCHW like the reference's encs/hiddens (TM:703-708)."""
         plan = self._active
-        if plan is None or self._results is None:
+        if plan is None or (self._results is None and not self._imagined):
             raise RuntimeError('call the model first')
         cfg = plan.cfg
         T1 = cfg.seq_len - 1
@@ -575,6 +680,6 @@ class Model(object):
     @property
     def conv_res(self):
         """TM:715, TM:734: [enc0..enc6, enc7] of the LAST timestep."""
-        if self._results is None:
+        if self._results is None and not self._imagined:
             return []
         return [self.tap(n) for n in ('enc0', 'enc1', 'enc2', 'enc3', 'enc4', 'enc5', 'enc6', 'enc7')]

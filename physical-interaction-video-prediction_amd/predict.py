@@ -1,7 +1,11 @@
 """Predict entry point with the reference's arguments (predict_model.py:57-76): load a checkpoint, resize the raw frames of
 one sequence to the trained size (bilinear, /255: predict_model.py:119-122), run ONE feed-self rollout
 (predict_model.py:126-128) and rescale every predicted frame to uint8 by its own min/max (predict_model.py:131-137).
-The strip / GIF rendering of predict_model.py:140-246 is out of scope; the frames are written as `.npy`."""
+The strip / GIF rendering of predict_model.py:140-246 is out of scope; the frames are written as `.npy`.
+
+--designated_pixel R,C (no counterpart in the reference): the rollout becomes an open-loop `Model.imagine` from the context frames alone, and
+the predicted distribution of pixel (R, C) of the last context frame (coordinates on the RESIZED frame) is written next to the frames as
+`pixel_distrib-<index>.npy` (steps, H, W), normalised per step."""
 import argparse
 import os
 
@@ -51,10 +55,28 @@ def build_parser():
     p.add_argument('--image_width', type=int, default=64)
     p.add_argument('--gpu', type=int, default=0)
     p.add_argument('--out', default='')
+    p.add_argument('--designated_pixel', default='', help='R,C on the resized frame: predict open-loop and track this pixel of the last context frame')
     return p
 
 
+def parse_designated_pixel(text, height, width):
+    """'R,C' -> (row, col), checked against the resized frame."""
+    parts = text.split(',')
+    try:
+        r, c = (int(v) for v in parts)
+    except ValueError:
+        raise ValueError("--designated_pixel takes R,C (two integers), got %r" % text)
+    if not (0 <= r < height and 0 <= c < width):
+        raise ValueError('--designated_pixel %d,%d is outside the %d x %d frame' % (r, c, height, width))
+    return r, c
+
+
 def predict(args):
+    return _predict(args)[:2]
+
+
+def _predict(args, designated_rc=None):
+    """-> (loss or None, uint8 frames, pixel distribution or None).  designated_rc: roll out open-loop with `Model.imagine` and track that pixel."""
     path = os.path.join(args.models_dir, args.model_dir)
     if not os.path.exists(os.path.join(path, args.model_name)):
         raise ValueError("Directory {} does not exists".format(path))
@@ -75,19 +97,35 @@ def predict(args):
     load_npz(os.path.join(path, args.model_name), model)
     T = img_pred.shape[0]
     resized = torch.stack([resize_images(img_pred[t], (args.image_height, args.image_width), device, 1.0 / 255.0) for t in range(T)])
-    with using_config('train', False):
-        loss = model([resized, act_pred, sta_pred], 0)
-        predicted = model.gen_images
+    distrib = None
+    if designated_rc is not None:
+        from .planning import one_hot_planes
+        ctx = args.context_frames
+        B = resized.shape[1]
+        planes = one_hot_planes(np.broadcast_to(np.asarray(designated_rc).reshape(1, 1, 2), (B, 1, 2)), args.image_height, args.image_width)
+        model.imagine(resized[:ctx], act_pred[:T - 1], sta_pred[0], designated=planes, normalize=True)
+        loss = None
+        distrib = model.pixel_distrib[:, 0, 0].cpu().numpy()
+    else:
+        with using_config('train', False):
+            loss = float(model([resized, act_pred, sta_pred], 0))
+    predicted = model.gen_images
     frames = np.stack([rescale_to_uint8(p[0].cpu().numpy()) for p in predicted])
-    return float(loss), frames
+    return loss, frames, distrib
 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    loss, frames = predict(args)
+    rc = parse_designated_pixel(args.designated_pixel, args.image_height, args.image_width) if args.designated_pixel else None
+    loss, frames, distrib = _predict(args, rc)
     out = args.out or os.path.join(args.models_dir, args.model_dir, 'prediction-%d.npy' % args.data_index)
     np.save(out, frames)
-    print('loss %.6f; %d predicted frames -> %s' % (loss, len(frames), out))
+    if distrib is None:
+        print('loss %.6f; %d predicted frames -> %s' % (loss, len(frames), out))
+    else:
+        dout = os.path.join(os.path.dirname(out), 'pixel_distrib-%d.npy' % args.data_index)
+        np.save(dout, distrib)
+        print('open-loop; %d predicted frames -> %s; distribution of pixel %s -> %s' % (len(frames), out, args.designated_pixel, dout))
 
 
 if __name__ == '__main__':
