@@ -474,6 +474,43 @@ int pivp_composite(const float* prev, const float* mask_logits, const float* lay
 int pivp_pixel_track(const float* planes_in, const float* masks, const float* aux, float* planes_out,
                      int B, int P, int H, int W, int num_masks, int model_type, int stp_zero_border, void* stream);
 
+/* Expected-distance cost of tracked planes (Finn & Levine 2017, eq. 2), each plane read once.  Added in ABI 17 without a version change, like
+ * pivp_rollout_predict: backward compatible, nothing else moved.
+ *   track [S][K][P][H*W]: the RAW track_out of pivp_rollout_predict at batch K (S steps); goals [P][2]: (row, col) as float; step_w [S]; plane_w [P]
+ *   mass [S][K][P]  = sum over the plane's pixels of d
+ *   edist [S][K][P] = sum over pixels of d * sqrt((row - goal_row)^2 + (col - goal_col)^2), divided by mass (pixel index i: row = i / W, col = i % W);
+ *                     a plane whose mass is <= 0 or not finite (NaN, inf) takes edist = miss_cost instead (its mass is still written as summed)
+ *   cost [K]        = sum_s step_w[s] * (sum_p plane_w[p] * edist[s][k][p]), s and p ascending
+ * With finite weights and a finite miss_cost (anything else: PIVP_ERR_BADARG) no NaN reaches cost.  1 <= P <= 8, S, K >= 1, any H, W that
+ * pivp_pixel_track accepts; bad arguments or null pointers: PIVP_ERR_BADARG, nothing launched.  fp32, fixed summation order, no atomics: the same
+ * bits on every launch.  Two launches; memory bound (S*K*P*H*W*4 bytes read). */
+int pivp_plan_cost(const float* track, const float* goals, const float* step_w, const float* plane_w, float miss_cost,
+                   float* cost, float* mass, float* edist, int S, int K, int P, int H, int W, void* stream);
+
+/* One refit + resample of the cross-entropy method over action sequences, in a single workgroup (1 <= K <= 1024).  Added in ABI 17 without a
+ * version change.
+ *   actions [steps][K][5]: the time-major action buffer of pivp_rollout_predict at batch K (steps = T-1).  Rows t0 .. steps-1 are the candidates
+ *           (Hh = steps - t0 of them; t0 = ctx-1 in planning: the steps before the last observed frame are the past); rows t < t0 are never touched.
+ *   mean, std [Hh][5]: the sampling distribution, read and updated in place; best_actions [Hh][5], best_cost [1]: the best candidate seen so far
+ *           (start best_cost at +inf); low, high [5]: the action box; elite_idx [elites] or NULL: receives the elite indices, best first.
+ * cost [K] given (NULL: skip to the resampling; mean, std, best_*, elite_idx are then left alone):
+ *   a NaN cost counts as +inf; rank_k = #{j : c_j < c_k or (c_j == c_k and j < k)} (ties go to the lower index); the elites are ranks 0 .. elites-1.
+ *   Per (t, d): elite_mean = mean of actions[t0+t][e][d] over the elites e, elite_std = sqrt(mean of (a - elite_mean)^2) (ddof = 0), taken in rank
+ *   order, accumulated in fp64;  mean = alpha * mean + (1 - alpha) * elite_mean;  std = max(alpha * std + (1 - alpha) * elite_std, min_std)
+ *   (the blends in fp64, rounded to fp32 once).  If the rank-0 cost is below best_cost[0], that candidate's rows t0 .. and its cost are copied
+ *   into best_actions / best_cost.
+ * Resampling (always), with the updated mean / std: Philox4x32-10 (Salmon et al. 2011) with key (seed & 0xffffffff, seed >> 32).  For candidate k and
+ * row t (the index into `actions`, t0 <= t < steps) the counter (k, t, iteration, 0) gives the words x0..x3 and the counter (k, t, iteration, 1) the
+ * words y0..y3.  A word x becomes the uniform u = ((x >> 8) + 0.5) * 2^-24, strictly inside (0, 1), taken exactly (the kernel evaluates ln u and
+ * the angle through the complement 1 - u where u itself has no exact fp32 form).  Box-Muller on a pair (xa, xb): r = sqrt(-2 ln u(xa)),
+ * z0 = r cos(2 pi u(xb)), z1 = r sin(2 pi u(xb)).  (x0, x1) -> z for d = 0, 1; (x2, x3) -> d = 2, 3; (y0, y1) -> its z0 for d = 4.  The accurate
+ * logf / log1pf / sincospif, not the fast intrinsics.  actions[t][k][d] = min(max(mean[t-t0][d] + std[t-t0][d] * z_d, low[d]), high[d]).
+ * 1 <= elites <= K, 0 <= alpha <= 1, min_std >= 0, 0 <= t0 < steps, iteration >= 0; anything else or a null pointer (cost and elite_idx aside):
+ * PIVP_ERR_BADARG, nothing launched.  Fixed order, no atomics: the same bits on every launch.  One launch; launch-latency bound. */
+int pivp_cem_update(const float* cost, float* actions, float* mean, float* std, float* best_actions, float* best_cost,
+                    const float* low, const float* high, int* elite_idx, int K, int steps, int t0, int elites, float alpha, float min_std,
+                    unsigned long long seed, int iteration, void* stream);
+
 /* The output side of one timestep in ONE launch: relu(norm_enc6(raw enc6)) (TM:601) -> mask logits + enc7 (TM:718-719, TM:315-317 /
  * 454-455 / 387-388) -> the motion head's finisher on the K-slice partial sums of its Linear (TM:321-329 CDNA kernels / TM:458-468 STP
  * parameters) -> flat softmax + transform + compositing (TM:720-728).  Bit-identical to pivp_heads + pivp_cdna_kernels / pivp_stp_params +

@@ -931,6 +931,16 @@ extern "C" int pivp_pixel_track(const float* planes_in, const float* masks, cons
                                 int B, int P, int H, int W, int num_masks, int model_type, int stp_zero_border, void* stream) {
     return pixel_track(planes_in, masks, aux, planes_out, B, P, H, W, num_masks, model_type, stp_zero_border, (hipStream_t)stream);
 }
+extern "C" int pivp_plan_cost(const float* track, const float* goals, const float* step_w, const float* plane_w, float miss_cost, float* cost,
+                              float* mass, float* edist, int S, int K, int P, int H, int W, void* stream) {
+    return plan_cost(track, goals, step_w, plane_w, miss_cost, cost, mass, edist, S, K, P, H, W, (hipStream_t)stream);
+}
+extern "C" int pivp_cem_update(const float* cost, float* actions, float* mean, float* std, float* best_actions, float* best_cost,
+                               const float* low, const float* high, int* elite_idx, int K, int steps, int t0, int elites, float alpha,
+                               float min_std, unsigned long long seed, int iteration, void* stream) {
+    return cem_update(cost, actions, mean, std, best_actions, best_cost, low, high, elite_idx, K, steps, t0, elites, alpha, min_std, seed, iteration,
+                      (hipStream_t)stream);
+}
 extern "C" int pivp_resize_images(const float* in, float* out, int planes, int Hin, int Win, int Hout, int Wout, float scale, void* stream) {
     return resize_bilinear(in, out, planes, Hin, Win, Hout, Wout, scale, (hipStream_t)stream);
 }

@@ -210,6 +210,14 @@ int composite(const float* prev, const float* mask_logits, const float* layer0, 
 int pixel_track(const float* planes_in, const float* masks, const float* aux, float* planes_out, int B, int P, int H, int W,
                 int num_masks, int mode, int stp_zero_border, hipStream_t s);
 
+// Planning ops (csrc/cem.hip).  plan_cost: track [S][K][P][H*W] (the raw track_out of pivp_rollout_predict) -> mass / edist [S][K][P], cost [K].
+// cem_update: one CEM refit (cost != null) + resample of rows t0 .. steps-1 of actions [steps][K][5] in one workgroup, K <= 1024.
+int plan_cost(const float* track, const float* goals, const float* step_w, const float* plane_w, float miss_cost, float* cost, float* mass,
+              float* edist, int S, int K, int P, int H, int W, hipStream_t s);
+int cem_update(const float* cost, float* actions, float* mean, float* stdv, float* best_actions, float* best_cost, const float* low,
+               const float* high, int* elite_idx, int K, int steps, int t0, int elites, float alpha, float min_std, unsigned long long seed,
+               int iteration, hipStream_t s);
+
 // One launch for the output side of a timestep (csrc/frame_head.hip): norm_enc6 + ReLU + the 1x1 heads + the motion head's finisher +
 // flat softmax + transform + compositing; bit-identical to heads_1x1 + cdna_kernels / stp_params + composite.
 struct FrameHeadArgs {

@@ -519,35 +519,43 @@ class Model(object):
             actions = self._as_device(actions, (5,))
             state = self._as_device(state, (5,))
             planes = self._as_device(designated, ()) if P else None
-            self._ensure_params(H, W)
-            plan = self._plan_for(B, T, H, W, keep_activations=False)
-            self._active = plan
-            gen = torch.empty((T - 1, B, 3, H, W), dtype=torch.float32, device=self.device)
-            gen_states = torch.empty((T - 1, B, 5), dtype=torch.float32, device=self.device)
-            track = torch.empty((T - 1 - f, B, P, H, W), dtype=torch.float32, device=self.device) if P else None
-            pkey = (self._flat_params.data_ptr(), self._flat_params._version, getattr(self, '_params_epoch', 0))
-            if getattr(plan, 'packed_key', None) != pkey:
-                _lib.check(plan.lib.pivp_plan_params_changed(plan.h), 'pivp_plan_params_changed')
-                plan.packed_key = pkey
-            _lib.check(plan.lib.pivp_rollout_predict(plan.h, images.data_ptr(), actions.data_ptr(), state.data_ptr(),
-                                                     planes.data_ptr() if P else None, P, f, gen.data_ptr(), gen_states.data_ptr(),
-                                                     track.data_ptr() if P else None, self._stream()), 'pivp_rollout_predict')
-            self._inputs = (images, actions, state, planes)   # keep alive until the stream has consumed them
-            self._gt_mask = None
-            self._gen = gen
-            self._gen_states = gen_states
-            self._results = None
-            self._imagined = True
-            self.gen_images = [gen[t] for t in range(T - 1)]
-            self.gen_states = [gen_states[t] for t in range(T - 1)]
+            gen, track = self._rollout_predict(images, actions, state, planes, f)
             if P:
                 mass = track.sum(dim=(3, 4))
                 self.pixel_mass = mass
                 self.pixel_distrib = track / mass[..., None, None] if normalize else track
-            else:
-                self.pixel_mass = None
-                self.pixel_distrib = None
         return gen
+
+    def _rollout_predict(self, images, actions, state, planes, f):
+        """pivp_rollout_predict on checked, contiguous fp32 tensors of this device (the caller holds the device context): -> (frames, raw tracked
+        planes or None).  Sets what `imagine` sets, with `pixel_distrib` / `pixel_mass` cleared; no torch pass over the planes."""
+        _, B, _, H, W = images.shape
+        T = actions.shape[0] + 1
+        P = planes.shape[1] if planes is not None else 0
+        self._ensure_params(H, W)
+        plan = self._plan_for(B, T, H, W, keep_activations=False)
+        self._active = plan
+        gen = torch.empty((T - 1, B, 3, H, W), dtype=torch.float32, device=self.device)
+        gen_states = torch.empty((T - 1, B, 5), dtype=torch.float32, device=self.device)
+        track = torch.empty((T - 1 - f, B, P, H, W), dtype=torch.float32, device=self.device) if P else None
+        pkey = (self._flat_params.data_ptr(), self._flat_params._version, getattr(self, '_params_epoch', 0))
+        if getattr(plan, 'packed_key', None) != pkey:
+            _lib.check(plan.lib.pivp_plan_params_changed(plan.h), 'pivp_plan_params_changed')
+            plan.packed_key = pkey
+        _lib.check(plan.lib.pivp_rollout_predict(plan.h, images.data_ptr(), actions.data_ptr(), state.data_ptr(),
+                                                 planes.data_ptr() if P else None, P, f, gen.data_ptr(), gen_states.data_ptr(),
+                                                 track.data_ptr() if P else None, self._stream()), 'pivp_rollout_predict')
+        self._inputs = (images, actions, state, planes)   # keep alive until the stream has consumed them
+        self._gt_mask = None
+        self._gen = gen
+        self._gen_states = gen_states
+        self._results = None
+        self._imagined = True
+        self.gen_images = [gen[t] for t in range(T - 1)]
+        self.gen_states = [gen_states[t] for t in range(T - 1)]
+        self.pixel_mass = None
+        self.pixel_distrib = None
+        return gen, track
 
     # ---- training surface (Chainer: model.cleargrads(); loss.backward(); TM:950 via optimizer.update) -------
     def cleargrads(self):

@@ -1,11 +1,24 @@
-"""Helpers for planning with `Model.imagine` (Finn & Levine 2017, "Deep visual foresight for planning robot motion"): designate pixels of the
-current frame, roll the model forward under candidate action sequences, and score each candidate by where the model expects the pixels to end up.
+"""Planning with `Model.imagine` (Finn & Levine 2017, "Deep visual foresight for planning robot motion"): designate pixels of the current frame,
+roll the model forward under candidate action sequences, score each candidate by where the model expects the pixels to end up, and optimise the
+action sequence.
 
-Only the scoring is here; the optimiser over action sequences (CEM, MPPI) is the caller's.  Everything is plain torch on whatever device the
-planes live on: the arithmetic that matters runs inside `imagine`."""
+`cem_plan` is the optimiser: the cross-entropy method over action sequences, on the device from the first sample to the returned plan.  Its loop
+body is three stream-ordered calls -- pivp_cem_update (refit + Philox resample, one workgroup), pivp_rollout_predict (the rollout with raw
+tracked planes) and pivp_plan_cost (expected distance to the goals, each plane read once) -- with every input uploaded before the loop, no host
+synchronisation and no host-to-device copy inside it.  It knows about PAST actions: the steps before the last observed frame are fixed, only the
+horizon is optimised (the MPC case).
+
+`score_actions` scores a given set of candidates with one `imagine` and plain torch (`one_hot_planes`, `expected_position`,
+`expected_distance`); it is kept as it was for callers that bring their own optimiser."""
+import contextlib
+import ctypes
+import math
+from types import SimpleNamespace
+
 import numpy as np
 import torch
 
+from . import _lib
 from .model import Model
 
 
@@ -85,3 +98,219 @@ def score_actions(model, context_images, state, candidates, designated_rc, goal_
     planes = one_hot_planes(np.broadcast_to(rc, (K, 1, 2)), H, W)
     model.imagine(ctx_k, actions, state_k, designated=planes, normalize=True)
     return expected_distance(model.pixel_distrib[:, :, 0], goal_rc).sum(dim=0)
+
+
+MAX_CEM_SAMPLES = 1024
+
+
+def _host_array(a, what):
+    """An argument as a float64 NumPy array on the host (tensors included), for the checks and the one upload before the loop."""
+    if torch.is_tensor(a):
+        a = a.detach().cpu().numpy()
+    try:
+        return np.asarray(a, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError('%s must be numeric' % what)
+
+
+def _pixel_coords(rc, what, H, W, whole):
+    a = _host_array(rc, what)
+    if a.ndim == 1 and a.shape == (2,):
+        a = a.reshape(1, 2)
+    if a.ndim != 2 or a.shape[1] != 2:
+        raise ValueError('%s must be (P, 2) of (row, col), got shape %s' % (what, a.shape))
+    if not 1 <= a.shape[0] <= Model.MAX_TRACK_PLANES:
+        raise ValueError('%s holds %d pixels; 1 to %d are served' % (what, a.shape[0], Model.MAX_TRACK_PLANES))
+    if not np.isfinite(a).all() or (whole and (a != np.round(a)).any()):
+        raise ValueError('%s must be %s pixel coordinates' % (what, 'whole' if whole else 'finite'))
+    if (a < 0).any() or (a[:, 0] > H - 1).any() or (a[:, 1] > W - 1).any():
+        raise ValueError('%s outside the %d x %d frame' % (what, H, W))
+    return a
+
+
+def _per_step(a, what, horizon, default):
+    """None | scalar | (5,) | (horizon, 5) -> (horizon, 5) float64."""
+    if a is None:
+        return np.full((horizon, 5), float(default))
+    a = _host_array(a, what)
+    if a.shape not in ((), (5,), (horizon, 5)):
+        raise ValueError('%s must be a scalar, (5,) or (%d, 5), got shape %s' % (what, horizon, a.shape))
+    if not np.isfinite(a).all():
+        raise ValueError('%s must be finite' % what)
+    return np.ascontiguousarray(np.broadcast_to(a, (horizon, 5)))
+
+
+def _check_cem_args(model, context_images, state, designated_rc, goal_rc, horizon, past_actions, iterations, samples, elites, init_mean, init_std,
+                    min_std, alpha, action_low, action_high, step_weights, plane_weights, miss_cost, chunk, seed):
+    """Every complaint of `cem_plan` is a ValueError raised here, before the GPU or the library is needed.  -> the checked host-side values."""
+    ctx = int(model.num_frame_before_prediction)
+    si = Model._host_shape(context_images)
+    if len(si) != 5 or si[1] != 1 or si[2] != 3:
+        raise ValueError('context_images must be (ctx, 1, 3, H, W), got shape %s' % (si,))
+    if ctx < 1 or si[0] != ctx:
+        raise ValueError('context_images holds %d frames, the model was built with num_frame_before_prediction=%d' % (si[0], ctx))
+    H, W = si[3:]
+    if H < 2 or W < 2:
+        raise ValueError('context_images is empty: shape %s' % (si,))
+    if Model._host_shape(state) != (1, 5):
+        raise ValueError('state must be (1, 5), got shape %s' % (Model._host_shape(state),))
+    for name, v, lo in (('horizon', horizon, 1), ('iterations', iterations, 1), ('samples', samples, 1), ('elites', elites, 1)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo:
+            raise ValueError('%s must be an integer >= %d, not %r' % (name, lo, v))
+    if samples > MAX_CEM_SAMPLES:
+        raise ValueError('samples = %d: the refit runs in one workgroup and serves at most %d' % (samples, MAX_CEM_SAMPLES))
+    if elites > samples:
+        raise ValueError('elites = %d exceeds samples = %d' % (elites, samples))
+    if chunk is None:
+        chunk = samples
+    if isinstance(chunk, bool) or not isinstance(chunk, (int, np.integer)) or chunk < 1 or chunk > samples or samples % chunk:
+        raise ValueError('chunk must divide samples = %d, not %r' % (samples, chunk))
+    designated = _pixel_coords(designated_rc, 'designated_rc', H, W, whole=True)
+    goals = _pixel_coords(goal_rc, 'goal_rc', H, W, whole=False)
+    P = designated.shape[0]
+    if goals.shape[0] != P:
+        raise ValueError('goal_rc holds %d goals for %d designated pixels' % (goals.shape[0], P))
+    if ctx > 1:
+        if past_actions is None:
+            raise ValueError('past_actions (%d, 5) is required with %d context frames: the actions taken between the observed frames' % (ctx - 1, ctx))
+        past = _host_array(past_actions, 'past_actions')
+        if past.shape != (ctx - 1, 5) or not np.isfinite(past).all():
+            raise ValueError('past_actions must be finite and (%d, 5), got shape %s' % (ctx - 1, past.shape))
+    else:
+        if past_actions is not None and _host_array(past_actions, 'past_actions').size:
+            raise ValueError('past_actions given, but with one context frame there is no past step')
+        past = np.zeros((0, 5))
+    mean = _per_step(init_mean, 'init_mean', horizon, 0.0)
+    std = _per_step(init_std, 'init_std', horizon, 1.0)
+    if (std < 0).any():
+        raise ValueError('init_std must be non-negative')
+    for name, v in (('min_std', min_std), ('alpha', alpha)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v) or v < 0:
+            raise ValueError('%s must be a finite non-negative number, not %r' % (name, v))
+    if alpha > 1:
+        raise ValueError('alpha must lie in [0, 1], not %r' % (alpha,))
+    bounds = []
+    for name, v, default in (('action_low', action_low, -np.inf), ('action_high', action_high, np.inf)):
+        a = np.full(5, default) if v is None else _host_array(v, name)
+        if a.shape not in ((), (5,)) or np.isnan(a).any():
+            raise ValueError('%s must be a scalar or (5,) without NaN, got shape %s' % (name, a.shape))
+        bounds.append(np.ascontiguousarray(np.broadcast_to(a, (5,))))
+    if (bounds[0] > bounds[1]).any():
+        raise ValueError('action_low exceeds action_high')
+    weights = []
+    for name, v, n in (('step_weights', step_weights, horizon), ('plane_weights', plane_weights, P)):
+        a = np.ones(n) if v is None else _host_array(v, name)
+        if a.shape != (n,) or not np.isfinite(a).all():
+            raise ValueError('%s must be finite and (%d,), got shape %s' % (name, n, a.shape))
+        weights.append(a)
+    if miss_cost is None:
+        miss_cost = math.sqrt((H - 1) ** 2 + (W - 1) ** 2)
+    if isinstance(miss_cost, bool) or not isinstance(miss_cost, (int, float, np.integer, np.floating)) or not math.isfinite(miss_cost):
+        raise ValueError('miss_cost must be a finite number, not %r' % (miss_cost,))
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= seed < 2 ** 64:
+        raise ValueError('seed must be an integer in [0, 2**64), not %r' % (seed,))
+    return SimpleNamespace(ctx=ctx, H=H, W=W, P=P, K=int(samples), M=int(elites), chunk=int(chunk), horizon=int(horizon), iterations=int(iterations),
+                           designated=designated, goals=goals, past=past, mean=mean, std=std, low=bounds[0], high=bounds[1],
+                           step_w=weights[0], plane_w=weights[1], miss_cost=float(miss_cost), min_std=float(min_std), alpha=float(alpha), seed=int(seed))
+
+
+def cem_plan(model, context_images, state, designated_rc, goal_rc, horizon, past_actions=None, iterations=3, samples=32, elites=8, init_mean=None,
+             init_std=1.0, min_std=1e-3, alpha=0.0, action_low=None, action_high=None, step_weights=None, plane_weights=None, miss_cost=None,
+             chunk=None, seed=0, trace=False):
+    """Cross-entropy-method planning of `horizon` actions that move P designated pixels to their goals, entirely on the model's device.
+
+    context_images (ctx, 1, 3, H, W), state (1, 5): what the robot sees now; designated_rc (P, 2) whole (row, col) pixels of the LAST context frame,
+    goal_rc (P, 2) where each should go (1 <= P <= 8); past_actions (ctx-1, 5): the actions taken between the observed frames, required when
+    ctx > 1 -- rows t < ctx-1 of every candidate are these, rows ctx-1 .. ctx-2+horizon are optimised (T-1 = ctx-1 + horizon).
+
+    Per iteration `samples` candidates are drawn from N(mean, std) per (step, action dimension), clamped to [action_low, action_high], rolled
+    out by `imagine`'s rollout at batch `chunk` (default: all at once; samples % chunk == 0) and scored by
+    cost = sum_steps step_weights[s] * sum_planes plane_weights[p] * E[distance of plane (s, p) to goal p], with `miss_cost` (default: the frame
+    diagonal) for a plane that lost all its mass; the `elites` cheapest refit the distribution: mean = alpha * mean + (1 - alpha) * elite mean,
+    std likewise, floored at min_std.  init_mean / init_std: scalar, (5,) or (horizon, 5).  The same seed gives the same bits.
+
+    -> an object with `actions` (horizon, 5), the best sequence ever evaluated, and its `cost`; the final `mean`, `std` (horizon, 5);
+    `best_cost_per_iteration` (iterations,); and, with trace=True, `trace`: per iteration a dict of `actions` (T-1, samples, 5), `cost` (samples,),
+    `elites` (elites,) int32 best first, `mass` and `edist` (horizon, samples, P).  All device tensors; nothing is synchronised.
+
+    Side effect: the rollouts run on `model` as `imagine` does, so afterwards `model.gen_images` / `gen_states` hold the LAST rollout (the last
+    chunk of the last iteration), `pixel_distrib` / `pixel_mass` are None and `backward()` raises until the model is called again.  With
+    chunk < samples every rollout copies its slice of the action buffer and allocates its own frames, on the stream, without a host round trip."""
+    a = _check_cem_args(model, context_images, state, designated_rc, goal_rc, horizon, past_actions, iterations, samples, elites, init_mean,
+                        init_std, min_std, alpha, action_low, action_high, step_weights, plane_weights, miss_cost, chunk, seed)
+    with torch.cuda.device(model.device) if torch.cuda.is_available() else contextlib.nullcontext():
+        return _cem_iterate(model, a, _cem_upload(model, a, context_images, state), trace)
+
+
+def _cem_upload(model, a, context_images, state):
+    """Everything the loop reads or writes, uploaded or built ONCE: -> the device buffers of one `cem_plan` call."""
+    model._require_gpu()
+    dev = model.device
+    H, W, P, K, M, C, Hh = a.H, a.W, a.P, a.K, a.M, a.chunk, a.horizon
+    t0, steps = a.ctx - 1, a.ctx - 1 + Hh
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    b = SimpleNamespace()
+    b.context = model._as_device(context_images, ()).expand(-1, C, -1, -1, -1).contiguous()
+    b.state = model._as_device(state, (5,)).expand(C, -1).contiguous()
+    # the small arrays travel in ONE host-to-device copy; the buffers below are views of it
+    parts = [('goals', a.goals), ('step_w', a.step_w), ('plane_w', a.plane_w), ('low', a.low), ('high', a.high), ('mean', a.mean), ('std', a.std),
+             ('past', a.past), ('pixel', a.designated[:, 0] * W + a.designated[:, 1])]
+    packed = torch.from_numpy(np.concatenate([np.asarray(v, dtype=np.float32).ravel() for _, v in parts])).to(dev)
+    at = 0
+    for name, v in parts:
+        setattr(b, name, packed[at:at + np.size(v)].view(np.shape(v)))
+        at += np.size(v)
+    b.planes = torch.zeros((C, P, H * W), dtype=torch.float32, device=dev)
+    b.planes.scatter_(2, b.pixel.to(torch.int64).view(1, P, 1).expand(C, P, 1), 1.0)      # one-hot planes, built on the device (H * W < 2^24: exact)
+    b.planes = b.planes.view(C, P, H, W)
+    b.actions = torch.zeros((steps, K, 5), dtype=torch.float32, device=dev)
+    if t0:
+        b.actions[:t0] = b.past.unsqueeze(1)
+    b.best_actions = torch.zeros((Hh, 5), dtype=torch.float32, device=dev)
+    b.best_cost = torch.full((1,), float('inf'), dtype=torch.float32, device=dev)
+    b.per_iter, b.cost, b.mass, b.edist = new(a.iterations), new(K), new(Hh, K, P), new(Hh, K, P)
+    b.part = (new(Hh, C, P), new(Hh, C, P)) if C != K else None      # a chunk's moments: [Hh][C][P] is not a slice of [Hh][K][P]
+    b.elite_idx = torch.empty((M,), dtype=torch.int32, device=dev)
+    model._ensure_params(H, W)
+    model._plan_for(C, steps + 1, H, W, keep_activations=False)      # sized and bound here, not inside the loop
+    return b
+
+
+def _cem_iterate(model, a, b, trace=False):
+    """The loop of `cem_plan` on the buffers of `_cem_upload`: pivp_cem_update, the rollout, pivp_plan_cost -- stream-ordered launches and
+    device-to-device copies only (tests/test_gpu_planning.py runs it under torch's sync debug mode)."""
+    lib = _lib.load()
+    P, K, M, C, Hh = a.P, a.K, a.M, a.chunk, a.horizon
+    t0, steps = a.ctx - 1, a.ctx - 1 + Hh
+    stream = model._stream()
+
+    def update(have_cost, it):
+        _lib.check(lib.pivp_cem_update(b.cost.data_ptr() if have_cost else None, b.actions.data_ptr(), b.mean.data_ptr(), b.std.data_ptr(),
+                                       b.best_actions.data_ptr(), b.best_cost.data_ptr(), b.low.data_ptr(), b.high.data_ptr(),
+                                       b.elite_idx.data_ptr(), K, steps, t0, M, a.alpha, a.min_std, ctypes.c_ulonglong(a.seed), it, stream),
+                   'pivp_cem_update')
+
+    records = []
+    for it in range(a.iterations):
+        update(it > 0, it)
+        if it > 0:
+            b.per_iter[it - 1:it].copy_(b.best_cost)
+            if trace:
+                records[-1]['elites'] = b.elite_idx.clone()
+        for k0 in range(0, K, C):
+            _, track = model._rollout_predict(b.context, b.actions if C == K else b.actions[:, k0:k0 + C].contiguous(), b.state, b.planes, t0)
+            m_out, e_out = (b.mass, b.edist) if C == K else b.part
+            _lib.check(lib.pivp_plan_cost(track.data_ptr(), b.goals.data_ptr(), b.step_w.data_ptr(), b.plane_w.data_ptr(), a.miss_cost,
+                                          b.cost.data_ptr() + 4 * k0, m_out.data_ptr(), e_out.data_ptr(), Hh, C, P, a.H, a.W, stream),
+                       'pivp_plan_cost')
+            if C != K and trace:
+                b.mass[:, k0:k0 + C].copy_(m_out)
+                b.edist[:, k0:k0 + C].copy_(e_out)
+        if trace:
+            records.append(dict(actions=b.actions.clone(), cost=b.cost.clone(), mass=b.mass.clone(), edist=b.edist.clone()))
+    update(True, a.iterations)      # the last candidates count too: best_*, mean and std reflect them (the resampled rows are not used)
+    b.per_iter[a.iterations - 1:].copy_(b.best_cost)
+    if trace:
+        records[-1]['elites'] = b.elite_idx.clone()
+    return SimpleNamespace(actions=b.best_actions, cost=b.best_cost[0], mean=b.mean, std=b.std, best_cost_per_iteration=b.per_iter,
+                           trace=records if trace else None)
