@@ -402,6 +402,73 @@ int pivp_gates_backward_ln(const float* gates, const float* c_old, const float* 
                            const float* gamma, const float* stat, const float* h, const float* dh_b, int ldb, float* dc,
                            int dc_valid, float* dG, float* dgamma, float* dbeta, float* scratch, int B, int npix, int C,
                            void* stream);
+/* ---- Backward of the output heads and of the small ops at both ends of the trunk, one op per entry (the launchers the BPTT sweep calls; added in
+ * ABI 17 without a version change: nothing else moved).  All fp32.  "planar" = [B][planes][H*W], "NHWC" = [B*pixels][channels].  Buffers marked
+ * ACCUMULATED are added into (the caller provides the prior contents), all other outputs are overwritten.  `det_part` (optional scratch): the
+ * bit-reproducible form -- per-block rows summed in a fixed order instead of float atomics; its contents before and after the call are unspecified.
+ * A null required pointer or a refused geometry returns PIVP_ERR_BADARG before anything is launched. */
+
+/* Rows of tiles per sample that pivp_composite_backward splits an H x W frame into (8-row tiles up to W = 64, 4-row tiles above). */
+int pivp_composite_backward_tiles(int H, int W);
+/* Backward of pivp_composite (TM:720-728 + the transform) given go = d loss / d out, planar [B][3][H*W].
+ *   inputs: prev, mask_logits (the ReLU'd logits, planar [B][num_masks+1][H*W]), layer0 (the forward's sigmoid layer [B][3][H*W]; unused by DNA,
+ *           may be NULL there), aux as pivp_composite: CDNA the normalised kernels [B][num_masks][25], STP theta [B][6], DNA enc7 planar [B][25][H*W].
+ *   dmk  [B][num_masks+1][H*W]: gradient w.r.t. the SOFTMAXED masks (pivp_mask_softmax_backward turns it into the logits' gradient); overwritten.
+ *   dz   gradient w.r.t. the enc7 pre-activation: [B][3][H*W] (CDNA: behind ReLU + sigmoid; STP: behind sigmoid), DNA [B][25][H*W]; overwritten.
+ *   part (CDNA, STP; unused by DNA, may be NULL there), T = pivp_composite_backward_tiles(H, W): CDNA [B][T][256], per-tile partial sums of the
+ *        gradient w.r.t. kernel k's tap ij at slot k*25+ij for k < num_masks-1 (the last generated kernel never reaches the output, TM:726: its
+ *        slots and the slots >= num_masks*25 hold unspecified values); STP [B][T][8], per-tile partial sums of d theta in slots 0..5.  Overwritten.
+ *   dprev (NULL: not computed) [B][3][H*W]: gradient w.r.t. prev.  CDNA, DNA: overwritten when dprev_accum == 0, ACCUMULATED when 1 (DNA: only the
+ *        mask-0 term, the reference detaches its 25 shifted copies, TM:404).  STP: always ACCUMULATED (scattered with atomics; dprev_accum must be 1).
+ *   det_acc (STP with dprev only, else NULL): B*3*H*W 64-bit integers, ALL ZERO on entry and all zero again on return: the scattered terms are
+ *        added in fixed point, units of 2^-48 (each term's magnitude must stay below 2^15; terms below 2^-49 vanish), and reach dprev in one
+ *        rounding per element, independent of the order of arrival.
+ * Limits: H, W > 1.  CDNA 1 <= num_masks <= 10 and, with R = 12 (W <= 64) or 8 (W > 64) rows in an extended tile, W <= 252,
+ *        R * W + 2 * num_masks <= 2,048, R * (W + 4) <= 2,048 and the tile's staging within 160 KB of LDS: every num_masks at W <= 128, which is as
+ *        far as it is validated; wider frames are accepted with fewer masks.  STP 2 <= num_masks <= 10 and its staging within 150 KB of LDS.
+ *        DNA num_masks == 1. */
+int pivp_composite_backward(int model_type, const float* prev, const float* mask_logits, const float* layer0, const float* aux,
+                            const float* go, float* dmk, float* dz, float* part, float* dprev, int dprev_accum, int B, int H, int W,
+                            int num_masks, int stp_zero_border, unsigned long long* det_acc, void* stream);
+/* Backward of the flat softmax over groups of NP consecutive elements and of the ReLU in front of it (TM:719-722), in place: dmk [B][NP][HW]
+ * holds d loss / d masks on entry and d loss / d (pre-ReLU logits) on return; mask_logits are the ReLU'd logits (zero = inactive).  2 <= NP <= 12. */
+int pivp_mask_softmax_backward(const float* mask_logits, float* dmk, int B, int HW, int NP, void* stream);
+/* Backward of the two 1x1 heads (pivp_heads; TM:718, TM:315): e6 NHWC [B*HW][64]; wm [64][NP], we [64][NE]; dpm planar [B][NP][HW] and dpe planar
+ * [B][NE][HW] are the gradients at the heads' pre-activations.  de6 NHWC [B*HW][64] overwritten; dwm [64][NP], dbm [NP], dwe [64][NE], dbe [NE]
+ * ACCUMULATED.  NP + NE <= 32.  det_part: pivp_heads_backward_det_floats floats. */
+long long pivp_heads_backward_det_floats(int B, int HW, int NP, int NE);
+int pivp_heads_backward(const float* e6, const float* wm, const float* we, const float* dpm, const float* dpe, float* de6,
+                        float* dwm, float* dbm, float* dwe, float* dbe, int B, int HW, int NP, int NE, float* det_part, void* stream);
+/* Backward of pivp_cdna_kernels (TM:321-329): hidden5 [B][K], wt [K][256], vpre [B][256] the Linear's output (pivp_frame_head's vpre_out),
+ * dkpart [B][ntiles][256] the `part` of pivp_composite_backward (only the slots of the first num_masks-1 kernels are read).
+ *   dv [B][256]: gradient w.r.t. vpre, overwritten (columns >= num_masks*25 and the last kernel's: zero);  dhidden5 [B][K]: overwritten, or
+ *   ACCUMULATED when accum_dx;  dwt [K][256] and db [num_masks*25] ACCUMULATED.  det_part: B*256 floats. */
+int pivp_cdna_kernels_backward(const float* hidden5, const float* wt, const float* vpre, const float* dkpart, int ntiles, float* dv,
+                               float* dhidden5, int accum_dx, float* dwt, float* db, int B, int K, int num_masks, float* det_part,
+                               void* stream);
+/* Backward of pivp_stp_params (TM:457-468): hidden5 [B][K], wt1 [K][256] (100 columns used), s1 [B][256] the hidden layer behind its ReLU
+ * (columns < 100), w2 [6][100], dthpart [B][ntiles][8] the `part` of pivp_composite_backward.  dv [B][256]: gradient at the hidden layer's
+ * pre-activation, overwritten (columns >= 100 zero); dhidden5 [B][K] overwritten; dwt1 [K][256], db1 [100], dw2 [6][100], db2 [6] ACCUMULATED.
+ * det_part: B*706 floats. */
+int pivp_stp_params_backward(const float* hidden5, const float* wt1, const float* s1, const float* w2, const float* dthpart, int ntiles,
+                             float* dv, float* dhidden5, float* dwt1, float* db1, float* dw2, float* db2, int B, int K, float* det_part,
+                             void* stream);
+/* Backward of pivp_enc3_state (TM:556-567, 503, 730): e2, e3 NHWC [B*HW8][64] (e3 behind its ReLU), de3 [B*HW8] rows of ldd3 floats whose first 64
+ * are d loss / d e3 (ldd3 >= 64, a multiple of 4), action / state [B][5], w3 [64 | 74][64] ([input][output]; rows 64..73: the smeared action and
+ * state, only with use_state), wcs [5][10], dsnew [B][5] = d loss / d state_out.  de2 NHWC overwritten (mask_e2: multiplied by e2 > 0, the
+ * gradient in front of enc2's ReLU); dw3, db3 [64], dwcs [5][10], dbcs [5], dstate_prev [B][5] ACCUMULATED.
+ * det_part: pivp_enc3_state_backward_det_floats floats. */
+long long pivp_enc3_state_backward_det_floats(int B, int HW8, int use_state);
+int pivp_enc3_state_backward(const float* e2, const float* e3, const float* de3, int ldd3, const float* action, const float* state,
+                             const float* w3, const float* wcs, const float* dsnew, float* de2, float* dw3, float* db3, float* dwcs,
+                             float* dbcs, float* dstate_prev, int B, int HW8, int use_state, int mask_e2, float* det_part, void* stream);
+/* Backward of pivp_conv_enc0 (TM:500): img planar [B][3][H*W], w [75][32], d NHWC [B*(H/2)*(W/2)][32] = d loss / d out.  dw [75][32], db [32]
+ * ACCUMULATED; dimg (NULL: not computed; needs even H and W) planar [B][3][H*W] overwritten, or ACCUMULATED when dimg_accum.
+ * det_part: pivp_enc0_backward_det_floats floats. */
+long long pivp_enc0_backward_det_floats(int B, int H, int W);
+int pivp_enc0_backward(const float* img, const float* w, const float* d, float* dw, float* db, float* dimg, int dimg_accum,
+                       int B, int H, int W, float* det_part, void* stream);
+
 /* Chainer 2 Adam over a flat buffer (TM:860): lr_t = alpha*sqrt(1-beta2^t)/(1-beta1^t) from the host; g is scaled by gscale. */
 int pivp_adam_step(float* p, const float* g, float* m, float* v, long long n, double lr_t, double beta1, double beta2,
                    double eps, double gscale, void* stream);

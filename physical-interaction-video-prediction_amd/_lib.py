@@ -103,6 +103,17 @@ SIGNATURES = {
     'pivp_layernorm_backward': (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     'pivp_gates_backward_ln_scratch_floats': (_ll, [_i, _i]),
     'pivp_gates_backward_ln': (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    'pivp_composite_backward_tiles': (_i, [_i, _i]),
+    'pivp_composite_backward': (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    'pivp_mask_softmax_backward': (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    'pivp_heads_backward_det_floats': (_ll, [_i, _i, _i, _i]),
+    'pivp_heads_backward': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    'pivp_cdna_kernels_backward': (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    'pivp_stp_params_backward': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    'pivp_enc3_state_backward_det_floats': (_ll, [_i, _i, _i]),
+    'pivp_enc3_state_backward': (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    'pivp_enc0_backward_det_floats': (_ll, [_i, _i, _i]),
+    'pivp_enc0_backward': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     'pivp_adam_step': (_i, [_vp, _vp, _vp, _vp, _ll, _c.c_double, _c.c_double, _c.c_double, _c.c_double, _c.c_double, _vp]),
     'pivp_grad_pack_bf16': (_i, [_vp, _vp, _ll, _vp]),
     'pivp_grad_unpack_bf16': (_i, [_vp, _vp, _ll, _vp]),

@@ -806,6 +806,76 @@ extern "C" int pivp_gates_backward_ln(const float* gates, const float* c_old, co
     if (rc != PIVP_OK) return rc;
     return ln_bwd_params_reduce(part, dgamma, dbeta, B, n, s);
 }
+// Op entries of the head-side backward kernels (backward_heads.hip), one launcher each: what the BPTT sweep of pivp_plan.hip calls, reachable one at a
+// time (tests/test_gpu_backward_heads.py).  The SideFork of the sweep (a second stream for the weight gradients) is not exposed: everything on `stream`.
+extern "C" int pivp_composite_backward_tiles(int H, int W) {
+    if (H <= 0 || W <= 0) return PIVP_ERR_BADARG;
+    return composite_bwd_tiles(H, W);
+}
+extern "C" int pivp_composite_backward(int model_type, const float* prev, const float* mask_logits, const float* layer0, const float* aux,
+                                       const float* go, float* dmk, float* dz, float* part, float* dprev, int dprev_accum, int B, int H, int W,
+                                       int num_masks, int stp_zero_border, unsigned long long* det_acc, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (model_type == PIVP_MODEL_CDNA) {
+        if (det_acc) return PIVP_ERR_BADARG;
+        return composite_bwd_cdna(prev, mask_logits, layer0, aux, go, dmk, dz, part, dprev, dprev_accum, B, H, W, num_masks, s);
+    }
+    if (model_type == PIVP_MODEL_STP) {
+        if (dprev && !dprev_accum) return PIVP_ERR_BADARG;      // the scatter only ever adds into d prev
+        return composite_bwd_stp(prev, mask_logits, layer0, aux, go, dmk, dz, part, dprev, B, H, W, num_masks, stp_zero_border, s, det_acc);
+    }
+    if (model_type == PIVP_MODEL_DNA) {
+        if (det_acc || num_masks != 1) return PIVP_ERR_BADARG;
+        return composite_bwd_dna(prev, mask_logits, aux, go, dmk, dz, dprev, dprev_accum, B, H, W, s);
+    }
+    return PIVP_ERR_BADARG;
+}
+extern "C" int pivp_mask_softmax_backward(const float* mask_logits, float* dmk, int B, int HW, int NP, void* stream) {
+    return mask_softmax_bwd(mask_logits, dmk, B, HW, NP, (hipStream_t)stream);
+}
+extern "C" long long pivp_heads_backward_det_floats(int B, int HW, int NP, int NE) {
+    if (B <= 0 || HW <= 0 || NP <= 0 || NE <= 0) return PIVP_ERR_BADARG;
+    return heads_bwd_det_floats(B, HW, NP, NE);
+}
+extern "C" int pivp_heads_backward(const float* e6, const float* wm, const float* we, const float* dpm, const float* dpe, float* de6,
+                                   float* dwm, float* dbm, float* dwe, float* dbe, int B, int HW, int NP, int NE, float* det_part,
+                                   void* stream) {
+    if (NP <= 0 || NE <= 0) return PIVP_ERR_BADARG;
+    return heads_bwd(e6, wm, we, dpm, dpe, de6, dwm, dbm, dwe, dbe, B, HW, NP, NE, (hipStream_t)stream, det_part);
+}
+extern "C" int pivp_cdna_kernels_backward(const float* hidden5, const float* wt, const float* vpre, const float* dkpart, int ntiles, float* dv,
+                                          float* dhidden5, int accum_dx, float* dwt, float* db, int B, int K, int num_masks, float* det_part,
+                                          void* stream) {
+    if (ntiles <= 0) return PIVP_ERR_BADARG;
+    return cdna_kernels_bwd(hidden5, wt, vpre, dkpart, ntiles, dv, dhidden5, accum_dx, dwt, db, B, K, num_masks, (hipStream_t)stream, nullptr, det_part);
+}
+extern "C" int pivp_stp_params_backward(const float* hidden5, const float* wt1, const float* s1, const float* w2, const float* dthpart, int ntiles,
+                                        float* dv, float* dhidden5, float* dwt1, float* db1, float* dw2, float* db2, int B, int K,
+                                        float* det_part, void* stream) {
+    if (ntiles <= 0) return PIVP_ERR_BADARG;
+    return stp_params_bwd(hidden5, wt1, s1, w2, dthpart, ntiles, dv, dhidden5, dwt1, db1, dw2, db2, B, K, (hipStream_t)stream, det_part);
+}
+extern "C" long long pivp_enc3_state_backward_det_floats(int B, int HW8, int use_state) {
+    if (B <= 0 || HW8 <= 0) return PIVP_ERR_BADARG;
+    return enc3_state_bwd_det_floats(B, HW8, use_state);
+}
+extern "C" int pivp_enc3_state_backward(const float* e2, const float* e3, const float* de3, int ldd3, const float* action, const float* state,
+                                        const float* w3, const float* wcs, const float* dsnew, float* de2, float* dw3, float* db3, float* dwcs,
+                                        float* dbcs, float* dstate_prev, int B, int HW8, int use_state, int mask_e2, float* det_part,
+                                        void* stream) {
+    if (ldd3 < 64 || ldd3 % 4) return PIVP_ERR_BADARG;
+    return enc3_state_bwd(e2, e3, de3, ldd3, action, state, w3, wcs, dsnew, de2, dw3, db3, dwcs, dbcs, dstate_prev, B, HW8, use_state,
+                          (hipStream_t)stream, mask_e2, det_part);
+}
+extern "C" long long pivp_enc0_backward_det_floats(int B, int H, int W) {
+    if (B <= 0 || H <= 1 || W <= 1) return PIVP_ERR_BADARG;
+    return enc0_bwd_det_floats(B, H, W);
+}
+extern "C" int pivp_enc0_backward(const float* img, const float* w, const float* d, float* dw, float* db, float* dimg, int dimg_accum,
+                                  int B, int H, int W, float* det_part, void* stream) {
+    if (H <= 1 || W <= 1) return PIVP_ERR_BADARG;
+    return enc0_bwd(img, w, d, dw, db, dimg, dimg_accum, B, H, W, (hipStream_t)stream, nullptr, det_part);
+}
 extern "C" int pivp_adam_step(float* p, const float* g, float* m, float* v, long long n, double lr_t, double beta1, double beta2,
                               double eps, double gscale, void* stream) {
     return adam_step(p, g, m, v, (long)n, lr_t, beta1, beta2, eps, gscale, (hipStream_t)stream);
