@@ -578,6 +578,24 @@ int pivp_cem_update(const float* cost, float* actions, float* mean, float* std, 
                     const float* low, const float* high, int* elite_idx, int K, int steps, int t0, int elites, float alpha, float min_std,
                     unsigned long long seed, int iteration, void* stream);
 
+/* Per-sample quality of predicted frames, on the device: mean squared error and SSIM (Wang et al. 2004, as tf.image.ssim and scikit-image with
+ * gaussian_weights=True, use_sample_covariance=False compute it).  Added in ABI 17 without a version change.
+ *   pred, truth [N][C][H][W] contiguous fp32 (gen[ctx-1:] and images[ctx:] of a rollout, N = (T-ctx)*B); the two may alias.
+ *   mse [N]  = mean over C*H*W of (pred - truth)^2.
+ *   ssim [N] = mean over the channels and the (H-win+1) x (W-win+1) VALID window positions (no padding) of
+ *              S = ((2 mu_x mu_y + C1)(2 s_xy + C2)) / ((mu_x^2 + mu_y^2 + C1)(s_x + s_y + C2)),  C1 = (0.01 L)^2, C2 = (0.03 L)^2, L = data_range,
+ *              with the window's weighted means mu and biased weighted moments s_x = E[x^2] - mu_x^2, s_y, s_xy = E[xy] - mu_x mu_y.  The window is
+ *              separable, w_i ~ exp(-(i - (win-1)/2)^2 / (2 sigma^2)), i = 0 .. win-1, normalised to sum 1 in double and built inside the kernel;
+ *              sigma <= 0: the uniform window 1/win.
+ *   Either output may be NULL and is then not computed; the other one's bits do not change.
+ * The five window moments, the differences and the squared error are accumulated in fp64 (a flat bright frame cancels 1e-4 of its SSIM in fp32); the
+ * outputs are fp32.  Fixed summation order, no atomics, no workspace: image n's results depend on that image's data and on C, H, W, win, sigma and
+ * data_range alone -- not on N, the launch grid or n.  N, C >= 1; win odd, 3 .. 11; H, W >= win; C*H*W < 2^31; data_range > 0 and finite; sigma
+ * finite; pred, truth and at least one output non-null; anything else: PIVP_ERR_BADARG, nothing launched.  One launch, stream-ordered, no
+ * synchronisation, no allocation. */
+int pivp_frame_metrics(const float* pred, const float* truth, int N, int C, int H, int W, int win, float sigma, float data_range,
+                       float* mse, float* ssim, void* stream);
+
 /* The output side of one timestep in ONE launch: relu(norm_enc6(raw enc6)) (TM:601) -> mask logits + enc7 (TM:718-719, TM:315-317 /
  * 454-455 / 387-388) -> the motion head's finisher on the K-slice partial sums of its Linear (TM:321-329 CDNA kernels / TM:458-468 STP
  * parameters) -> flat softmax + transform + compositing (TM:720-728).  Bit-identical to pivp_heads + pivp_cdna_kernels / pivp_stp_params +

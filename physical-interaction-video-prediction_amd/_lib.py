@@ -137,6 +137,7 @@ SIGNATURES = {
     'pivp_pixel_track': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     'pivp_plan_cost': (_i, [_vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     'pivp_cem_update': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _c.c_ulonglong, _i, _vp]),
+    'pivp_frame_metrics': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp]),
     'pivp_resize_images': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _vp]),
     'pivp_select_frames': (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),
     'pivp_wgrad5x5_f32_part_floats': (_ll, [_i, _i, _i, _i, _i, _i]),

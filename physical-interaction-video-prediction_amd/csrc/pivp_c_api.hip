@@ -1011,6 +1011,10 @@ extern "C" int pivp_cem_update(const float* cost, float* actions, float* mean, f
     return cem_update(cost, actions, mean, std, best_actions, best_cost, low, high, elite_idx, K, steps, t0, elites, alpha, min_std, seed, iteration,
                       (hipStream_t)stream);
 }
+extern "C" int pivp_frame_metrics(const float* pred, const float* truth, int N, int C, int H, int W, int win, float sigma, float data_range,
+                                  float* mse, float* ssim, void* stream) {
+    return frame_metrics(pred, truth, N, C, H, W, win, sigma, data_range, mse, ssim, (hipStream_t)stream);
+}
 extern "C" int pivp_resize_images(const float* in, float* out, int planes, int Hin, int Win, int Hout, int Wout, float scale, void* stream) {
     return resize_bilinear(in, out, planes, Hin, Win, Hout, Wout, scale, (hipStream_t)stream);
 }

@@ -218,6 +218,10 @@ int cem_update(const float* cost, float* actions, float* mean, float* stdv, floa
                const float* high, int* elite_idx, int K, int steps, int t0, int elites, float alpha, float min_std, unsigned long long seed,
                int iteration, hipStream_t s);
 
+// Per-sample evaluation (csrc/metrics.hip): mse / ssim [N] of pred against truth [N][C][H][W]; either output may be null.  One launch, fp64 moments.
+int frame_metrics(const float* pred, const float* truth, int N, int C, int H, int W, int win, float sigma, float data_range, float* mse,
+                  float* ssim, hipStream_t s);
+
 // One launch for the output side of a timestep (csrc/frame_head.hip): norm_enc6 + ReLU + the 1x1 heads + the motion head's finisher +
 // flat softmax + transform + compositing; bit-identical to heads_1x1 + cdna_kernels / stp_params + composite.
 struct FrameHeadArgs {

@@ -210,6 +210,7 @@ class Model(object):
         self._imagined = False         # the last rollout was imagine(): taps exist, a loss does not
         self.pixel_distrib = None      # imagine(designated=...): (T-1-f, B, P, H, W) tracked planes on the predicted frames
         self.pixel_mass = None         # ... and their raw sums (T-1-f, B, P)
+        self.metrics = None            # evaluate(): per-sample mse / psnr / ssim (T-ctx, B) of the last evaluated rollout
 
     # ---- parameters ---------------------------------------------------------------------
     def _shapes(self):
@@ -449,6 +450,28 @@ class Model(object):
             self.loss = results[0]
             self.psnr_all = results[1]
         return self.loss
+
+    # ---- evaluation surface (no counterpart in the reference, whose only quality number is psnr_all: the PSNR of the batch-mean MSE) -------
+    def evaluate(self, x, win=11, sigma=1.5, data_range=1.0):
+        """Per-sample quality of a feed-self rollout: `__call__(x)` under using_config('train', False) -- ground truth enters through the context
+        frames only --, then ONE pivp_frame_metrics launch on the scored frames gen[ctx-1:] against images[ctx:], on the same stream and without
+        a host synchronisation in between.  -> SimpleNamespace(mse, psnr, ssim) of (T-ctx, B) device tensors (`metrics.frame_metrics`), also kept
+        as `model.metrics`; feed it to `metrics.StepCurves`.  `loss`, `psnr_all`, `summaries`, `gen_images` and `gen_states` are what that
+        `__call__` leaves."""
+        from . import metrics as M
+        images = x[0]
+        shp = self._host_shape(images)
+        ctx = int(self.num_frame_before_prediction)
+        if len(shp) != 5 or shp[2] != 3:
+            raise ValueError('images must be time-major (T, B, 3, H, W)')
+        if not 1 <= ctx < shp[0]:
+            raise ValueError('no scored frames: %d frames with num_frame_before_prediction=%d' % (shp[0], ctx))
+        lead, N, C, H, W, win, sigma, data_range = M._check_metric_args((shp[0] - ctx,) + shp[1:], (shp[0] - ctx,) + shp[1:], win, sigma, data_range)
+        with using_config('train', False):
+            self(x)
+        with torch.cuda.device(self.device):
+            self.metrics = M._launch(self._gen[ctx - 1:], self._inputs[0][ctx:], N, C, H, W, win, sigma, data_range, lead)
+        return self.metrics
 
     # ---- planning surface (no counterpart in the reference: Finn & Levine 2017 roll this model forward under candidate actions) -------
     MAX_TRACK_PLANES = 8
