@@ -1,6 +1,6 @@
-// C-ABI layer: the plan (Model.__init__ / reset_state / __call__ of the reference, TM:484-764) and
-// the per-op entry points declared in include/pivp_hip.h.  The whole per-timestep op program is
-// sequenced here in native code on one HIP stream, so the Python host only passes pointers.
+// C-ABI layer: the host-side launch helpers of pivp_host.h and the per-op entry points declared in include/pivp_hip.h.
+// The plan (Model.__init__ / reset_state / __call__ of the reference, TM:484-764), which sequences the whole per-timestep
+// op program in native code on one HIP stream, lives in pivp_plan.hip.
 #include <string.h>
 #include <string>
 #include <vector>
@@ -16,12 +16,13 @@ namespace pivp {
 long long view_bytes(int B, int H, int W, int ld) { return (long long)B * H * W * ld * 4; }
 bool fits31(long long v) { return v > 0 && v < (1LL << 31); }
 int run_convlstm(const float* x, int cx, int ldx, const float* h_prev, int C, const float* w, const float* bias,
-                 const float* c_in, float* c_out, float* h_out, int B, int H, int W, hipStream_t s, int variant,
-                 float* gates_out, float* ln_part, int ln_cap, int* ln_nparts, const unsigned short* w_bf16, int bf16_planes, const LnIn* ln_in) {
+                 const float* c_in, float* c_out, float* h_out, int B, int H, int W, hipStream_t s, const ConvLstmOpts& o) {
+    const LnIn* const ln_in = o.ln_in;
+    const bool pieces = o.bf16_planes == 3 || o.bf16_planes == -2;
     IgemmDesc d;
     memset(&d, 0, sizeof(d));
     if (ln_in) {
-        if (!w_bf16 || !convlstm_ln_in_ok(bf16_planes, cx, ldx, C, B, H, W) || !ln_in->gamma || !ln_in->beta || !ln_in->part || ln_in->np <= 0 || ln_in->part == ln_part)
+        if (!o.w_bf16 || !convlstm_ln_in_ok(o.bf16_planes, cx, ldx, C, B, H, W) || !ln_in->gamma || !ln_in->beta || !ln_in->part || ln_in->np <= 0 || ln_in->part == o.ln_out.part)
             return PIVP_ERR_BADARG;
         d.in_g = ln_in->gamma; d.in_b = ln_in->beta; d.in_part = ln_in->part; d.in_np = ln_in->np; d.in_eps = ln_in->eps;
     }
@@ -33,17 +34,17 @@ int run_convlstm(const float* x, int cx, int ldx, const float* h_prev, int C, co
     d.N = 4 * C; d.M = B * H * W;
     d.nphase = 1; d.deconv = 0; d.ksize = 5; d.pad = 2;
     const long long b0 = view_bytes(B, H, W, ldx), b1 = view_bytes(B, H, W, C), bw = 25LL * (cx + C) * 4 * C * 4;
-    if (!fits31(b0) || !fits31(b1) || !fits31(bw) || (gates_out && !fits31(4 * b1))) return PIVP_ERR_BADARG;   // (epilogue: 32-bit buffer offsets)
+    if (!fits31(b0) || !fits31(b1) || !fits31(bw) || (o.gates_out && !fits31(4 * b1))) return PIVP_ERR_BADARG;   // (epilogue: 32-bit buffer offsets)
     d.bytes0 = (int)b0; d.bytes1 = (int)b1; d.bytesw = (int)bw;
     d.out_step = 1; d.Hout = H; d.Wout = W;
-    d.cstate_in = c_in; d.cstate_out = c_out; d.hout = h_out; d.C = C; d.gates_out = gates_out;
-    d.ln_part = ln_part; d.ln_cap = ln_cap;
+    d.cstate_in = c_in; d.cstate_out = c_out; d.hout = h_out; d.C = C; d.gates_out = o.gates_out;
+    d.ln_part = o.ln_out.part; d.ln_cap = o.ln_out.cap;
     // w_bf16: the bf16 pack of w (pack_lstm_bf16) selects the bf16-operand kernel; variant then is its channels per block
     // (three pieces: maps the three-plane tile does not serve -- 8 wide -- take the fp32 kernel, which is what that mode stands in for)
     // (two fp16 pieces: 8-wide maps need an even batch for the tile to fit)
-    if (w_bf16 && (bf16_planes == 3 || bf16_planes == -2) && !convlstm_bf16_ok(d)) return w ? igemm_lstm(d, s, 0, ln_nparts) : PIVP_ERR_BADARG;      // (an 8-wide map with an odd batch: the fp32 kernel)
-    if (w_bf16) return convlstm_bf16(d, w_bf16, s, ln_nparts, ((bf16_planes == 3 || bf16_planes == -2) && variant != 16 && variant != 32) ? 0 : variant, bf16_planes);
-    return igemm_lstm(d, s, variant, ln_nparts);
+    if (o.w_bf16 && pieces && !convlstm_bf16_ok(d)) return w ? igemm_lstm(d, s, 0, o.ln_out.nparts) : PIVP_ERR_BADARG;      // (an 8-wide map with an odd batch: the fp32 kernel)
+    if (o.w_bf16) return convlstm_bf16(d, o.w_bf16, s, o.ln_out.nparts, (pieces && o.variant != 16 && o.variant != 32) ? 0 : o.variant, o.bf16_planes);
+    return igemm_lstm(d, s, o.variant, o.ln_out.nparts);
 }
 
 // the eight-wave L2-direct kernels of the split modes take it: a 16-wide map, x contiguous in one 64-channel group, and a grid that picks those kernels
@@ -84,42 +85,49 @@ bool conv3x3s2_ln_ok(int cin, int cout, int B, int Hin, int Win) {
     return igemm_in_ln_ok(d) && fits31(view_bytes(B, Hin, Win, cin)) && fits31(9LL * cin * cout * 4);
 }
 int run_conv3x3s2_ln(const float* x_raw, int cin, const float* w, const float* bias, float* out, int cout, int ldo, int relu,
-                     int B, int Hin, int Win, hipStream_t s, const float* gamma, const float* beta, const float* partials, int nparts, float eps,
-                     const Enc3Fuse* fuse3, float* norm_out, int norm_ld, float* stat_out) {
-    if (!x_raw || !w || !out || !gamma || !beta || !partials || nparts <= 0 || !conv3x3s2_ln_ok(cin, cout, B, Hin, Win)) return PIVP_ERR_BADARG;
+                     int B, int Hin, int Win, hipStream_t s, const LnIn& ln, const Conv3x3LnOpts& o) {
+    if (!x_raw || !w || !out || !ln.gamma || !ln.beta || !ln.part || ln.np <= 0 || !conv3x3s2_ln_ok(cin, cout, B, Hin, Win)) return PIVP_ERR_BADARG;
     IgemmDesc d;
     conv3x3s2_ln_desc(d, x_raw, cin, w, bias, out, cout, ldo, relu, B, Hin, Win);
     d.bytes0 = (int)view_bytes(B, Hin, Win, cin); d.bytesw = (int)(9LL * cin * cout * 4);
-    d.in_g = gamma; d.in_b = beta; d.in_part = partials; d.in_np = nparts; d.in_eps = eps;
-    d.in_out = norm_out; d.in_out_ld = norm_ld; d.in_stat_out = stat_out;
-    if (fuse3 && fuse3->e3) {
+    d.in_g = ln.gamma; d.in_b = ln.beta; d.in_part = ln.part; d.in_np = ln.np; d.in_eps = ln.eps;
+    d.in_out = o.keep.out; d.in_out_ld = o.keep.ld; d.in_stat_out = o.keep.stat;
+    if (o.fuse3 && o.fuse3->e3) {
         if (cout != 64 || ldo != 64 || !relu || !bias) return PIVP_ERR_BADARG;
-        d.f3_w = fuse3->w3; d.f3_b = fuse3->b3; d.f3_action = fuse3->action; d.f3_state = fuse3->state; d.f3_wcs = fuse3->wcs; d.f3_bcs = fuse3->bcs;
-        d.f3_out = fuse3->e3; d.f3_state_out = fuse3->state_out; d.f3_use_state = fuse3->use_state;
+        d.f3_w = o.fuse3->w3; d.f3_b = o.fuse3->b3; d.f3_action = o.fuse3->action; d.f3_state = o.fuse3->state; d.f3_wcs = o.fuse3->wcs; d.f3_bcs = o.fuse3->bcs;
+        d.f3_out = o.fuse3->e3; d.f3_state_out = o.fuse3->state_out; d.f3_use_state = o.fuse3->use_state;
     }
     int rc = igemm_validate(d, false);
     if (rc != PIVP_OK) return rc;
     return igemm_small(d, s);
 }
 
-int run_deconv3x3s2(const float* x, int cin, int ldx, const float* w, const float* bias, float* out, int cout,
-                    int ldo, int relu, int B, int Hin, int Win, hipStream_t s, int accum, float* ln_part, int ln_cap,
-                    int* ln_nparts, int bf16, const float* wscale_part) {
-    IgemmDesc d;
+// IgemmDesc of a transposed 3x3 stride-2 conv of concat(x0 [c0 channels, stride ld0], x1 [c1, ld1]; null: x0 alone): the four output parities as phases over
+// the INPUT map's anchors
+static int deconv3x3s2_desc(IgemmDesc& d, const float* x0, int c0, int ld0, const float* x1, int c1, int ld1, const float* w, const float* bias,
+                            float* out, int cout, int ldo, int relu, int B, int Hin, int Win) {
     memset(&d, 0, sizeof(d));
-    if (bf16 == 3 && !wscale_part) return PIVP_ERR_BADARG;
-    d.wscale_part = wscale_part;
-    d.bf16 = bf16;                   // precision mode bf16: honoured by the all-parities tile kernel (deconv_tile.hip), fp32 otherwise
-    d.x0 = x; d.c0 = cin; d.ld0 = ldx; d.wcin = cin; d.w = w; d.bias = bias;
+    d.x0 = x0; d.c0 = c0; d.ld0 = ld0; d.x1 = x1; d.c1 = x1 ? c1 : 0; d.ld1 = ld1; d.wcin = c0 + d.c1; d.w = w; d.bias = bias;
     d.B = B; d.Hin = Hin; d.Win = Win; d.Hg = Hin; d.Wg = Win; d.in_step = 1;
     d.N = cout; d.M = B * Hin * Win;
     d.nphase = 4; d.deconv = 1; d.ksize = 3; d.pad = 1;
-    const long long b0 = view_bytes(B, Hin, Win, ldx), bw = 9LL * cin * cout * 4;
-    if (!fits31(b0) || !fits31(bw)) return PIVP_ERR_BADARG;
-    d.bytes0 = (int)b0; d.bytesw = (int)bw;
-    d.out_step = 2; d.Hout = 2 * Hin; d.Wout = 2 * Win; d.out = out; d.ldo = ldo; d.relu = relu; d.accum = accum;
-    d.ln_part = ln_part; d.ln_cap = ln_cap;
-    return igemm_conv(d, s, ln_nparts);
+    const long long b0 = view_bytes(B, Hin, Win, ld0), b1 = d.c1 ? view_bytes(B, Hin, Win, ld1) : 0, bw = 9LL * d.wcin * cout * 4;
+    if (!fits31(b0) || (d.c1 && !fits31(b1)) || !fits31(bw)) return PIVP_ERR_BADARG;
+    d.bytes0 = (int)b0; d.bytes1 = (int)b1; d.bytesw = (int)bw;
+    d.out_step = 2; d.Hout = 2 * Hin; d.Wout = 2 * Win; d.out = out; d.ldo = ldo; d.relu = relu;
+    return PIVP_OK;
+}
+int run_deconv3x3s2(const float* x, int cin, int ldx, const float* w, const float* bias, float* out, int cout,
+                    int ldo, int relu, int B, int Hin, int Win, hipStream_t s, const DeconvOpts& o) {
+    if (o.bf16 == 3 && !o.wscale_part) return PIVP_ERR_BADARG;
+    IgemmDesc d;
+    int rc = deconv3x3s2_desc(d, x, cin, ldx, nullptr, 0, 0, w, bias, out, cout, ldo, relu, B, Hin, Win);
+    if (rc != PIVP_OK) return rc;
+    d.wscale_part = o.wscale_part;
+    d.bf16 = o.bf16;                // precision mode bf16: honoured by the all-parities tile kernel (deconv_tile.hip), fp32 otherwise
+    d.accum = o.accum;
+    d.ln_part = o.ln_out.part; d.ln_cap = o.ln_out.cap;
+    return igemm_conv(d, s, o.ln_out.nparts);
 }
 
 // run_deconv3x3s2(x, ...) AND motion_partials(x, wt, partials, ...) -- two independent launches that read the same tensor and fill a
@@ -128,19 +136,12 @@ int run_deconv3x3s2(const float* x, int cin, int ldx, const float* w, const floa
 int run_deconv3x3s2_and_partials(const float* x, int cin, const float* w, const float* bias, float* out, int cout, int ldo, int relu,
                                  int B, int Hin, int Win, hipStream_t s, const float* wt, float* partials, int dbl) {
     IgemmDesc d;
-    memset(&d, 0, sizeof(d));
-    d.x0 = x; d.c0 = cin; d.ld0 = cin; d.wcin = cin; d.w = w; d.bias = bias;
-    d.B = B; d.Hin = Hin; d.Win = Win; d.Hg = Hin; d.Wg = Win; d.in_step = 1;
-    d.N = cout; d.M = B * Hin * Win;
-    d.nphase = 4; d.deconv = 1; d.ksize = 3; d.pad = 1;
-    const long long b0 = view_bytes(B, Hin, Win, cin), bw = 9LL * cin * cout * 4;
-    if (!fits31(b0) || !fits31(bw)) return PIVP_ERR_BADARG;
-    d.bytes0 = (int)b0; d.bytesw = (int)bw;
-    d.out_step = 2; d.Hout = 2 * Hin; d.Wout = 2 * Win; d.out = out; d.ldo = ldo; d.relu = relu;
+    int rc = deconv3x3s2_desc(d, x, cin, cin, nullptr, 0, 0, w, bias, out, cout, ldo, relu, B, Hin, Win);
+    if (rc != PIVP_OK) return rc;
     const int K = Hin * Win * cin;
     // (Both in ONE grid -- round 4's igemm_small_partials_kernel -- took 21.4-22.0 us against 12.7 + 9.2 for the two launches, whichever kind of block
     // was dispatched first, and the rollout did not move: profiles/r04/NOTES.md.  Two launches; the fused grid is in the history.)
-    int rc = igemm_conv(d, s);
+    rc = igemm_conv(d, s);
     if (rc != PIVP_OK) return rc;
     return motion_partials(x, wt, partials, B, K, dbl, s);
 }
@@ -148,46 +149,32 @@ int run_deconv3x3s2_and_partials(const float* x, int cin, const float* w, const 
 // deconv3x3s2 of concat(LayerNorm(h_raw), x1): the norm of the first c_ln channels (per-element gamma / beta, statistics from the
 // producer's partials) is applied while the all-parities tile kernel stages its patch -- no launch of its own, and the normalised tensor
 // is never written (inference rollouts: [hidden6 | enc1] -> enc5, [hidden7 | enc0] -> enc6).  h_raw [B][Hin*Win][c_ln] contiguous.
-static int deconv3x3s2_ln_desc(IgemmDesc& d, const float* h_raw, int c_ln, const float* x1, int c1, int ld1, const float* w, const float* bias,
-                               float* out, int cout, int ldo, int relu, int B, int Hin, int Win) {
-    memset(&d, 0, sizeof(d));
-    d.x0 = h_raw; d.c0 = c_ln; d.ld0 = c_ln; d.x1 = x1; d.c1 = x1 ? c1 : 0; d.ld1 = ld1; d.wcin = c_ln + d.c1; d.w = w; d.bias = bias;
-    d.B = B; d.Hin = Hin; d.Win = Win; d.Hg = Hin; d.Wg = Win; d.in_step = 1;
-    d.N = cout; d.M = B * Hin * Win;
-    d.nphase = 4; d.deconv = 1; d.ksize = 3; d.pad = 1;
-    const long long b0 = view_bytes(B, Hin, Win, c_ln), b1 = d.c1 ? view_bytes(B, Hin, Win, ld1) : 0, bw = 9LL * d.wcin * cout * 4;
-    if (!fits31(b0) || (d.c1 && !fits31(b1)) || !fits31(bw)) return PIVP_ERR_BADARG;
-    d.bytes0 = (int)b0; d.bytes1 = (int)b1; d.bytesw = (int)bw;
-    d.out_step = 2; d.Hout = 2 * Hin; d.Wout = 2 * Win; d.out = out; d.ldo = ldo; d.relu = relu;
-    return PIVP_OK;
-}
 bool deconv3x3s2_ln_ok(int c_ln, int c1, int cout, int B, int Hin, int Win) {
     if (c_ln <= 0 || c_ln % 32 || c1 < 0 || c1 % 32 || cout % 32 || Hin % 8 || Win % 16) return false;
     return (long)B * (Hin / 8) * (Win / 16) * (cout / 32) >= 16;
 }
-int run_deconv3x3s2_ln(const float* h_raw, int c_ln, const float* x1, int c1, int ld1, const float* w, const float* bias, float* out, int cout,
-                       int ldo, int relu, int B, int Hin, int Win, hipStream_t s, const float* gamma, const float* beta, const float* partials,
-                       int nparts, float eps, float* ln_part, int ln_cap, int* ln_nparts, int bf16, float* norm_out, int norm_ld, float* stat_out,
-                       const float* wscale_part, const MotionRider* rider) {
-    if (!h_raw || !w || !out || !gamma || !beta || !partials || nparts <= 0 || !deconv3x3s2_ln_ok(c_ln, x1 ? c1 : 0, cout, B, Hin, Win)) return PIVP_ERR_BADARG;
-    if (norm_out && (norm_ld < c_ln || norm_ld % 4 || ((uintptr_t)norm_out & 15))) return PIVP_ERR_BADARG;
-    if (ln_part && ln_part == partials) return PIVP_ERR_BADARG;      // blocks finish (and write their output partial) while others still read the input's
+int run_deconv3x3s2_ln(const float* h_raw, int c_ln, const float* w, const float* bias, float* out, int cout, int ldo, int relu,
+                       int B, int Hin, int Win, hipStream_t s, const LnIn& ln, const DeconvLnOpts& o) {
+    const NormKeep& keep = o.keep;
+    if (!h_raw || !w || !out || !ln.gamma || !ln.beta || !ln.part || ln.np <= 0 || !deconv3x3s2_ln_ok(c_ln, o.x1 ? o.c1 : 0, cout, B, Hin, Win)) return PIVP_ERR_BADARG;
+    if (keep.out && (keep.ld < c_ln || keep.ld % 4 || ((uintptr_t)keep.out & 15))) return PIVP_ERR_BADARG;
+    if (o.ln_out.part && o.ln_out.part == ln.part) return PIVP_ERR_BADARG;      // blocks finish (and write their output partial) while others still read the input's
     IgemmDesc d;
-    int rc = deconv3x3s2_ln_desc(d, h_raw, c_ln, x1, c1, ld1, w, bias, out, cout, ldo, relu, B, Hin, Win);
+    int rc = deconv3x3s2_desc(d, h_raw, c_ln, c_ln, o.x1, o.c1, o.ld1, w, bias, out, cout, ldo, relu, B, Hin, Win);
     if (rc != PIVP_OK) return rc;
-    if (bf16 == 3 && !wscale_part) return PIVP_ERR_BADARG;
-    d.bf16 = bf16; d.wscale_part = wscale_part;
-    d.in_g = gamma; d.in_b = beta; d.in_part = partials; d.in_np = nparts; d.in_eps = eps;
-    d.ln_part = ln_part; d.ln_cap = ln_cap;
-    d.in_out = norm_out; d.in_out_ld = norm_ld; d.in_stat_out = stat_out;
-    if (rider && rider->mode) {
-        d.rd_mode = rider->mode; d.rd_blocks = B; d.rd_KS = rider->KS; d.rd_nout = rider->nout;
-        d.rd_partials = rider->partials; d.rd_bias = rider->bias; d.rd_w2 = rider->w2; d.rd_b2 = rider->b2; d.rd_out = rider->out; d.rd_vpre = rider->vpre;
+    if (o.bf16 == 3 && !o.wscale_part) return PIVP_ERR_BADARG;
+    d.bf16 = o.bf16; d.wscale_part = o.wscale_part;
+    d.in_g = ln.gamma; d.in_b = ln.beta; d.in_part = ln.part; d.in_np = ln.np; d.in_eps = ln.eps;
+    d.ln_part = o.ln_out.part; d.ln_cap = o.ln_out.cap;
+    d.in_out = keep.out; d.in_out_ld = keep.ld; d.in_stat_out = keep.stat;
+    if (o.rider && o.rider->mode) {
+        d.rd_mode = o.rider->mode; d.rd_blocks = B; d.rd_KS = o.rider->KS; d.rd_nout = o.rider->nout;
+        d.rd_partials = o.rider->partials; d.rd_bias = o.rider->bias; d.rd_w2 = o.rider->w2; d.rd_b2 = o.rider->b2; d.rd_out = o.rider->out; d.rd_vpre = o.rider->vpre;
     }
     rc = igemm_validate(d, false);
     if (rc != PIVP_OK) return rc;
     if (!deconv_tile_ok(d)) return PIVP_ERR_BADARG;
-    return deconv_tile(d, s, ln_nparts, bf16);
+    return deconv_tile(d, s, o.ln_out.nparts, o.bf16);
 }
 
 // stride-1 K x K "same" convolution through the generic kernel (used as the ConvLSTM data gradient)
@@ -215,12 +202,12 @@ bool conv_s1_splits_k(int cin, int cout, int ldo, int ksize, int B, int H, int W
     return d.ksplit_ok && igemm_conv_ksplit(d) > 1;
 }
 int run_conv_s1(const float* x, int cin, int ldx, const float* w, float* out, int cout, int ldo, int ksize, int B, int H, int W,
-                hipStream_t s, int accum, int wN, int dest_zeroed, int no_split) {
+                hipStream_t s, const ConvS1Opts& o) {
     IgemmDesc d;
-    int rc = conv_s1_desc(d, x, cin, ldx, w, out, cout, ldo, ksize, B, H, W, accum, wN);
+    int rc = conv_s1_desc(d, x, cin, ldx, w, out, cout, ldo, ksize, B, H, W, o.accum, o.wN);
     if (rc != PIVP_OK) return rc;
-    if (no_split && d.ksplit_ok) { d.ksplit_ok = 0; d.no_ksplit = 1; }      // deterministic sweeps: an unsplit grid, plain stores
-    if (d.ksplit_ok && !dest_zeroed && igemm_conv_ksplit(d) > 1 &&
+    if (o.no_split && d.ksplit_ok) { d.ksplit_ok = 0; d.no_ksplit = 1; }      // deterministic sweeps: an unsplit grid, plain stores
+    if (d.ksplit_ok && !o.dest_zeroed && igemm_conv_ksplit(d) > 1 &&
         hipMemsetAsync(out, 0, (size_t)B * H * W * ldo * 4, s) != hipSuccess) return PIVP_ERR_LAUNCH;
     return igemm_conv(d, s);
 }
@@ -246,195 +233,62 @@ bool conv5x5_bf16_splits_k(int cin, int cout, int ldo, int B, int H, int W, int 
     return d.ksplit_ok && conv5x5_bf16_ksplit(d, planes) > 1;
 }
 int run_conv5x5_bf16(const float* x, int cin, int ldx, const unsigned short* wb, float* out, int cout, int ldo, int accum,
-                     int B, int H, int W, hipStream_t s, int planes, int dest_zeroed, const float* ascale_part, const EpSpec* ep, int no_split) {
+                     int B, int H, int W, hipStream_t s, const Conv5x5Bf16Opts& o) {
+    const EpSpec* const ep = o.ep;
     IgemmDesc d;
     int rc = conv5x5_bf16_desc(d, x, cin, ldx, out, cout, ldo, accum, B, H, W);
     if (rc != PIVP_OK) return rc;
-    if (no_split) d.ksplit_ok = 0;      // deterministic sweeps: one block per output tile over the whole K (no atomics)
-    d.wscale_part = ascale_part;
+    if (o.no_split) d.ksplit_ok = 0;      // deterministic sweeps: one block per output tile over the whole K (no atomics)
+    d.wscale_part = o.ascale_part;
     if (ep && ep->applied) *ep->applied = 0;
-    if (ep && ep->src && ep->mode && !(d.ksplit_ok && conv5x5_bf16_ksplit(d, planes) > 1)) {
+    if (ep && ep->src && ep->mode && !(d.ksplit_ok && conv5x5_bf16_ksplit(d, o.planes) > 1)) {
         d.ep_src = ep->src; d.ep_ld = ep->ld; d.ep_cols = ep->cols < cout ? ep->cols : cout; d.ep_mode = ep->mode;
         if (ep->applied) *ep->applied = 1;
     }
-    if (d.ksplit_ok && !dest_zeroed && conv5x5_bf16_ksplit(d, planes) > 1 &&
+    if (d.ksplit_ok && !o.dest_zeroed && conv5x5_bf16_ksplit(d, o.planes) > 1 &&
         hipMemsetAsync(out, 0, (size_t)B * H * W * cout * 4, s) != hipSuccess) return PIVP_ERR_LAUNCH;
-    return conv5x5_bf16(d, wb, s, planes);
+    return conv5x5_bf16(d, wb, s, o.planes);
 }
 
-// weight gradient of: mode 0 = conv K x K stride `stride` pad `pad`; mode 1 = transposed 3x3 s2 p1
-int run_wgrad(int mode, const float* x0, int c0, int ld0, const float* x1, int c1, int ld1, int wcin, const float* dy, int ldy, int N,
-              float* dw, int B, int Hx, int Wx, int Hy, int Wy, int ksize, int pad, int stride, hipStream_t s, float* db,
-              int* bias_done, int bf16, int tcount, long long ts_x0, long long ts_x1, long long ts_dy, float* part, WgradDesc* desc_out,
-              const float* dy_absmax, int dy_absmax_stride, int form, int part_overwrite, int slot_ntw, int slot_j) {
-    WgradDesc d;
-    memset(&d, 0, sizeof(d));
-    d.x0 = x0; d.c0 = c0; d.ld0 = ld0; d.x1 = x1; d.c1 = x1 ? c1 : 0; d.ld1 = ld1; d.cin = c0 + (x1 ? c1 : 0); d.wcin = wcin;
-    d.dy = dy; d.ldy = ldy; d.N = N; d.dw = dw;
-    d.B = B; d.Hx = Hx; d.Wx = Wx; d.Hy = Hy; d.Wy = Wy;
-    d.deconv = mode; d.ksize = ksize; d.pad = pad; d.stride = stride;
-    d.Hg = mode ? Hx : Hy; d.Wg = mode ? Wx : Wy; d.M = B * d.Hg * d.Wg;
-    const long long b0 = view_bytes(B, Hx, Wx, ld0), b1 = x1 ? view_bytes(B, Hx, Wx, ld1) : 0, by = view_bytes(B, Hy, Wy, ldy);
-    if (!fits31(b0) || (x1 && !fits31(b1)) || !fits31(by)) return PIVP_ERR_BADARG;
-    d.bytes0 = (int)b0; d.bytes1 = (int)b1; d.bytesy = (int)by;
-    d.db = db;
-    d.tcount = tcount; d.ts_x0 = ts_x0; d.ts_x1 = ts_x1; d.ts_dy = ts_dy;
-    d.part = part; d.part_overwrite = part_overwrite;
-    d.dy_absmax = dy_absmax; d.dy_absmax_stride = dy_absmax_stride;
-    d.pieces = bf16 == 3 ? 3 : 0;       // (bf16: 1 = operands rounded to bf16; 3 = three bf16 pieces per operand, fp32-grade)
-    d.form = form;
-    d.slot_ntw = slot_ntw; d.slot_j = slot_j;
-    if (desc_out) *desc_out = d;
-    if (bf16 || dy_absmax) {   // bf16 precision mode (5x5 ConvLSTM case only): operands rounded to bf16, fp32 accumulation; db summed on the side in fp32
-        if (bias_done) *bias_done = db != nullptr;
-        return wgrad5x5_bf16(d, s);
-    }
-    return igemm_wgrad(d, s, bias_done);
-}
-
-// ConvLSTM cell backward (TM:262-272): gate math, data gradient d[x,h_prev], weight and bias gradients.
-//   d_in [M][cx+C] receives d x (first cx channels) and d h_{t-1} (last C); dc is updated in place to d c_{t-1}.
-static int fork_begin(const SideFork* f, hipStream_t s, hipStream_t* sw) {
-    *sw = s;
-    if (!f || !f->side) return PIVP_OK;
-    if (hipEventRecord(f->ready, s) != hipSuccess || hipStreamWaitEvent(f->side, f->ready, 0) != hipSuccess) return PIVP_ERR_LAUNCH;
-    *sw = f->side;
-    return PIVP_OK;
-}
-static int fork_end(const SideFork* f) {
-    if (!f || !f->side) return PIVP_OK;
-    return hipEventRecord(f->done, f->side) == hipSuccess ? PIVP_OK : PIVP_ERR_LAUNCH;
-}
-
-int run_convlstm_backward(const float* x, int cx, int ldx, const float* h_prev, int C, const float* w, const float* gates,
-                          const float* c_old, const float* c_new, const float* dh_a, int lda, const float* dh_b, int ldb,
-                          float* dc, int dc_valid, float* dG, float* wt, float* d_in, float* dW, float* db,
-                          int B, int H, int W, hipStream_t s, int wt_ready, unsigned short* wt_bf16, int bf16_planes, const SideFork* fork,
-                          const LnFuse* ln, int dx_only, float* dg_absmax, const EpSpec* ep, int det) {
-    const int M = B * H * W, cin = cx + C, N = 4 * C;
-    if (wt_bf16 && bf16_planes == -2 && !dg_absmax) return PIVP_ERR_BADARG;
-    // a K-split data gradient adds into d_in: the gate kernel clears it on the side (one launch less than a memset per cell and timestep).
-    // det (deterministic sweeps): never split, so that every element of d_in is one block's plain store.
-    const bool zero = wt_bf16 ? conv5x5_bf16_splits_k(N, cin, cin, B, H, W, bf16_planes, det)
-                              : (dx_only ? conv_s1_splits_k(N, cx, cin, 5, B, H, W, cin, det) : conv_s1_splits_k(N, cin, cin, 5, B, H, W, 0, det));
-    int rc = lstm_gates_bwd(gates, c_old, c_new, dh_a, lda, dh_b, ldb, dc, dc_valid, dG, M, C, s, B, ln, zero ? d_in : nullptr, (long long)M * cin);
-    if (rc != PIVP_OK) return rc;
-    if (dg_absmax) {      // fp16 pieces: dG's power-of-two scale from its largest |value| (gradients lie far below fp16's normal range); in front of the
-        // fork, because the weight gradient on the side stream reads it too.
-        // (The maximum taken by the gate backward itself -- an atomic maximum of float bits per wave, behind a "can I raise it" load -- instead of this
-        // launch was built and measured: the train step 21.5 ms against 21.1 with the launch, 22.5 with three bf16 pieces.  Removed.)
-        rc = absmax_partials(dG, (long)M * N, dg_absmax, s);
-        if (rc != PIVP_OK) return rc;
-    }
-    // dG is final: the weight gradient can start (on the side stream when forked), next to this layer's own data gradient
-    hipStream_t sw;
-    rc = fork_begin(fork, s, &sw);
-    if (rc != PIVP_OK) return rc;
-    if (!wt_ready) {
-        rc = repack_transpose(w, wt, 25, cin, N, 1, s);                   // [25][cin/32][4C][32] -> flipped [25][4C/32][cin][32]
-        if (rc != PIVP_OK) return rc;
-    }
-    if (wt_bf16) {   // bf16 precision mode: the data gradient with bf16 operands (wt_bf16 = bf16 pack of wt, built here unless wt_ready)
-        if (!wt_ready) {
-            rc = pack_lstm_bf16(wt, wt_bf16, N, cin, s, conv5x5_bf16_rows(cin), bf16_planes, 1);      // fragment-major plain pack, every map width
-            if (rc != PIVP_OK) return rc;
-        }
-        rc = run_conv5x5_bf16(dG, N, N, wt_bf16, d_in, cin, cin, 0, B, H, W, s, bf16_planes, zero, dg_absmax, ep, det);
-    } else {
-        if (ep && ep->applied) *ep->applied = 0;      // (the fp32 data-gradient kernels have no such hook)
-        // d[x,h] = conv5x5(dG, W^T flipped); dx_only: the x columns alone (the pack's first cx of cin; the h columns of d_in stay unwritten)
-        rc = dx_only ? run_conv_s1(dG, N, N, wt, d_in, cx, cin, 5, B, H, W, s, 0, cin, zero, det)
-                     : run_conv_s1(dG, N, N, wt, d_in, cin, cin, 5, B, H, W, s, 0, 0, zero, det);
-    }
-    if (rc != PIVP_OK) return rc;
-    if (!dW) return PIVP_OK;   // the caller batches this layer's weight gradient over several timesteps itself (pivp_plan.hip)
-    int bias_done = 0;   // the 5x5 weight-gradient kernel sums dG's columns on the side
-    // (the weight gradient has a bf16 form but no split form: in the split mode it stays the fp32 kernel)
-    rc = run_wgrad(0, x, cx, ldx, h_prev, C, C, cin, dG, N, N, dW, B, H, W, H, W, 5, 2, 1, sw, db, &bias_done, wt_bf16 != nullptr && bf16_planes == 1);
-    if (rc != PIVP_OK) return rc;
-    if (!bias_done) { rc = bias_grad(dG, N, N, M, db, sw); if (rc != PIVP_OK) return rc; }
-    return fork_end(fork);
-}
-
-int run_layernorm(const float* x, const float* g, const float* b, float* out, float* partials, int B, int n, int C,
-                  int ldo, float eps, int relu, hipStream_t s, float* stat_out, int fused_nparts) {
-    // fused_nparts > 0: the kernel that produced x already wrote that many (count, mean, M2) partials per sample
-    if (fused_nparts <= 0) {
-        int rc = ln_stats(x, partials, B, n, s);
-        if (rc != PIVP_OK) return rc;
-    }
-    return ln_apply(x, partials, g, b, out, B, n, C, ldo, eps, relu, s, stat_out, fused_nparts);
-}
-
-__global__ __launch_bounds__(256) void select_frames_kernel(const float* __restrict__ gt, const float* __restrict__ gen,
-                                                            const unsigned char* __restrict__ take, float* __restrict__ out,
-                                                            int frame_numel) {
-    const int b = blockIdx.y;
-    const float* src = take[b] ? gt : gen;
-    const size_t base = (size_t)b * frame_numel;
-    for (int i = (blockIdx.x * 256 + threadIdx.x) * 4; i < frame_numel; i += gridDim.x * 1024)
-        *reinterpret_cast<f32x4*>(out + base + i) = *reinterpret_cast<const f32x4*>(src + base + i);
-}
-
-int run_select_frames(const float* gt, const float* gen, const unsigned char* take, float* out, int B, int frame_numel, hipStream_t s) {
-    if (!gt || !gen || !take || !out || B <= 0 || frame_numel <= 0 || frame_numel % 4) return PIVP_ERR_BADARG;
-    hipLaunchKernelGGL(select_frames_kernel, dim3(8, B), dim3(256), 0, s, gt, gen, take, out, frame_numel);
-    return PIVP_LAUNCH_STATUS();
-}
-
-// conv3x3s2 (mode 0) / deconv3x3s2 (mode 1) backward.  dy is masked in place by (y > 0) when y != null (fused ReLU).
-int run_conv_backward(int mode, const float* x, int cin, int ldx, const float* w, float* dy, int cout, int ldy, const float* y, int ldyy,
-                      float* wt, float* dx, int lddx, int accum_dx, float* dW, float* db, int B, int Hin, int Win, hipStream_t s,
-                      int wt_ready, const SideFork* fork, float* part, WgradDesc* desc_out, const float* dy_add, int ld_add, int prec) {
-    const int Hout = mode ? 2 * Hin : Hin / 2, Wout = mode ? 2 * Win : Win / 2;
-    int rc = PIVP_OK;
-    if (y) { rc = relu_mask(dy, ldy, y, ldyy, cout, (long)B * Hout * Wout, s, dy_add, ld_add); if (rc != PIVP_OK) return rc; }
-    else if (dy_add) { rc = add_strided(dy, ldy, dy_add, ld_add, cout, (long)B * Hout * Wout, s); if (rc != PIVP_OK) return rc; }
-    hipStream_t sw;
-    rc = fork_begin(fork, s, &sw);      // dy is final here
-    if (rc != PIVP_OK) return rc;
-    if (dx) {
-        if (!wt_ready) {
-            rc = repack_transpose(w, wt, 9, cin, cout, 0, s);
-            if (rc != PIVP_OK) return rc;
-        }
-        rc = mode ? run_conv3x3s2(dy, cout, ldy, wt, nullptr, dx, cin, lddx, 0, B, Hout, Wout, s, accum_dx)
-                  : run_deconv3x3s2(dy, cout, ldy, wt, nullptr, dx, cin, lddx, 0, B, Hout, Wout, s, accum_dx, nullptr, 0, nullptr, prec == 1 ? 1 : 0);
-        if (rc != PIVP_OK) return rc;
-    }
-    if (!dW) return PIVP_OK;     // the caller batches this layer's weight gradient over several timesteps itself (pivp_plan.hip); the fork's `ready` is recorded
-    int bias_done = 0;     // the weight-gradient kernel sums dY's columns on the side when it can
-    rc = run_wgrad(mode, x, cin, ldx, nullptr, 0, 0, cin, dy, ldy, cout, dW, B, Hin, Win, Hout, Wout, 3, 1, 2, sw, db, &bias_done, 0,
-                   1, 0, 0, 0, part, desc_out);
-    if (rc != PIVP_OK) return rc;
-    if (!bias_done) { rc = bias_grad(dy, ldy, cout, B * Hout * Wout, db, sw); if (rc != PIVP_OK) return rc; }
-    return fork_end(fork);
-}
-
-long long conv_backward_part_floats(int mode, int cin, int cout, int B, int Hin, int Win) {
-    const int Hout = mode ? 2 * Hin : Hin / 2, Wout = mode ? 2 * Win : Win / 2;
-    WgradDesc d;
-    memset(&d, 0, sizeof(d));
-    d.c0 = cin; d.ld0 = cin; d.cin = cin; d.wcin = cin; d.N = cout; d.ldy = cout; d.B = B; d.Hx = Hin; d.Wx = Win; d.Hy = Hout; d.Wy = Wout;
-    d.deconv = mode; d.ksize = 3; d.pad = 1; d.stride = 2;
-    d.Hg = mode ? Hin : Hout; d.Wg = mode ? Win : Wout; d.M = B * d.Hg * d.Wg;
-    return igemm_wgrad_part_floats(d);
-}
-bool conv_backward_fixed_order(int mode, int cin, int cout, int B, int Hin, int Win) {
-    const int Hout = mode ? 2 * Hin : Hin / 2, Wout = mode ? 2 * Win : Win / 2;
-    WgradDesc d;
-    memset(&d, 0, sizeof(d));
-    d.c0 = cin; d.ld0 = cin; d.cin = cin; d.wcin = cin; d.N = cout; d.ldy = cout; d.B = B; d.Hx = Hin; d.Wx = Win; d.Hy = Hout; d.Wy = Wout;
-    d.deconv = mode; d.ksize = 3; d.pad = 1; d.stride = 2;
-    d.Hg = mode ? Hin : Hout; d.Wg = mode ? Win : Wout; d.M = B * d.Hg * d.Wg;
-    return wgrad3x3s2_ok(d);
-}
+// ---- weight gradients ----
 // descriptor of a ConvLSTM weight gradient's ONE-timestep geometry (what the partial buffer's size and the reduction depend on)
-static void lstm_wgrad_geom(WgradDesc& d, int cx, int C, int B, int H, int W) {
+void lstm_wgrad_geom(WgradDesc& d, int cx, int C, int B, int H, int W) {
     memset(&d, 0, sizeof(d));
     d.c0 = cx; d.ld0 = cx; d.c1 = C; d.ld1 = C; d.cin = cx + C; d.wcin = cx + C; d.N = 4 * C; d.ldy = 4 * C;
     d.B = B; d.Hx = H; d.Wx = W; d.Hy = H; d.Wy = W; d.Hg = H; d.Wg = W; d.M = B * H * W;
     d.ksize = 5; d.pad = 2; d.stride = 1;
+}
+// ... of a stride-2 3x3 conv (mode 0: anchors = output pixels) / transposed conv (mode 1: anchors = input pixels)
+void conv3x3s2_wgrad_geom(WgradDesc& d, int mode, int cin, int cout, int B, int Hin, int Win) {
+    const int Hout = mode ? 2 * Hin : Hin / 2, Wout = mode ? 2 * Win : Win / 2;
+    memset(&d, 0, sizeof(d));
+    d.c0 = cin; d.ld0 = cin; d.cin = cin; d.wcin = cin; d.N = cout; d.ldy = cout; d.B = B; d.Hx = Hin; d.Wx = Win; d.Hy = Hout; d.Wy = Wout;
+    d.deconv = mode; d.ksize = 3; d.pad = 1; d.stride = 2;
+    d.Hg = mode ? Hin : Hout; d.Wg = mode ? Win : Wout; d.M = B * d.Hg * d.Wg;
+}
+int run_wgrad(WgradDesc& d, hipStream_t s, int* bias_done, int bf16) {
+    if (!d.x1) d.c1 = 0;      // (the sweep's t = 0 has no h operand: its launch differentiates the x rows only)
+    d.cin = d.c0 + d.c1;
+    if (d.tcount < 1) d.tcount = 1;
+    const long long b0 = view_bytes(d.B, d.Hx, d.Wx, d.ld0), b1 = d.x1 ? view_bytes(d.B, d.Hx, d.Wx, d.ld1) : 0, by = view_bytes(d.B, d.Hy, d.Wy, d.ldy);
+    if (!fits31(b0) || (d.x1 && !fits31(b1)) || !fits31(by)) return PIVP_ERR_BADARG;
+    d.bytes0 = (int)b0; d.bytes1 = (int)b1; d.bytesy = (int)by;
+    d.pieces = bf16 == 3 ? 3 : 0;       // (bf16: 1 = operands rounded to bf16; 3 = three bf16 pieces per operand, fp32-grade)
+    if (bf16 || d.dy_absmax) {   // bf16 precision mode (5x5 ConvLSTM case only): operands rounded to bf16, fp32 accumulation; db summed on the side in fp32
+        if (bias_done) *bias_done = d.db != nullptr;
+        return wgrad5x5_bf16(d, s);
+    }
+    return igemm_wgrad(d, s, bias_done);
+}
+long long conv_backward_part_floats(int mode, int cin, int cout, int B, int Hin, int Win) {
+    WgradDesc d;
+    conv3x3s2_wgrad_geom(d, mode, cin, cout, B, Hin, Win);
+    return igemm_wgrad_part_floats(d);
+}
+bool conv_backward_fixed_order(int mode, int cin, int cout, int B, int Hin, int Win) {
+    WgradDesc d;
+    conv3x3s2_wgrad_geom(d, mode, cin, cout, B, Hin, Win);
+    return wgrad3x3s2_ok(d);
 }
 // (the sweep's t = 0 has no h operand: its launch differentiates the x rows only -- fewer tiles, another partition of the same buffer, reduced on its own)
 long long lstm_wgrad_part_floats(int cx, int C, int B, int H, int W, int slot_ntw, int slot_j) {
@@ -454,6 +308,130 @@ int lstm_wgrad_reduce(int cx, int C, int has_h, float* part, float* dW, float* d
     if (!has_h) { d.c1 = 0; d.cin = cx; }
     d.part = part; d.dw = dW; d.db = db;
     return igemm_wgrad_reduce(d, s);
+}
+
+// ---- backward ----
+static int fork_begin(const SideFork* f, hipStream_t s, hipStream_t* sw) {
+    *sw = s;
+    if (!f || !f->side) return PIVP_OK;
+    if (hipEventRecord(f->ready, s) != hipSuccess || hipStreamWaitEvent(f->side, f->ready, 0) != hipSuccess) return PIVP_ERR_LAUNCH;
+    *sw = f->side;
+    return PIVP_OK;
+}
+static int fork_end(const SideFork* f) {
+    if (!f || !f->side) return PIVP_OK;
+    return hipEventRecord(f->done, f->side) == hipSuccess ? PIVP_OK : PIVP_ERR_LAUNCH;
+}
+
+
+int run_convlstm_backward(const ConvLstmBwdArgs& a, hipStream_t s) {
+    const int B = a.B, H = a.H, W = a.W, cx = a.cx, C = a.C, det = a.det;
+    const int M = B * H * W, cin = cx + C, N = 4 * C;
+    if (a.wt_bf16 && a.bf16_planes == -2 && !a.dg_absmax) return PIVP_ERR_BADARG;
+    // a K-split data gradient adds into d_in: the gate kernel clears it on the side (one launch less than a memset per cell and timestep).
+    // det (deterministic sweeps): never split, so that every element of d_in is one block's plain store.
+    const bool zero = a.wt_bf16 ? conv5x5_bf16_splits_k(N, cin, cin, B, H, W, a.bf16_planes, det)
+                                : (a.dx_only ? conv_s1_splits_k(N, cx, cin, 5, B, H, W, cin, det) : conv_s1_splits_k(N, cin, cin, 5, B, H, W, 0, det));
+    int rc = lstm_gates_bwd(a.gates, a.c_old, a.c_new, a.dh_a, a.lda, a.dh_b, a.ldb, a.dc, a.dc_valid, a.dG, M, C, s, B, a.ln, zero ? a.d_in : nullptr, (long long)M * cin);
+    if (rc != PIVP_OK) return rc;
+    if (a.dg_absmax) {      // fp16 pieces: dG's power-of-two scale from its largest |value| (gradients lie far below fp16's normal range); in front of the
+        // fork, because the weight gradient on the side stream reads it too.
+        // (The maximum taken by the gate backward itself -- an atomic maximum of float bits per wave, behind a "can I raise it" load -- instead of this
+        // launch was built and measured: the train step 21.5 ms against 21.1 with the launch, 22.5 with three bf16 pieces.  Removed.)
+        rc = absmax_partials(a.dG, (long)M * N, a.dg_absmax, s);
+        if (rc != PIVP_OK) return rc;
+    }
+    // dG is final: the weight gradient can start (on the side stream when forked), next to this layer's own data gradient
+    hipStream_t sw;
+    rc = fork_begin(a.fork, s, &sw);
+    if (rc != PIVP_OK) return rc;
+    if (!a.wt_ready) {
+        rc = repack_transpose(a.w, a.wt, 25, cin, N, 1, s);                   // [25][cin/32][4C][32] -> flipped [25][4C/32][cin][32]
+        if (rc != PIVP_OK) return rc;
+    }
+    if (a.wt_bf16) {   // bf16 precision mode: the data gradient with bf16 operands (wt_bf16 = bf16 pack of wt, built here unless wt_ready)
+        if (!a.wt_ready) {
+            rc = pack_lstm_bf16(a.wt, a.wt_bf16, N, cin, s, conv5x5_bf16_rows(cin), a.bf16_planes, 1);      // fragment-major plain pack, every map width
+            if (rc != PIVP_OK) return rc;
+        }
+        Conv5x5Bf16Opts o{};
+        o.planes = a.bf16_planes; o.dest_zeroed = zero; o.ascale_part = a.dg_absmax; o.ep = a.ep; o.no_split = det;
+        rc = run_conv5x5_bf16(a.dG, N, N, a.wt_bf16, a.d_in, cin, cin, 0, B, H, W, s, o);
+    } else {
+        if (a.ep && a.ep->applied) *a.ep->applied = 0;      // (the fp32 data-gradient kernels have no such hook)
+        // d[x,h] = conv5x5(dG, W^T flipped); dx_only: the x columns alone (the pack's first cx of cin; the h columns of d_in stay unwritten)
+        ConvS1Opts o{};
+        o.dest_zeroed = zero; o.no_split = det;
+        if (a.dx_only) o.wN = cin;
+        rc = run_conv_s1(a.dG, N, N, a.wt, a.d_in, a.dx_only ? cx : cin, cin, 5, B, H, W, s, o);
+    }
+    if (rc != PIVP_OK) return rc;
+    if (!a.dW) return PIVP_OK;   // the caller batches this layer's weight gradient over several timesteps itself (pivp_plan.hip)
+    int bias_done = 0;   // the 5x5 weight-gradient kernel sums dG's columns on the side
+    // (the weight gradient has a bf16 form but no split form: in the split mode it stays the fp32 kernel)
+    WgradDesc d;
+    lstm_wgrad_geom(d, cx, C, B, H, W);
+    d.x0 = a.x; d.ld0 = a.ldx; d.x1 = a.h_prev; d.dy = a.dG; d.dw = a.dW; d.db = a.db;
+    rc = run_wgrad(d, sw, &bias_done, a.wt_bf16 != nullptr && a.bf16_planes == 1);
+    if (rc != PIVP_OK) return rc;
+    if (!bias_done) { rc = bias_grad(a.dG, N, N, M, a.db, sw); if (rc != PIVP_OK) return rc; }
+    return fork_end(a.fork);
+}
+
+int run_layernorm(const float* x, const float* g, const float* b, float* out, float* partials, int B, int n, int C,
+                  int ldo, float eps, int relu, hipStream_t s, const LayerNormOpts& o) {
+    if (o.fused_nparts <= 0) {
+        int rc = ln_stats(x, partials, B, n, s);
+        if (rc != PIVP_OK) return rc;
+    }
+    return ln_apply(x, partials, g, b, out, B, n, C, ldo, eps, relu, s, o.stat_out, o.fused_nparts);
+}
+
+__global__ __launch_bounds__(256) void select_frames_kernel(const float* __restrict__ gt, const float* __restrict__ gen,
+                                                            const unsigned char* __restrict__ take, float* __restrict__ out,
+                                                            int frame_numel) {
+    const int b = blockIdx.y;
+    const float* src = take[b] ? gt : gen;
+    const size_t base = (size_t)b * frame_numel;
+    for (int i = (blockIdx.x * 256 + threadIdx.x) * 4; i < frame_numel; i += gridDim.x * 1024)
+        *reinterpret_cast<f32x4*>(out + base + i) = *reinterpret_cast<const f32x4*>(src + base + i);
+}
+
+int run_select_frames(const float* gt, const float* gen, const unsigned char* take, float* out, int B, int frame_numel, hipStream_t s) {
+    if (!gt || !gen || !take || !out || B <= 0 || frame_numel <= 0 || frame_numel % 4) return PIVP_ERR_BADARG;
+    hipLaunchKernelGGL(select_frames_kernel, dim3(8, B), dim3(256), 0, s, gt, gen, take, out, frame_numel);
+    return PIVP_LAUNCH_STATUS();
+}
+
+int run_conv_backward(const ConvBwdArgs& a, hipStream_t s) {
+    const int mode = a.mode, B = a.B, Hin = a.Hin, Win = a.Win;
+    const int Hout = mode ? 2 * Hin : Hin / 2, Wout = mode ? 2 * Win : Win / 2;
+    int rc = PIVP_OK;
+    if (a.y) { rc = relu_mask(a.dy, a.ldy, a.y, a.ldyy, a.cout, (long)B * Hout * Wout, s, a.dy_add, a.ld_add); if (rc != PIVP_OK) return rc; }
+    else if (a.dy_add) { rc = add_strided(a.dy, a.ldy, a.dy_add, a.ld_add, a.cout, (long)B * Hout * Wout, s); if (rc != PIVP_OK) return rc; }
+    hipStream_t sw;
+    rc = fork_begin(a.fork, s, &sw);      // dy is final here
+    if (rc != PIVP_OK) return rc;
+    if (a.dx) {
+        if (!a.wt_ready) {
+            rc = repack_transpose(a.w, a.wt, 9, a.cin, a.cout, 0, s);
+            if (rc != PIVP_OK) return rc;
+        }
+        DeconvOpts o{};
+        o.accum = a.accum_dx; o.bf16 = a.prec == 1 ? 1 : 0;
+        rc = mode ? run_conv3x3s2(a.dy, a.cout, a.ldy, a.wt, nullptr, a.dx, a.cin, a.lddx, 0, B, Hout, Wout, s, a.accum_dx)
+                  : run_deconv3x3s2(a.dy, a.cout, a.ldy, a.wt, nullptr, a.dx, a.cin, a.lddx, 0, B, Hout, Wout, s, o);
+        if (rc != PIVP_OK) return rc;
+    }
+    if (!a.dW) return PIVP_OK;     // the caller batches this layer's weight gradient over several timesteps itself (pivp_plan.hip); the fork's `ready` is recorded
+    int bias_done = 0;     // the weight-gradient kernel sums dY's columns on the side when it can
+    WgradDesc d;
+    conv3x3s2_wgrad_geom(d, mode, a.cin, a.cout, B, Hin, Win);
+    d.x0 = a.x; d.ld0 = a.ldx; d.dy = a.dy; d.ldy = a.ldy; d.dw = a.dW; d.db = a.db; d.part = a.part;
+    rc = run_wgrad(d, sw, &bias_done, 0);
+    if (rc != PIVP_OK) return rc;
+    if (!bias_done) { rc = bias_grad(a.dy, a.ldy, a.cout, B * Hout * Wout, a.db, sw); if (rc != PIVP_OK) return rc; }
+    return fork_end(a.fork);
 }
 
 }  // namespace pivp
@@ -476,28 +454,45 @@ extern "C" int pivp_convlstm(const float* x, int cx, int ldx, const float* h_pre
 extern "C" int pivp_convlstm_v(const float* x, int cx, int ldx, const float* h_prev, int C, const float* w, const float* bias,
                                const float* c_in, float* c_out, float* h_out, int B, int H, int W, int variant, void* stream) {
     if (!x || !w || !bias || !c_in || !c_out || !h_out || variant < 0 || variant > 4) return PIVP_ERR_BADARG;
-    return run_convlstm(x, cx, ldx, h_prev, C, w, bias, c_in, c_out, h_out, B, H, W, (hipStream_t)stream, variant);
+    ConvLstmOpts o{};
+    o.variant = variant;
+    return run_convlstm(x, cx, ldx, h_prev, C, w, bias, c_in, c_out, h_out, B, H, W, (hipStream_t)stream, o);
 }
 extern "C" int pivp_convlstm_train(const float* x, int cx, int ldx, const float* h_prev, int C, const float* w, const float* bias,
                                    const float* c_in, float* c_out, float* h_out, float* gates_out, int B, int H, int W, void* stream) {
     if (!x || !w || !bias || !c_in || !c_out || !h_out || !gates_out) return PIVP_ERR_BADARG;
-    return run_convlstm(x, cx, ldx, h_prev, C, w, bias, c_in, c_out, h_out, B, H, W, (hipStream_t)stream, 0, gates_out);
+    ConvLstmOpts o{};
+    o.gates_out = gates_out;
+    return run_convlstm(x, cx, ldx, h_prev, C, w, bias, c_in, c_out, h_out, B, H, W, (hipStream_t)stream, o);
+}
+// the cell backward of the op entries: everything on `stream`, transposed pack built by the call, weight gradient included
+static int convlstm_backward_op(const float* x, int cx, int ldx, const float* h_prev, int C, const float* w, const float* gates,
+                                const float* c_old, const float* c_new, const float* dh_a, int lda, const float* dh_b, int ldb,
+                                float* dc, int dc_valid, float* dG, float* wt, float* d_in, float* dW, float* db,
+                                int B, int H, int W, void* stream, int dx_only) {
+    if (!x || !w || !gates || !c_old || !c_new || !dc || !dG || !wt || !d_in || !dW || !db) return PIVP_ERR_BADARG;
+    ConvLstmBwdArgs a{};
+    a.x = x; a.cx = cx; a.ldx = ldx; a.h_prev = h_prev; a.C = C; a.w = w; a.gates = gates; a.c_old = c_old; a.c_new = c_new;
+    a.dh_a = dh_a; a.lda = lda; a.dh_b = dh_b; a.ldb = ldb; a.dc = dc; a.dc_valid = dc_valid; a.dG = dG; a.wt = wt; a.d_in = d_in;
+    a.dW = dW; a.db = db; a.B = B; a.H = H; a.W = W;
+    a.dx_only = dx_only;
+    return run_convlstm_backward(a, (hipStream_t)stream);
 }
 extern "C" int pivp_convlstm_backward(const float* x, int cx, int ldx, const float* h_prev, int C, const float* w, const float* gates,
                                       const float* c_old, const float* c_new, const float* dh_a, int lda, const float* dh_b, int ldb,
                                       float* dc, int dc_valid, float* dG, float* wt, float* d_in, float* dW, float* db,
                                       int B, int H, int W, void* stream) {
-    if (!x || !w || !gates || !c_old || !c_new || !dc || !dG || !wt || !d_in || !dW || !db) return PIVP_ERR_BADARG;
-    return run_convlstm_backward(x, cx, ldx, h_prev, C, w, gates, c_old, c_new, dh_a, lda, dh_b, ldb, dc, dc_valid, dG, wt, d_in,
-                                 dW, db, B, H, W, (hipStream_t)stream);
+    return convlstm_backward_op(x, cx, ldx, h_prev, C, w, gates, c_old, c_new, dh_a, lda, dh_b, ldb, dc, dc_valid, dG, wt, d_in, dW, db, B, H, W, stream, 0);
 }
 // conv3x3s2 (mode 0) / deconv3x3s2 (mode 1) backward given dy (already ReLU-masked): dx (optionally accumulated), dW, db
 extern "C" int pivp_conv_backward(int mode, const float* x, int cin, int ldx, const float* w, const float* dy, int cout, int ldy,
                                   float* wt, float* dx, int lddx, int accum_dx, float* dW, float* db, int B, int Hin, int Win,
                                   void* stream) {
     if (!x || !w || !dy || !wt || !dW || !db || mode < 0 || mode > 1) return PIVP_ERR_BADARG;
-    return run_conv_backward(mode, x, cin, ldx, w, const_cast<float*>(dy), cout, ldy, nullptr, 0, wt, dx, lddx, accum_dx, dW, db, B, Hin, Win,
-                             (hipStream_t)stream);
+    ConvBwdArgs a{};
+    a.mode = mode; a.x = x; a.cin = cin; a.ldx = ldx; a.w = w; a.dy = const_cast<float*>(dy); a.cout = cout; a.ldy = ldy;
+    a.wt = wt; a.dx = dx; a.lddx = lddx; a.accum_dx = accum_dx; a.dW = dW; a.db = db; a.B = B; a.Hin = Hin; a.Win = Win;
+    return run_conv_backward(a, (hipStream_t)stream);
 }
 // The weight-gradient half of pivp_conv_backward as the BPTT sweep runs it: `repeats` launches (one per timestep there; here the same
 // operands every time) add their tiles into the per-block partial planes `part` (pivp_conv_backward_part_floats floats, zeroed by the
@@ -512,10 +507,11 @@ extern "C" int pivp_conv_wgrad_partial(int mode, const float* x, int cin, int ld
     if (!x || !dy || !part || !dW || !db || mode < 0 || mode > 1 || repeats < 1) return PIVP_ERR_BADARG;
     const int Hout = mode ? 2 * Hin : Hin / 2, Wout = mode ? 2 * Win : Win / 2;
     WgradDesc desc;
+    conv3x3s2_wgrad_geom(desc, mode, cin, cout, B, Hin, Win);
+    desc.x0 = x; desc.ld0 = ldx; desc.dy = dy; desc.ldy = ldy; desc.dw = dW; desc.db = db; desc.part = part;
     for (int r = 0; r < repeats; ++r) {
         int bias_done = 0;
-        int rc = run_wgrad(mode, x, cin, ldx, nullptr, 0, 0, cin, dy, ldy, cout, dW, B, Hin, Win, Hout, Wout, 3, 1, 2, (hipStream_t)stream, db,
-                           &bias_done, 0, 1, 0, 0, 0, part, &desc);
+        int rc = run_wgrad(desc, (hipStream_t)stream, &bias_done, 0);
         if (rc != PIVP_OK) return rc;
         if (!bias_done) { rc = bias_grad(dy, ldy, cout, B * Hout * Wout, db, (hipStream_t)stream); if (rc != PIVP_OK) return rc; }
     }
@@ -530,8 +526,12 @@ extern "C" int pivp_conv_wgrad_partial_batch(int mode, const float* x, int cin, 
     if (!x || !dy || !part || !dW || !db || mode < 0 || mode > 1 || tcount < 1) return PIVP_ERR_BADARG;
     const int Hout = mode ? 2 * Hin : Hin / 2, Wout = mode ? 2 * Win : Win / 2;
     int bias_done = 0;
-    int rc = run_wgrad(mode, x, cin, ldx, nullptr, 0, 0, cin, dy, ldy, cout, dW, B, Hin, Win, Hout, Wout, 3, 1, 2, (hipStream_t)stream, db, &bias_done, 0,
-                       tcount, x_step_bytes, 0, dy_step_bytes, part, nullptr, nullptr, 0, 0, overwrite ? 1 : 0);
+    WgradDesc d;
+    conv3x3s2_wgrad_geom(d, mode, cin, cout, B, Hin, Win);
+    d.x0 = x; d.ld0 = ldx; d.dy = dy; d.ldy = ldy; d.dw = dW; d.db = db;
+    d.tcount = tcount; d.ts_x0 = x_step_bytes; d.ts_dy = dy_step_bytes;
+    d.part = part; d.part_overwrite = overwrite ? 1 : 0;
+    int rc = run_wgrad(d, (hipStream_t)stream, &bias_done, 0);
     if (rc != PIVP_OK) return rc;
     if (!bias_done)
         for (int j = 0; j < tcount; ++j) {
@@ -542,29 +542,35 @@ extern "C" int pivp_conv_wgrad_partial_batch(int mode, const float* x, int cin, 
 }
 extern "C" int pivp_conv_wgrad_partial_reduce(int mode, int cin, int cout, float* part, float* dW, float* db, int B, int Hin, int Win, void* stream) {
     if (!part || !dW || !db || mode < 0 || mode > 1) return PIVP_ERR_BADARG;
-    const int Hout = mode ? 2 * Hin : Hin / 2, Wout = mode ? 2 * Win : Win / 2;
     WgradDesc d;
-    memset(&d, 0, sizeof(d));
-    d.c0 = cin; d.ld0 = cin; d.cin = cin; d.wcin = cin; d.N = cout; d.ldy = cout; d.B = B; d.Hx = Hin; d.Wx = Win; d.Hy = Hout; d.Wy = Wout;
-    d.deconv = mode; d.ksize = 3; d.pad = 1; d.stride = 2;
-    d.Hg = mode ? Hin : Hout; d.Wg = mode ? Win : Wout; d.M = B * d.Hg * d.Wg;
+    conv3x3s2_wgrad_geom(d, mode, cin, cout, B, Hin, Win);
     d.part = part; d.dw = dW; d.db = db;      // (the nine-tap kernel leaves its column sums in the planes: the reduction adds them into db)
     return igemm_wgrad_reduce(d, (hipStream_t)stream);
 }
 // The fp32 ConvLSTM weight gradient on its own (the sweep runs it on the side stream): a batch of `tcount` timesteps per launch as pivp_wgrad5x5_bf16_batch.
 // part == NULL: the round-2 kernel (atomics straight into dW / db).  part != NULL (pivp_wgrad5x5_f32_part_floats floats): the round-6 kernel adds -- overwrite
 // != 0: stores -- its segments into the partial slots; pivp_wgrad5x5_f32_reduce then adds the slots' sum into dW and db (fixed order: bit-reproducible).
+// the ConvLSTM weight-gradient entries' common operands: a batch of tcount timesteps, operand j at byte offsets j * ts_*
+static void lstm_wgrad_op(WgradDesc& d, const float* x, int cx, int ldx, const float* h_prev, int C, const float* dG, float* dW, float* db,
+                          int B, int H, int W, int tcount, long long ts_x, long long ts_h, long long ts_dG) {
+    lstm_wgrad_geom(d, cx, C, B, H, W);
+    d.x0 = x; d.ld0 = ldx; d.x1 = h_prev; d.dy = dG; d.dw = dW; d.db = db;
+    d.tcount = tcount; d.ts_x0 = ts_x; d.ts_x1 = ts_h; d.ts_dy = ts_dG;
+}
 extern "C" long long pivp_wgrad5x5_f32_part_floats(int cx, int C, int B, int H, int W, int form) {
     if (cx <= 0 || C <= 0 || B <= 0 || H <= 0 || W <= 0 || form < 0 || form > 2) return PIVP_ERR_BADARG;
-    return lstm_wgrad_part_floats(cx, C, B, H, W, form);
+    return lstm_wgrad_part_floats(cx, C, B, H, W, form, 0);
 }
 extern "C" int pivp_wgrad5x5_f32_batch(const float* x, int cx, int ldx, const float* h_prev, int C, const float* dG, float* part, int overwrite,
                                        float* dW, float* db, int B, int H, int W, int tcount, long long ts_x, long long ts_h, long long ts_dG, int form,
                                        void* stream) {
-    if (!x || !dG || !dW || tcount < 1 || form < 0 || form > 2 || (part && lstm_wgrad_part_floats(cx, C, B, H, W, form) <= 0)) return PIVP_ERR_BADARG;
+    if (!x || !dG || !dW || tcount < 1 || form < 0 || form > 2 || (part && lstm_wgrad_part_floats(cx, C, B, H, W, form, 0) <= 0)) return PIVP_ERR_BADARG;
     int bias_done = 0;
-    int rc = run_wgrad(0, x, cx, ldx, h_prev, C, C, cx + C, dG, 4 * C, 4 * C, dW, B, H, W, H, W, 5, 2, 1, (hipStream_t)stream, db, &bias_done, 0,
-                       tcount, ts_x, ts_h, ts_dG, part, nullptr, nullptr, 0, form, overwrite ? 1 : 0, form);      // (form: the wave form without part, the slot form's columns per wave with it)
+    WgradDesc d;
+    lstm_wgrad_op(d, x, cx, ldx, h_prev, C, dG, dW, db, B, H, W, tcount, ts_x, ts_h, ts_dG);
+    d.part = part; d.part_overwrite = overwrite ? 1 : 0;
+    d.form = form; d.slot_ntw = form;      // (form: the wave form without part, the slot form's columns per wave with it)
+    int rc = run_wgrad(d, (hipStream_t)stream, &bias_done, 0);
     if (rc != PIVP_OK) return rc;
     if (db && !bias_done)
         for (int j = 0; j < tcount; ++j) {
@@ -574,8 +580,8 @@ extern "C" int pivp_wgrad5x5_f32_batch(const float* x, int cx, int ldx, const fl
     return PIVP_OK;
 }
 extern "C" int pivp_wgrad5x5_f32_reduce(int cx, int C, int has_h, float* part, float* dW, float* db, int B, int H, int W, int form, void* stream) {
-    if (!part || !dW || form < 0 || form > 2 || lstm_wgrad_part_floats(cx, C, B, H, W, form) <= 0) return PIVP_ERR_BADARG;
-    return lstm_wgrad_reduce(cx, C, has_h, part, dW, db, B, H, W, (hipStream_t)stream, form);
+    if (!part || !dW || form < 0 || form > 2 || lstm_wgrad_part_floats(cx, C, B, H, W, form, 0) <= 0) return PIVP_ERR_BADARG;
+    return lstm_wgrad_reduce(cx, C, has_h, part, dW, db, B, H, W, (hipStream_t)stream, form, 0);      // (slot_j = 0: blocks per XCD by the device's CU count)
 }
 // The slot kernel's partition walked on the host (no GPU work): geom8 = {blocks per XCD, pixel parts, tile parts, 32-column tiles per wave, tiles, 16-pixel chunks per
 // timestep, slots per block, floats per slot}; segs: (block, segment, tile, first chunk, end chunk) per segment in kernel order; slots: (tile, slot) pairs in the
@@ -595,7 +601,7 @@ extern "C" int pivp_wgrad5x5_f32_partition(int cx, int C, int has_h, int B, int 
 // gradient the flipped, transposed weight) into out [B*H*W][cout] (contiguous); tile and K split as the sweep chooses them (out is cleared first when K is split).
 extern "C" int pivp_conv5x5_f32(const float* x, int cin, int ldx, const float* wt, float* out, int cout, int B, int H, int W, void* stream) {
     if (!x || !wt || !out) return PIVP_ERR_BADARG;
-    return run_conv_s1(x, cin, ldx, wt, out, cout, cout, 5, B, H, W, (hipStream_t)stream, 0, 0, 0);
+    return run_conv_s1(x, cin, ldx, wt, out, cout, cout, 5, B, H, W, (hipStream_t)stream);
 }
 // pivp_convlstm_backward for the sweep's LAST timestep (t = 0): nobody reads d h_{-1}, so only the cx columns of d_in are computed
 // (the data gradient runs on the first cx columns of the transposed weight pack) and the h columns of d_in are not computed (left as they are, or cleared with the rest of d_in for a K-split data gradient).
@@ -603,18 +609,25 @@ extern "C" int pivp_convlstm_backward_dx_only(const float* x, int cx, int ldx, c
                                               const float* c_old, const float* c_new, const float* dh_a, int lda, const float* dh_b, int ldb,
                                               float* dc, int dc_valid, float* dG, float* wt, float* d_in, float* dW, float* db,
                                               int B, int H, int W, void* stream) {
-    if (!x || !w || !gates || !c_old || !c_new || !dc || !dG || !wt || !d_in || !dW || !db) return PIVP_ERR_BADARG;
-    return run_convlstm_backward(x, cx, ldx, h_prev, C, w, gates, c_old, c_new, dh_a, lda, dh_b, ldb, dc, dc_valid, dG, wt, d_in,
-                                 dW, db, B, H, W, (hipStream_t)stream, 0, nullptr, 1, nullptr, nullptr, 1);
+    return convlstm_backward_op(x, cx, ldx, h_prev, C, w, gates, c_old, c_new, dh_a, lda, dh_b, ldb, dc, dc_valid, dG, wt, d_in, dW, db, B, H, W, stream, 1);
 }
 extern "C" int pivp_layernorm_train(const float* x, const float* gamma, const float* beta, float* out, float* partials, float* stat,
                                     int B, int n, int C, int ldo, float eps, int relu, void* stream) {
     if (!stat) return PIVP_ERR_BADARG;
-    return run_layernorm(x, gamma, beta, out, partials, B, n, C, ldo, eps, relu, (hipStream_t)stream, stat);
+    LayerNormOpts o{};
+    o.stat_out = stat;
+    return run_layernorm(x, gamma, beta, out, partials, B, n, C, ldo, eps, relu, (hipStream_t)stream, o);
 }
 // bf16-operand ConvLSTM (BASELINE.json config 3): weights re-packed to bf16 once, operands rounded to bf16 on the way into LDS,
 // fp32 accumulation / gates / state.  nch: 0 automatic, 16 or 32 channels per block.
 // Split mode (three bf16 MFMAs per product, 16 bits of product mantissa): weights packed as hi / lo planes, twice the elements.
+// the packed-weight ConvLSTM entries' options
+static ConvLstmOpts packed_lstm_opts(const void* w_bf16, int planes, int nch, float* gates_out, float* ln_part, int ln_cap, int* ln_nparts) {
+    ConvLstmOpts o{};
+    o.w_bf16 = (const unsigned short*)w_bf16; o.bf16_planes = planes; o.variant = nch; o.gates_out = gates_out;
+    o.ln_out.part = ln_part; o.ln_out.cap = ln_cap; o.ln_out.nparts = ln_nparts;
+    return o;
+}
 extern "C" int pivp_pack_lstm_bf16x3(const float* w, void* w_bf16, int cin_total, int C, void* stream) {
     if (C <= 0) return PIVP_ERR_BADARG;
     return pack_lstm_bf16(w, (unsigned short*)w_bf16, cin_total, 4 * C, (hipStream_t)stream, 0, 2);
@@ -623,8 +636,8 @@ extern "C" int pivp_convlstm_bf16x3(const float* x, int cx, int ldx, const float
                                     const float* c_in, float* c_out, float* h_out, float* gates_out, float* ln_part, int ln_cap,
                                     int* ln_nparts, int B, int H, int W, int nch, void* stream) {
     if (!x || !w_bf16 || !bias || !c_in || !c_out || !h_out) return PIVP_ERR_BADARG;
-    return run_convlstm(x, cx, ldx, h_prev, C, nullptr, bias, c_in, c_out, h_out, B, H, W, (hipStream_t)stream, nch, gates_out,
-                        ln_part, ln_cap, ln_nparts, (const unsigned short*)w_bf16, 2);
+    const ConvLstmOpts o = packed_lstm_opts(w_bf16, 2, nch, gates_out, ln_part, ln_cap, ln_nparts);
+    return run_convlstm(x, cx, ldx, h_prev, C, nullptr, bias, c_in, c_out, h_out, B, H, W, (hipStream_t)stream, o);
 }
 extern "C" int pivp_pack_lstm_bf16x6(const float* w, void* w_bf16, int cin_total, int C, void* stream) {
     if (C <= 0) return PIVP_ERR_BADARG;
@@ -634,8 +647,8 @@ extern "C" int pivp_convlstm_bf16x6(const float* x, int cx, int ldx, const float
                                     const float* c_in, float* c_out, float* h_out, float* gates_out, float* ln_part, int ln_cap,
                                     int* ln_nparts, int B, int H, int W, int nch, void* stream) {
     if (!x || !w_bf16 || !bias || !c_in || !c_out || !h_out || (nch != 0 && nch != 16 && nch != 32)) return PIVP_ERR_BADARG;
-    return run_convlstm(x, cx, ldx, h_prev, C, nullptr, bias, c_in, c_out, h_out, B, H, W, (hipStream_t)stream, nch, gates_out,
-                        ln_part, ln_cap, ln_nparts, (const unsigned short*)w_bf16, 3);
+    const ConvLstmOpts o = packed_lstm_opts(w_bf16, 3, nch, gates_out, ln_part, ln_cap, ln_nparts);
+    return run_convlstm(x, cx, ldx, h_prev, C, nullptr, bias, c_in, c_out, h_out, B, H, W, (hipStream_t)stream, o);
 }
 extern "C" int pivp_pack_lstm_fp16x3(const float* w, void* w_bf16, int cin_total, int C, int map_width, void* stream) {
     if (C <= 0 || map_width <= 0) return PIVP_ERR_BADARG;
@@ -646,8 +659,8 @@ extern "C" int pivp_convlstm_fp16x3(const float* x, int cx, int ldx, const float
                                     const float* c_in, float* c_out, float* h_out, float* gates_out, float* ln_part, int ln_cap,
                                     int* ln_nparts, int B, int H, int W, int nch, void* stream) {
     if (!x || !w_bf16 || !bias || !c_in || !c_out || !h_out || (nch != 0 && nch != 16 && nch != 32 && nch != 256)) return PIVP_ERR_BADARG;
-    return run_convlstm(x, cx, ldx, h_prev, C, nullptr, bias, c_in, c_out, h_out, B, H, W, (hipStream_t)stream, nch, gates_out,
-                        ln_part, ln_cap, ln_nparts, (const unsigned short*)w_bf16, -2);
+    const ConvLstmOpts o = packed_lstm_opts(w_bf16, -2, nch, gates_out, ln_part, ln_cap, ln_nparts);
+    return run_convlstm(x, cx, ldx, h_prev, C, nullptr, bias, c_in, c_out, h_out, B, H, W, (hipStream_t)stream, o);
 }
 extern "C" long long pivp_lstm_bf16_weight_elems(int cin_total, int C) {
     if (cin_total <= 0 || cin_total % 32 || C <= 0) return PIVP_ERR_BADARG;
@@ -661,8 +674,8 @@ extern "C" int pivp_convlstm_bf16(const float* x, int cx, int ldx, const float* 
                                   const float* c_in, float* c_out, float* h_out, float* gates_out, float* ln_part, int ln_cap,
                                   int* ln_nparts, int B, int H, int W, int nch, void* stream) {
     if (!x || !w_bf16 || !bias || !c_in || !c_out || !h_out) return PIVP_ERR_BADARG;
-    return run_convlstm(x, cx, ldx, h_prev, C, nullptr, bias, c_in, c_out, h_out, B, H, W, (hipStream_t)stream, nch, gates_out,
-                        ln_part, ln_cap, ln_nparts, (const unsigned short*)w_bf16);
+    const ConvLstmOpts o = packed_lstm_opts(w_bf16, 1, nch, gates_out, ln_part, ln_cap, ln_nparts);
+    return run_convlstm(x, cx, ldx, h_prev, C, nullptr, bias, c_in, c_out, h_out, B, H, W, (hipStream_t)stream, o);
 }
 // Plain 5x5 stride-1 "same" convolution with bf16 operands (the ConvLSTM data gradient of the bf16 mode): w fp32 K-inner packed
 // [25][cin/32][cout][32]; w_bf16: scratch of pivp_conv5x5_bf16_weight_elems(cin, cout) 2-byte elements, (re)built by this call.
@@ -683,7 +696,9 @@ extern "C" int pivp_conv5x5_bf16x3(const float* x, int cin, int ldx, const float
     if (!x || !w || !w_bf16 || !out || cin <= 0 || cout <= 0) return PIVP_ERR_BADARG;
     int rc = pack_lstm_bf16(w, (unsigned short*)w_bf16, cin, cout, (hipStream_t)stream, conv5x5_bf16_rows(cout), 2);
     if (rc != PIVP_OK) return rc;
-    return run_conv5x5_bf16(x, cin, ldx, (const unsigned short*)w_bf16, out, cout, ldo, accum, B, H, W, (hipStream_t)stream, 2);
+    Conv5x5Bf16Opts o{};
+    o.planes = 2;
+    return run_conv5x5_bf16(x, cin, ldx, (const unsigned short*)w_bf16, out, cout, ldo, accum, B, H, W, (hipStream_t)stream, o);
 }
 // three-piece form (six MFMAs per product, fp32-grade): w_bf16 holds 3 * pivp_conv5x5_bf16_weight_elems(cin, cout) elements; W % 16 == 0
 extern "C" int pivp_conv5x5_bf16x6(const float* x, int cin, int ldx, const float* w, void* w_bf16, float* out, int cout, int ldo, int accum,
@@ -691,7 +706,9 @@ extern "C" int pivp_conv5x5_bf16x6(const float* x, int cin, int ldx, const float
     if (!x || !w || !w_bf16 || !out || cin <= 0 || cout <= 0 || (W % 16 && (W % 8 || B % 2))) return PIVP_ERR_BADARG;
     int rc = pack_lstm_bf16(w, (unsigned short*)w_bf16, cin, cout, (hipStream_t)stream, conv5x5_bf16_rows(cout), 3, 1);
     if (rc != PIVP_OK) return rc;
-    return run_conv5x5_bf16(x, cin, ldx, (const unsigned short*)w_bf16, out, cout, ldo, accum, B, H, W, (hipStream_t)stream, 3);
+    Conv5x5Bf16Opts o{};
+    o.planes = 3;
+    return run_conv5x5_bf16(x, cin, ldx, (const unsigned short*)w_bf16, out, cout, ldo, accum, B, H, W, (hipStream_t)stream, o);
 }
 // two-fp16-piece form (three MFMAs per product, fp32-grade; the fp16x3 mode's data gradients): x is staged times the power of two that puts its largest
 // |value| into [2^14, 2^15) (gradients lie far below fp16's normal range), w as in pivp_pack_lstm_fp16x3; w_bf16 holds 2 * pivp_conv5x5_bf16_weight_elems
@@ -703,14 +720,17 @@ extern "C" int pivp_conv5x5_fp16x3(const float* x, int cin, int ldx, const float
     if (rc != PIVP_OK) return rc;
     rc = absmax_partials(x, (long)B * H * W * cin, scratch, (hipStream_t)stream);
     if (rc != PIVP_OK) return rc;
-    return run_conv5x5_bf16(x, cin, ldx, (const unsigned short*)w_bf16, out, cout, ldo, accum, B, H, W, (hipStream_t)stream, -2, 0, scratch);
+    Conv5x5Bf16Opts o{};
+    o.planes = -2; o.ascale_part = scratch;
+    return run_conv5x5_bf16(x, cin, ldx, (const unsigned short*)w_bf16, out, cout, ldo, accum, B, H, W, (hipStream_t)stream, o);
 }
 // ConvLSTM weight gradient with bf16 operands: dW (K-inner packed like the weight, [25][(cx+C)/32][4C][32]) += x|h^T . dG per tap.
 extern "C" int pivp_wgrad5x5_bf16(const float* x, int cx, int ldx, const float* h_prev, int C, const float* dG, float* dW, float* db,
                                   int B, int H, int W, void* stream) {
     if (!x || !dG || !dW || C <= 0 || cx <= 0) return PIVP_ERR_BADARG;
-    return run_wgrad(0, x, cx, ldx, h_prev, C, C, cx + C, dG, 4 * C, 4 * C, dW, B, H, W, H, W, 5, 2, 1, (hipStream_t)stream, db,
-                     nullptr, 1);
+    WgradDesc d;
+    lstm_wgrad_op(d, x, cx, ldx, h_prev, C, dG, dW, db, B, H, W, 1, 0, 0, 0);
+    return run_wgrad(d, (hipStream_t)stream, nullptr, 1);
 }
 // ... with two fp16 pieces per operand and three MFMAs per product (fp32-grade; the fp16x3 mode's weight gradient), a batch of timesteps as below:
 // scratch: 72 * tcount floats (the partial maxima of every timestep's dG: it is staged times a power of two from the largest of the batch)
@@ -722,31 +742,37 @@ extern "C" int pivp_wgrad5x5_fp16x3_batch(const float* x, int cx, int ldx, const
                                        scratch + (size_t)j * 72, (hipStream_t)stream);
         if (rc != PIVP_OK) return rc;
     }
-    return run_wgrad(0, x, cx, ldx, h_prev, C, C, cx + C, dG, 4 * C, 4 * C, dW, B, H, W, H, W, 5, 2, 1, (hipStream_t)stream, db,
-                     nullptr, 0, tcount, ts_x, ts_h, ts_dG, nullptr, nullptr, scratch, 72);
+    WgradDesc d;
+    lstm_wgrad_op(d, x, cx, ldx, h_prev, C, dG, dW, db, B, H, W, tcount, ts_x, ts_h, ts_dG);
+    d.dy_absmax = scratch; d.dy_absmax_stride = 72;
+    return run_wgrad(d, (hipStream_t)stream, nullptr, 0);
 }
 // ... with three bf16 pieces per operand and six MFMAs per product (fp32-grade, fp32's exponent range; the bf16x6 mode's weight gradient)
 extern "C" int pivp_wgrad5x5_bf16x6_batch(const float* x, int cx, int ldx, const float* h_prev, int C, const float* dG, float* dW, float* db,
                                           int B, int H, int W, int tcount, long long ts_x, long long ts_h, long long ts_dG, void* stream) {
     if (!x || !dG || !dW || C <= 0 || cx <= 0 || tcount < 1) return PIVP_ERR_BADARG;
-    return run_wgrad(0, x, cx, ldx, h_prev, C, C, cx + C, dG, 4 * C, 4 * C, dW, B, H, W, H, W, 5, 2, 1, (hipStream_t)stream, db,
-                     nullptr, 3, tcount, ts_x, ts_h, ts_dG);
+    WgradDesc d;
+    lstm_wgrad_op(d, x, cx, ldx, h_prev, C, dG, dW, db, B, H, W, tcount, ts_x, ts_h, ts_dG);
+    return run_wgrad(d, (hipStream_t)stream, nullptr, 3);
 }
 // ... of a BATCH of timesteps in one launch (the sum over pixels runs over timesteps too): timestep j reads x + j * ts_x, h_prev + j * ts_h,
 // dG + j * ts_dG (byte strides, multiples of 16, may be negative: the backward sweep walks time downwards)
 extern "C" int pivp_wgrad5x5_bf16_batch(const float* x, int cx, int ldx, const float* h_prev, int C, const float* dG, float* dW, float* db,
                                         int B, int H, int W, int tcount, long long ts_x, long long ts_h, long long ts_dG, void* stream) {
     if (!x || !dG || !dW || C <= 0 || cx <= 0 || tcount < 1) return PIVP_ERR_BADARG;
-    return run_wgrad(0, x, cx, ldx, h_prev, C, C, cx + C, dG, 4 * C, 4 * C, dW, B, H, W, H, W, 5, 2, 1, (hipStream_t)stream, db,
-                     nullptr, 1, tcount, ts_x, ts_h, ts_dG);
+    WgradDesc d;
+    lstm_wgrad_op(d, x, cx, ldx, h_prev, C, dG, dW, db, B, H, W, tcount, ts_x, ts_h, ts_dG);
+    return run_wgrad(d, (hipStream_t)stream, nullptr, 1);
 }
 // ... with the block form chosen by the caller: 1 = four-wave blocks (32 channels x 32 columns, about one per CU: they co-reside with the backward sweep's
 // small kernels), 2 = eight-wave blocks (32 x 64: half the patch traffic per multiply-add), 0 = by size as pivp_wgrad5x5_bf16_batch does
 extern "C" int pivp_wgrad5x5_bf16_batch_form(const float* x, int cx, int ldx, const float* h_prev, int C, const float* dG, float* dW, float* db,
                                              int B, int H, int W, int tcount, long long ts_x, long long ts_h, long long ts_dG, int form, void* stream) {
     if (!x || !dG || !dW || C <= 0 || cx <= 0 || tcount < 1 || form < 0 || form > 2) return PIVP_ERR_BADARG;
-    return run_wgrad(0, x, cx, ldx, h_prev, C, C, cx + C, dG, 4 * C, 4 * C, dW, B, H, W, H, W, 5, 2, 1, (hipStream_t)stream, db,
-                     nullptr, 1, tcount, ts_x, ts_h, ts_dG, nullptr, nullptr, nullptr, 0, form);
+    WgradDesc d;
+    lstm_wgrad_op(d, x, cx, ldx, h_prev, C, dG, dW, db, B, H, W, tcount, ts_x, ts_h, ts_dG);
+    d.form = form;
+    return run_wgrad(d, (hipStream_t)stream, nullptr, 1);
 }
 static int convlstm_ln_cap(int H, int W, int C) {
     const int tiles = ((H * W + 31) / 32) * (C / 32), slices = ln_stats_slices(H * W * C);
@@ -764,11 +790,14 @@ extern "C" int pivp_convlstm_ln(const float* x, int cx, int ldx, const float* h_
         return PIVP_ERR_BADARG;
     if (C <= 0 || C % 32) return PIVP_ERR_BADARG;
     int np = 0;
-    int rc = run_convlstm(x, cx, ldx, h_prev, C, w, bias, c_in, c_out, h_out, B, H, W, (hipStream_t)stream, variant, nullptr,
-                          partials, convlstm_ln_cap(H, W, C), &np);
+    ConvLstmOpts o{};
+    o.variant = variant; o.ln_out.part = partials; o.ln_out.cap = convlstm_ln_cap(H, W, C); o.ln_out.nparts = &np;
+    int rc = run_convlstm(x, cx, ldx, h_prev, C, w, bias, c_in, c_out, h_out, B, H, W, (hipStream_t)stream, o);
     if (rc != PIVP_OK) return rc;
     if (fused) *fused = np > 0;
-    return run_layernorm(h_out, gamma, beta, ln_out, partials, B, H * W * C, C, ldo, eps, 0, (hipStream_t)stream, nullptr, np);
+    LayerNormOpts lo{};
+    lo.fused_nparts = np;
+    return run_layernorm(h_out, gamma, beta, ln_out, partials, B, H * W * C, C, ldo, eps, 0, (hipStream_t)stream, lo);
 }
 extern "C" long long pivp_layernorm_backward_scratch_floats(int B, int n) {
     if (B <= 0 || n <= 0) return PIVP_ERR_BADARG;
@@ -892,7 +921,7 @@ extern "C" int pivp_grad_unpack_bf16(const void* src_bf16, float* dst, long long
 extern "C" int pivp_conv3x3s2(const float* x, int cin, int ldx, const float* w, const float* bias, float* out, int cout,
                               int ldo, int relu, int B, int Hin, int Win, void* stream) {
     if (!x || !w || !out) return PIVP_ERR_BADARG;
-    return run_conv3x3s2(x, cin, ldx, w, bias, out, cout, ldo, relu, B, Hin, Win, (hipStream_t)stream);
+    return run_conv3x3s2(x, cin, ldx, w, bias, out, cout, ldo, relu, B, Hin, Win, (hipStream_t)stream, 0);
 }
 extern "C" int pivp_deconv3x3s2(const float* x, int cin, int ldx, const float* w, const float* bias, float* out, int cout,
                                 int ldo, int relu, int B, int Hin, int Win, void* stream) {
@@ -914,20 +943,26 @@ extern "C" int pivp_deconv3x3s2_ln(const float* h_raw, int c_ln, const float* x1
     const int n = Hin * Win * c_ln;
     int rc = ln_stats(h_raw, partials, B, n, (hipStream_t)stream);
     if (rc != PIVP_OK) return rc;
-    return run_deconv3x3s2_ln(h_raw, c_ln, x1, c1, ld1, w, bias, out, cout, ldo, relu, B, Hin, Win, (hipStream_t)stream, gamma, beta, partials,
-                              ln_stats_slices(n), eps, nullptr, 0, nullptr, precision);
+    const LnIn ln{gamma, beta, partials, ln_stats_slices(n), eps};
+    DeconvLnOpts o{};
+    o.x1 = x1; o.c1 = c1; o.ld1 = ld1; o.bf16 = precision;
+    return run_deconv3x3s2_ln(h_raw, c_ln, w, bias, out, cout, ldo, relu, B, Hin, Win, (hipStream_t)stream, ln, o);
 }
 // bf16-operand form (precision mode bf16): x and w rounded to bf16 on the way into LDS, fp32 accumulation / bias / ReLU.  Only maps that the
 // all-parities tile kernel takes (Hin % 8 == 0, Win % 16 == 0, at least 16 blocks) run in bf16; others fall to the fp32 kernels.
 extern "C" int pivp_deconv3x3s2_bf16(const float* x, int cin, int ldx, const float* w, const float* bias, float* out, int cout,
                                      int ldo, int relu, int B, int Hin, int Win, void* stream) {
     if (!x || !w || !out) return PIVP_ERR_BADARG;
-    return run_deconv3x3s2(x, cin, ldx, w, bias, out, cout, ldo, relu, B, Hin, Win, (hipStream_t)stream, 0, nullptr, 0, nullptr, 1);
+    DeconvOpts o{};
+    o.bf16 = 1;
+    return run_deconv3x3s2(x, cin, ldx, w, bias, out, cout, ldo, relu, B, Hin, Win, (hipStream_t)stream, o);
 }
 extern "C" int pivp_deconv3x3s2_bf16x3(const float* x, int cin, int ldx, const float* w, const float* bias, float* out, int cout,
                                        int ldo, int relu, int B, int Hin, int Win, void* stream) {   // split mode: two bf16 pieces per operand
     if (!x || !w || !out) return PIVP_ERR_BADARG;
-    return run_deconv3x3s2(x, cin, ldx, w, bias, out, cout, ldo, relu, B, Hin, Win, (hipStream_t)stream, 0, nullptr, 0, nullptr, 2);
+    DeconvOpts o{};
+    o.bf16 = 2;
+    return run_deconv3x3s2(x, cin, ldx, w, bias, out, cout, ldo, relu, B, Hin, Win, (hipStream_t)stream, o);
 }
 // two fp16 pieces per operand, three MFMAs per product (precision mode PIVP_PRECISION_FP16X3): scratch = 66 floats (the weights' partial maxima)
 extern "C" int pivp_deconv3x3s2_fp16x3(const float* x, int cin, int ldx, const float* w, const float* bias, float* out, int cout,
@@ -935,7 +970,9 @@ extern "C" int pivp_deconv3x3s2_fp16x3(const float* x, int cin, int ldx, const f
     if (!x || !w || !out || !scratch || cin <= 0 || cout <= 0) return PIVP_ERR_BADARG;
     int rc = absmax_partials(w, 9L * cin * cout, scratch, (hipStream_t)stream);
     if (rc != PIVP_OK) return rc;
-    return run_deconv3x3s2(x, cin, ldx, w, bias, out, cout, ldo, relu, B, Hin, Win, (hipStream_t)stream, 0, nullptr, 0, nullptr, 3, scratch);
+    DeconvOpts o{};
+    o.bf16 = 3; o.wscale_part = scratch;
+    return run_deconv3x3s2(x, cin, ldx, w, bias, out, cout, ldo, relu, B, Hin, Win, (hipStream_t)stream, o);
 }
 extern "C" int pivp_conv_enc0(const float* img, const float* w, const float* bias, float* out, int B, int H, int W, void* stream) {
     return conv_enc0(img, w, bias, out, B, H, W, (hipStream_t)stream);

@@ -1,4 +1,4 @@
-// Internal launcher interface between the C-ABI layer (pivp_c_api.hip) and the gfx950 kernels.
+// Internal launcher interface between the host layer (the launch helpers and per-op C ABI of pivp_c_api.hip, the plan of pivp_plan.hip) and the gfx950 kernels.
 // Internal data layout (DESIGN.md "Data layout in HBM"):
 //   * feature maps: NHWC fp32, `ld` = floats between consecutive pixels (lets a producer write
 //     straight into a channel slice of a skip-concat buffer; TM:569-576 never materialises a copy)

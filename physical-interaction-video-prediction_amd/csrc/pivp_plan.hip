@@ -13,10 +13,58 @@ using namespace pivp;
 
 namespace {
 
-struct LstmSpec { const char* name; int cx; int C; int level; };  // level: 2 -> H/2, 4 -> H/4, 8 -> H/8
+// ---- the layer tables: every per-layer size of this file comes from here ----
+struct MapSize { int H, W; };
+static MapSize level_map(const pivp_config_t& c, int level) { return {c.height / level, c.width / level}; }   // pyramid level: 1 = the frame, 2 -> H/2, 4 -> H/4, 8 -> H/8
+struct LstmSpec { const char* name; int cx; int C; int level; };
 const LstmSpec kLstm[7] = {
     {"lstm1", 32, 32, 2}, {"lstm2", 32, 32, 2}, {"lstm3", 32, 64, 4}, {"lstm4", 64, 64, 4},
     {"lstm5", 64, 128, 8}, {"lstm6", 128, 64, 4}, {"lstm7", 96, 32, 2}};
+static MapSize lstm_map(const pivp_config_t& c, int i) { return level_map(c, kLstm[i].level); }   // cell i's (H, W)
+// The five stride-2 3x3 layers in the order of their side-stream slots 7..11 and of Grads::wg_part: enc6, enc5, enc4 (transposed: anchors = their INPUT maps),
+// enc2, enc1 (convs).  c: channels in = out; ldx / ldo: pixel strides of the forward input / output (enc1 writes into cat6); ldy: of dY in the backward sweep
+// (a ring slot of its own, or the x columns of the next cell's input gradient); level: of the input map.
+struct EncSpec { int mode, layer, c, ldx, ldo, ldy, level; };
+const EncSpec kEnc[5] = {{1, 6, 64, 64, 64, 64, 2}, {1, 5, 96, 96, 96, 128, 4}, {1, 4, 128, 128, 128, 192, 8}, {0, 2, 64, 64, 64, 64, 4}, {0, 1, 32, 32, 96, 96, 2}};
+// parameter sizes: enc0 5x5 on 3 channels, enc3 1x1 on e2 (+ the smeared action / state), the others 3x3 with as many channels in as out
+const int kEncB[7] = {32, 32, 64, 64, 128, 96, 64};
+static long long enc_w_numel(const pivp_config_t& c, int i) {
+    return i == 0 ? 75 * 32 : i == 3 ? (64 + (c.use_state ? 10 : 0)) * 64LL : 9LL * kEncB[i] * kEncB[i];
+}
+// elements per sample of the nine LayerNorms: norm_enc0, hidden1..hidden7 (behind cell j - 1), norm_enc6
+static long long ln_numel(const pivp_config_t& c, int j) {
+    if (j == 0) return 32LL * (c.height / 2) * (c.width / 2);
+    if (j == 8) return 64LL * c.height * c.width;
+    const MapSize m = lstm_map(c, j - 1);
+    return (long long)kLstm[j - 1].C * m.H * m.W;
+}
+
+// ---- the precision mode: everything the plan derives from the PIVP_PRECISION_* integer ----
+struct Modes {
+    int precision;        // PIVP_PRECISION_*
+    int lstm_bf16;        // 1: the ConvLSTM forward runs on weight packs (every mode but F32)
+    int lstm_planes;      // the packs' form: 1 rounded to bf16; 2: split mode (hi / lo planes, three MFMAs per product); 3: three pieces, six MFMAs; -2: two fp16 pieces
+    int bwd_planes;       // the data gradients' form of lstm_planes (fp16 pieces in the sweep: they take dG times a power of two from its largest |value|)
+    int bf16_all;         // precision mode BF16: also the ConvLSTM gradients and the enc5 / enc6 transposed convs
+    bool x3_wgrad;        // fp16x3 mode: the ConvLSTM weight gradients with two fp16 pieces too (wgrad25_bf16_kernel<.., 2>, batched like the bf16 mode's), two timesteps per launch
+    bool x6_wgrad;        // bf16x6 mode: ... with three bf16 pieces (wgrad25_bf16_kernel<.., 3>), same schedule
+    // the transposed convs' precision code (DeconvOpts::bf16).  has_wabs: the layer keeps its weights' absmax partials (enc5 / enc6: pivp_plan::o_wabs), which the
+    // fp16-piece form needs; a layer without them (enc4) stays fp32 in that mode
+    int deconv_prec(bool has_wabs) const { return bf16_all ? 1 : lstm_planes == 2 ? 2 : (lstm_planes == -2 && has_wabs) ? 3 : 0; }
+};
+static Modes modes_of(int precision) {
+    Modes m{};
+    m.precision = precision;
+    m.lstm_bf16 = precision != PIVP_PRECISION_F32;
+    m.lstm_planes = precision == PIVP_PRECISION_BF16X3 ? 2 : precision == PIVP_PRECISION_BF16X6 ? 3 : precision == PIVP_PRECISION_FP16X3 ? -2 : 1;
+    m.bwd_planes = m.lstm_planes;
+    m.x3_wgrad = m.lstm_planes == -2;
+    m.x6_wgrad = m.lstm_planes == 3;
+    m.bf16_all = precision == PIVP_PRECISION_BF16;
+    return m;
+}
+// the two-image tile of the piece modes' kernels serves this map (an 8-wide map needs an even batch; otherwise the fp32 kernel takes it)
+static bool pair_tile_serves(int W, int B) { return W % 16 == 0 || B % 2 == 0; }
 
 struct ParamInfo { std::string name; long long numel; const float* ptr; float* grad; int group; };
 
@@ -103,16 +151,9 @@ struct pivp_plan {
     size_t o_zero, o_lnpart, o_lnpart2, o_linpart, o_masks, o_losspart;   // o_lnpart2: enc6 reads hidden7's partials while writing its own
     size_t o_wabs[2];                 // precision mode FP16X3: absmax_partials of the enc5 / enc6 weights (rebuilt at the start of a rollout)
     size_t o_wbf16[7];                // bf16 packs of the ConvLSTM weights (pivp_plan_set_precision), rebuilt at the start of a rollout
-    int lstm_bf16 = 0;                // 1: bf16 operands in the ConvLSTM forward (precision modes BF16 and BF16X3)
-    int precision = 0;                // PIVP_PRECISION_*
+    Modes mode = modes_of(PIVP_PRECISION_F32);      // pivp_plan_set_precision
     int pack_cache = 0, packs_valid = 0;   // pivp_plan_set_pack_cache: keep the precision modes' weight packs across rollouts until pivp_plan_params_changed
-    int bwd_planes = 1;               // the data gradients' form of lstm_planes
-    bool x3_wgrad = false;            // fp16x3 mode: the ConvLSTM weight gradients with two fp16 pieces too (wgrad25_bf16_kernel<.., 2>, batched like the bf16 mode's)
-    bool x6_wgrad = false;            // bf16x6 mode: ... with three bf16 pieces (wgrad25_bf16_kernel<.., 3>), same schedule
-    int lstm_planes = 1;              // 2: split mode (hi / lo planes, three MFMAs per product); 3: three pieces, six MFMAs (forward gate convs only: the
-                                      // backward sweep and every other op of that mode are the fp32 ones)
     int main_prio = -1;               // pivp_plan_set_main_priority: -1 = on unless a gradient listener is registered (data parallelism), 0 / 1 = as said
-    int bf16_all = 0;                 // precision mode BF16: also the ConvLSTM gradients and the enc5 / enc6 transposed convs
     int det = 0;                      // pivp_plan_set_deterministic: fixed-order forms of every sum of the sweep (no float atomics)
     bool lstm_started[7] = {};        // deterministic sweeps: the cell's weight-gradient slots hold this sweep's sums (before: stored, not added)
     pivp_grad_group_cb grad_cb = nullptr; void* grad_cb_user = nullptr;   // gradient-group-final notifications (t = 0 sweep)
@@ -180,9 +221,9 @@ static int wgrad_batch_env() {
 // dG ring slots per ring: timesteps t = T-2 .. 1 batch (t = 0, no h input, goes alone), as many slots as a launch may take timesteps.
 // (fp16-piece / three-piece weight gradients: TWO timesteps per launch on half the CUs -- measured grid, profiles/r04/fp16x3_train_wgrad_batch_slots.txt:
 // 8 per launch on every CU, what the bf16 mode does, leaves all of that work to the end of the sweep: 16.85 ms against 16.34)
-static int wg_cap_of(const pivp_plan* p) {
-    const int T = p->cfg.seq_len, e = wgrad_batch_env();
-    const int want = e ? e : (p->bf16_all ? WG_BATCH_MAX : (p->x3_wgrad || p->x6_wgrad) ? 2 : 1);
+static int wg_cap_of(int T, const Modes& m) {
+    const int e = wgrad_batch_env();
+    const int want = e ? e : (m.bf16_all ? WG_BATCH_MAX : (m.x3_wgrad || m.x6_wgrad) ? 2 : 1);
     int cap = T - 2 < 1 ? 1 : (T - 2 > WG_BATCH_MAX ? WG_BATCH_MAX : T - 2);
     if (want < cap) cap = want < 1 ? 1 : want;
     return cap;
@@ -190,15 +231,11 @@ static int wg_cap_of(const pivp_plan* p) {
 static void plan_layout(pivp_plan* p) {
     const pivp_config_t* cfg = &p->cfg;
     const int H = cfg->height, W = cfg->width, B = cfg->batch, T = cfg->seq_len;
-    const int cin3 = 64 + (cfg->use_state ? 10 : 0);
-    const long long encw[7] = {75 * 32, 9 * 32 * 32, 9 * 64 * 64, (long long)cin3 * 64, 9 * 128 * 128, 9 * 96 * 96, 9 * 64 * 64};
-    const long long lnsz[9] = {32LL * p->H2 * p->W2, 32LL * p->H2 * p->W2, 32LL * p->H2 * p->W2, 64LL * p->H4 * p->W4,
-                               64LL * p->H4 * p->W4, 128LL * p->H8 * p->W8, 64LL * p->H4 * p->W4, 32LL * p->H2 * p->W2,
-                               64LL * H * W};
     size_t off = 0;
     auto carve = [&](size_t n) { size_t o = off; off += (n + 63) / 64 * 64; return o; };
     const size_t HW = (size_t)H * W, HW2 = (size_t)p->H2 * p->W2, HW4 = (size_t)p->H4 * p->W4, HW8 = (size_t)p->H8 * p->W8;
-    const size_t hsz[7] = {HW2 * 32, HW2 * 32, HW4 * 64, HW4 * 64, HW8 * 128, HW4 * 64, HW2 * 32};
+    size_t hsz[7];      // floats per sample of a cell's h / c
+    for (int i = 0; i < 7; ++i) { const MapSize m = lstm_map(*cfg, i); hsz[i] = (size_t)m.H * m.W * kLstm[i].C; }
     const bool train = cfg->keep_activations != 0;
     p->o_zero = carve((size_t)B * HW2 * 32);
     p->o_lnpart = carve((size_t)B * ln_partial_cap((int)HW) * 4);
@@ -211,7 +248,7 @@ static void plan_layout(pivp_plan* p) {
     for (int i = 0; i < 7; ++i)       // 2-byte elements in a float-counted workspace
         p->o_wbf16[i] = carve(lstm_bf16_weight_elems(kLstm[i].cx + kLstm[i].C, 4 * kLstm[i].C) * 3 / 2 + 64);   // room for the three planes of PIVP_PRECISION_BF16X6
     p->nslabs = train ? T - 1 : 2;
-    p->wg_cap = wg_cap_of(p);
+    p->wg_cap = wg_cap_of(T, p->mode);
     p->eg_cap = T - 2 < 1 ? 1 : (T - 2 > WG_BATCH_MAX ? WG_BATCH_MAX : T - 2);      // whatever the precision mode: every mode batches these
     if (train) {
         // ... bounded by bytes: a ring slot holds the dY of all five layers (60 MB at B = 32 on 64 x 64 frames, 240 MB on 128 x 128), and there are
@@ -253,14 +290,16 @@ static void plan_layout(pivp_plan* p) {
             g.dG[i] = carve(M * 4 * kLstm[i].C * 2 * p->wg_cap);
             g.wt_lstm[i] = carve((size_t)25 * (kLstm[i].cx + kLstm[i].C) * 4 * kLstm[i].C);
             g.wtb_lstm[i] = carve(lstm_bf16_weight_elems(4 * kLstm[i].C, conv5x5_bf16_rows(kLstm[i].cx + kLstm[i].C)) * 3 / 2 + 64);   // up to three planes
-            g.wt_enc[i] = (i == 0 || i == 3) ? 0 : carve((size_t)encw[i]);
+            g.wt_enc[i] = (i == 0 || i == 3) ? 0 : carve((size_t)enc_w_numel(*cfg, i));
         }
         g.dg_absmax = carve((size_t)7 * 2 * p->wg_cap * 72);     // dG's partial maxima per (cell, ring, slot): the fp16-piece gradients' scales
         for (int i = 0; i < 7; ++i) g.lstm_part[i] = 0;
         g.det_heads = g.det_dv = g.det_enc3 = g.det_enc0 = g.det_stp = g.det_stp_acc = 0;
         if (p->det) {      // (pivp_plan_set_deterministic has checked that every cell's shape is served)
-            const int hh[7] = {p->H2, p->H2, p->H4, p->H4, p->H8, p->H4, p->H2}, wv[7] = {p->W2, p->W2, p->W4, p->W4, p->W8, p->W4, p->W2};
-            for (int i = 0; i < 7; ++i) g.lstm_part[i] = carve((size_t)lstm_wgrad_part_floats(kLstm[i].cx, kLstm[i].C, B, hh[i], wv[i], 0, DET_SLOT_J));
+            for (int i = 0; i < 7; ++i) {
+                const MapSize m = lstm_map(*cfg, i);
+                g.lstm_part[i] = carve((size_t)lstm_wgrad_part_floats(kLstm[i].cx, kLstm[i].C, B, m.H, m.W, 0, DET_SLOT_J));
+            }
             g.det_heads = carve((size_t)heads_bwd_det_floats(B, (int)HW, p->NP, p->NE));
             g.det_dv = carve((size_t)B * 256);
             g.det_enc3 = carve((size_t)enc3_state_bwd_det_floats(B, (int)HW8, cfg->use_state));
@@ -274,19 +313,16 @@ static void plan_layout(pivp_plan* p) {
         g.lnpart = carve((size_t)B * ln_bwd_slices((int)(64 * HW)) * 2);
         g.ln_ppart_floats = 0;
         for (int j = 0; j < 9; ++j) {
-            const size_t n = (size_t)ln_bwd_param_part_floats((int)lnsz[j]);
+            const size_t n = (size_t)ln_bwd_param_part_floats((int)ln_numel(*cfg, j));
             g.ln_ppart[j] = carve(n);
             g.ln_ppart_floats = g.ln_ppart[j] + n - g.ln_ppart[0];
         }
-        {   // slots 7..11 = enc6, enc5, enc4 (transposed, anchors = their INPUT maps), enc2, enc1 (stride-2 convs)
-            const int mode[5] = {1, 1, 1, 0, 0}, ci[5] = {64, 96, 128, 64, 32};
-            const int hin[5] = {p->H2, p->H4, p->H8, p->H4, p->H2}, win[5] = {p->W2, p->W4, p->W8, p->W4, p->W2};
-            g.wg_part_floats = 0;
-            for (int k = 0; k < 5; ++k) {
-                const size_t n = (size_t)conv_backward_part_floats(mode[k], ci[k], ci[k], B, hin[k], win[k]);
-                g.wg_part[k] = carve(n);
-                g.wg_part_floats = g.wg_part[k] + n - g.wg_part[0];      // carve() aligns: measure the region, not the sum
-            }
+        g.wg_part_floats = 0;
+        for (int k = 0; k < 5; ++k) {
+            const MapSize m = level_map(*cfg, kEnc[k].level);
+            const size_t n = (size_t)conv_backward_part_floats(kEnc[k].mode, kEnc[k].c, kEnc[k].c, B, m.H, m.W);
+            g.wg_part[k] = carve(n);
+            g.wg_part_floats = g.wg_part[k] + n - g.wg_part[0];      // carve() aligns: measure the region, not the sum
         }
     }
     p->ws_floats = (long long)off;
@@ -314,12 +350,9 @@ extern "C" int pivp_plan_create(const pivp_config_t* cfg, pivp_plan_t** out) {
     { const char* e = getenv("PIVP_LN_FOLD_TRAIN"); p->ln_fold_train = !(e && e[0] == '0'); }
 
     auto add = [&](const std::string& name, long long n) { p->params.push_back({name, n, nullptr, nullptr, grad_group_of(name)}); return (int)p->params.size() - 1; };
-    const int cin3 = 64 + (cfg->use_state ? 10 : 0);
-    const long long encw[7] = {75 * 32, 9 * 32 * 32, 9 * 64 * 64, (long long)cin3 * 64, 9 * 128 * 128, 9 * 96 * 96, 9 * 64 * 64};
-    const int encb[7] = {32, 32, 64, 64, 128, 96, 64};
     for (int i = 0; i < 7; ++i) {
-        p->i_enc_w[i] = add("enc" + std::to_string(i) + "/W", encw[i]);
-        p->i_enc_b[i] = add("enc" + std::to_string(i) + "/b", encb[i]);
+        p->i_enc_w[i] = add("enc" + std::to_string(i) + "/W", enc_w_numel(*cfg, i));
+        p->i_enc_b[i] = add("enc" + std::to_string(i) + "/b", kEncB[i]);
     }
     for (int i = 0; i < 7; ++i) {
         const LstmSpec& L = kLstm[i];
@@ -327,12 +360,9 @@ extern "C" int pivp_plan_create(const pivp_config_t* cfg, pivp_plan_t** out) {
         p->i_lstm_b[i] = add(std::string(L.name) + "/conv/b", 4 * L.C);
     }
     const char* lnn[9] = {"norm_enc0", "hidden1", "hidden2", "hidden3", "hidden4", "hidden5", "hidden6", "hidden7", "norm_enc6"};
-    const long long lnsz[9] = {32LL * p->H2 * p->W2, 32LL * p->H2 * p->W2, 32LL * p->H2 * p->W2, 64LL * p->H4 * p->W4,
-                               64LL * p->H4 * p->W4, 128LL * p->H8 * p->W8, 64LL * p->H4 * p->W4, 32LL * p->H2 * p->W2,
-                               64LL * H * W};
     for (int i = 0; i < 9; ++i) {
-        p->i_ln_g[i] = add(std::string(lnn[i]) + "/norm/gamma", lnsz[i]);
-        p->i_ln_b[i] = add(std::string(lnn[i]) + "/norm/beta", lnsz[i]);
+        p->i_ln_g[i] = add(std::string(lnn[i]) + "/norm/gamma", ln_numel(*cfg, i));
+        p->i_ln_b[i] = add(std::string(lnn[i]) + "/norm/beta", ln_numel(*cfg, i));
     }
     p->i_masks_w = add("masks/W", 64LL * p->NP);
     p->i_masks_b = add("masks/b", p->NP);
@@ -397,34 +427,21 @@ extern "C" int pivp_plan_set_precision(pivp_plan_t* plan, int precision) {
     if (!plan || precision < PIVP_PRECISION_F32 || precision > PIVP_PRECISION_FP16X3) return PIVP_ERR_BADARG;
     if (plan->det && !det_supported(plan, precision)) return PIVP_ERR_BADARG;      // a deterministic plan keeps to the modes its sweep serves
     if (precision == PIVP_PRECISION_BF16 || precision == PIVP_PRECISION_BF16X3) {   // (BF16X6: a layer its tile does not serve runs the fp32 kernel)
-        const int hs[7] = {plan->H2, plan->H2, plan->H4, plan->H4, plan->H8, plan->H4, plan->H2};
-        const int wsz[7] = {plan->W2, plan->W2, plan->W4, plan->W4, plan->W8, plan->W4, plan->W2};
         for (int i = 0; i < 7; ++i) {
+            const MapSize m = lstm_map(plan->cfg, i);
             IgemmDesc d;
             memset(&d, 0, sizeof(d));
             d.ksize = 5; d.pad = 2; d.in_step = 1; d.C = kLstm[i].C; d.c0 = kLstm[i].cx; d.c1 = kLstm[i].C;
-            d.ld0 = 4; d.ld1 = 4; d.B = plan->cfg.batch; d.Hin = hs[i]; d.Win = wsz[i];
+            d.ld0 = 4; d.ld1 = 4; d.B = plan->cfg.batch; d.Hin = m.H; d.Win = m.W;
             if (!convlstm_bf16_ok(d)) return PIVP_ERR_BADARG;
         }
     }
-    pivp_plan& m = *plan;
-    struct Modes { int lstm_bf16, lstm_planes, bwd_planes, bf16_all, precision; bool x3_wgrad, x6_wgrad; };
-    const Modes old{m.lstm_bf16, m.lstm_planes, m.bwd_planes, m.bf16_all, m.precision, m.x3_wgrad, m.x6_wgrad};
-    m.lstm_bf16 = precision != PIVP_PRECISION_F32;
-    m.lstm_planes = precision == PIVP_PRECISION_BF16X3 ? 2 : precision == PIVP_PRECISION_BF16X6 ? 3 : precision == PIVP_PRECISION_FP16X3 ? -2 : 1;
-    m.bwd_planes = m.lstm_planes;          // fp16 pieces in the sweep: the data gradients take dG times a power of two from its largest |value|
-    m.x3_wgrad = m.lstm_planes == -2;      // ... and the weight gradients two fp16 pieces, two timesteps per launch
-    m.x6_wgrad = m.lstm_planes == 3;       // three-piece mode: the weight gradients with three bf16 pieces, same schedule
-    m.bf16_all = precision == PIVP_PRECISION_BF16;
-    m.precision = precision;
     // The dG rings' depth follows the precision, so the order is set_precision -> workspace_bytes -> set_workspace (include/pivp_hip.h).  With a
     // workspace already bound the layout it was sized for stays; a mode that needs deeper rings than it has is refused, not run short.
-    if (m.ws && m.has_grads && wg_cap_of(plan) > m.wg_cap) {
-        m.lstm_bf16 = old.lstm_bf16; m.lstm_planes = old.lstm_planes; m.bwd_planes = old.bwd_planes; m.bf16_all = old.bf16_all;
-        m.precision = old.precision; m.x3_wgrad = old.x3_wgrad; m.x6_wgrad = old.x6_wgrad;
-        return PIVP_ERR_STATE;
-    }
-    m.packs_valid = 0;
+    const Modes cand = modes_of(precision);
+    if (plan->ws && plan->has_grads && wg_cap_of(plan->cfg.seq_len, cand) > plan->wg_cap) return PIVP_ERR_STATE;
+    plan->mode = cand;
+    plan->packs_valid = 0;
     if (!plan->ws) plan_layout(plan);
     return PIVP_OK;
 }
@@ -434,18 +451,21 @@ extern "C" int pivp_plan_set_precision(pivp_plan_t* plan, int precision) {
 static bool det_supported(const pivp_plan* p, int precision) {
     if (precision != PIVP_PRECISION_F32 && precision != PIVP_PRECISION_BF16 && precision != PIVP_PRECISION_BF16X3) return false;
     const int B = p->cfg.batch;
-    const int hh[7] = {p->H2, p->H2, p->H4, p->H4, p->H8, p->H4, p->H2}, wv[7] = {p->W2, p->W2, p->W4, p->W4, p->W8, p->W4, p->W2};
-    for (int i = 0; i < 7; ++i) if (lstm_wgrad_part_floats(kLstm[i].cx, kLstm[i].C, B, hh[i], wv[i], 0, DET_SLOT_J) <= 0) return false;
-    const int mode[5] = {1, 1, 1, 0, 0}, ci[5] = {64, 96, 128, 64, 32};
-    const int hin[5] = {p->H2, p->H4, p->H8, p->H4, p->H2}, win[5] = {p->W2, p->W4, p->W8, p->W4, p->W2};
-    for (int k = 0; k < 5; ++k) if (!conv_backward_fixed_order(mode[k], ci[k], ci[k], B, hin[k], win[k])) return false;
+    for (int i = 0; i < 7; ++i) {
+        const MapSize m = lstm_map(p->cfg, i);
+        if (lstm_wgrad_part_floats(kLstm[i].cx, kLstm[i].C, B, m.H, m.W, 0, DET_SLOT_J) <= 0) return false;
+    }
+    for (const EncSpec& E : kEnc) {
+        const MapSize m = level_map(p->cfg, E.level);
+        if (!conv_backward_fixed_order(E.mode, E.c, E.c, B, m.H, m.W)) return false;
+    }
     return true;
 }
 extern "C" int pivp_plan_set_deterministic(pivp_plan_t* plan, int on) {
     if (!plan) return PIVP_ERR_BADARG;
     const int want = on ? 1 : 0;
     if (want == plan->det) return PIVP_OK;
-    if (want && !det_supported(plan, plan->precision)) return PIVP_ERR_BADARG;
+    if (want && !det_supported(plan, plan->mode.precision)) return PIVP_ERR_BADARG;
     if (plan->ws) {      // a bound workspace keeps its layout: switching on needs the slots it was sized with
         if (want && plan->has_grads && plan->g.det_heads == 0) return PIVP_ERR_STATE;
         plan->det = want;
@@ -469,8 +489,7 @@ extern "C" int pivp_plan_params_changed(pivp_plan_t* plan) {
     plan->packs_valid = 0;
     return PIVP_OK;
 }
-static int lstm_w_of(const pivp_plan_t* p, int i) { const int ws[7] = {p->W2, p->W2, p->W4, p->W4, p->W8, p->W4, p->W2}; return ws[i]; }
-extern "C" int pivp_plan_get_precision(const pivp_plan_t* plan) { return plan ? plan->precision : PIVP_ERR_BADARG; }
+extern "C" int pivp_plan_get_precision(const pivp_plan_t* plan) { return plan ? plan->mode.precision : PIVP_ERR_BADARG; }
 extern "C" long long pivp_plan_workspace_bytes(const pivp_plan_t* plan) { return plan ? plan->ws_floats * 4 : PIVP_ERR_BADARG; }
 extern "C" int pivp_plan_set_workspace(pivp_plan_t* plan, void* dptr, long long bytes) {
     if (!plan || !dptr || bytes < plan->ws_floats * 4 || ((uintptr_t)dptr & 255)) return PIVP_ERR_BADARG;
@@ -529,14 +548,20 @@ static int run_step(pivp_plan* p, int t, const float* prev, const float* action,
     auto cp = [&](int i) { return Sp ? ws + Sp->c[i] : ws + p->o_zero; };
     const int ln_cap = ln_partial_cap(H * W);   // partial slots per sample in lnp (see the workspace carve)
     int np = 0;
-    auto lstm = [&](int i, const float* x, int ldx, int hh, int wwid, const LnIn* ln_in = nullptr, float* part_out = nullptr) {
+    const Modes& md = p->mode;
+    // cell i on x; ln_in: x is the raw output of the cell in front, normalised while staged -- the partials of this cell's own output then go to part_out
+    auto lstm = [&](int i, const float* x, int ldx, const LnIn* ln_in = nullptr, float* part_out = nullptr) {
         const bool prof = p->prof_on && p->prof_used + 2 <= p->prof_ev.size();
         if (prof) (void)hipEventRecord(p->prof_ev[p->prof_used], s);
+        const MapSize m = lstm_map(c, i);
+        ConvLstmOpts o{};
+        if (train) o.gates_out = ws + S.gates[i];
         // the LayerNorm behind every ConvLSTM gets its statistics from the ConvLSTM epilogue (np partials per sample)
+        o.ln_out.part = part_out ? part_out : lnp; o.ln_out.cap = ln_cap; o.ln_out.nparts = &np;
+        if (md.lstm_bf16) { o.w_bf16 = reinterpret_cast<const unsigned short*>(ws + p->o_wbf16[i]); o.bf16_planes = md.lstm_planes; }
+        o.ln_in = ln_in;
         int rc = run_convlstm(x, kLstm[i].cx, ldx, hp(i), kLstm[i].C, P(p, p->i_lstm_w[i]), P(p, p->i_lstm_b[i]),
-                              cp(i), ws + S.c[i], ws + S.h[i], B, hh, wwid, s, 0, train ? ws + S.gates[i] : nullptr,
-                              part_out ? part_out : lnp, ln_cap, &np,
-                              p->lstm_bf16 ? reinterpret_cast<const unsigned short*>(ws + p->o_wbf16[i]) : nullptr, p->lstm_planes, ln_in);
+                              cp(i), ws + S.c[i], ws + S.h[i], B, m.H, m.W, s, o);
         if (prof) {
             (void)hipEventRecord(p->prof_ev[p->prof_used + 1], s);
             p->prof_layer[p->prof_used / 2] = i + (Sp ? 0 : 8);   // +8: first-step launch without the h half of K
@@ -545,63 +570,64 @@ static int run_step(pivp_plan* p, int t, const float* prev, const float* action,
         return rc;
     };
     auto ln = [&](int j, const float* x, float* out, int n, int C, int ldo, int relu, int fused_nparts) {
-        return run_layernorm(x, P(p, p->i_ln_g[j]), P(p, p->i_ln_b[j]), out, lnp, B, n, C, ldo, eps, relu, s,
-                             ws + S.lnstat + (size_t)j * B * 2, fused_nparts);
+        LayerNormOpts o{};
+        o.stat_out = ws + S.lnstat + (size_t)j * B * 2; o.fused_nparts = fused_nparts;
+        return run_layernorm(x, P(p, p->i_ln_g[j]), P(p, p->i_ln_b[j]), out, lnp, B, n, C, ldo, eps, relu, s, o);
     };
+    auto norm_in = [&](int j) { return LnIn{P(p, p->i_ln_g[j]), P(p, p->i_ln_b[j]), lnp, np, eps}; };      // norm j applied by its consumer, from the current partials
+    auto keep = [&](int j, float* out, int ld) { return NormKeep{out, ld, ws + S.lnstat + (size_t)j * B * 2}; };      // ... which a training plan has it write
     const int n2 = 32 * p->H2 * p->W2, n4 = 64 * p->H4 * p->W4, n8 = 128 * p->H8 * p->W8;
 
     // group 0 (TM:595): enc0 -> norm_enc0 -> relu   => cat7[:, 32:64]
     RC(conv_enc0(prev, P(p, p->i_enc_w[0]), P(p, p->i_enc_b[0]), ws + S.e0raw, B, H, W, s, lnp, ln_cap, &np));
     RC(ln(0, ws + S.e0raw, ws + S.cat7 + 32, n2, 32, 64, 1, np));
     // group 1 (TM:596): lstm1 -> hidden1 -> lstm2 -> hidden2 -> enc1 -> relu  => cat6[:, 64:96]
-    RC(lstm(0, ws + S.cat7 + 32, 64, p->H2, p->W2));
+    RC(lstm(0, ws + S.cat7 + 32, 64));
     // Inference rollouts in the split precision modes: hidden1 / hidden3 feed only lstm2 / lstm4, whose eight-wave kernels apply the norm while
     // they stage their patch (the partials of their own output go to the second buffer: their blocks finish while others still read the input's).
     float* const lnpA = ws + p->o_lnpart, * const lnpB = ws + p->o_lnpart2;
     auto other = [&](float* q) { return q == lnpA ? lnpB : lnpA; };
-    const bool fold_l2 = !train && p->lstm_bf16 && np > 0 && convlstm_ln_in_ok(p->lstm_planes, 32, 32, 32, B, p->H2, p->W2) &&
+    const bool fold_l2 = !train && md.lstm_bf16 && np > 0 && convlstm_ln_in_ok(md.lstm_planes, 32, 32, 32, B, p->H2, p->W2) &&
                          (long)B * (p->H2 / 8) * (p->W2 / 16) >= 128;
     if (fold_l2) {
-        const LnIn li{P(p, p->i_ln_g[1]), P(p, p->i_ln_b[1]), lnp, np, eps};
+        const LnIn li = norm_in(1);
         float* q = other(lnp);
-        RC(lstm(1, ws + S.h[0], 32, p->H2, p->W2, &li, q));
+        RC(lstm(1, ws + S.h[0], 32, &li, q));
         lnp = q;
     } else {
         RC(ln(1, ws + S.h[0], ws + S.n1, n2, 32, 32, 0, np));
-        RC(lstm(1, ws + S.n1, 32, p->H2, p->W2));
+        RC(lstm(1, ws + S.n1, 32));
     }
     // Inference rollouts: hidden2 / hidden4 feed only enc1 / enc2, so their norms are applied while those convs stage their input
     // (run_conv3x3s2_ln) instead of by a launch of their own; training keeps the materialised tensors (the backward sweep reads them).
     // Training plans take the same launch (round 6) and have it WRITE the normalised hidden2 / hidden4 (every input pixel of a stride-2 3x3 conv is the
     // tap (1..2, 1..2) of exactly one anchor) and the samples' (mean, rstd) for the backward sweep: two ln_apply launches per timestep less.
-    if (np > 0 && p->ln_fold_train && conv3x3s2_ln_ok(32, 32, B, p->H2, p->W2)) {
-        RC(run_conv3x3s2_ln(ws + S.h[1], 32, P(p, p->i_enc_w[1]), P(p, p->i_enc_b[1]), ws + S.cat6 + 64, 32, 96, 1, B, p->H2, p->W2, s,
-                            P(p, p->i_ln_g[2]), P(p, p->i_ln_b[2]), lnp, np, eps, nullptr,
-                            train ? ws + S.n2 : nullptr, 32, train ? ws + S.lnstat + (size_t)2 * B * 2 : nullptr));
-    } else if (!train && np > 0 && conv3x3s2_ln_ok(32, 32, B, p->H2, p->W2)) {
-        RC(run_conv3x3s2_ln(ws + S.h[1], 32, P(p, p->i_enc_w[1]), P(p, p->i_enc_b[1]), ws + S.cat6 + 64, 32, 96, 1, B, p->H2, p->W2, s,
-                            P(p, p->i_ln_g[2]), P(p, p->i_ln_b[2]), lnp, np, eps));
+    if (np > 0 && (p->ln_fold_train || !train) && conv3x3s2_ln_ok(32, 32, B, p->H2, p->W2)) {
+        Conv3x3LnOpts o{};
+        if (train) o.keep = keep(2, ws + S.n2, 32);
+        RC(run_conv3x3s2_ln(ws + S.h[1], 32, P(p, p->i_enc_w[1]), P(p, p->i_enc_b[1]), ws + S.cat6 + 64, 32, 96, 1, B, p->H2, p->W2, s, norm_in(2), o));
     } else {
         RC(ln(2, ws + S.h[1], ws + S.n2, n2, 32, 32, 0, np));
-        RC(run_conv3x3s2(ws + S.n2, 32, 32, P(p, p->i_enc_w[1]), P(p, p->i_enc_b[1]), ws + S.cat6 + 64, 32, 96, 1, B, p->H2, p->W2, s));
+        RC(run_conv3x3s2(ws + S.n2, 32, 32, P(p, p->i_enc_w[1]), P(p, p->i_enc_b[1]), ws + S.cat6 + 64, 32, 96, 1, B, p->H2, p->W2, s, 0));
     }
     // group 2 (TM:597)
-    RC(lstm(2, ws + S.cat6 + 64, 96, p->H4, p->W4));
-    const bool fold_l4 = !train && p->lstm_bf16 && np > 0 && convlstm_ln_in_ok(p->lstm_planes, 64, 64, 64, B, p->H4, p->W4) &&
+    RC(lstm(2, ws + S.cat6 + 64, 96));
+    const bool fold_l4 = !train && md.lstm_bf16 && np > 0 && convlstm_ln_in_ok(md.lstm_planes, 64, 64, 64, B, p->H4, p->W4) &&
                          (long)B * (p->H4 / 8) * (p->W4 / 16) >= 64;
     if (fold_l4) {
-        const LnIn li{P(p, p->i_ln_g[3]), P(p, p->i_ln_b[3]), lnp, np, eps};
+        const LnIn li = norm_in(3);
         float* q = other(lnp);
-        RC(lstm(3, ws + S.h[2], 64, p->H4, p->W4, &li, q));
+        RC(lstm(3, ws + S.h[2], 64, &li, q));
         lnp = q;
     } else {
         RC(ln(3, ws + S.h[2], ws + S.n3, n4, 64, 64, 0, np));
-        RC(lstm(3, ws + S.n3, 64, p->H4, p->W4));
+        RC(lstm(3, ws + S.n3, 64));
     }
     bool enc3_done = false;
     if (train && np > 0 && p->ln_fold_train && conv3x3s2_ln_ok(64, 64, B, p->H4, p->W4)) {
-        RC(run_conv3x3s2_ln(ws + S.h[3], 64, P(p, p->i_enc_w[2]), P(p, p->i_enc_b[2]), ws + S.e2, 64, 64, 1, B, p->H4, p->W4, s,
-                            P(p, p->i_ln_g[4]), P(p, p->i_ln_b[4]), lnp, np, eps, nullptr, ws + S.n4, 64, ws + S.lnstat + (size_t)4 * B * 2));
+        Conv3x3LnOpts o{};
+        o.keep = keep(4, ws + S.n4, 64);
+        RC(run_conv3x3s2_ln(ws + S.h[3], 64, P(p, p->i_enc_w[2]), P(p, p->i_enc_b[2]), ws + S.e2, 64, 64, 1, B, p->H4, p->W4, s, norm_in(4), o));
     } else
     if (!train && np > 0 && conv3x3s2_ln_ok(64, 64, B, p->H4, p->W4)) {
         // Inference: group 3 (TM:598) and the state predictor (TM:730) in enc2's epilogue (round 6): enc3_state_kernel's launch
@@ -613,18 +639,19 @@ static int run_step(pivp_plan* p, int t, const float* prev, const float* action,
             f3.e3 = ws + S.e3; f3.state_out = state_out; f3.use_state = c.use_state;
             enc3_done = true;
         }
-        RC(run_conv3x3s2_ln(ws + S.h[3], 64, P(p, p->i_enc_w[2]), P(p, p->i_enc_b[2]), ws + S.e2, 64, 64, 1, B, p->H4, p->W4, s,
-                            P(p, p->i_ln_g[4]), P(p, p->i_ln_b[4]), lnp, np, eps, &f3));
+        Conv3x3LnOpts o{};
+        o.fuse3 = &f3;
+        RC(run_conv3x3s2_ln(ws + S.h[3], 64, P(p, p->i_enc_w[2]), P(p, p->i_enc_b[2]), ws + S.e2, 64, 64, 1, B, p->H4, p->W4, s, norm_in(4), o));
     } else {
         RC(ln(4, ws + S.h[3], ws + S.n4, n4, 64, 64, 0, np));
-        RC(run_conv3x3s2(ws + S.n4, 64, 64, P(p, p->i_enc_w[2]), P(p, p->i_enc_b[2]), ws + S.e2, 64, 64, 1, B, p->H4, p->W4, s));
+        RC(run_conv3x3s2(ws + S.n4, 64, 64, P(p, p->i_enc_w[2]), P(p, p->i_enc_b[2]), ws + S.e2, 64, 64, 1, B, p->H4, p->W4, s, 0));
     }
     // group 3 (TM:598) + state predictor (TM:730)
     if (!enc3_done)
     RC(enc3_state(ws + S.e2, action, state_prev, P(p, p->i_enc_w[3]), P(p, p->i_enc_b[3]), P(p, p->i_cs_w), P(p, p->i_cs_b),
                   ws + S.e3, state_out, B, p->H8 * p->W8, c.use_state, s));
     // group 4 (TM:599)
-    RC(lstm(4, ws + S.e3, 64, p->H8, p->W8));
+    RC(lstm(4, ws + S.e3, 64));
     // (hidden5's norm was folded the same way into enc4's four-phase form and the motion head's Linear, which then has to run here, in front
     // of lstm6: the two consumers lost more than the launch saves, rollout 8.52 -> 8.60 ms.  It keeps its own launch.)
     RC(ln(5, ws + S.h[4], ws + S.n5, n8, 128, 128, 0, np));
@@ -633,16 +660,18 @@ static int run_step(pivp_plan* p, int t, const float* prev, const float* action,
     const bool fh = frame_head_pays(c.model_type, B, H, W, c.num_masks);
     const bool fh_fin = fh && c.model_type != PIVP_MODEL_DNA && frame_head_finishes(p->K5);
     bool partials_done = false;
-    if (fh_fin && !p->bf16_all && p->lstm_planes != 2) {
+    if (fh_fin && md.deconv_prec(false) == 0) {
         RC(run_deconv3x3s2_and_partials(ws + S.n5, 128, P(p, p->i_enc_w[4]), P(p, p->i_enc_b[4]), ws + S.e4, 128, 128, 1, B, p->H8, p->W8, s,
                                         P(p, p->i_head_w), ws + p->o_linpart, c.model_type == PIVP_MODEL_STP ? 1 : 0));
         partials_done = true;
-    } else
-    RC(run_deconv3x3s2(ws + S.n5, 128, 128, P(p, p->i_enc_w[4]), P(p, p->i_enc_b[4]), ws + S.e4, 128, 128, 1, B, p->H8, p->W8, s, 0,
-                       nullptr, 0, nullptr, p->bf16_all ? 1 : p->lstm_planes == 2 ? 2 : 0));
+    } else {
+        DeconvOpts o{};
+        o.bf16 = md.deconv_prec(false);
+        RC(run_deconv3x3s2(ws + S.n5, 128, 128, P(p, p->i_enc_w[4]), P(p, p->i_enc_b[4]), ws + S.e4, 128, 128, 1, B, p->H8, p->W8, s, o));
+    }
     // group 5 (TM:600): lstm6 -> hidden6 -> concat(., enc1) -> enc5 -> relu
-    RC(lstm(5, ws + S.e4, 128, p->H4, p->W4));
-    const int dprec = p->bf16_all ? 1 : p->lstm_planes == 2 ? 2 : p->lstm_planes == -2 ? 3 : 0;      // (-2: two fp16 pieces, fp32-grade)
+    RC(lstm(5, ws + S.e4, 128));
+    const int dprec = md.deconv_prec(true);      // enc5 / enc6 (3: two fp16 pieces, fp32-grade)
     // The norms of hidden6 / hidden7 feed only enc5 / enc6, whose tile kernel applies them while it stages its patch ([hidden6 | enc1],
     // [hidden7 | enc0] as two sources).
     // Training plans take the same launch and have it WRITE the normalised hidden6 / hidden7 (each pixel by the block that owns it) and the
@@ -665,28 +694,37 @@ static int run_step(pivp_plan* p, int t, const float* prev, const float* action,
             else rd.out = ws + S.kerns;
             finished = true;
         }
-        RC(run_deconv3x3s2_ln(ws + S.h[5], 64, ws + S.cat6 + 64, 32, 96, P(p, p->i_enc_w[5]), P(p, p->i_enc_b[5]), ws + S.e5, 96, 96, 1, B, p->H4, p->W4,
-                              s, P(p, p->i_ln_g[6]), P(p, p->i_ln_b[6]), lnp, np, eps, nullptr, 0, nullptr, dprec,
-                              train ? ws + S.cat6 : nullptr, 96, train ? ws + S.lnstat + (size_t)6 * B * 2 : nullptr, ws + p->o_wabs[0], &rd));
+        DeconvLnOpts o{};
+        o.x1 = ws + S.cat6 + 64; o.c1 = 32; o.ld1 = 96;
+        o.bf16 = dprec; o.wscale_part = ws + p->o_wabs[0];
+        if (train) o.keep = keep(6, ws + S.cat6, 96);
+        o.rider = &rd;
+        RC(run_deconv3x3s2_ln(ws + S.h[5], 64, P(p, p->i_enc_w[5]), P(p, p->i_enc_b[5]), ws + S.e5, 96, 96, 1, B, p->H4, p->W4, s, norm_in(6), o));
     } else {
         RC(ln(6, ws + S.h[5], ws + S.cat6, n4, 64, 96, 0, np));
-        RC(run_deconv3x3s2(ws + S.cat6, 96, 96, P(p, p->i_enc_w[5]), P(p, p->i_enc_b[5]), ws + S.e5, 96, 96, 1, B, p->H4, p->W4, s, 0,
-                           nullptr, 0, nullptr, dprec, ws + p->o_wabs[0]));
+        DeconvOpts o{};
+        o.bf16 = dprec; o.wscale_part = ws + p->o_wabs[0];
+        RC(run_deconv3x3s2(ws + S.cat6, 96, 96, P(p, p->i_enc_w[5]), P(p, p->i_enc_b[5]), ws + S.e5, 96, 96, 1, B, p->H4, p->W4, s, o));
     }
     // group 6 (TM:601): lstm7 -> hidden7 -> concat(., enc0) -> enc6 -> norm_enc6 -> relu
-    RC(lstm(6, ws + S.e5, 96, p->H2, p->W2));
+    RC(lstm(6, ws + S.e5, 96));
     if (np > 0 && fold_small((long long)B * n2) && deconv3x3s2_ln_ok(32, 32, 64, B, p->H2, p->W2)) {
         // enc6's blocks write the partials of norm_enc6 while others still read hidden7's: the second partial buffer
         float* lnp2 = other(lnp);
-        const int np_in = np;
-        RC(run_deconv3x3s2_ln(ws + S.h[6], 32, ws + S.cat7 + 32, 32, 64, P(p, p->i_enc_w[6]), P(p, p->i_enc_b[6]), ws + S.e6raw, 64, 64, 0, B, p->H2, p->W2,
-                              s, P(p, p->i_ln_g[7]), P(p, p->i_ln_b[7]), lnp, np_in, eps, lnp2, ln_cap, &np, dprec,
-                              train ? ws + S.cat7 : nullptr, 64, train ? ws + S.lnstat + (size_t)7 * B * 2 : nullptr, ws + p->o_wabs[1]));
+        const LnIn li = norm_in(7);      // (np as hidden7's producer left it: the launch overwrites it)
+        DeconvLnOpts o{};
+        o.x1 = ws + S.cat7 + 32; o.c1 = 32; o.ld1 = 64;
+        o.ln_out.part = lnp2; o.ln_out.cap = ln_cap; o.ln_out.nparts = &np;
+        o.bf16 = dprec; o.wscale_part = ws + p->o_wabs[1];
+        if (train) o.keep = keep(7, ws + S.cat7, 64);
+        RC(run_deconv3x3s2_ln(ws + S.h[6], 32, P(p, p->i_enc_w[6]), P(p, p->i_enc_b[6]), ws + S.e6raw, 64, 64, 0, B, p->H2, p->W2, s, li, o));
         lnp = lnp2;
     } else {
         RC(ln(7, ws + S.h[6], ws + S.cat7, n2, 32, 64, 0, np));
-        RC(run_deconv3x3s2(ws + S.cat7, 64, 64, P(p, p->i_enc_w[6]), P(p, p->i_enc_b[6]), ws + S.e6raw, 64, 64, 0, B, p->H2, p->W2, s, 0,
-                           lnp, ln_cap, &np, dprec, ws + p->o_wabs[1]));
+        DeconvOpts o{};
+        o.ln_out.part = lnp; o.ln_out.cap = ln_cap; o.ln_out.nparts = &np;
+        o.bf16 = dprec; o.wscale_part = ws + p->o_wabs[1];
+        RC(run_deconv3x3s2(ws + S.cat7, 64, 64, P(p, p->i_enc_w[6]), P(p, p->i_enc_b[6]), ws + S.e6raw, 64, 64, 0, B, p->H2, p->W2, s, o));
     }
     // heads (TM:711-728).  One launch (csrc/frame_head.hip) for norm_enc6 + relu + the 1x1 heads + the motion head's finisher + flat softmax +
     // transform + compositing, behind the Linear's partial sums: bit-identical to the four launches below it, which remain for geometries
@@ -766,20 +804,20 @@ static int rollout_prepare_packs(pivp_plan* plan, hipStream_t s) {
     // The precision modes' weight packs: rebuilt at the start of every rollout (the parameters may have changed since the last call: optimizer step,
     // checkpoint load) unless the caller keeps them -- pivp_plan_set_pack_cache(plan, 1) -- and reports every change with pivp_plan_params_changed.
     const bool repack = !(plan->pack_cache && plan->packs_valid);
-    if (repack && plan->lstm_planes == -2) {  // two fp16 pieces: the enc5 / enc6 weights' scales (their tile kernel splits the fp32 weights while it stages them)
+    const Modes& md = plan->mode;
+    if (repack && md.lstm_planes == -2) {  // two fp16 pieces: the enc5 / enc6 weights' scales (their tile kernel splits the fp32 weights while it stages them)
         RC(absmax_partials(P(plan, plan->i_enc_w[5]), 9L * 96 * 96, plan->ws + plan->o_wabs[0], s));
         RC(absmax_partials(P(plan, plan->i_enc_w[6]), 9L * 64 * 64, plan->ws + plan->o_wabs[1], s));
     }
-    if (repack && plan->lstm_bf16 && plan->lstm_planes == 1) {      // one bf16 plane: the seven packs in one launch
+    if (repack && md.lstm_bf16 && md.lstm_planes == 1) {      // one bf16 plane: the seven packs in one launch
         WeightPrepJob jobs[7];
         for (int i = 0; i < 7; ++i)
             jobs[i] = WeightPrepJob{1, P(plan, plan->i_lstm_w[i]), plan->ws + plan->o_wbf16[i], kLstm[i].cx + kLstm[i].C, 4 * kLstm[i].C, 4 * kLstm[i].C, 0};
         RC(weight_prep_batch(jobs, 7, s));
-    } else if (repack && plan->lstm_bf16)
+    } else if (repack && md.lstm_bf16)
         for (int i = 0; i < 7; ++i)
             RC(pack_lstm_bf16(P(plan, plan->i_lstm_w[i]), reinterpret_cast<unsigned short*>(plan->ws + plan->o_wbf16[i]),
-                              kLstm[i].cx + kLstm[i].C, 4 * kLstm[i].C, s, 0, plan->lstm_planes,
-                              0));
+                              kLstm[i].cx + kLstm[i].C, 4 * kLstm[i].C, s, 0, md.lstm_planes, 0));
     plan->packs_valid = 1;
     return PIVP_OK;
 }
@@ -930,11 +968,11 @@ static int backward_step(pivp_plan* p, int t, const float* prev, bool prev_has_g
     auto DIN = [&](int i, bool cur) -> float* { return ws + g.din[i] + (size_t)(i >= 5 ? (cur ? eq : eq_next) : (cur ? par : npar)) * g.din_sz[i]; };
     const int n2 = 32 * p->H2 * p->W2, n4 = 64 * p->H4 * p->W4, n8 = 128 * p->H8 * p->W8;
     float* lnpart = ws + g.lnpart;
-    const long long ln_n[9] = {n2, n2, n2, n4, n4, n8, n4, n2, 64LL * HW};   // elements per sample of norm_enc0, hidden1..7, norm_enc6
+    const Modes& md = p->mode;
     auto ln_finish = [&](int j) -> int {
         if (!p->ln_touched[j]) return PIVP_OK;
         p->ln_touched[j] = false;
-        return ln_bwd_params_reduce(ws + g.ln_ppart[j], G(p, p->i_ln_g[j]), G(p, p->i_ln_b[j]), B, (int)ln_n[j], s);
+        return ln_bwd_params_reduce(ws + g.ln_ppart[j], G(p, p->i_ln_g[j]), G(p, p->i_ln_b[j]), B, (int)ln_numel(c, j), s);
     };
     auto lnb = [&](int j, const float* dy, int lddy, const float* y, int ldy, const float* x, float* dx, int n, int C, int relu) -> int {
         RC(ln_backward(dy, lddy, y, ldy, x, ws + S.lnstat + (size_t)j * B * 2, P(p, p->i_ln_g[j]), lnpart, dx,
@@ -973,26 +1011,38 @@ static int backward_step(pivp_plan* p, int t, const float* prev, bool prev_has_g
         return ln_backward(dy, lddy, nullptr, 0, ws + S.h[i], lf[i].stat, lf[i].gamma, lnpart, nullptr,
                            G(p, p->i_ln_g[j]), G(p, p->i_ln_b[j]), B, n, C, 0, s, ws + g.ln_ppart[j]);
     };
-    auto lstmb = [&](int i, const float* x, int ldx, int hh, int wwid, const EpSpec* ep = nullptr) -> int {
+    auto lstmb = [&](int i, const float* x, int ldx, const EpSpec* ep = nullptr) -> int {
         const LstmSpec& L = kLstm[i];
+        const MapSize m = lstm_map(c, i);
         const int cin = L.cx + L.C, N = 4 * L.C;
-        const size_t dG1 = (size_t)B * hh * wwid * N;                      // floats of one timestep's dG
+        const size_t dG1 = (size_t)B * m.H * m.W * N;                      // floats of one timestep's dG
         float* ring = ws + g.dG[i] + (size_t)wg_ring * p->wg_cap * dG1;
         const float* h_prev = Sp ? ws + Sp->h[i] : nullptr;
+        // the piece modes' two-image tiles (data gradient, weight gradient) do not fit an 8-wide map with an odd batch: the fp32 kernels take the cell
+        const bool pieces_ok = pair_tile_serves(m.W, B);
+        float* const absmax_ring = ws + g.dg_absmax + (size_t)(i * 2 + wg_ring) * p->wg_cap * 72;      // dG's partial maxima, 72 floats per ring slot
         SideFork f;
         if (wg_slot == 0) {     // a new batch: the ring's previous weight-gradient launch (two batches ago) must have read it
             if (p->side && hipStreamWaitEvent(s, p->ev_ring_done[i][wg_ring], 0) != hipSuccess) return PIVP_ERR_LAUNCH;
             p->wg_x[i] = x; p->wg_h[i] = h_prev;
         }
-        RC(run_convlstm_backward(x, L.cx, ldx, h_prev, L.C, P(p, p->i_lstm_w[i]), ws + S.gates[i],
-                                 Sp ? ws + Sp->c[i] : ws + p->o_zero, ws + S.c[i], nullptr, L.C,
-                                 last_step ? nullptr : DIN(i, false) + L.cx, cin, ws + g.dc[i], last_step ? 0 : 1,
-                                 ring + (size_t)wg_slot * dG1, ws + g.wt_lstm[i], DIN(i, true), nullptr, nullptr, B, hh, wwid,
-                                 s, 1, (p->lstm_bf16 && ((p->bwd_planes != 3 && p->bwd_planes != -2) || wwid % 16 == 0 || B % 2 == 0)) ? reinterpret_cast<unsigned short*>(ws + g.wtb_lstm[i]) : nullptr, p->bwd_planes,
-                                 wg_flush ? fork_of(i, f) : nullptr, &lf[i],    // dW = null: only the fork's `ready` (behind the gate math) is used
-                                 t == 0 ? 1 : 0,
-                                 (p->bwd_planes == -2 || p->x3_wgrad) ? ws + g.dg_absmax + ((size_t)(i * 2 + wg_ring) * p->wg_cap + wg_slot) * 72 : nullptr,    // t = 0: nobody reads d h_{-1}
-                                 ep, p->det));
+        ConvLstmBwdArgs a{};
+        a.x = x; a.cx = L.cx; a.ldx = ldx; a.h_prev = h_prev; a.C = L.C; a.w = P(p, p->i_lstm_w[i]); a.gates = ws + S.gates[i];
+        a.c_old = Sp ? ws + Sp->c[i] : ws + p->o_zero; a.c_new = ws + S.c[i];
+        a.lda = L.C;      // (dh_a = null: formed from the norm behind the cell, a.ln)
+        if (!last_step) { a.dh_b = DIN(i, false) + L.cx; a.dc_valid = 1; }
+        a.ldb = cin; a.dc = ws + g.dc[i];
+        a.dG = ring + (size_t)wg_slot * dG1; a.wt = ws + g.wt_lstm[i]; a.d_in = DIN(i, true);
+        a.B = B; a.H = m.H; a.W = m.W;      // dW = null: the weight gradient is batched below; only the fork's `ready` (behind the gate math) is used
+        a.wt_ready = 1;
+        if (md.lstm_bf16 && ((md.bwd_planes != 3 && md.bwd_planes != -2) || pieces_ok)) a.wt_bf16 = reinterpret_cast<unsigned short*>(ws + g.wtb_lstm[i]);
+        a.bf16_planes = md.bwd_planes;
+        if (wg_flush) a.fork = fork_of(i, f);
+        a.ln = &lf[i];
+        a.dx_only = t == 0 ? 1 : 0;      // t = 0: nobody reads d h_{-1}
+        if (md.bwd_planes == -2 || md.x3_wgrad) a.dg_absmax = absmax_ring + (size_t)wg_slot * 72;
+        a.ep = ep; a.det = p->det;
+        RC(run_convlstm_backward(a, s));
         if (t == 0) RC(ln_finish(i + 1));       // the sweep's last timestep: the norm's partial parameter planes (written by the gate kernel) become its gradient
         if (!wg_flush) return PIVP_OK;
         // weight + bias gradient of the whole batch: timestep j of it reads slab (first - j) and ring slot j; on the side stream it
@@ -1000,6 +1050,10 @@ static int backward_step(pivp_plan* p, int t, const float* prev, bool prev_has_g
         hipStream_t sw = p->side ? p->side_of(i) : s;
         const int cnt = wg_slot + 1;
         int bias_done = 0;
+        WgradDesc d;
+        lstm_wgrad_geom(d, L.cx, L.C, B, m.H, m.W);
+        d.x0 = p->wg_x[i]; d.ld0 = ldx; d.x1 = p->wg_h[i]; d.dy = ring; d.dw = G(p, p->i_lstm_w[i]); d.db = G(p, p->i_lstm_b[i]);
+        d.tcount = cnt; d.ts_x0 = -slab_bytes; d.ts_x1 = -slab_bytes; d.ts_dy = (long long)dG1 * 4;
         if (p->det) {
             // deterministic sweeps: the fp32 slot form (wgrad5x5p) in every precision mode -- each launch adds into the cell's slots (the sweep's first
             // stores), the slots are summed in a fixed order once: t = 0 has no h operand and cuts the slots another way, so the batches with h are
@@ -1007,23 +1061,22 @@ static int backward_step(pivp_plan* p, int t, const float* prev, bool prev_has_g
             // (the slot form takes every shape pivp_plan_set_deterministic admits, and it sums the columns of dG itself: bias_done is always set)
             float* part = ws + g.lstm_part[i];
             if (t == 0 && p->lstm_started[i])
-                RC(lstm_wgrad_reduce(L.cx, L.C, 1, part, G(p, p->i_lstm_w[i]), G(p, p->i_lstm_b[i]), B, hh, wwid, sw, 0, DET_SLOT_J));
-            RC(run_wgrad(0, p->wg_x[i], L.cx, ldx, p->wg_h[i], L.C, L.C, cin, ring, N, N, G(p, p->i_lstm_w[i]), B, hh, wwid, hh, wwid, 5, 2, 1, sw,
-                         G(p, p->i_lstm_b[i]), &bias_done, 0, cnt, -slab_bytes, -slab_bytes, (long long)dG1 * 4, part, nullptr, nullptr, 0, 0,
-                         (t == 0 || !p->lstm_started[i]) ? 1 : 0, 0, DET_SLOT_J));
+                RC(lstm_wgrad_reduce(L.cx, L.C, 1, part, G(p, p->i_lstm_w[i]), G(p, p->i_lstm_b[i]), B, m.H, m.W, sw, 0, DET_SLOT_J));
+            d.part = part; d.part_overwrite = (t == 0 || !p->lstm_started[i]) ? 1 : 0;
+            d.slot_j = DET_SLOT_J;
+            RC(run_wgrad(d, sw, &bias_done, 0));
             if (t == 0)
-                RC(lstm_wgrad_reduce(L.cx, L.C, p->wg_h[i] ? 1 : 0, part, G(p, p->i_lstm_w[i]), G(p, p->i_lstm_b[i]), B, hh, wwid, sw, 0, DET_SLOT_J));
+                RC(lstm_wgrad_reduce(L.cx, L.C, p->wg_h[i] ? 1 : 0, part, G(p, p->i_lstm_w[i]), G(p, p->i_lstm_b[i]), B, m.H, m.W, sw, 0, DET_SLOT_J));
             else p->lstm_started[i] = true;
-        } else
-        RC(run_wgrad(0, p->wg_x[i], L.cx, ldx, p->wg_h[i], L.C, L.C, cin, ring, N, N, G(p, p->i_lstm_w[i]), B, hh, wwid, hh, wwid, 5, 2, 1, sw,
-                     G(p, p->i_lstm_b[i]), &bias_done, p->bf16_all ? 1 : (p->x6_wgrad && (wwid % 16 == 0 || B % 2 == 0)) ? 3 : 0, cnt, -slab_bytes, -slab_bytes,
-                     (long long)dG1 * 4, nullptr, nullptr,
-                     // (fp16 pieces; an 8-wide map with an odd batch does not fit that kernel's two-image tiles: the fp32 kernel takes the batch)
-                     (p->x3_wgrad && (wwid % 16 == 0 || B % 2 == 0)) ? ws + g.dg_absmax + (size_t)(i * 2 + wg_ring) * p->wg_cap * 72 : nullptr, 72,
-                     (long)B * c.height * c.width > 32L * 64 * 64 ? 2 : 0));      // (frames above 64 x 64 x 32: the eight-wave weight gradient on every layer, WgradDesc::form)
+        } else {
+            if (md.x3_wgrad && pieces_ok) d.dy_absmax = absmax_ring;      // two fp16 pieces per operand
+            d.dy_absmax_stride = 72;
+            d.form = (long)B * c.height * c.width > 32L * 64 * 64 ? 2 : 0;      // (frames above 64 x 64 x 32: the eight-wave weight gradient on every layer)
+            RC(run_wgrad(d, sw, &bias_done, md.bf16_all ? 1 : (md.x6_wgrad && pieces_ok) ? 3 : 0));
+        }
         if (!bias_done && p->det) return PIVP_ERR_STATE;      // (unreachable: see above)
         if (!bias_done)
-            for (int j = 0; j < cnt; ++j) RC(bias_grad(ring + (size_t)j * dG1, N, N, B * hh * wwid, G(p, p->i_lstm_b[i]), sw));
+            for (int j = 0; j < cnt; ++j) RC(bias_grad(ring + (size_t)j * dG1, N, N, B * m.H * m.W, G(p, p->i_lstm_b[i]), sw));
         if (p->side && hipEventRecord(p->ev_ring_done[i][wg_ring], p->side_of(i)) != hipSuccess) return PIVP_ERR_LAUNCH;
         return PIVP_OK;
     };
@@ -1034,14 +1087,11 @@ static int backward_step(pivp_plan* p, int t, const float* prev, bool prev_has_g
     // timestep the side stream still has the previous timestep's last launches (lstm1's and enc0's weight gradients) in front of it, and the main stream
     // sat idle for ~40 us per timestep.
     SideFork fe;
-    const int encp = p->bf16_all ? 1 : 0;      // bf16 mode: enc1's data gradient (the transposed conv's tile kernel) on bf16 operands too
+    const int encp = md.bf16_all ? 1 : 0;      // bf16 mode: enc1's data gradient (the transposed conv's tile kernel) on bf16 operands too
     // Weight gradients of the stride-2 3x3 layers (k = 0..4: enc6, enc5, enc4, enc2, enc1): a step adds itself to the layer's open batch -- its dY sits in slot
     // eg_slot of the ring, its forward input one slab below the previous step's -- and the step that closes the batch launches ONE weight gradient over all of
     // them on the side stream (wgrad3x3s2.hip: per launch a block pays 37-150 KB of partial planes, per timestep nothing).  run_conv_backward (dW = null) has
     // recorded the fork's `ready` behind the final dY and in front of the data gradient.
-    struct EncSpec { int mode, layer, c, ldx, ldy, Hin, Win; };
-    const EncSpec kEnc[5] = {{1, 6, 64, 64, 64, p->H2, p->W2}, {1, 5, 96, 96, 128, p->H4, p->W4}, {1, 4, 128, 128, 192, p->H8, p->W8},
-                             {0, 2, 64, 64, 64, p->H4, p->W4}, {0, 1, 32, 32, 96, p->H2, p->W2}};
     auto enc_add = [&](int k, const float* x) { if (!p->enc_cnt[k]++) p->enc_x0[k] = x; };
     auto enc_flush = [&](int k, bool forked) -> int {
         const int cnt = p->enc_cnt[k];
@@ -1057,17 +1107,38 @@ static int backward_step(pivp_plan* p, int t, const float* prev, bool prev_has_g
                             hipStreamWaitEvent(p->side, p->ev_ready[7 + k][eg_ring], 0) != hipSuccess)) return PIVP_ERR_LAUNCH;
             sw = p->side_of(7 + k);
         }
-        const int Hout = E.mode ? 2 * E.Hin : E.Hin / 2, Wout = E.mode ? 2 * E.Win : E.Win / 2;
+        const MapSize m = level_map(c, E.level);
         int bias_done = 0;
-        RC(run_wgrad(E.mode, p->enc_x0[k], E.c, E.ldx, nullptr, 0, 0, E.c, dy0, E.ldy, E.c, G(p, p->i_enc_w[E.layer]), B, E.Hin, E.Win, Hout, Wout, 3, 1, 2, sw,
-                     G(p, p->i_enc_b[E.layer]), &bias_done, 0, cnt, -slab_bytes, 0, dy_step, ws + g.wg_part[k], &p->enc_desc[k], nullptr, 0, 0,
-                     p->enc_started[k] ? 0 : 1));
+        WgradDesc& d = p->enc_desc[k];      // kept: the sweep's last step reduces the partial planes by it
+        conv3x3s2_wgrad_geom(d, E.mode, E.c, E.c, B, m.H, m.W);
+        d.x0 = p->enc_x0[k]; d.ld0 = E.ldx; d.dy = dy0; d.ldy = E.ldy; d.dw = G(p, p->i_enc_w[E.layer]); d.db = G(p, p->i_enc_b[E.layer]);
+        d.tcount = cnt; d.ts_x0 = -slab_bytes; d.ts_dy = dy_step;
+        d.part = ws + g.wg_part[k]; d.part_overwrite = p->enc_started[k] ? 0 : 1;
+        RC(run_wgrad(d, sw, &bias_done, 0));
         if (!bias_done && p->det) return PIVP_ERR_STATE;      // (unreachable: set_deterministic admits only shapes wgrad3x3s2 serves, column sums included)
         if (!bias_done)
-            for (int j = 0; j < cnt; ++j) RC(bias_grad(dy0 + (size_t)j * (dy_step / 4), E.ldy, E.c, B * Hout * Wout, G(p, p->i_enc_b[E.layer]), sw));
+            for (int j = 0; j < cnt; ++j) RC(bias_grad(dy0 + (size_t)j * (dy_step / 4), E.ldy, E.c, B * d.Hy * d.Wy, G(p, p->i_enc_b[E.layer]), sw));
         if (p->side && hipEventRecord(p->ev_done[7 + k][eg_ring], sw) != hipSuccess) return PIVP_ERR_LAUNCH;
         p->enc_started[k] = true; p->enc_desc_valid[k] = true; p->enc_cnt[k] = 0;
         return PIVP_OK;
+    };
+    // data gradient of stride-2 3x3 layer k (dW = null: its weight gradient is batched by enc_add / enc_flush).  y: the layer's output when its ReLU mask is still
+    // to be applied to dy; dy_add: a second gradient into the same output
+    auto encb = [&](int k, const float* x, float* dy, const float* y, float* dx, int accum_dx, const float* dy_add = nullptr, int ld_add = 0) -> int {
+        const EncSpec& E = kEnc[k];
+        const MapSize m = level_map(c, E.level);
+        enc_add(k, x);
+        ConvBwdArgs a{};
+        a.mode = E.mode; a.x = x; a.cin = E.c; a.ldx = E.ldx; a.w = P(p, p->i_enc_w[E.layer]); a.dy = dy; a.cout = E.c; a.ldy = E.ldy;
+        a.y = y; a.ldyy = E.ldo;
+        a.wt = ws + g.wt_enc[E.layer]; a.dx = dx; a.lddx = E.c; a.accum_dx = accum_dx;
+        a.B = B; a.Hin = m.H; a.Win = m.W;
+        a.wt_ready = 1;
+        if (eg_flush) a.fork = fork_of(7 + k, fe);
+        a.dy_add = dy_add; a.ld_add = ld_add;
+        a.prec = encp;
+        RC(run_conv_backward(a, s));
+        return eg_flush ? enc_flush(k, true) : PIVP_OK;
     };
     // ---- heads (TM:711-728) ----
     if (has_go) {
@@ -1096,10 +1167,7 @@ static int backward_step(pivp_plan* p, int t, const float* prev, bool prev_has_g
         // group 6 (TM:601), reversed: norm_enc6 (+relu) <- enc6 deconv <- [hidden7 | enc0]
         RC(join(7));       // d e6raw
         RC(lnb(8, ws + g.e6, 64, ws + S.e6, 64, ws + S.e6raw, d_e6raw, 64 * HW, 64, 1));
-        enc_add(0, ws + S.cat7);
-        RC(run_conv_backward(1, ws + S.cat7, 64, 64, P(p, p->i_enc_w[6]), d_e6raw, 64, 64, nullptr, 0, ws + g.wt_enc[6], ws + g.cat7, 64, 0,
-                             nullptr, nullptr, B, p->H2, p->W2, s, 1, eg_flush ? fork_of(7, fe) : nullptr, nullptr, nullptr, nullptr, 0, encp));
-        if (eg_flush) RC(enc_flush(0, true));
+        RC(encb(0, ws + S.cat7, d_e6raw, nullptr, ws + g.cat7, 0));
     } else {
         if (eg_flush) RC(enc_flush(0, false));      // a batch whose last steps no frame gradient reaches
         // no gradient reaches this step's frame: only the recurrent paths are live
@@ -1140,25 +1208,19 @@ static int backward_step(pivp_plan* p, int t, const float* prev, bool prev_has_g
     // split-precision forms: 27 relu_mask / add_strided launches fewer per train step at B = 32); otherwise the separate pass runs as before.
     int ep_ok6 = 0, ep_ok5 = 0, ep_ok0 = 0;
     const EpSpec ep6{ws + S.e5, 96, 96, 1, &ep_ok6}, ep5{ws + S.e4, 128, 128, 1, &ep_ok5}, ep0{ws + g.cat7 + 32, 64, 32, 2, &ep_ok0};
-    RC(lstmb(6, ws + S.e5, 96, p->H2, p->W2, &ep6));
+    RC(lstmb(6, ws + S.e5, 96, &ep6));
     RC(done(1));
     RC(join(11));          // enc1's dY lives in d cat6, which enc5's data gradient rewrites
     // group 5 (TM:600): d e5 = x-part of lstm7's d_in (ReLU fused in enc5) <- enc5 deconv <- [hidden6 | enc1]
-    enc_add(1, ws + S.cat6);
-    RC(run_conv_backward(1, ws + S.cat6, 96, 96, P(p, p->i_enc_w[5]), DIN(6, true), 96, 128, ep_ok6 ? nullptr : ws + S.e5, 96, ws + g.wt_enc[5], d_cat6, 96, 0,
-                         nullptr, nullptr, B, p->H4, p->W4, s, 1, eg_flush ? fork_of(8, fe) : nullptr, nullptr, nullptr, nullptr, 0, encp));
-    if (eg_flush) RC(enc_flush(1, true));
+    RC(encb(1, ws + S.cat6, DIN(6, true), ep_ok6 ? nullptr : ws + S.e5, d_cat6, 0));
     RC(lnb_cell(5, d_cat6, 96, n4, 64));
     RC(join(9));           // enc4's dY = the x part of lstm6's d_in, likewise
-    RC(lstmb(5, ws + S.e4, 128, p->H4, p->W4, &ep5));
+    RC(lstmb(5, ws + S.e4, 128, &ep5));
     RC(done(2));
     // group 4 (TM:599): d e4 = x-part of lstm6's d_in <- enc4 deconv <- hidden5 (also read by the CDNA kernel generator)
-    enc_add(2, ws + S.n5);
-    RC(run_conv_backward(1, ws + S.n5, 128, 128, P(p, p->i_enc_w[4]), DIN(5, true), 128, 192, ep_ok5 ? nullptr : ws + S.e4, 128, ws + g.wt_enc[4], ws + g.n5, 128, 1,
-                         nullptr, nullptr, B, p->H8, p->W8, s, 1, eg_flush ? fork_of(9, fe) : nullptr, nullptr, nullptr, nullptr, 0, encp));
-    if (eg_flush) RC(enc_flush(2, true));
+    RC(encb(2, ws + S.n5, DIN(5, true), ep_ok5 ? nullptr : ws + S.e4, ws + g.n5, 1));
     RC(lnb_cell(4, ws + g.n5, 128, n8, 128));
-    RC(lstmb(4, ws + S.e3, 64, p->H8, p->W8));
+    RC(lstmb(4, ws + S.e3, 64));
     RC(done(3));
     // group 3 (TM:598) + state predictor (TM:730): d e3 = x-part of lstm5's d_in (ld 192)
     RC(join(10));          // d e2
@@ -1167,25 +1229,18 @@ static int backward_step(pivp_plan* p, int t, const float* prev, bool prev_has_g
                       G(p, p->i_cs_b), t > 0 ? ws + g.dstate + (size_t)(t - 1) * B * 5 : ws + g.dstate + (size_t)(c.seq_len - 1) * B * 5,
                       B, p->H8 * p->W8, c.use_state, s, 1, p->det ? ws + g.det_enc3 : nullptr));      // d e2 comes out masked by enc2's ReLU
     // group 2 (TM:597): enc2 conv (ReLU) <- hidden4 <- lstm4 <- hidden3 <- lstm3 <- enc1
-    enc_add(3, ws + S.n4);
-    RC(run_conv_backward(0, ws + S.n4, 64, 64, P(p, p->i_enc_w[2]), d_e2, 64, 64, nullptr, 0, ws + g.wt_enc[2], ws + g.n4, 64, 0,
-                         nullptr, nullptr, B, p->H4, p->W4, s, 1, eg_flush ? fork_of(10, fe) : nullptr, nullptr, nullptr, nullptr, 0, encp));
-    if (eg_flush) RC(enc_flush(3, true));
+    RC(encb(3, ws + S.n4, d_e2, nullptr, ws + g.n4, 0));
     RC(lnb_cell(3, ws + g.n4, 64, n4, 64));
-    RC(lstmb(3, ws + S.n3, 64, p->H4, p->W4));      // its data gradient's x columns = the dy of hidden3
+    RC(lstmb(3, ws + S.n3, 64));      // its data gradient's x columns = the dy of hidden3
     RC(lnb_cell(2, DIN(3, true), 128, n4, 64));
-    RC(lstmb(2, ws + S.cat6 + 64, 96, p->H4, p->W4));
+    RC(lstmb(2, ws + S.cat6 + 64, 96));
     RC(done(4));
     // group 1 (TM:596): enc1 conv (ReLU) <- hidden2 <- lstm2 <- hidden1 <- lstm1 <- enc0
-    enc_add(4, ws + S.n2);
-    RC(run_conv_backward(0, ws + S.n2, 32, 32, P(p, p->i_enc_w[1]), d_cat6 + 64, 32, 96, ws + S.cat6 + 64, 96, ws + g.wt_enc[1], ws + g.n2, 32, 0,
-                         nullptr, nullptr, B, p->H2, p->W2, s, 1, eg_flush ? fork_of(11, fe) : nullptr, nullptr, nullptr,
-                         DIN(2, true), 96, encp));      // d enc1 = enc5's concat part (in d cat6) + lstm3's x gradient, summed in the ReLU-mask pass
-    if (eg_flush) RC(enc_flush(4, true));
+    RC(encb(4, ws + S.n2, d_cat6 + 64, ws + S.cat6 + 64, ws + g.n2, 0, DIN(2, true), 96));      // d enc1 = enc5's concat part (in d cat6) + lstm3's x gradient, summed in the ReLU-mask pass
     RC(lnb_cell(1, ws + g.n2, 32, n2, 32));
-    RC(lstmb(1, ws + S.n1, 32, p->H2, p->W2));      // ... of hidden1
+    RC(lstmb(1, ws + S.n1, 32));      // ... of hidden1
     RC(lnb_cell(0, DIN(1, true), 64, n2, 32));
-    RC(lstmb(0, ws + S.cat7 + 32, 64, p->H2, p->W2, &ep0));
+    RC(lstmb(0, ws + S.cat7 + 32, 64, &ep0));
     if (!ep_ok0) RC(add_strided(ws + g.cat7 + 32, 64, DIN(0, true), 64, 32, px2, s));          // d enc0: from enc6's concat + from lstm1
     // group 0 (TM:595): norm_enc0 (+relu) <- enc0 conv <- frame
     RC(join(12));          // d e0raw
@@ -1237,6 +1292,7 @@ static int rollout_backward_sweep(pivp_plan_t* plan, const float* images, const 
     const Grads& g = plan->g;
     const float fscale = 2.0f / ((float)fr * (float)(T - ctx));              // d/d gen of mean-squared error / (T - ctx)
     const float sscale = 2.0f * 1e-4f / ((float)(B * 5) * (float)(T - ctx));
+    const Modes& md = plan->mode;
     RC(ensure_side(plan));
     RC(apply_main_prio(plan, s));
     {   // Timesteps per ConvLSTM weight-gradient launch (PIVP_WGRAD_BATCH overrides, 1..wg_cap).  fp32: 1 (batches arrive in bursts and
@@ -1244,7 +1300,7 @@ static int rollout_backward_sweep(pivp_plan_t* plan, const float* images, const 
         // fetches every operand tile once per 32 x 64 output slice, and what a block pays per launch (205 KB of atomics, the first tile's
         // latency) is amortised over the batch (csrc/wgrad_bf16.hip).
         const int e = wgrad_batch_env();
-        int gb = e ? e : ((plan->bf16_all || plan->x3_wgrad || plan->x6_wgrad) ? plan->wg_cap : 1);
+        int gb = e ? e : ((md.bf16_all || md.x3_wgrad || md.x6_wgrad) ? plan->wg_cap : 1);
         if (gb < 1) gb = 1;
         if (gb > plan->wg_cap) gb = plan->wg_cap;
         plan->wg_batch = gb;
@@ -1265,27 +1321,26 @@ static int rollout_backward_sweep(pivp_plan_t* plan, const float* images, const 
     RC(scaled_diff(gen_images + (size_t)(ctx - 1) * fr, images + (size_t)ctx * fr, ws + g.go + (size_t)(ctx - 1) * fr, (long)(T - ctx) * (long)fr, fscale, 0, s));
     // weights are constant during the sweep: the transposed packs for the data gradients, all twelve in one launch (7 + 5 launches before round 5)
     {
-        const int ecin[7] = {0, 32, 64, 0, 128, 96, 64};
         WeightPrepJob jobs[12];
         int n = 0;
         for (int i = 0; i < 7; ++i)
             jobs[n++] = WeightPrepJob{0, P(plan, plan->i_lstm_w[i]), ws + g.wt_lstm[i], 25, kLstm[i].cx + kLstm[i].C, 4 * kLstm[i].C, 1};
-        for (int i : {1, 2, 4, 5, 6}) jobs[n++] = WeightPrepJob{0, P(plan, plan->i_enc_w[i]), ws + g.wt_enc[i], 9, ecin[i], ecin[i], 0};
+        for (int k = 4; k >= 0; --k)      // (enc1, enc2, enc4, enc5, enc6)
+            jobs[n++] = WeightPrepJob{0, P(plan, plan->i_enc_w[kEnc[k].layer]), ws + g.wt_enc[kEnc[k].layer], 9, kEnc[k].c, kEnc[k].c, 0};
         RC(weight_prep_batch(jobs, n, s));
     }
-    if (plan->lstm_bf16 && plan->bwd_planes == 1) {      // bf16 mode: the ConvLSTM data gradients run on one-plane bf16 packs of those: one launch
+    if (md.lstm_bf16 && md.bwd_planes == 1) {      // bf16 mode: the ConvLSTM data gradients run on one-plane bf16 packs of those: one launch
         WeightPrepJob jobs[7];
         for (int i = 0; i < 7; ++i) {
             const int cin = kLstm[i].cx + kLstm[i].C;
             jobs[i] = WeightPrepJob{1, ws + g.wt_lstm[i], ws + g.wtb_lstm[i], 4 * kLstm[i].C, cin, conv5x5_bf16_rows(cin), 0};
         }
         RC(weight_prep_batch(jobs, 7, s));
-    } else if (plan->lstm_bf16)        // split modes: the hi / lo pair, the three pieces or the fp16 pieces (their own pack kernels, per layer)
+    } else if (md.lstm_bf16)        // split modes: the hi / lo pair, the three pieces or the fp16 pieces (their own pack kernels, per layer)
         for (int i = 0; i < 7; ++i) {
             const int cin = kLstm[i].cx + kLstm[i].C;
             RC(pack_lstm_bf16(ws + g.wt_lstm[i], reinterpret_cast<unsigned short*>(ws + g.wtb_lstm[i]), 4 * kLstm[i].C, cin, s,
-                              conv5x5_bf16_rows(cin), plan->bwd_planes,
-                              1));
+                              conv5x5_bf16_rows(cin), md.bwd_planes, 1));
         }
     bool has_go = false;
     int eq_next = 0;      // the enc dY ring slot of step t + 1 (unused at t = T - 2)
@@ -1399,11 +1454,11 @@ extern "C" long long pivp_get_tap(pivp_plan_t* plan, const char* name, int step,
         const F folded[] = {{"hidden2", 1, 2, S.n2, 32, HW2, 32}, {"hidden4", 3, 4, S.n4, 64, HW4, 64}, {"hidden6", 5, 6, S.cat6, 64, HW4, 96},
                             {"hidden7", 6, 7, S.cat7, 32, HW2, 64},
                             {"hidden1", 0, 1, S.n1, 32, HW2, 32, 1}, {"hidden3", 2, 3, S.n3, 64, HW4, 64, 1}};      // (the split modes: inside lstm2 / lstm4)
-        const bool split = plan->lstm_planes == 3 || plan->lstm_planes == -2;
+        const bool split = plan->mode.lstm_planes == 3 || plan->mode.lstm_planes == -2;
         for (const F& f : folded)
             if (strcmp(f.n, name) == 0 && (!f.split_only || split)) {
                 int rc = run_layernorm(ws + S.h[f.layer], P(plan, plan->i_ln_g[f.norm]), P(plan, plan->i_ln_b[f.norm]), ws + f.dst,
-                                       ws + plan->o_lnpart, B, f.C * f.hw, f.C, f.ld, c.ln_eps, 0, s, nullptr, 0);
+                                       ws + plan->o_lnpart, B, f.C * f.hw, f.C, f.ld, c.ln_eps, 0, s);
                 if (rc != PIVP_OK) return rc;
             }
     }
