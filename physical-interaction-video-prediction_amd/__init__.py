@@ -12,6 +12,7 @@ with importlib or through the `pivp_amd` alias module at the repo root:
 from .model import Model, config, using_config, reference_param_shapes, default_init, scheduled_sampling_masks
 from .checkpoint import save_npz, load_npz, to_internal, from_internal, save_optimizer_npz, load_optimizer_npz
 from . import dataset
+from .dataset import DeviceDataset, DeviceBatcher
 from . import planning
 from . import metrics
 from .metrics import frame_metrics, StepCurves
@@ -22,4 +23,4 @@ from .parallel import GradAllReduce, shard_batch
 __all__ = ['Model', 'config', 'using_config', 'reference_param_shapes', 'default_init',
            'scheduled_sampling_masks', 'save_npz', 'load_npz', 'to_internal', 'from_internal', 'concat_examples',
            'Adam', 'GradAllReduce', 'shard_batch', 'save_optimizer_npz', 'load_optimizer_npz', 'dataset', 'planning',
-           'metrics', 'frame_metrics', 'StepCurves']
+           'metrics', 'frame_metrics', 'StepCurves', 'DeviceDataset', 'DeviceBatcher']

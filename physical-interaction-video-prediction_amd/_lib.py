@@ -1,4 +1,4 @@
-"""ctypes binding of libpivp_hip.so (the C ABI declared in include/pivp_hip.h).
+"""ctypes binding of libpivp_hip.so (the C ABI declared in include/pivp_hip.h, and the data feed's entry points of include/pivp_data.h).
 
 There is no CPU fallback: if the library is missing or fails to load, `load()` raises."""
 import ctypes
@@ -147,6 +147,11 @@ SIGNATURES = {
     'pivp_wgrad5x5_f32_partition': (_i, [_i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp]),
 }
 
+# ... and every symbol include/pivp_data.h declares (the data feed, beside the model's ABI)
+DATA_SIGNATURES = {
+    'pivp_gather_batch': (_i, [_vp, _i, _vp, _vp, _vp, _i, _ll, _i, _i, _i, _vp, _vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -160,7 +165,7 @@ def load():
             "libpivp_hip.so is missing (%s). Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "or `python physical-interaction-video-prediction_amd/build.py`. There is no CPU fallback." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(DATA_SIGNATURES.items()):
         fn = getattr(lib, name)   # AttributeError if the ABI and the header drift apart
         fn.restype = res
         fn.argtypes = args
@@ -171,7 +176,7 @@ def load():
         shipped = _digest.source_digest()
     except OSError as e:      # a copied / installed package without csrc/ or the repo's include/: say what is missing instead of a bare open() error
         raise RuntimeError('cannot check libpivp_hip.so against its sources: %s is missing (the package needs csrc/*.hip, csrc/*.h and '
-                           '../include/pivp_hip.h next to it; there is no CPU fallback)' % e.filename) from e
+                           '../include/pivp_hip.h and pivp_data.h next to it; there is no CPU fallback)' % e.filename) from e
     built = lib.pivp_build_digest().decode()
     if built != shipped:
         raise RuntimeError(

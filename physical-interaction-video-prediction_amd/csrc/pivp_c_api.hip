@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "../../include/pivp_hip.h"
+#include "../../include/pivp_data.h"
 #include "pivp_host.h"
 
 using namespace pivp;
@@ -1051,6 +1052,10 @@ extern "C" int pivp_cem_update(const float* cost, float* actions, float* mean, f
 extern "C" int pivp_frame_metrics(const float* pred, const float* truth, int N, int C, int H, int W, int win, float sigma, float data_range,
                                   float* mse, float* ssim, void* stream) {
     return frame_metrics(pred, truth, N, C, H, W, win, sigma, data_range, mse, ssim, (hipStream_t)stream);
+}
+extern "C" int pivp_gather_batch(const void* frames, int frames_u8, const float* actions, const float* states, const int* index, int B,
+                                 long long N, int T, int H, int W, float* out_images, float* out_actions, float* out_states, void* stream) {
+    return gather_batch(frames, frames_u8, actions, states, index, B, N, T, H, W, out_images, out_actions, out_states, (hipStream_t)stream);
 }
 extern "C" int pivp_resize_images(const float* in, float* out, int planes, int Hin, int Win, int Hout, int Wout, float scale, void* stream) {
     return resize_bilinear(in, out, planes, Hin, Win, Hout, Wout, scale, (hipStream_t)stream);

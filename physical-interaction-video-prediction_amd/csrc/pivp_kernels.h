@@ -222,6 +222,11 @@ int cem_update(const float* cost, float* actions, float* mean, float* stdv, floa
 int frame_metrics(const float* pred, const float* truth, int N, int C, int H, int W, int win, float sigma, float data_range, float* mse,
                   float* ssim, hipStream_t s);
 
+// Batch gather out of a device-resident data set (csrc/batch_gather.hip): frames [N][T][H][W][3] (float32, or uint8 levels k = k / 255) + actions /
+// states [N][T][5], index [B] on the device -> images [T][B][3][H][W], actions / states [T][B][5].  One launch, bit-exact.
+int gather_batch(const void* frames, int frames_u8, const float* actions, const float* states, const int* index, int B, long long N, int T, int H,
+                 int W, float* out_images, float* out_actions, float* out_states, hipStream_t s);
+
 // One launch for the output side of a timestep (csrc/frame_head.hip): norm_enc6 + ReLU + the 1x1 heads + the motion head's finisher +
 // flat softmax + transform + compositing; bit-identical to heads_1x1 + cdna_kernels / stp_params + composite.
 struct FrameHeadArgs {

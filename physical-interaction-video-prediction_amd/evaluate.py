@@ -41,6 +41,11 @@ def build_parser():
     p.add_argument('--max_sequences', type=int, default=0, help='0: every sequence from data_index on')
     p.add_argument('--win', type=int, default=11)
     p.add_argument('--sigma', type=float, default=1.5)
+    # 1: the raw frames of the whole data set are uploaded once (dataset.DeviceDataset) and every batch is gathered on the device.  As float32
+    # the results are those of the host walk bit for bit; as uint8 a level k reaches the resize as k / 255 instead of being scaled after it,
+    # which moves a frame by an ulp or so
+    p.add_argument('--device_dataset', type=int, default=0, choices=(0, 1))
+    p.add_argument('--device_storage', default='auto', choices=ds.STORAGES)
     return p
 
 
@@ -85,6 +90,21 @@ def evaluate(args):
                   prefix='evaluate', device=device)
     load_npz(os.path.join(path, args.model_name), model)
     curves = StepCurves()
+    size = (args.image_height, args.image_width)
+    if args.device_dataset:
+        from . import _lib
+        lib = _lib.load()
+        dset = ds.DeviceDataset.from_dir(args.data_dir, device, storage=args.device_storage, raw=True)
+        for lo in range(args.data_index, stop, args.batch_size):
+            img, act, sta = dset.gather(list(range(lo, min(lo + args.batch_size, stop))))
+            T, B = img.shape[:2]
+            resized = torch.empty((T, B, 3) + size, dtype=torch.float32, device=img.device)
+            with torch.cuda.device(img.device):
+                _lib.check(lib.pivp_resize_images(img.data_ptr(), resized.data_ptr(), T * B * 3, dset.H, dset.W, size[0], size[1], dset.scale,
+                                                  torch.cuda.current_stream(img.device).cuda_stream), 'pivp_resize_images')
+            curves.add(model.evaluate([resized, act, sta], win=args.win, sigma=args.sigma))
+            model.reset_state()
+        return curves_to_arrays(curves.result()), stop - args.data_index
     for lo in range(args.data_index, stop, args.batch_size):
         batch = []
         for i in range(lo, min(lo + args.batch_size, stop)):

@@ -52,6 +52,11 @@ def build_parser():
     # 1: bit-reproducible training (Model(deterministic=True)) and host RNGs seeded with 0 -- shuffle, scheduled sampling, initial weights --
     # so that two runs over the same data write identical training-N / state-N arrays
     p.add_argument('--deterministic', type=int, default=0, choices=(0, 1))
+    # 1: the data set lives on the GPU as the files hold it (dataset.DeviceDataset) and every batch is one gather launch from the drawn sequence
+    # numbers (dataset.DeviceBatcher) instead of concat_examples + a host-to-device copy; same batches, same bits.  --device_storage: how the
+    # frames are held there, uint8 only for frames on the k/255 grid (auto: decided from the first sequences)
+    p.add_argument('--device_dataset', type=int, default=0, choices=(0, 1))
+    p.add_argument('--device_storage', default='auto', choices=ds.STORAGES)
     return p
 
 
@@ -78,9 +83,17 @@ def main(argv=None):
         dp = GradAllReduce()
     device = 'cuda:%d' % local_rank
 
-    images, actions, states = ds.load_dataset(args.data_dir)
-    (tr_i, tr_a, tr_s), (va_i, va_a, va_s) = ds.split_train_val(images, actions, states, args.train_val_split)
-    logger.info('Data set contain %d, %d will be use for training and %d will be use for validation', len(images), len(tr_i), len(va_i))
+    if args.device_dataset:
+        dset = ds.DeviceDataset.from_dir(args.data_dir, device, storage=args.device_storage)
+        train_set, valid_set = ds.split_index_ranges(dset.N, args.train_val_split)      # sequence numbers: the iterators draw those
+        n_all = dset.N
+        logger.info('Data set on %s as %s: %.1f MB', device, dset.storage, dset.nbytes / 1e6)
+    else:
+        images, actions, states = ds.load_dataset(args.data_dir)
+        (tr_i, tr_a, tr_s), (va_i, va_a, va_s) = ds.split_train_val(images, actions, states, args.train_val_split)
+        train_set, valid_set = ds.group_examples(tr_i, tr_a, tr_s), ds.group_examples(va_i, va_a, va_s)
+        n_all = len(images)
+    logger.info('Data set contain %d, %d will be use for training and %d will be use for validation', n_all, len(train_set), len(valid_set))
     model = Model(num_masks=args.num_masks, is_cdna=args.model_type == 'CDNA', is_dna=args.model_type == 'DNA',
                   is_stp=args.model_type == 'STP', use_state=args.use_state, scheduled_sampling_k=args.schedsamp_k,
                   num_frame_before_prediction=args.context_frames, prefix='train', device=device, keep_activations=True,
@@ -94,8 +107,8 @@ def main(argv=None):
     np.random.seed(0 if world > 1 or args.deterministic else None)      # identical shuffles on every rank; each takes its shard of the batch
     if world > 1:                                 # ... but its own scheduled-sampling draws (rank-offset stream)
         model.sampling_rng = np.random.RandomState(1 + rank)
-    train_iter = ds.SerialIterator(ds.group_examples(tr_i, tr_a, tr_s), args.batch_size, repeat=True, shuffle=True)
-    valid_iter = ds.SerialIterator(ds.group_examples(va_i, va_a, va_s), args.batch_size, repeat=False, shuffle=True)
+    train_iter = ds.SerialIterator(train_set, args.batch_size, repeat=True, shuffle=True)
+    valid_iter = ds.SerialIterator(valid_set, args.batch_size, repeat=False, shuffle=True)
     save_dir = os.path.join(args.output_dir, '%s-%s-%d' % (time.strftime('%Y%m%d-%H%M%S'), args.model_type, args.batch_size))
     local_losses, local_psnr, g_loss, g_psnr, g_loss_v, g_psnr_v = [], [], [], [], [], []
     stat = lambda a: [float(np.mean(a)), float(np.std(a)), float(np.min(a)), float(np.max(a)), float(np.median(a))]
@@ -103,7 +116,13 @@ def main(argv=None):
     itr, start = 0, None
     # Host feed (TM:937-950 is synchronous): batch t + 1 is drawn, laid out (concat_examples), sharded and copied from pinned memory on a
     # second stream while the GPU works on batch t; iterator order, shards and epoch bookkeeping are those of the plain loop
-    feeder = ds.DeviceFeeder(train_iter, rank=rank, world=world, device=device)
+    # --device_dataset 1: nothing to lay out or copy, the batch is gathered on the device inside get() (every rank validates the whole batch, as below)
+    if args.device_dataset:
+        feeder = ds.DeviceBatcher(dset, train_iter, rank=rank, world=world)
+        valid_batches = ds.DeviceBatcher(dset, valid_iter)
+    else:
+        feeder = ds.DeviceFeeder(train_iter, rank=rank, world=world, device=device)
+        valid_batches = None
     while itr < args.num_iterations:
         x, epoch, is_new_epoch = feeder.get()
         start = start or time.time()
@@ -132,12 +151,12 @@ def main(argv=None):
             if rank == 0:
                 logger.info('[TRAIN] Epoch #: %d  elapsed %.2fs  loss %.6f  psnr %.3f', epoch + 1, time.time() - start, g_loss[-1][0], g_psnr[-1][0])
             local_losses, local_psnr, start = [], [], None
-            if (epoch + 1) % args.validation_interval == 0 and len(va_i) > 0:
+            if (epoch + 1) % args.validation_interval == 0 and len(valid_set) > 0:
                 vl, vp = [], []
-                for vb in valid_iter:
-                    vi, va, vs = concat_examples(vb)
+                for vb in (valid_batches or valid_iter):
+                    vx = vb if valid_batches else list(concat_examples(vb))
                     with using_config('train', False):
-                        vl.append(float(model([vi, va, vs], itr))); vp.append(float(model.psnr_all))
+                        vl.append(float(model(vx, itr))); vp.append(float(model.psnr_all))
                     model.reset_state()
                 g_loss_v.append(stat(vl)); g_psnr_v.append(stat(vp))
                 valid_iter.reset()
