@@ -217,68 +217,54 @@ size_t lstm_bf16_weight_elems(int wcin, int N) { return (size_t)((wcin + 63) / 6
 // rows of the bf16 pack of a plain 5x5 convolution with N output channels: whole 128- or 64-column blocks
 int conv5x5_bf16_rows(int N) { return N % 128 == 0 ? N : (N + 63) / 64 * 64; }
 
-// w: fp32 K-inner packed [25][wcin/32][N][32]; wb: [ceil(wcin/64)][25][planes][Np][64] bf16 (Np >= N rows, the extra ones zero; 0 = N;
-// planes = 2: the hi / lo split of the split mode, lstm_bf16_weight_elems(wcin, Np) * 2 elements)
-// planes = 3: three bf16 pieces, fragment-major; planes = -2: two fp16 pieces of 256 w, fragment-major (lstm_bf16_weight_elems * 2 elements)
-int pack_lstm_bf16(const float* w, unsigned short* wb, int wcin, int N, hipStream_t s, int Np, int planes, int plain) {
+// w: fp32 K-inner packed [25][wcin/32][N][32]; wb: the pack in `form` (Np >= N rows, the extra ones zero; 0 = N), lstm_bf16_weight_elems(wcin, Np) elements per piece.
+// BF16, BF16X3 (the hi / lo split): [ceil(wcin/64)][25][pieces][Np][64] bf16.  BF16X6: three bf16 pieces, fragment-major.  FP16X3: two fp16 pieces of w times
+// the tensor's power-of-two scale, fragment-major, the scale's tail behind them.
+int pack_lstm_bf16(const float* w, unsigned short* wb, int wcin, int N, hipStream_t s, Operand form, int Np, int plain) {
     if (Np == 0) Np = N;
-    PIVP_CHECK_ARG(w && wb && wcin > 0 && wcin % 32 == 0 && N > 0 && Np >= N && ((planes >= 1 && planes <= 3) || planes == -2));
+    PIVP_CHECK_ARG(w && wb && wcin > 0 && wcin % 32 == 0 && N > 0 && Np >= N && form != Operand::F32);
     PIVP_CHECK_ARG(plain == 0 || plain == 1);      // a layout selector, not a flag: a future third layout must not be read as "plain"
-    const int pieces = planes == -2 ? 2 : planes;
+    const int pieces = operand_pieces(form);
     const long total = (long)lstm_bf16_weight_elems(wcin, Np) * pieces;
-    if (planes == -2)        // the tensor's scale first: 64 partial maxima into the pack's tail
+    if (operand_needs_scale(form))        // the tensor's scale first: 64 partial maxima into the pack's tail
         hipLaunchKernelGGL(absmax_partials_kernel, dim3(64), dim3(512), 0, s, w, (long)25 * wcin * N, reinterpret_cast<float*>(wb + total));
-    if (planes == 3 || planes == -2) {       // the three-piece kernels' fragment-major pack: the cell's (N = 4 C, gate-interleaved fragments) or a plain conv's
+    if (operand_l2_direct(form)) {       // the fragment-major pack: the cell's (N = 4 C, gate-interleaved fragments) or a plain conv's
         PIVP_CHECK_ARG(Np % 64 == 0 && (plain || (Np == N && N % 32 == 0)));
         const long nthreads = (long)lstm_bf16_weight_elems(wcin, Np) / 8;
         hipLaunchKernelGGL(pack_lstm_x6_kernel, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, s, w, wb, wcin, N, Np, plain, pieces, nthreads);
         return PIVP_LAUNCH_STATUS();
     }
-    hipLaunchKernelGGL(pack_lstm_bf16_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, w, wb, wcin, N, Np, planes, total);
+    hipLaunchKernelGGL(pack_lstm_bf16_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, w, wb, wcin, N, Np, pieces, total);
     return PIVP_LAUNCH_STATUS();
 }
 
 bool convlstm_bf16_ok(const IgemmDesc& d) { return bf16_geometry_ok(d) && d.C > 0 && d.C % 16 == 0; }
 bool convlstm_bf16x6_ok(const IgemmDesc& d) { return convlstm_bf16_ok(d) && d.Win % 16 == 0; }
 
-// d as for igemm_lstm (validated by the caller's igemm_validate(d, true) equivalent); wb = pack_lstm_bf16(d.w, ..., planes).
-int convlstm_bf16(const IgemmDesc& d, const unsigned short* wb, hipStream_t stream, int* ln_nparts, int nch, int planes) {
-    PIVP_CHECK_ARG(wb && convlstm_bf16_ok(d) && (nch == 0 || nch == 16 || (nch == 32 && d.C % 32 == 0)) && ((planes >= 1 && planes <= 3) || planes == -2));
+// d as for igemm_lstm (validated by the caller's igemm_validate(d, true) equivalent); wb = pack_lstm_bf16(d.w, ..., form).
+int convlstm_bf16(const IgemmDesc& d, const unsigned short* wb, hipStream_t stream, Operand form, int* ln_nparts, int nch) {
+    PIVP_CHECK_ARG(wb && convlstm_bf16_ok(d) && (nch == 0 || nch == 16 || (nch == 32 && d.C % 32 == 0)));
+    const bool l2d = operand_l2_direct(form), w16 = d.Win % 16 == 0;      // (an 8-wide map, an even batch: tiles of two images)
     // LayerNorm-on-load (d.in_g) exists in the L2-direct kernels only (launch_x6g): every other form would consume the raw tensor
-    PIVP_CHECK_ARG(!d.in_g || ((planes == 3 || planes == -2) && convlstm_bf16x6_ok(d)));
-    if (planes == 3 && !convlstm_bf16x6_ok(d)) {    // three pieces on an 8-wide map (an even batch: convlstm_bf16_ok): the L2-direct kernel on tiles of two images
-        const long b32 = d.C % 32 ? 0 : (long)(d.B / 2) * (d.Hin / TH) * (d.Win / 8) * (d.C / 32);
-        if ((nch == 32 && b32 > 0) || (nch == 0 && b32 >= pivp_cu_count())) return launch_x6g_w8<2, 4>(d, wb, stream, ln_nparts);
-        return launch_x6g_w8<4, 2>(d, wb, stream, ln_nparts);
+    PIVP_CHECK_ARG(!d.in_g || (l2d && w16));
+    // 32-channel blocks where asked for, or where they still give every CU a block (the L2-direct kernels: of this device; the ring kernels: 256), else 16-channel ones
+    const long b32 = d.C % 32 ? 0 : (long)(d.B / (w16 ? 1 : 2)) * (d.Hin / TH) * (d.Win / (w16 ? 16 : 8)) * (d.C / 32);
+    const bool c32 = nch == 32 || (nch == 0 && b32 >= (l2d ? pivp_cu_count() : 256));
+    // (the launchers below stand in the order their kernels have in the code object, which follows their first mention here: the order has no other meaning
+    // and may become the enum's once a byte-identical code object no longer matters)
+    if (l2d && !w16)
+        return form == Operand::BF16X6 ? (c32 ? launch_x6g_w8<2, 4>(d, wb, stream, ln_nparts) : launch_x6g_w8<4, 2>(d, wb, stream, ln_nparts))
+                                       : (c32 ? launch_x6g_w8<2, 4, 2>(d, wb, stream, ln_nparts) : launch_x6g_w8<4, 2, 2>(d, wb, stream, ln_nparts));
+    switch (form) {
+        case Operand::F32: break;
+        case Operand::FP16X3: return c32 ? launch_x6g<2, 4, 2>(d, wb, stream, ln_nparts) : launch_x6g<4, 2, 2>(d, wb, stream, ln_nparts);
+        case Operand::BF16X6: return c32 ? launch_x6g<2, 4>(d, wb, stream, ln_nparts) : launch_x6g<4, 2>(d, wb, stream, ln_nparts);      // weights straight from L2
+        case Operand::BF16X3:      // 32-channel blocks: two ring slots
+            return c32 ? launch_bf16<32, true, 2>(d, wb, stream, ln_nparts, d.C / 32, 1, 0) : launch_bf16<16, true, 2>(d, wb, stream, ln_nparts, d.C / 16, 1, 0);
+        case Operand::BF16:
+            return !c32 ? launch_bf16<16, true>(d, wb, stream, ln_nparts, d.C / 16, 1, 0) : launch_bf16<32, true>(d, wb, stream, ln_nparts, d.C / 32, 1, 0);
     }
-    if (planes == -2 && !convlstm_bf16x6_ok(d)) {   // two fp16 pieces on an 8-wide map (an even batch): the L2-direct kernel on tiles of two images
-        const long b32 = d.C % 32 ? 0 : (long)(d.B / 2) * (d.Hin / TH) * (d.Win / 8) * (d.C / 32);
-        if ((nch == 32 && b32 > 0) || (nch == 0 && b32 >= pivp_cu_count())) return launch_x6g_w8<2, 4, 2>(d, wb, stream, ln_nparts);
-        return launch_x6g_w8<4, 2, 2>(d, wb, stream, ln_nparts);
-    }
-    if (planes == -2) {   // two fp16 pieces, three MFMAs per product (wb = pack_lstm_bf16(..., planes = -2)): the L2-direct kernel, 16-wide tiles
-        PIVP_CHECK_ARG(convlstm_bf16x6_ok(d));
-        const long b32 = d.C % 32 ? 0 : (long)d.B * (d.Hin / TH) * (d.Win / 16) * (d.C / 32);
-        if ((nch == 32 && b32 > 0) || (nch == 0 && b32 >= pivp_cu_count())) return launch_x6g<2, 4, 2>(d, wb, stream, ln_nparts);
-        return launch_x6g<4, 2, 2>(d, wb, stream, ln_nparts);
-    }
-    if (planes == 3) {   // three pieces, 16-wide tiles
-        // weights straight from L2: 32-channel blocks where they give every CU a block, else 16-channel blocks
-        const long b32 = d.C % 32 ? 0 : (long)d.B * (d.Hin / TH) * (d.Win / 16) * (d.C / 32);
-        if ((nch == 32 && b32 > 0) || (nch == 0 && b32 >= pivp_cu_count())) return launch_x6g<2, 4>(d, wb, stream, ln_nparts);
-        return launch_x6g<4, 2>(d, wb, stream, ln_nparts);
-    }
-    if (planes == 2) {   // split mode: 32-channel blocks (two ring slots) when they still give every CU a block, else 16-channel ones
-        const int tw2 = d.Win % 16 == 0 ? 16 : 8, ti2 = tw2 == 16 ? 1 : 2;
-        const long b32 = d.C % 32 ? 0 : (long)(d.B / ti2) * (d.Hin / TH) * (d.Win / tw2) * (d.C / 32);
-        if (nch == 32 || (nch == 0 && b32 >= 256)) return launch_bf16<32, true, 2>(d, wb, stream, ln_nparts, d.C / 32, 1, 0);
-        return launch_bf16<16, true, 2>(d, wb, stream, ln_nparts, d.C / 16, 1, 0);
-    }
-    const int tw = d.Win % 16 == 0 ? 16 : 8, ti_n = tw == 16 ? 1 : 2;
-    const long blocks32 = (long)(d.B / ti_n) * (d.Hin / TH) * (d.Win / tw) * (d.C / 32);
-    if (nch == 0) nch = (d.C % 32 || blocks32 < 256) ? 16 : 32;
-    return nch == 16 ? launch_bf16<16, true>(d, wb, stream, ln_nparts, d.C / 16, 1, 0)
-                     : launch_bf16<32, true>(d, wb, stream, ln_nparts, d.C / 32, 1, 0);
+    return PIVP_ERR_BADARG;
 }
 
 }  // namespace pivp

@@ -337,8 +337,16 @@ bool deconv_tile_ok(const IgemmDesc& d) {
 }
 
 // d as igemm_conv takes it for the transposed conv (validated by the caller); ln_nparts as there.
-int deconv_tile(const IgemmDesc& d, hipStream_t stream, int* ln_nparts, int prec) {
+int deconv_tile(const IgemmDesc& d, hipStream_t stream, int* ln_nparts) {
     PIVP_CHECK_ARG(deconv_tile_ok(d));
+    int prec = 0;      // the kernel's PREC
+    switch (d.operand) {
+        case Operand::F32: break;
+        case Operand::BF16: prec = 1; break;
+        case Operand::BF16X3: prec = 2; break;
+        case Operand::FP16X3: prec = 3; break;
+        case Operand::BF16X6: return PIVP_ERR_BADARG;      // (no three-piece form)
+    }
     constexpr int lds_f32 = (A_FL + 9 * B_FL) * 4;        // 64,512 (the bf16 images fit inside)
     static PerDeviceOnce once0, once2, once0n, once2n, once3, once3n;
     if (prec == 3 && (pivp_ensure_dyn_lds(once3, reinterpret_cast<const void*>(&deconv3x3s2_tile_kernel<3, false>), 2 * (A_HB + 9 * B_HB)) != PIVP_OK ||

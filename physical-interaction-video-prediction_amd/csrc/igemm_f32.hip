@@ -775,7 +775,7 @@ int igemm_conv(const IgemmDesc& d, hipStream_t stream, int* ln_nparts) {
     const int nt = d.N / 32;
     // transposed conv on maps that tile into 8 x 16 input patches: all four parities per block (deconv_tile.hip), unless the grid would be tiny
     if (deconv_tile_ok(d) && (long)d.B * (d.Hin / 8) * (d.Win / 16) * nt >= 16)
-        return deconv_tile(d, stream, ln_nparts, d.bf16);
+        return deconv_tile(d, stream, ln_nparts);
     const long full = (long)((d.M + 127) / 128) * d.nphase;   // blocks with BM = 128 and the whole N in one block
     int bt = -1, bks = 1;
     if (dgrad_choice(d, bt, bks)) {

@@ -19,11 +19,12 @@ bool fits31(long long v) { return v > 0 && v < (1LL << 31); }
 int run_convlstm(const float* x, int cx, int ldx, const float* h_prev, int C, const float* w, const float* bias,
                  const float* c_in, float* c_out, float* h_out, int B, int H, int W, hipStream_t s, const ConvLstmOpts& o) {
     const LnIn* const ln_in = o.ln_in;
-    const bool pieces = o.bf16_planes == 3 || o.bf16_planes == -2;
+    const bool l2d = operand_l2_direct(o.operand);
+    if ((o.w_bf16 != nullptr) != (o.operand != Operand::F32)) return PIVP_ERR_BADARG;
     IgemmDesc d;
     memset(&d, 0, sizeof(d));
     if (ln_in) {
-        if (!o.w_bf16 || !convlstm_ln_in_ok(o.bf16_planes, cx, ldx, C, B, H, W) || !ln_in->gamma || !ln_in->beta || !ln_in->part || ln_in->np <= 0 || ln_in->part == o.ln_out.part)
+        if (!convlstm_ln_in_ok(o.operand, cx, ldx, C, B, H, W) || !ln_in->gamma || !ln_in->beta || !ln_in->part || ln_in->np <= 0 || ln_in->part == o.ln_out.part)
             return PIVP_ERR_BADARG;
         d.in_g = ln_in->gamma; d.in_b = ln_in->beta; d.in_part = ln_in->part; d.in_np = ln_in->np; d.in_eps = ln_in->eps;
     }
@@ -40,17 +41,16 @@ int run_convlstm(const float* x, int cx, int ldx, const float* h_prev, int C, co
     d.out_step = 1; d.Hout = H; d.Wout = W;
     d.cstate_in = c_in; d.cstate_out = c_out; d.hout = h_out; d.C = C; d.gates_out = o.gates_out;
     d.ln_part = o.ln_out.part; d.ln_cap = o.ln_out.cap;
-    // w_bf16: the bf16 pack of w (pack_lstm_bf16) selects the bf16-operand kernel; variant then is its channels per block
-    // (three pieces: maps the three-plane tile does not serve -- 8 wide -- take the fp32 kernel, which is what that mode stands in for)
-    // (two fp16 pieces: 8-wide maps need an even batch for the tile to fit)
-    if (o.w_bf16 && pieces && !convlstm_bf16_ok(d)) return w ? igemm_lstm(d, s, 0, o.ln_out.nparts) : PIVP_ERR_BADARG;      // (an 8-wide map with an odd batch: the fp32 kernel)
-    if (o.w_bf16) return convlstm_bf16(d, o.w_bf16, s, o.ln_out.nparts, (pieces && o.variant != 16 && o.variant != 32) ? 0 : o.variant, o.bf16_planes);
+    // any form but F32 runs on w_bf16, the pack of w in that form (pack_lstm_bf16); variant then is the kernel's channels per block
+    // (the L2-direct forms: a map their tiles do not serve -- 8 wide with an odd batch -- takes the fp32 kernel, which is what those modes stand in for)
+    if (l2d && !convlstm_bf16_ok(d)) return w ? igemm_lstm(d, s, 0, o.ln_out.nparts) : PIVP_ERR_BADARG;
+    if (o.w_bf16) return convlstm_bf16(d, o.w_bf16, s, o.operand, o.ln_out.nparts, (l2d && o.variant != 16 && o.variant != 32) ? 0 : o.variant);
     return igemm_lstm(d, s, o.variant, o.ln_out.nparts);
 }
 
-// the eight-wave L2-direct kernels of the split modes take it: a 16-wide map, x contiguous in one 64-channel group, and a grid that picks those kernels
-bool convlstm_ln_in_ok(int planes, int cx, int ldx, int C, int B, int H, int W) {
-    return (planes == 3 || planes == -2) && cx <= 64 && ldx == cx && cx % 8 == 0 && C % 16 == 0 && H % 8 == 0 && W % 16 == 0;
+// the eight-wave L2-direct kernels take it: a 16-wide map, x contiguous in one 64-channel group, and a grid that picks those kernels
+bool convlstm_ln_in_ok(Operand form, int cx, int ldx, int C, int B, int H, int W) {
+    return operand_l2_direct(form) && cx <= 64 && ldx == cx && cx % 8 == 0 && C % 16 == 0 && H % 8 == 0 && W % 16 == 0;
 }
 int run_conv3x3s2(const float* x, int cin, int ldx, const float* w, const float* bias, float* out, int cout,
                   int ldo, int relu, int B, int Hin, int Win, hipStream_t s, int accum) {
@@ -118,14 +118,16 @@ static int deconv3x3s2_desc(IgemmDesc& d, const float* x0, int c0, int ld0, cons
     d.out_step = 2; d.Hout = 2 * Hin; d.Wout = 2 * Win; d.out = out; d.ldo = ldo; d.relu = relu;
     return PIVP_OK;
 }
+// the transposed conv's tile kernel has no three-piece form, and its fp16-piece form needs the weights' absmax partials
+static bool deconv_form_ok(Operand form, const float* wscale_part) { return form != Operand::BF16X6 && (!operand_needs_scale(form) || wscale_part); }
 int run_deconv3x3s2(const float* x, int cin, int ldx, const float* w, const float* bias, float* out, int cout,
                     int ldo, int relu, int B, int Hin, int Win, hipStream_t s, const DeconvOpts& o) {
-    if (o.bf16 == 3 && !o.wscale_part) return PIVP_ERR_BADARG;
+    if (!deconv_form_ok(o.operand, o.wscale_part)) return PIVP_ERR_BADARG;
     IgemmDesc d;
     int rc = deconv3x3s2_desc(d, x, cin, ldx, nullptr, 0, 0, w, bias, out, cout, ldo, relu, B, Hin, Win);
     if (rc != PIVP_OK) return rc;
     d.wscale_part = o.wscale_part;
-    d.bf16 = o.bf16;                // precision mode bf16: honoured by the all-parities tile kernel (deconv_tile.hip), fp32 otherwise
+    d.operand = o.operand;          // honoured by the all-parities tile kernel (deconv_tile.hip), fp32 otherwise
     d.accum = o.accum;
     d.ln_part = o.ln_out.part; d.ln_cap = o.ln_out.cap;
     return igemm_conv(d, s, o.ln_out.nparts);
@@ -163,8 +165,8 @@ int run_deconv3x3s2_ln(const float* h_raw, int c_ln, const float* w, const float
     IgemmDesc d;
     int rc = deconv3x3s2_desc(d, h_raw, c_ln, c_ln, o.x1, o.c1, o.ld1, w, bias, out, cout, ldo, relu, B, Hin, Win);
     if (rc != PIVP_OK) return rc;
-    if (o.bf16 == 3 && !o.wscale_part) return PIVP_ERR_BADARG;
-    d.bf16 = o.bf16; d.wscale_part = o.wscale_part;
+    if (!deconv_form_ok(o.operand, o.wscale_part)) return PIVP_ERR_BADARG;
+    d.operand = o.operand; d.wscale_part = o.wscale_part;
     d.in_g = ln.gamma; d.in_b = ln.beta; d.in_part = ln.part; d.in_np = ln.np; d.in_eps = ln.eps;
     d.ln_part = o.ln_out.part; d.ln_cap = o.ln_out.cap;
     d.in_out = keep.out; d.in_out_ld = keep.ld; d.in_stat_out = keep.stat;
@@ -175,7 +177,7 @@ int run_deconv3x3s2_ln(const float* h_raw, int c_ln, const float* w, const float
     rc = igemm_validate(d, false);
     if (rc != PIVP_OK) return rc;
     if (!deconv_tile_ok(d)) return PIVP_ERR_BADARG;
-    return deconv_tile(d, s, o.ln_out.nparts, o.bf16);
+    return deconv_tile(d, s, o.ln_out.nparts);
 }
 
 // stride-1 K x K "same" convolution through the generic kernel (used as the ConvLSTM data gradient)
@@ -226,12 +228,12 @@ static int conv5x5_bf16_desc(IgemmDesc& d, const float* x, int cin, int ldx, flo
     if (!accum && ldo == cout) d.ksplit_ok = 1;     // contiguous fresh output: the K-split path may be used; it needs a zeroed destination
     return PIVP_OK;
 }
-bool conv5x5_bf16_splits_k(int cin, int cout, int ldo, int B, int H, int W, int planes, int no_split) {
+bool conv5x5_bf16_splits_k(int cin, int cout, int ldo, int B, int H, int W, Operand form, int no_split) {
     if (no_split) return false;
     IgemmDesc d;
     static float dummy;
     if (conv5x5_bf16_desc(d, &dummy, cin, cin, &dummy, cout, ldo, 0, B, H, W) != PIVP_OK) return false;
-    return d.ksplit_ok && conv5x5_bf16_ksplit(d, planes) > 1;
+    return d.ksplit_ok && conv5x5_bf16_ksplit(d, form) > 1;
 }
 int run_conv5x5_bf16(const float* x, int cin, int ldx, const unsigned short* wb, float* out, int cout, int ldo, int accum,
                      int B, int H, int W, hipStream_t s, const Conv5x5Bf16Opts& o) {
@@ -242,13 +244,13 @@ int run_conv5x5_bf16(const float* x, int cin, int ldx, const unsigned short* wb,
     if (o.no_split) d.ksplit_ok = 0;      // deterministic sweeps: one block per output tile over the whole K (no atomics)
     d.wscale_part = o.ascale_part;
     if (ep && ep->applied) *ep->applied = 0;
-    if (ep && ep->src && ep->mode && !(d.ksplit_ok && conv5x5_bf16_ksplit(d, o.planes) > 1)) {
+    if (ep && ep->src && ep->mode && !(d.ksplit_ok && conv5x5_bf16_ksplit(d, o.operand) > 1)) {
         d.ep_src = ep->src; d.ep_ld = ep->ld; d.ep_cols = ep->cols < cout ? ep->cols : cout; d.ep_mode = ep->mode;
         if (ep->applied) *ep->applied = 1;
     }
-    if (d.ksplit_ok && !o.dest_zeroed && conv5x5_bf16_ksplit(d, o.planes) > 1 &&
+    if (d.ksplit_ok && !o.dest_zeroed && conv5x5_bf16_ksplit(d, o.operand) > 1 &&
         hipMemsetAsync(out, 0, (size_t)B * H * W * cout * 4, s) != hipSuccess) return PIVP_ERR_LAUNCH;
-    return conv5x5_bf16(d, wb, s, o.planes);
+    return conv5x5_bf16(d, wb, s, o.operand);
 }
 
 // ---- weight gradients ----
@@ -267,15 +269,15 @@ void conv3x3s2_wgrad_geom(WgradDesc& d, int mode, int cin, int cout, int B, int 
     d.deconv = mode; d.ksize = 3; d.pad = 1; d.stride = 2;
     d.Hg = mode ? Hin : Hout; d.Wg = mode ? Win : Wout; d.M = B * d.Hg * d.Wg;
 }
-int run_wgrad(WgradDesc& d, hipStream_t s, int* bias_done, int bf16) {
+int run_wgrad(WgradDesc& d, hipStream_t s, int* bias_done, Operand form) {
     if (!d.x1) d.c1 = 0;      // (the sweep's t = 0 has no h operand: its launch differentiates the x rows only)
     d.cin = d.c0 + d.c1;
     if (d.tcount < 1) d.tcount = 1;
     const long long b0 = view_bytes(d.B, d.Hx, d.Wx, d.ld0), b1 = d.x1 ? view_bytes(d.B, d.Hx, d.Wx, d.ld1) : 0, by = view_bytes(d.B, d.Hy, d.Wy, d.ldy);
     if (!fits31(b0) || (d.x1 && !fits31(b1)) || !fits31(by)) return PIVP_ERR_BADARG;
     d.bytes0 = (int)b0; d.bytes1 = (int)b1; d.bytesy = (int)by;
-    d.pieces = bf16 == 3 ? 3 : 0;       // (bf16: 1 = operands rounded to bf16; 3 = three bf16 pieces per operand, fp32-grade)
-    if (bf16 || d.dy_absmax) {   // bf16 precision mode (5x5 ConvLSTM case only): operands rounded to bf16, fp32 accumulation; db summed on the side in fp32
+    d.operand = form;
+    if (form != Operand::F32) {   // 5x5 ConvLSTM case only: operands as bf16 or as pieces, fp32 accumulation; db summed on the side in fp32
         if (bias_done) *bias_done = d.db != nullptr;
         return wgrad5x5_bf16(d, s);
     }
@@ -328,10 +330,10 @@ static int fork_end(const SideFork* f) {
 int run_convlstm_backward(const ConvLstmBwdArgs& a, hipStream_t s) {
     const int B = a.B, H = a.H, W = a.W, cx = a.cx, C = a.C, det = a.det;
     const int M = B * H * W, cin = cx + C, N = 4 * C;
-    if (a.wt_bf16 && a.bf16_planes == -2 && !a.dg_absmax) return PIVP_ERR_BADARG;
+    if ((a.wt_bf16 != nullptr) != (a.operand != Operand::F32) || (operand_needs_scale(a.operand) && !a.dg_absmax)) return PIVP_ERR_BADARG;
     // a K-split data gradient adds into d_in: the gate kernel clears it on the side (one launch less than a memset per cell and timestep).
     // det (deterministic sweeps): never split, so that every element of d_in is one block's plain store.
-    const bool zero = a.wt_bf16 ? conv5x5_bf16_splits_k(N, cin, cin, B, H, W, a.bf16_planes, det)
+    const bool zero = a.wt_bf16 ? conv5x5_bf16_splits_k(N, cin, cin, B, H, W, a.operand, det)
                                 : (a.dx_only ? conv_s1_splits_k(N, cx, cin, 5, B, H, W, cin, det) : conv_s1_splits_k(N, cin, cin, 5, B, H, W, 0, det));
     int rc = lstm_gates_bwd(a.gates, a.c_old, a.c_new, a.dh_a, a.lda, a.dh_b, a.ldb, a.dc, a.dc_valid, a.dG, M, C, s, B, a.ln, zero ? a.d_in : nullptr, (long long)M * cin);
     if (rc != PIVP_OK) return rc;
@@ -350,13 +352,13 @@ int run_convlstm_backward(const ConvLstmBwdArgs& a, hipStream_t s) {
         rc = repack_transpose(a.w, a.wt, 25, cin, N, 1, s);                   // [25][cin/32][4C][32] -> flipped [25][4C/32][cin][32]
         if (rc != PIVP_OK) return rc;
     }
-    if (a.wt_bf16) {   // bf16 precision mode: the data gradient with bf16 operands (wt_bf16 = bf16 pack of wt, built here unless wt_ready)
+    if (a.wt_bf16) {   // the data gradient on bf16 operands or pieces (wt_bf16 = the pack of wt in that form, built here unless wt_ready)
         if (!a.wt_ready) {
-            rc = pack_lstm_bf16(a.wt, a.wt_bf16, N, cin, s, conv5x5_bf16_rows(cin), a.bf16_planes, 1);      // fragment-major plain pack, every map width
+            rc = pack_lstm_bf16(a.wt, a.wt_bf16, N, cin, s, a.operand, conv5x5_bf16_rows(cin), 1);      // (L2-direct forms: the fragment-major plain pack, every map width)
             if (rc != PIVP_OK) return rc;
         }
         Conv5x5Bf16Opts o{};
-        o.planes = a.bf16_planes; o.dest_zeroed = zero; o.ascale_part = a.dg_absmax; o.ep = a.ep; o.no_split = det;
+        o.operand = a.operand; o.dest_zeroed = zero; o.ascale_part = a.dg_absmax; o.ep = a.ep; o.no_split = det;
         rc = run_conv5x5_bf16(a.dG, N, N, a.wt_bf16, a.d_in, cin, cin, 0, B, H, W, s, o);
     } else {
         if (a.ep && a.ep->applied) *a.ep->applied = 0;      // (the fp32 data-gradient kernels have no such hook)
@@ -369,11 +371,11 @@ int run_convlstm_backward(const ConvLstmBwdArgs& a, hipStream_t s) {
     if (rc != PIVP_OK) return rc;
     if (!a.dW) return PIVP_OK;   // the caller batches this layer's weight gradient over several timesteps itself (pivp_plan.hip)
     int bias_done = 0;   // the 5x5 weight-gradient kernel sums dG's columns on the side
-    // (the weight gradient has a bf16 form but no split form: in the split mode it stays the fp32 kernel)
+    // (a single timestep's weight gradient: bf16 operands in that form, the fp32 kernel in every other)
     WgradDesc d;
     lstm_wgrad_geom(d, cx, C, B, H, W);
     d.x0 = a.x; d.ld0 = a.ldx; d.x1 = a.h_prev; d.dy = a.dG; d.dw = a.dW; d.db = a.db;
-    rc = run_wgrad(d, sw, &bias_done, a.wt_bf16 != nullptr && a.bf16_planes == 1);
+    rc = run_wgrad(d, sw, &bias_done, a.operand == Operand::BF16 ? Operand::BF16 : Operand::F32);
     if (rc != PIVP_OK) return rc;
     if (!bias_done) { rc = bias_grad(a.dG, N, N, M, a.db, sw); if (rc != PIVP_OK) return rc; }
     return fork_end(a.fork);
@@ -419,7 +421,7 @@ int run_conv_backward(const ConvBwdArgs& a, hipStream_t s) {
             if (rc != PIVP_OK) return rc;
         }
         DeconvOpts o{};
-        o.accum = a.accum_dx; o.bf16 = a.prec == 1 ? 1 : 0;
+        o.accum = a.accum_dx; o.operand = a.operand;
         rc = mode ? run_conv3x3s2(a.dy, a.cout, a.ldy, a.wt, nullptr, a.dx, a.cin, a.lddx, 0, B, Hout, Wout, s, a.accum_dx)
                   : run_deconv3x3s2(a.dy, a.cout, a.ldy, a.wt, nullptr, a.dx, a.cin, a.lddx, 0, B, Hout, Wout, s, o);
         if (rc != PIVP_OK) return rc;
@@ -429,7 +431,7 @@ int run_conv_backward(const ConvBwdArgs& a, hipStream_t s) {
     WgradDesc d;
     conv3x3s2_wgrad_geom(d, mode, a.cin, a.cout, B, Hin, Win);
     d.x0 = a.x; d.ld0 = a.ldx; d.dy = a.dy; d.ldy = a.ldy; d.dw = a.dW; d.db = a.db; d.part = a.part;
-    rc = run_wgrad(d, sw, &bias_done, 0);
+    rc = run_wgrad(d, sw, &bias_done, Operand::F32);
     if (rc != PIVP_OK) return rc;
     if (!bias_done) { rc = bias_grad(a.dy, a.ldy, a.cout, B * Hout * Wout, a.db, sw); if (rc != PIVP_OK) return rc; }
     return fork_end(a.fork);
@@ -512,7 +514,7 @@ extern "C" int pivp_conv_wgrad_partial(int mode, const float* x, int cin, int ld
     desc.x0 = x; desc.ld0 = ldx; desc.dy = dy; desc.ldy = ldy; desc.dw = dW; desc.db = db; desc.part = part;
     for (int r = 0; r < repeats; ++r) {
         int bias_done = 0;
-        int rc = run_wgrad(desc, (hipStream_t)stream, &bias_done, 0);
+        int rc = run_wgrad(desc, (hipStream_t)stream, &bias_done, Operand::F32);
         if (rc != PIVP_OK) return rc;
         if (!bias_done) { rc = bias_grad(dy, ldy, cout, B * Hout * Wout, db, (hipStream_t)stream); if (rc != PIVP_OK) return rc; }
     }
@@ -532,7 +534,7 @@ extern "C" int pivp_conv_wgrad_partial_batch(int mode, const float* x, int cin, 
     d.x0 = x; d.ld0 = ldx; d.dy = dy; d.ldy = ldy; d.dw = dW; d.db = db;
     d.tcount = tcount; d.ts_x0 = x_step_bytes; d.ts_dy = dy_step_bytes;
     d.part = part; d.part_overwrite = overwrite ? 1 : 0;
-    int rc = run_wgrad(d, (hipStream_t)stream, &bias_done, 0);
+    int rc = run_wgrad(d, (hipStream_t)stream, &bias_done, Operand::F32);
     if (rc != PIVP_OK) return rc;
     if (!bias_done)
         for (int j = 0; j < tcount; ++j) {
@@ -571,7 +573,7 @@ extern "C" int pivp_wgrad5x5_f32_batch(const float* x, int cx, int ldx, const fl
     lstm_wgrad_op(d, x, cx, ldx, h_prev, C, dG, dW, db, B, H, W, tcount, ts_x, ts_h, ts_dG);
     d.part = part; d.part_overwrite = overwrite ? 1 : 0;
     d.form = form; d.slot_ntw = form;      // (form: the wave form without part, the slot form's columns per wave with it)
-    int rc = run_wgrad(d, (hipStream_t)stream, &bias_done, 0);
+    int rc = run_wgrad(d, (hipStream_t)stream, &bias_done, Operand::F32);
     if (rc != PIVP_OK) return rc;
     if (db && !bias_done)
         for (int j = 0; j < tcount; ++j) {
@@ -623,44 +625,44 @@ extern "C" int pivp_layernorm_train(const float* x, const float* gamma, const fl
 // fp32 accumulation / gates / state.  nch: 0 automatic, 16 or 32 channels per block.
 // Split mode (three bf16 MFMAs per product, 16 bits of product mantissa): weights packed as hi / lo planes, twice the elements.
 // the packed-weight ConvLSTM entries' options
-static ConvLstmOpts packed_lstm_opts(const void* w_bf16, int planes, int nch, float* gates_out, float* ln_part, int ln_cap, int* ln_nparts) {
+static ConvLstmOpts packed_lstm_opts(const void* w_bf16, Operand form, int nch, float* gates_out, float* ln_part, int ln_cap, int* ln_nparts) {
     ConvLstmOpts o{};
-    o.w_bf16 = (const unsigned short*)w_bf16; o.bf16_planes = planes; o.variant = nch; o.gates_out = gates_out;
+    o.w_bf16 = (const unsigned short*)w_bf16; o.operand = form; o.variant = nch; o.gates_out = gates_out;
     o.ln_out.part = ln_part; o.ln_out.cap = ln_cap; o.ln_out.nparts = ln_nparts;
     return o;
 }
 extern "C" int pivp_pack_lstm_bf16x3(const float* w, void* w_bf16, int cin_total, int C, void* stream) {
     if (C <= 0) return PIVP_ERR_BADARG;
-    return pack_lstm_bf16(w, (unsigned short*)w_bf16, cin_total, 4 * C, (hipStream_t)stream, 0, 2);
+    return pack_lstm_bf16(w, (unsigned short*)w_bf16, cin_total, 4 * C, (hipStream_t)stream, Operand::BF16X3);
 }
 extern "C" int pivp_convlstm_bf16x3(const float* x, int cx, int ldx, const float* h_prev, int C, const void* w_bf16, const float* bias,
                                     const float* c_in, float* c_out, float* h_out, float* gates_out, float* ln_part, int ln_cap,
                                     int* ln_nparts, int B, int H, int W, int nch, void* stream) {
     if (!x || !w_bf16 || !bias || !c_in || !c_out || !h_out) return PIVP_ERR_BADARG;
-    const ConvLstmOpts o = packed_lstm_opts(w_bf16, 2, nch, gates_out, ln_part, ln_cap, ln_nparts);
+    const ConvLstmOpts o = packed_lstm_opts(w_bf16, Operand::BF16X3, nch, gates_out, ln_part, ln_cap, ln_nparts);
     return run_convlstm(x, cx, ldx, h_prev, C, nullptr, bias, c_in, c_out, h_out, B, H, W, (hipStream_t)stream, o);
 }
 extern "C" int pivp_pack_lstm_bf16x6(const float* w, void* w_bf16, int cin_total, int C, void* stream) {
     if (C <= 0) return PIVP_ERR_BADARG;
-    return pack_lstm_bf16(w, (unsigned short*)w_bf16, cin_total, 4 * C, (hipStream_t)stream, 0, 3);
+    return pack_lstm_bf16(w, (unsigned short*)w_bf16, cin_total, 4 * C, (hipStream_t)stream, Operand::BF16X6);
 }
 extern "C" int pivp_convlstm_bf16x6(const float* x, int cx, int ldx, const float* h_prev, int C, const void* w_bf16, const float* bias,
                                     const float* c_in, float* c_out, float* h_out, float* gates_out, float* ln_part, int ln_cap,
                                     int* ln_nparts, int B, int H, int W, int nch, void* stream) {
     if (!x || !w_bf16 || !bias || !c_in || !c_out || !h_out || (nch != 0 && nch != 16 && nch != 32)) return PIVP_ERR_BADARG;
-    const ConvLstmOpts o = packed_lstm_opts(w_bf16, 3, nch, gates_out, ln_part, ln_cap, ln_nparts);
+    const ConvLstmOpts o = packed_lstm_opts(w_bf16, Operand::BF16X6, nch, gates_out, ln_part, ln_cap, ln_nparts);
     return run_convlstm(x, cx, ldx, h_prev, C, nullptr, bias, c_in, c_out, h_out, B, H, W, (hipStream_t)stream, o);
 }
 extern "C" int pivp_pack_lstm_fp16x3(const float* w, void* w_bf16, int cin_total, int C, int map_width, void* stream) {
     if (C <= 0 || map_width <= 0) return PIVP_ERR_BADARG;
     // (fragment-major for every map width; map_width is kept in the signature for ABI stability)
-    return pack_lstm_bf16(w, (unsigned short*)w_bf16, cin_total, 4 * C, (hipStream_t)stream, 0, -2, 0);
+    return pack_lstm_bf16(w, (unsigned short*)w_bf16, cin_total, 4 * C, (hipStream_t)stream, Operand::FP16X3);
 }
 extern "C" int pivp_convlstm_fp16x3(const float* x, int cx, int ldx, const float* h_prev, int C, const void* w_bf16, const float* bias,
                                     const float* c_in, float* c_out, float* h_out, float* gates_out, float* ln_part, int ln_cap,
                                     int* ln_nparts, int B, int H, int W, int nch, void* stream) {
     if (!x || !w_bf16 || !bias || !c_in || !c_out || !h_out || (nch != 0 && nch != 16 && nch != 32 && nch != 256)) return PIVP_ERR_BADARG;
-    const ConvLstmOpts o = packed_lstm_opts(w_bf16, -2, nch, gates_out, ln_part, ln_cap, ln_nparts);
+    const ConvLstmOpts o = packed_lstm_opts(w_bf16, Operand::FP16X3, nch, gates_out, ln_part, ln_cap, ln_nparts);
     return run_convlstm(x, cx, ldx, h_prev, C, nullptr, bias, c_in, c_out, h_out, B, H, W, (hipStream_t)stream, o);
 }
 extern "C" long long pivp_lstm_bf16_weight_elems(int cin_total, int C) {
@@ -669,13 +671,13 @@ extern "C" long long pivp_lstm_bf16_weight_elems(int cin_total, int C) {
 }
 extern "C" int pivp_pack_lstm_bf16(const float* w, void* w_bf16, int cin_total, int C, void* stream) {
     if (C <= 0) return PIVP_ERR_BADARG;
-    return pack_lstm_bf16(w, (unsigned short*)w_bf16, cin_total, 4 * C, (hipStream_t)stream);
+    return pack_lstm_bf16(w, (unsigned short*)w_bf16, cin_total, 4 * C, (hipStream_t)stream, Operand::BF16);
 }
 extern "C" int pivp_convlstm_bf16(const float* x, int cx, int ldx, const float* h_prev, int C, const void* w_bf16, const float* bias,
                                   const float* c_in, float* c_out, float* h_out, float* gates_out, float* ln_part, int ln_cap,
                                   int* ln_nparts, int B, int H, int W, int nch, void* stream) {
     if (!x || !w_bf16 || !bias || !c_in || !c_out || !h_out) return PIVP_ERR_BADARG;
-    const ConvLstmOpts o = packed_lstm_opts(w_bf16, 1, nch, gates_out, ln_part, ln_cap, ln_nparts);
+    const ConvLstmOpts o = packed_lstm_opts(w_bf16, Operand::BF16, nch, gates_out, ln_part, ln_cap, ln_nparts);
     return run_convlstm(x, cx, ldx, h_prev, C, nullptr, bias, c_in, c_out, h_out, B, H, W, (hipStream_t)stream, o);
 }
 // Plain 5x5 stride-1 "same" convolution with bf16 operands (the ConvLSTM data gradient of the bf16 mode): w fp32 K-inner packed
@@ -687,28 +689,30 @@ extern "C" long long pivp_conv5x5_bf16_weight_elems(int cin, int cout) {
 extern "C" int pivp_conv5x5_bf16(const float* x, int cin, int ldx, const float* w, void* w_bf16, float* out, int cout, int ldo, int accum,
                                  int B, int H, int W, void* stream) {
     if (!x || !w || !w_bf16 || !out || cin <= 0 || cout <= 0) return PIVP_ERR_BADARG;
-    int rc = pack_lstm_bf16(w, (unsigned short*)w_bf16, cin, cout, (hipStream_t)stream, conv5x5_bf16_rows(cout));
+    int rc = pack_lstm_bf16(w, (unsigned short*)w_bf16, cin, cout, (hipStream_t)stream, Operand::BF16, conv5x5_bf16_rows(cout));
     if (rc != PIVP_OK) return rc;
-    return run_conv5x5_bf16(x, cin, ldx, (const unsigned short*)w_bf16, out, cout, ldo, accum, B, H, W, (hipStream_t)stream);
+    Conv5x5Bf16Opts o{};
+    o.operand = Operand::BF16;
+    return run_conv5x5_bf16(x, cin, ldx, (const unsigned short*)w_bf16, out, cout, ldo, accum, B, H, W, (hipStream_t)stream, o);
 }
 // split form (two bf16 pieces per operand): w_bf16 holds 2 * pivp_conv5x5_bf16_weight_elems(cin, cout) elements
 extern "C" int pivp_conv5x5_bf16x3(const float* x, int cin, int ldx, const float* w, void* w_bf16, float* out, int cout, int ldo, int accum,
                                    int B, int H, int W, void* stream) {
     if (!x || !w || !w_bf16 || !out || cin <= 0 || cout <= 0) return PIVP_ERR_BADARG;
-    int rc = pack_lstm_bf16(w, (unsigned short*)w_bf16, cin, cout, (hipStream_t)stream, conv5x5_bf16_rows(cout), 2);
+    int rc = pack_lstm_bf16(w, (unsigned short*)w_bf16, cin, cout, (hipStream_t)stream, Operand::BF16X3, conv5x5_bf16_rows(cout));
     if (rc != PIVP_OK) return rc;
     Conv5x5Bf16Opts o{};
-    o.planes = 2;
+    o.operand = Operand::BF16X3;
     return run_conv5x5_bf16(x, cin, ldx, (const unsigned short*)w_bf16, out, cout, ldo, accum, B, H, W, (hipStream_t)stream, o);
 }
 // three-piece form (six MFMAs per product, fp32-grade): w_bf16 holds 3 * pivp_conv5x5_bf16_weight_elems(cin, cout) elements; W % 16 == 0
 extern "C" int pivp_conv5x5_bf16x6(const float* x, int cin, int ldx, const float* w, void* w_bf16, float* out, int cout, int ldo, int accum,
                                    int B, int H, int W, void* stream) {
     if (!x || !w || !w_bf16 || !out || cin <= 0 || cout <= 0 || (W % 16 && (W % 8 || B % 2))) return PIVP_ERR_BADARG;
-    int rc = pack_lstm_bf16(w, (unsigned short*)w_bf16, cin, cout, (hipStream_t)stream, conv5x5_bf16_rows(cout), 3, 1);
+    int rc = pack_lstm_bf16(w, (unsigned short*)w_bf16, cin, cout, (hipStream_t)stream, Operand::BF16X6, conv5x5_bf16_rows(cout), 1);
     if (rc != PIVP_OK) return rc;
     Conv5x5Bf16Opts o{};
-    o.planes = 3;
+    o.operand = Operand::BF16X6;
     return run_conv5x5_bf16(x, cin, ldx, (const unsigned short*)w_bf16, out, cout, ldo, accum, B, H, W, (hipStream_t)stream, o);
 }
 // two-fp16-piece form (three MFMAs per product, fp32-grade; the fp16x3 mode's data gradients): x is staged times the power of two that puts its largest
@@ -717,12 +721,12 @@ extern "C" int pivp_conv5x5_bf16x6(const float* x, int cin, int ldx, const float
 extern "C" int pivp_conv5x5_fp16x3(const float* x, int cin, int ldx, const float* w, void* w_bf16, float* out, int cout, int ldo, int accum,
                                    int B, int H, int W, float* scratch, void* stream) {
     if (!x || !w || !w_bf16 || !out || !scratch || cin <= 0 || cout <= 0 || (W % 16 && (W % 8 || B % 2)) || ldx != cin || B <= 0 || H <= 0) return PIVP_ERR_BADARG;
-    int rc = pack_lstm_bf16(w, (unsigned short*)w_bf16, cin, cout, (hipStream_t)stream, conv5x5_bf16_rows(cout), -2, 1);
+    int rc = pack_lstm_bf16(w, (unsigned short*)w_bf16, cin, cout, (hipStream_t)stream, Operand::FP16X3, conv5x5_bf16_rows(cout), 1);
     if (rc != PIVP_OK) return rc;
     rc = absmax_partials(x, (long)B * H * W * cin, scratch, (hipStream_t)stream);
     if (rc != PIVP_OK) return rc;
     Conv5x5Bf16Opts o{};
-    o.planes = -2; o.ascale_part = scratch;
+    o.operand = Operand::FP16X3; o.ascale_part = scratch;
     return run_conv5x5_bf16(x, cin, ldx, (const unsigned short*)w_bf16, out, cout, ldo, accum, B, H, W, (hipStream_t)stream, o);
 }
 // ConvLSTM weight gradient with bf16 operands: dW (K-inner packed like the weight, [25][(cx+C)/32][4C][32]) += x|h^T . dG per tap.
@@ -731,7 +735,7 @@ extern "C" int pivp_wgrad5x5_bf16(const float* x, int cx, int ldx, const float* 
     if (!x || !dG || !dW || C <= 0 || cx <= 0) return PIVP_ERR_BADARG;
     WgradDesc d;
     lstm_wgrad_op(d, x, cx, ldx, h_prev, C, dG, dW, db, B, H, W, 1, 0, 0, 0);
-    return run_wgrad(d, (hipStream_t)stream, nullptr, 1);
+    return run_wgrad(d, (hipStream_t)stream, nullptr, Operand::BF16);
 }
 // ... with two fp16 pieces per operand and three MFMAs per product (fp32-grade; the fp16x3 mode's weight gradient), a batch of timesteps as below:
 // scratch: 72 * tcount floats (the partial maxima of every timestep's dG: it is staged times a power of two from the largest of the batch)
@@ -746,7 +750,7 @@ extern "C" int pivp_wgrad5x5_fp16x3_batch(const float* x, int cx, int ldx, const
     WgradDesc d;
     lstm_wgrad_op(d, x, cx, ldx, h_prev, C, dG, dW, db, B, H, W, tcount, ts_x, ts_h, ts_dG);
     d.dy_absmax = scratch; d.dy_absmax_stride = 72;
-    return run_wgrad(d, (hipStream_t)stream, nullptr, 0);
+    return run_wgrad(d, (hipStream_t)stream, nullptr, Operand::FP16X3);
 }
 // ... with three bf16 pieces per operand and six MFMAs per product (fp32-grade, fp32's exponent range; the bf16x6 mode's weight gradient)
 extern "C" int pivp_wgrad5x5_bf16x6_batch(const float* x, int cx, int ldx, const float* h_prev, int C, const float* dG, float* dW, float* db,
@@ -754,7 +758,7 @@ extern "C" int pivp_wgrad5x5_bf16x6_batch(const float* x, int cx, int ldx, const
     if (!x || !dG || !dW || C <= 0 || cx <= 0 || tcount < 1) return PIVP_ERR_BADARG;
     WgradDesc d;
     lstm_wgrad_op(d, x, cx, ldx, h_prev, C, dG, dW, db, B, H, W, tcount, ts_x, ts_h, ts_dG);
-    return run_wgrad(d, (hipStream_t)stream, nullptr, 3);
+    return run_wgrad(d, (hipStream_t)stream, nullptr, Operand::BF16X6);
 }
 // ... of a BATCH of timesteps in one launch (the sum over pixels runs over timesteps too): timestep j reads x + j * ts_x, h_prev + j * ts_h,
 // dG + j * ts_dG (byte strides, multiples of 16, may be negative: the backward sweep walks time downwards)
@@ -763,7 +767,7 @@ extern "C" int pivp_wgrad5x5_bf16_batch(const float* x, int cx, int ldx, const f
     if (!x || !dG || !dW || C <= 0 || cx <= 0 || tcount < 1) return PIVP_ERR_BADARG;
     WgradDesc d;
     lstm_wgrad_op(d, x, cx, ldx, h_prev, C, dG, dW, db, B, H, W, tcount, ts_x, ts_h, ts_dG);
-    return run_wgrad(d, (hipStream_t)stream, nullptr, 1);
+    return run_wgrad(d, (hipStream_t)stream, nullptr, Operand::BF16);
 }
 // ... with the block form chosen by the caller: 1 = four-wave blocks (32 channels x 32 columns, about one per CU: they co-reside with the backward sweep's
 // small kernels), 2 = eight-wave blocks (32 x 64: half the patch traffic per multiply-add), 0 = by size as pivp_wgrad5x5_bf16_batch does
@@ -773,7 +777,7 @@ extern "C" int pivp_wgrad5x5_bf16_batch_form(const float* x, int cx, int ldx, co
     WgradDesc d;
     lstm_wgrad_op(d, x, cx, ldx, h_prev, C, dG, dW, db, B, H, W, tcount, ts_x, ts_h, ts_dG);
     d.form = form;
-    return run_wgrad(d, (hipStream_t)stream, nullptr, 1);
+    return run_wgrad(d, (hipStream_t)stream, nullptr, Operand::BF16);
 }
 static int convlstm_ln_cap(int H, int W, int C) {
     const int tiles = ((H * W + 31) / 32) * (C / 32), slices = ln_stats_slices(H * W * C);
@@ -945,8 +949,9 @@ extern "C" int pivp_deconv3x3s2_ln(const float* h_raw, int c_ln, const float* x1
     int rc = ln_stats(h_raw, partials, B, n, (hipStream_t)stream);
     if (rc != PIVP_OK) return rc;
     const LnIn ln{gamma, beta, partials, ln_stats_slices(n), eps};
+    static const Operand form_of[3] = {Operand::F32, Operand::BF16, Operand::BF16X3};      // this entry's precision codes
     DeconvLnOpts o{};
-    o.x1 = x1; o.c1 = c1; o.ld1 = ld1; o.bf16 = precision;
+    o.x1 = x1; o.c1 = c1; o.ld1 = ld1; o.operand = form_of[precision];
     return run_deconv3x3s2_ln(h_raw, c_ln, w, bias, out, cout, ldo, relu, B, Hin, Win, (hipStream_t)stream, ln, o);
 }
 // bf16-operand form (precision mode bf16): x and w rounded to bf16 on the way into LDS, fp32 accumulation / bias / ReLU.  Only maps that the
@@ -955,14 +960,14 @@ extern "C" int pivp_deconv3x3s2_bf16(const float* x, int cin, int ldx, const flo
                                      int ldo, int relu, int B, int Hin, int Win, void* stream) {
     if (!x || !w || !out) return PIVP_ERR_BADARG;
     DeconvOpts o{};
-    o.bf16 = 1;
+    o.operand = Operand::BF16;
     return run_deconv3x3s2(x, cin, ldx, w, bias, out, cout, ldo, relu, B, Hin, Win, (hipStream_t)stream, o);
 }
 extern "C" int pivp_deconv3x3s2_bf16x3(const float* x, int cin, int ldx, const float* w, const float* bias, float* out, int cout,
                                        int ldo, int relu, int B, int Hin, int Win, void* stream) {   // split mode: two bf16 pieces per operand
     if (!x || !w || !out) return PIVP_ERR_BADARG;
     DeconvOpts o{};
-    o.bf16 = 2;
+    o.operand = Operand::BF16X3;
     return run_deconv3x3s2(x, cin, ldx, w, bias, out, cout, ldo, relu, B, Hin, Win, (hipStream_t)stream, o);
 }
 // two fp16 pieces per operand, three MFMAs per product (precision mode PIVP_PRECISION_FP16X3): scratch = 66 floats (the weights' partial maxima)
@@ -972,7 +977,7 @@ extern "C" int pivp_deconv3x3s2_fp16x3(const float* x, int cin, int ldx, const f
     int rc = absmax_partials(w, 9L * cin * cout, scratch, (hipStream_t)stream);
     if (rc != PIVP_OK) return rc;
     DeconvOpts o{};
-    o.bf16 = 3; o.wscale_part = scratch;
+    o.operand = Operand::FP16X3; o.wscale_part = scratch;
     return run_deconv3x3s2(x, cin, ldx, w, bias, out, cout, ldo, relu, B, Hin, Win, (hipStream_t)stream, o);
 }
 extern "C" int pivp_conv_enc0(const float* img, const float* w, const float* bias, float* out, int B, int H, int W, void* stream) {

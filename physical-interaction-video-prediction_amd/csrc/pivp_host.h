@@ -1,8 +1,7 @@
 // Host-side launch helpers shared by the per-op C ABI (pivp_c_api.hip) and the plan (pivp_plan.hip).
 // A helper takes its required core positionally (tensors, channel counts, strides, B, H, W, stream) and everything optional as named fields of ONE
 // options struct behind it: callers value-initialise the struct (`T o{};`), assign what they use by name and pass it by reference.
-// Value-initialised means every field zero / null, with ONE exception: the pack-form fields (ConvLstmOpts::bf16_planes, Conv5x5Bf16Opts::planes,
-// ConvLstmBwdArgs::bf16_planes) start at 1, a single plane of operands rounded to bf16 -- the only non-zero default member initialisers of this header.
+// Value-initialised means every field zero / null; an operand form (Operand, pivp_kernels.h) then is F32.
 #pragma once
 #include "pivp_kernels.h"
 
@@ -33,11 +32,11 @@ struct ConvLstmOpts {
     int variant;                     // fp32 kernel: 0 auto, 1..4 wave layouts; with w_bf16: channels per block (0 auto, 16, 32)
     float* gates_out;                // training: the gate activations [M][4C]
     LnPartOut ln_out;                // the LayerNorm behind the cell gets its statistics from the cell's epilogue
-    const unsigned short* w_bf16;    // the bf16 pack of w (pack_lstm_bf16) selects the bf16-operand kernel ...
-    int bf16_planes = 1;             // ... of this form: 1 rounded, 2 hi / lo, 3 three pieces, -2 two fp16 pieces
-    const LnIn* ln_in;               // x is raw, normalised while staged (split precision modes' eight-wave kernels: convlstm_ln_in_ok)
+    Operand operand;                 // F32: the fp32 kernel on w.  Any other form runs on ...
+    const unsigned short* w_bf16;    // ... the pack of w in that form (pack_lstm_bf16): one is given exactly when the other is
+    const LnIn* ln_in;               // x is raw, normalised while staged (the L2-direct forms' eight-wave kernels: convlstm_ln_in_ok)
 };
-bool convlstm_ln_in_ok(int planes, int cx, int ldx, int C, int B, int H, int W);
+bool convlstm_ln_in_ok(Operand form, int cx, int ldx, int C, int B, int H, int W);
 int run_convlstm(const float* x, int cx, int ldx, const float* h_prev, int C, const float* w, const float* bias,
                  const float* c_in, float* c_out, float* h_out, int B, int H, int W, hipStream_t s, const ConvLstmOpts& o = ConvLstmOpts{});
 int run_conv3x3s2(const float* x, int cin, int ldx, const float* w, const float* bias, float* out, int cout,
@@ -51,8 +50,8 @@ int run_conv3x3s2_ln(const float* x_raw, int cin, const float* w, const float* b
 struct DeconvOpts {
     int accum;
     LnPartOut ln_out;
-    int bf16;                        // precision of the all-parities tile kernel (deconv_tile.hip), fp32 elsewhere: 1 bf16 operands, 2 split, 3 two fp16 pieces
-    const float* wscale_part;        // bf16 == 3: absmax_partials(w)
+    Operand operand;                 // form of the all-parities tile kernel (deconv_tile.hip), fp32 elsewhere; BF16X6 has none and is refused
+    const float* wscale_part;        // FP16X3: absmax_partials(w)
 };
 int run_deconv3x3s2(const float* x, int cin, int ldx, const float* w, const float* bias, float* out, int cout,
                     int ldo, int relu, int B, int Hin, int Win, hipStream_t s, const DeconvOpts& o = DeconvOpts{});
@@ -64,7 +63,7 @@ bool deconv3x3s2_ln_ok(int c_ln, int c1, int cout, int B, int Hin, int Win);
 struct DeconvLnOpts {
     const float* x1; int c1, ld1;    // the second source of the concat (null: h_raw alone)
     LnPartOut ln_out;
-    int bf16;                        // as DeconvOpts::bf16
+    Operand operand;                 // as DeconvOpts::operand
     const float* wscale_part;        // as DeconvOpts::wscale_part
     NormKeep keep;
     const MotionRider* rider;
@@ -80,16 +79,16 @@ struct ConvS1Opts {
 int run_conv_s1(const float* x, int cin, int ldx, const float* w, float* out, int cout, int ldo, int ksize, int B, int H, int W,
                 hipStream_t s, const ConvS1Opts& o = ConvS1Opts{});
 bool conv_s1_splits_k(int cin, int cout, int ldo, int ksize, int B, int H, int W, int wN, int no_split);
-bool conv5x5_bf16_splits_k(int cin, int cout, int ldo, int B, int H, int W, int planes, int no_split);
+bool conv5x5_bf16_splits_k(int cin, int cout, int ldo, int B, int H, int W, Operand form, int no_split);
 struct Conv5x5Bf16Opts {
-    int planes = 1;              // the pack's form, as ConvLstmOpts::bf16_planes
+    Operand operand;             // the pack's form (never F32)
     int dest_zeroed;             // 1: the caller has cleared `out` (see conv5x5_bf16_splits_k)
-    const float* ascale_part;    // planes == -2: absmax_partials(x) (the activations' power-of-two scale)
+    const float* ascale_part;    // FP16X3: absmax_partials(x) (the activations' power-of-two scale)
     const EpSpec* ep;
     int no_split;                // 1: never split K (deterministic sweeps)
 };
 int run_conv5x5_bf16(const float* x, int cin, int ldx, const unsigned short* wb, float* out, int cout, int ldo, int accum,
-                     int B, int H, int W, hipStream_t s, const Conv5x5Bf16Opts& o = Conv5x5Bf16Opts{});
+                     int B, int H, int W, hipStream_t s, const Conv5x5Bf16Opts& o);
 struct LayerNormOpts {
     float* stat_out;       // receives the samples' (mean, rstd)
     int fused_nparts;      // > 0: the kernel that produced x already wrote that many (count, mean, M2) partials per sample
@@ -99,12 +98,12 @@ int run_layernorm(const float* x, const float* g, const float* b, float* out, fl
 
 // ---- weight gradients: the caller owns the WgradDesc (pivp_kernels.h documents every field) ----
 // One geometry filler per case clears the descriptor and sets ONE timestep's sizes for contiguous operands; the caller then assigns the operands (x0, ld0, x1, dy,
-// ldy, dw, db) and the options it wants (tcount / ts_*, part / part_overwrite, dy_absmax, form, slot_*) by name.
+// ldy, dw, db) and the options it wants (tcount / ts_*, part / part_overwrite, dy_absmax, form, slot_*) by name; WgradDesc::operand is run_wgrad's to fill.
 void lstm_wgrad_geom(WgradDesc& d, int cx, int C, int B, int H, int W);                                 // 5x5 ConvLSTM: x0 = x [cx], x1 = h_prev [C], dy = dG [4C]
 void conv3x3s2_wgrad_geom(WgradDesc& d, int mode, int cin, int cout, int B, int Hin, int Win);      // conv3x3s2 (mode 0) / deconv3x3s2 (mode 1)
-// completes d (x1 == null: no h operand; a single timestep; the byte extents), checks them and launches.  bf16, 5x5 ConvLSTM case only: 1 = operands rounded to
-// bf16, 3 = three bf16 pieces each (fp32-grade); d.dy_absmax selects the fp16-piece form.  *bias_done: the launch sums dy's columns into d.db itself.
-int run_wgrad(WgradDesc& d, hipStream_t s, int* bias_done, int bf16);
+// completes d (x1 == null: no h operand; a single timestep; the byte extents), checks them and launches in the given form.  Other than F32, 5x5 ConvLSTM case only:
+// BF16, BF16X6, FP16X3 (needs d.dy_absmax); BF16X3 has no weight-gradient form and is refused.  *bias_done: the launch sums dy's columns into d.db itself.
+int run_wgrad(WgradDesc& d, hipStream_t s, int* bias_done, Operand form);
 // floats of WgradDesc::part a conv3x3s2 / deconv3x3s2 weight gradient of these sizes needs
 long long conv_backward_part_floats(int mode, int cin, int cout, int B, int Hin, int Win);
 bool conv_backward_fixed_order(int mode, int cin, int cout, int B, int Hin, int Win);      // the partial-plane form with its column sums (wgrad3x3s2) serves it
@@ -127,12 +126,12 @@ struct ConvLstmBwdArgs {
     int B, H, W;
     // optional
     int wt_ready;                 // 1: wt (and wt_bf16) already hold the transposed pack
-    unsigned short* wt_bf16;      // the data gradient with bf16 operands: the bf16 pack of wt ...
-    int bf16_planes = 1;          // ... of this form (ConvLstmOpts::bf16_planes)
+    Operand operand;              // the data gradient's form: F32 = the fp32 kernels on wt; any other runs on ...
+    unsigned short* wt_bf16;      // ... the pack of wt in that form: one is given exactly when the other is
     const SideFork* fork;         // the weight gradient on a second stream
     const LnFuse* ln;             // dh_a is formed from the LayerNorm behind the cell
     int dx_only;                  // 1: d h_{t-1} is not needed (the sweep's last timestep): only the cx columns of d_in are computed
-    float* dg_absmax;             // 66 floats: receives dG's partial maxima (absmax_partials), the scale of the fp16-piece data gradient (bf16_planes == -2 needs
+    float* dg_absmax;             // 66 floats: receives dG's partial maxima (absmax_partials), the scale of the fp16-piece data gradient (operand FP16X3 needs
                                   // it) and of the fp16-piece weight gradient (WgradDesc::dy_absmax)
     const EpSpec* ep;             // the data gradient's epilogue hook (bf16 / split-precision data gradients on unsplit grids)
     int det;                      // deterministic sweeps: unsplit data gradients (the caller passes dW = null)
@@ -151,7 +150,7 @@ struct ConvBwdArgs {
     const SideFork* fork;
     float* part;                  // WgradDesc::part
     const float* dy_add; int ld_add;    // a second gradient into the same output, added in the ReLU-mask pass
-    int prec;                     // 1 (the bf16 precision mode): the data gradient's operands rounded to bf16 where the transposed conv's tile kernel takes it
+    Operand operand;              // BF16 (the bf16 precision mode): the data gradient's operands rounded to bf16 where the transposed conv's tile kernel takes it
                                   // (enc1's); the weight gradient stays fp32 (its bf16 form -- transposing LDS reads, 2 MFMAs per 32-pixel chunk -- was built and is
                                   // slower: profiles/r05/NOTES.md)
 };

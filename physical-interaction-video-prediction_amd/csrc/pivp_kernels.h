@@ -13,6 +13,28 @@
 
 namespace pivp {
 
+// How an fp32 operand travels into the matrix pipe.  The values are the precision modes' (PIVP_PRECISION_*, include/pivp_hip.h; pinned in pivp_plan.hip).
+enum class Operand : int {
+    F32 = 0,       // as it is (the fp32 kernels)
+    BF16 = 1,      // rounded to bf16
+    BF16X3 = 2,    // two bf16 pieces (hi / lo), three MFMAs per product
+    BF16X6 = 3,    // three bf16 pieces, six MFMAs per product (fp32-grade)
+    FP16X3 = 4     // two fp16 pieces of the operand times a power of two, three MFMAs per product (fp32-grade)
+};
+// 16-bit pieces one operand is carried as (the planes of a weight pack)
+constexpr int operand_pieces(Operand o) {
+    switch (o) {
+        case Operand::F32: case Operand::BF16: return 1;
+        case Operand::BF16X3: case Operand::FP16X3: return 2;
+        case Operand::BF16X6: return 3;
+    }
+    return 0;
+}
+// the L2-direct kernels (csrc/convlstm_l2direct.h) on fragment-major packs: 64-column blocks only, an 8-wide map needs an even batch, LayerNorm-on-load exists
+constexpr bool operand_l2_direct(Operand o) { return o == Operand::BF16X6 || o == Operand::FP16X3; }
+// the operand is staged times a power of two taken from its absmax_partials
+constexpr bool operand_needs_scale(Operand o) { return o == Operand::FP16X3; }
+
 struct IgemmDesc {
     const float* x0; const float* x1;   // input sources (channel-concatenated: x0 then x1)
     int c0, ld0, c1, ld1;
@@ -38,9 +60,9 @@ struct IgemmDesc {
     // each block writes (count, mean, M2) of its tile to ln_part[(b * ln_nparts + slot) * 4]; ln_apply merges them.
     // The launcher fills ln_nparts (0 = tiles straddle samples or exceed ln_cap: not fused, run ln_stats instead).
     float* ln_part; int ln_cap; int ln_nparts;
-    int bf16;                            // transposed conv only, when the tile kernel takes the call: 1 = bf16 operands, 2 = split (two bf16 pieces),
-                                         // 3 = two FP16 pieces (fp32-grade), the weights times the power of two of wscale_part
-    const float* wscale_part;            // bf16 == 3: absmax_partials(w) (64 partial maxima at [2..65]); conv5x5_bf16 with planes = -2: absmax_partials(x0),
+    Operand operand;                     // transposed conv only, when the tile kernel takes the call (host side only: the kernels are instantiated per form);
+                                         // BF16X6 has no form there.  FP16X3: the weights times the power of two of wscale_part
+    const float* wscale_part;            // transposed conv, FP16X3: absmax_partials(w) (64 partial maxima at [2..65]); conv5x5_bf16 with FP16X3: absmax_partials(x0),
                                          // the ACTIVATIONS' scale (the weights' one travels in the pack's tail)
     // LayerNorm of the INPUT applied while it is staged (inference rollouts: the norm's own launch disappears).  x0 then is the RAW tensor
     // [B][Hin*Win][c0] (all c0 channels are normalised), in_g / in_b the norm's per-element gamma / beta ([Hin*Win][c0], the checkpoint's
@@ -106,9 +128,10 @@ struct WgradDesc {
     int part_overwrite;                  // 1: this launch is the slot's first since the caller last consumed it: store instead of add (no zeroing needed)
     // wgrad5x5_bf16 only: two FP16 pieces per operand, three MFMAs per product (the fp16x3 mode's weight gradient).  dy_absmax = the absmax_partials tail of
     // timestep j's dy at dy_absmax + j * dy_absmax_stride floats (64 partial maxima at [2..65]): dy is staged times the power of two that puts the largest
-    // |value| of the whole batch into [2^14, 2^15) -- gradients lie far below fp16's normal range -- and the sums are scaled back exactly.  null: bf16 operands.
+    // |value| of the whole batch into [2^14, 2^15) -- gradients lie far below fp16's normal range -- and the sums are scaled back exactly.  Read by that form only.
     const float* dy_absmax; int dy_absmax_stride;
-    int pieces;                          // wgrad5x5_bf16 only: 3 = three bf16 pieces per operand, six MFMAs per product (the bf16x6 mode's weight gradient)
+    Operand operand;                     // filled by run_wgrad (host side only): F32 = the fp32 kernels; wgrad5x5_bf16 serves BF16, BF16X6 (three bf16 pieces, six MFMAs
+                                         // per product) and FP16X3 (needs dy_absmax); BF16X3 has no weight-gradient form
     int form;                            // wgrad5x5_bf16, plain bf16 operands, a batch of timesteps: 0 = by size (four-wave blocks that co-reside with the main stream's
                                          // kernels for maps of up to 32 x 32 x 32 pixels per timestep, else eight-wave blocks), 1 = four-wave, 2 = eight-wave
     // wgrad5x5p (the fp32 slot form) only -- its partition, which the batch launches, the slot buffer's size and the reduction must agree on:
@@ -137,7 +160,7 @@ int wgrad5x5_bf16(const WgradDesc& d, hipStream_t s);
 int repack_transpose(const float* w, float* wt, int taps, int cin, int N, int flip, hipStream_t s);
 // Several weight preparations in ONE launch (the weights change once per optimizer step, so every train step rebuilds its packs: 7 + 12 + 7 launches
 // of a few microseconds each in the bf16 mode before round 5).  kind 0: repack_transpose(src, dst, taps = p0, cin = p1, N = p2, flip = p3);
-// kind 1: pack_lstm_bf16(src, dst, wcin = p0, N = p1, Np = p2) with one bf16 plane.  Jobs of one call must not depend on each other.
+// kind 1: pack_lstm_bf16(src, dst, wcin = p0, N = p1, Operand::BF16, Np = p2).  Jobs of one call must not depend on each other.
 struct WeightPrepJob { int kind; const float* src; void* dst; int p0, p1, p2, p3; };
 constexpr int WEIGHT_PREP_MAX = 16;
 int weight_prep_batch(const WeightPrepJob* jobs, int n, hipStream_t s);
@@ -151,17 +174,17 @@ int igemm_small(const IgemmDesc& d, hipStream_t stream, int* ln_nparts = nullptr
 bool igemm_in_ln_ok(const IgemmDesc& d);   // can igemm_small apply d.in_g's LayerNorm while staging x0?
 // transposed 3x3 s2 conv, all four output parities per block (csrc/deconv_tile.hip); d validated by igemm_validate
 bool deconv_tile_ok(const IgemmDesc& d);
-int deconv_tile(const IgemmDesc& d, hipStream_t stream, int* ln_nparts = nullptr, int prec = 0);   // 0 fp32, 1 bf16 operands, 2 split (2 bf16 pieces), 3 two fp16 pieces
+int deconv_tile(const IgemmDesc& d, hipStream_t stream, int* ln_nparts = nullptr);   // in the form d.operand names
 int absmax_partials(const float* w, long n, float* tail, hipStream_t stream);   // 64 partial maxima of |w| into tail[2..65] (tail: 66 floats)
 // bf16-operand ConvLSTM (csrc/convlstm_bf16.hip): wb = pack_lstm_bf16 of d.w; nch: 0 auto, 16 / 32 channels per block
 size_t lstm_bf16_weight_elems(int wcin, int N);
-int pack_lstm_bf16(const float* w, unsigned short* wb, int wcin, int N, hipStream_t s, int Np = 0, int planes = 1, int plain = 0);   // plain: planes = 3 only (a plain conv's columns)
+int pack_lstm_bf16(const float* w, unsigned short* wb, int wcin, int N, hipStream_t s, Operand form, int Np = 0, int plain = 0);   // plain: the fragment-major forms only (a plain conv's columns)
 int conv5x5_bf16_rows(int N);
-int conv5x5_bf16_ksplit(const IgemmDesc& d, int planes = 1);   // > 1: the launch will split K and needs d.out zeroed
-int conv5x5_bf16(const IgemmDesc& d, const unsigned short* wb, hipStream_t stream, int planes = 1);   // plain 5x5 s1 conv (ConvLSTM data gradient)
+int conv5x5_bf16_ksplit(const IgemmDesc& d, Operand form);   // > 1: the launch will split K and needs d.out zeroed
+int conv5x5_bf16(const IgemmDesc& d, const unsigned short* wb, hipStream_t stream, Operand form);   // plain 5x5 s1 conv (ConvLSTM data gradient); wb packed in that form
 bool convlstm_bf16_ok(const IgemmDesc& d);
 bool convlstm_bf16x6_ok(const IgemmDesc& d);   // the three-piece form: 16-wide tiles only
-int convlstm_bf16(const IgemmDesc& d, const unsigned short* wb, hipStream_t stream, int* ln_nparts = nullptr, int nch = 0, int planes = 1);
+int convlstm_bf16(const IgemmDesc& d, const unsigned short* wb, hipStream_t stream, Operand form, int* ln_nparts = nullptr, int nch = 0);
 
 // enc0: 5x5 stride-2 pad-2 conv on a planar 3-channel frame -> NHWC 32 channels (TM:500)
 // ln_part (optional): the launch also writes *ln_nparts LayerNorm partials per sample of its output (0 = not supported for the shape)

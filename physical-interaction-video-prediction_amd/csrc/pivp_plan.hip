@@ -39,32 +39,27 @@ static long long ln_numel(const pivp_config_t& c, int j) {
     return (long long)kLstm[j - 1].C * m.H * m.W;
 }
 
-// ---- the precision mode: everything the plan derives from the PIVP_PRECISION_* integer ----
-struct Modes {
-    int precision;        // PIVP_PRECISION_*
-    int lstm_bf16;        // 1: the ConvLSTM forward runs on weight packs (every mode but F32)
-    int lstm_planes;      // the packs' form: 1 rounded to bf16; 2: split mode (hi / lo planes, three MFMAs per product); 3: three pieces, six MFMAs; -2: two fp16 pieces
-    int bwd_planes;       // the data gradients' form of lstm_planes (fp16 pieces in the sweep: they take dG times a power of two from its largest |value|)
-    int bf16_all;         // precision mode BF16: also the ConvLSTM gradients and the enc5 / enc6 transposed convs
-    bool x3_wgrad;        // fp16x3 mode: the ConvLSTM weight gradients with two fp16 pieces too (wgrad25_bf16_kernel<.., 2>, batched like the bf16 mode's), two timesteps per launch
-    bool x6_wgrad;        // bf16x6 mode: ... with three bf16 pieces (wgrad25_bf16_kernel<.., 3>), same schedule
-    // the transposed convs' precision code (DeconvOpts::bf16).  has_wabs: the layer keeps its weights' absmax partials (enc5 / enc6: pivp_plan::o_wabs), which the
-    // fp16-piece form needs; a layer without them (enc4) stays fp32 in that mode
-    int deconv_prec(bool has_wabs) const { return bf16_all ? 1 : lstm_planes == 2 ? 2 : (lstm_planes == -2 && has_wabs) ? 3 : 0; }
-};
-static Modes modes_of(int precision) {
-    Modes m{};
-    m.precision = precision;
-    m.lstm_bf16 = precision != PIVP_PRECISION_F32;
-    m.lstm_planes = precision == PIVP_PRECISION_BF16X3 ? 2 : precision == PIVP_PRECISION_BF16X6 ? 3 : precision == PIVP_PRECISION_FP16X3 ? -2 : 1;
-    m.bwd_planes = m.lstm_planes;
-    m.x3_wgrad = m.lstm_planes == -2;
-    m.x6_wgrad = m.lstm_planes == 3;
-    m.bf16_all = precision == PIVP_PRECISION_BF16;
-    return m;
-}
-// the two-image tile of the piece modes' kernels serves this map (an 8-wide map needs an even batch; otherwise the fp32 kernel takes it)
+// ---- the precision mode: everything the plan derives from it ----
+static_assert((int)Operand::F32 == PIVP_PRECISION_F32 && (int)Operand::BF16 == PIVP_PRECISION_BF16 && (int)Operand::BF16X3 == PIVP_PRECISION_BF16X3 &&
+              (int)Operand::BF16X6 == PIVP_PRECISION_BF16X6 && (int)Operand::FP16X3 == PIVP_PRECISION_FP16X3, "Operand is the PIVP_PRECISION_* code");
+// the two-image tile of the L2-direct forms' kernels serves this map (an 8-wide map needs an even batch; otherwise the fp32 kernel takes it)
 static bool pair_tile_serves(int W, int B) { return W % 16 == 0 || B % 2 == 0; }
+struct Modes {
+    Operand precision;      // the mode = the form of the ConvLSTM forward's operands
+    // the ConvLSTM forward runs on weight packs (of the form `precision`)
+    bool packs() const { return precision != Operand::F32; }
+    // the ConvLSTM data gradient on a W-wide map at batch B: the forward's form where its tiles serve the map
+    Operand dgrad(int W, int B) const { return operand_l2_direct(precision) && !pair_tile_serves(W, B) ? Operand::F32 : precision; }
+    // ... and the weight gradient of a batch of timesteps: the split mode has no form of its own and stays fp32
+    Operand wgrad(int W, int B) const { return precision == Operand::BF16X3 ? Operand::F32 : dgrad(W, B); }
+    // ... which those forms batch: BF16 as many timesteps per launch as the rings hold, the L2-direct forms two; fp32 none
+    bool wgrad_batches() const { return precision == Operand::BF16 || operand_l2_direct(precision); }
+    // a transposed conv.  has_wabs: the layer keeps its weights' absmax partials (enc5 / enc6: pivp_plan::o_wabs), which the fp16-piece form needs -- a layer
+    // without them (enc4) stays fp32 in that mode, as every layer does in the three-piece mode (the tile kernel has no such form)
+    Operand deconv(bool has_wabs) const { return precision == Operand::BF16X6 || (operand_needs_scale(precision) && !has_wabs) ? Operand::F32 : precision; }
+    // the stride-2 convs' data gradient (enc1's is a transposed conv the tile kernel takes): bf16 operands in that mode only
+    Operand enc_dgrad() const { return precision == Operand::BF16 ? Operand::BF16 : Operand::F32; }
+};
 
 struct ParamInfo { std::string name; long long numel; const float* ptr; float* grad; int group; };
 
@@ -151,7 +146,7 @@ struct pivp_plan {
     size_t o_zero, o_lnpart, o_lnpart2, o_linpart, o_masks, o_losspart;   // o_lnpart2: enc6 reads hidden7's partials while writing its own
     size_t o_wabs[2];                 // precision mode FP16X3: absmax_partials of the enc5 / enc6 weights (rebuilt at the start of a rollout)
     size_t o_wbf16[7];                // bf16 packs of the ConvLSTM weights (pivp_plan_set_precision), rebuilt at the start of a rollout
-    Modes mode = modes_of(PIVP_PRECISION_F32);      // pivp_plan_set_precision
+    Modes mode{Operand::F32};         // pivp_plan_set_precision
     int pack_cache = 0, packs_valid = 0;   // pivp_plan_set_pack_cache: keep the precision modes' weight packs across rollouts until pivp_plan_params_changed
     int main_prio = -1;               // pivp_plan_set_main_priority: -1 = on unless a gradient listener is registered (data parallelism), 0 / 1 = as said
     int det = 0;                      // pivp_plan_set_deterministic: fixed-order forms of every sum of the sweep (no float atomics)
@@ -223,7 +218,7 @@ static int wgrad_batch_env() {
 // 8 per launch on every CU, what the bf16 mode does, leaves all of that work to the end of the sweep: 16.85 ms against 16.34)
 static int wg_cap_of(int T, const Modes& m) {
     const int e = wgrad_batch_env();
-    const int want = e ? e : (m.bf16_all ? WG_BATCH_MAX : (m.x3_wgrad || m.x6_wgrad) ? 2 : 1);
+    const int want = e ? e : m.precision == Operand::BF16 ? WG_BATCH_MAX : m.wgrad_batches() ? 2 : 1;
     int cap = T - 2 < 1 ? 1 : (T - 2 > WG_BATCH_MAX ? WG_BATCH_MAX : T - 2);
     if (want < cap) cap = want < 1 ? 1 : want;
     return cap;
@@ -422,11 +417,12 @@ extern "C" int pivp_plan_set_grad(pivp_plan_t* plan, int idx, float* dptr) {
 // PIVP_PRECISION_BF16 = operands
 // rounded to bf16, fp32 accumulation / gates / state (csrc/convlstm_bf16.hip), and in the backward sweep their data and weight gradients
 // (csrc/convlstm_bf16.hip <NCH, false>, csrc/wgrad_bf16.hip).  Everything else stays fp32, as do the parameters, the gradients and Adam.  Refused when a layer's map does not fit the bf16 kernel's tiles (8-wide maps need an even batch).
-static bool det_supported(const pivp_plan* p, int precision);
-extern "C" int pivp_plan_set_precision(pivp_plan_t* plan, int precision) {
-    if (!plan || precision < PIVP_PRECISION_F32 || precision > PIVP_PRECISION_FP16X3) return PIVP_ERR_BADARG;
+static bool det_supported(const pivp_plan* p, Operand precision);
+extern "C" int pivp_plan_set_precision(pivp_plan_t* plan, int precision_code) {
+    if (!plan || precision_code < PIVP_PRECISION_F32 || precision_code > PIVP_PRECISION_FP16X3) return PIVP_ERR_BADARG;
+    const Operand precision = (Operand)precision_code;
     if (plan->det && !det_supported(plan, precision)) return PIVP_ERR_BADARG;      // a deterministic plan keeps to the modes its sweep serves
-    if (precision == PIVP_PRECISION_BF16 || precision == PIVP_PRECISION_BF16X3) {   // (BF16X6: a layer its tile does not serve runs the fp32 kernel)
+    if (precision == Operand::BF16 || precision == Operand::BF16X3) {   // (the L2-direct forms: a layer their tile does not serve runs the fp32 kernel)
         for (int i = 0; i < 7; ++i) {
             const MapSize m = lstm_map(plan->cfg, i);
             IgemmDesc d;
@@ -438,7 +434,7 @@ extern "C" int pivp_plan_set_precision(pivp_plan_t* plan, int precision) {
     }
     // The dG rings' depth follows the precision, so the order is set_precision -> workspace_bytes -> set_workspace (include/pivp_hip.h).  With a
     // workspace already bound the layout it was sized for stays; a mode that needs deeper rings than it has is refused, not run short.
-    const Modes cand = modes_of(precision);
+    const Modes cand{precision};
     if (plan->ws && plan->has_grads && wg_cap_of(plan->cfg.seq_len, cand) > plan->wg_cap) return PIVP_ERR_STATE;
     plan->mode = cand;
     plan->packs_valid = 0;
@@ -448,8 +444,8 @@ extern "C" int pivp_plan_set_precision(pivp_plan_t* plan, int precision) {
 // Deterministic training (include/pivp_hip.h): every sum of the forward and the backward sweep in an order fixed by the problem shape.  Served:
 // precision F32, BF16 and BF16X3 (the ConvLSTM weight gradients then take the fp32 slot form, wgrad5x5p), models CDNA, STP and DNA, and shapes whose
 // cells fit wgrad5x5p and whose stride-2 3x3 layers fit wgrad3x3s2 (both with their column sums: no bias_grad launch is needed).
-static bool det_supported(const pivp_plan* p, int precision) {
-    if (precision != PIVP_PRECISION_F32 && precision != PIVP_PRECISION_BF16 && precision != PIVP_PRECISION_BF16X3) return false;
+static bool det_supported(const pivp_plan* p, Operand precision) {
+    if (operand_l2_direct(precision)) return false;
     const int B = p->cfg.batch;
     for (int i = 0; i < 7; ++i) {
         const MapSize m = lstm_map(p->cfg, i);
@@ -489,7 +485,7 @@ extern "C" int pivp_plan_params_changed(pivp_plan_t* plan) {
     plan->packs_valid = 0;
     return PIVP_OK;
 }
-extern "C" int pivp_plan_get_precision(const pivp_plan_t* plan) { return plan ? plan->mode.precision : PIVP_ERR_BADARG; }
+extern "C" int pivp_plan_get_precision(const pivp_plan_t* plan) { return plan ? (int)plan->mode.precision : PIVP_ERR_BADARG; }
 extern "C" long long pivp_plan_workspace_bytes(const pivp_plan_t* plan) { return plan ? plan->ws_floats * 4 : PIVP_ERR_BADARG; }
 extern "C" int pivp_plan_set_workspace(pivp_plan_t* plan, void* dptr, long long bytes) {
     if (!plan || !dptr || bytes < plan->ws_floats * 4 || ((uintptr_t)dptr & 255)) return PIVP_ERR_BADARG;
@@ -558,7 +554,7 @@ static int run_step(pivp_plan* p, int t, const float* prev, const float* action,
         if (train) o.gates_out = ws + S.gates[i];
         // the LayerNorm behind every ConvLSTM gets its statistics from the ConvLSTM epilogue (np partials per sample)
         o.ln_out.part = part_out ? part_out : lnp; o.ln_out.cap = ln_cap; o.ln_out.nparts = &np;
-        if (md.lstm_bf16) { o.w_bf16 = reinterpret_cast<const unsigned short*>(ws + p->o_wbf16[i]); o.bf16_planes = md.lstm_planes; }
+        if (md.packs()) { o.w_bf16 = reinterpret_cast<const unsigned short*>(ws + p->o_wbf16[i]); o.operand = md.precision; }
         o.ln_in = ln_in;
         int rc = run_convlstm(x, kLstm[i].cx, ldx, hp(i), kLstm[i].C, P(p, p->i_lstm_w[i]), P(p, p->i_lstm_b[i]),
                               cp(i), ws + S.c[i], ws + S.h[i], B, m.H, m.W, s, o);
@@ -583,11 +579,11 @@ static int run_step(pivp_plan* p, int t, const float* prev, const float* action,
     RC(ln(0, ws + S.e0raw, ws + S.cat7 + 32, n2, 32, 64, 1, np));
     // group 1 (TM:596): lstm1 -> hidden1 -> lstm2 -> hidden2 -> enc1 -> relu  => cat6[:, 64:96]
     RC(lstm(0, ws + S.cat7 + 32, 64));
-    // Inference rollouts in the split precision modes: hidden1 / hidden3 feed only lstm2 / lstm4, whose eight-wave kernels apply the norm while
+    // Inference rollouts in the L2-direct modes: hidden1 / hidden3 feed only lstm2 / lstm4, whose eight-wave kernels apply the norm while
     // they stage their patch (the partials of their own output go to the second buffer: their blocks finish while others still read the input's).
     float* const lnpA = ws + p->o_lnpart, * const lnpB = ws + p->o_lnpart2;
     auto other = [&](float* q) { return q == lnpA ? lnpB : lnpA; };
-    const bool fold_l2 = !train && md.lstm_bf16 && np > 0 && convlstm_ln_in_ok(md.lstm_planes, 32, 32, 32, B, p->H2, p->W2) &&
+    const bool fold_l2 = !train && np > 0 && convlstm_ln_in_ok(md.precision, 32, 32, 32, B, p->H2, p->W2) &&
                          (long)B * (p->H2 / 8) * (p->W2 / 16) >= 128;
     if (fold_l2) {
         const LnIn li = norm_in(1);
@@ -612,7 +608,7 @@ static int run_step(pivp_plan* p, int t, const float* prev, const float* action,
     }
     // group 2 (TM:597)
     RC(lstm(2, ws + S.cat6 + 64, 96));
-    const bool fold_l4 = !train && md.lstm_bf16 && np > 0 && convlstm_ln_in_ok(md.lstm_planes, 64, 64, 64, B, p->H4, p->W4) &&
+    const bool fold_l4 = !train && np > 0 && convlstm_ln_in_ok(md.precision, 64, 64, 64, B, p->H4, p->W4) &&
                          (long)B * (p->H4 / 8) * (p->W4 / 16) >= 64;
     if (fold_l4) {
         const LnIn li = norm_in(3);
@@ -660,18 +656,18 @@ static int run_step(pivp_plan* p, int t, const float* prev, const float* action,
     const bool fh = frame_head_pays(c.model_type, B, H, W, c.num_masks);
     const bool fh_fin = fh && c.model_type != PIVP_MODEL_DNA && frame_head_finishes(p->K5);
     bool partials_done = false;
-    if (fh_fin && md.deconv_prec(false) == 0) {
+    if (fh_fin && md.deconv(false) == Operand::F32) {
         RC(run_deconv3x3s2_and_partials(ws + S.n5, 128, P(p, p->i_enc_w[4]), P(p, p->i_enc_b[4]), ws + S.e4, 128, 128, 1, B, p->H8, p->W8, s,
                                         P(p, p->i_head_w), ws + p->o_linpart, c.model_type == PIVP_MODEL_STP ? 1 : 0));
         partials_done = true;
     } else {
         DeconvOpts o{};
-        o.bf16 = md.deconv_prec(false);
+        o.operand = md.deconv(false);
         RC(run_deconv3x3s2(ws + S.n5, 128, 128, P(p, p->i_enc_w[4]), P(p, p->i_enc_b[4]), ws + S.e4, 128, 128, 1, B, p->H8, p->W8, s, o));
     }
     // group 5 (TM:600): lstm6 -> hidden6 -> concat(., enc1) -> enc5 -> relu
     RC(lstm(5, ws + S.e4, 128));
-    const int dprec = md.deconv_prec(true);      // enc5 / enc6 (3: two fp16 pieces, fp32-grade)
+    const Operand dform = md.deconv(true);      // enc5 / enc6
     // The norms of hidden6 / hidden7 feed only enc5 / enc6, whose tile kernel applies them while it stages its patch ([hidden6 | enc1],
     // [hidden7 | enc0] as two sources).
     // Training plans take the same launch and have it WRITE the normalised hidden6 / hidden7 (each pixel by the block that owns it) and the
@@ -696,14 +692,14 @@ static int run_step(pivp_plan* p, int t, const float* prev, const float* action,
         }
         DeconvLnOpts o{};
         o.x1 = ws + S.cat6 + 64; o.c1 = 32; o.ld1 = 96;
-        o.bf16 = dprec; o.wscale_part = ws + p->o_wabs[0];
+        o.operand = dform; o.wscale_part = ws + p->o_wabs[0];
         if (train) o.keep = keep(6, ws + S.cat6, 96);
         o.rider = &rd;
         RC(run_deconv3x3s2_ln(ws + S.h[5], 64, P(p, p->i_enc_w[5]), P(p, p->i_enc_b[5]), ws + S.e5, 96, 96, 1, B, p->H4, p->W4, s, norm_in(6), o));
     } else {
         RC(ln(6, ws + S.h[5], ws + S.cat6, n4, 64, 96, 0, np));
         DeconvOpts o{};
-        o.bf16 = dprec; o.wscale_part = ws + p->o_wabs[0];
+        o.operand = dform; o.wscale_part = ws + p->o_wabs[0];
         RC(run_deconv3x3s2(ws + S.cat6, 96, 96, P(p, p->i_enc_w[5]), P(p, p->i_enc_b[5]), ws + S.e5, 96, 96, 1, B, p->H4, p->W4, s, o));
     }
     // group 6 (TM:601): lstm7 -> hidden7 -> concat(., enc0) -> enc6 -> norm_enc6 -> relu
@@ -715,7 +711,7 @@ static int run_step(pivp_plan* p, int t, const float* prev, const float* action,
         DeconvLnOpts o{};
         o.x1 = ws + S.cat7 + 32; o.c1 = 32; o.ld1 = 64;
         o.ln_out.part = lnp2; o.ln_out.cap = ln_cap; o.ln_out.nparts = &np;
-        o.bf16 = dprec; o.wscale_part = ws + p->o_wabs[1];
+        o.operand = dform; o.wscale_part = ws + p->o_wabs[1];
         if (train) o.keep = keep(7, ws + S.cat7, 64);
         RC(run_deconv3x3s2_ln(ws + S.h[6], 32, P(p, p->i_enc_w[6]), P(p, p->i_enc_b[6]), ws + S.e6raw, 64, 64, 0, B, p->H2, p->W2, s, li, o));
         lnp = lnp2;
@@ -723,7 +719,7 @@ static int run_step(pivp_plan* p, int t, const float* prev, const float* action,
         RC(ln(7, ws + S.h[6], ws + S.cat7, n2, 32, 64, 0, np));
         DeconvOpts o{};
         o.ln_out.part = lnp; o.ln_out.cap = ln_cap; o.ln_out.nparts = &np;
-        o.bf16 = dprec; o.wscale_part = ws + p->o_wabs[1];
+        o.operand = dform; o.wscale_part = ws + p->o_wabs[1];
         RC(run_deconv3x3s2(ws + S.cat7, 64, 64, P(p, p->i_enc_w[6]), P(p, p->i_enc_b[6]), ws + S.e6raw, 64, 64, 0, B, p->H2, p->W2, s, o));
     }
     // heads (TM:711-728).  One launch (csrc/frame_head.hip) for norm_enc6 + relu + the 1x1 heads + the motion head's finisher + flat softmax +
@@ -805,19 +801,19 @@ static int rollout_prepare_packs(pivp_plan* plan, hipStream_t s) {
     // checkpoint load) unless the caller keeps them -- pivp_plan_set_pack_cache(plan, 1) -- and reports every change with pivp_plan_params_changed.
     const bool repack = !(plan->pack_cache && plan->packs_valid);
     const Modes& md = plan->mode;
-    if (repack && md.lstm_planes == -2) {  // two fp16 pieces: the enc5 / enc6 weights' scales (their tile kernel splits the fp32 weights while it stages them)
+    if (repack && operand_needs_scale(md.precision)) {  // two fp16 pieces: the enc5 / enc6 weights' scales (their tile kernel splits the fp32 weights while it stages them)
         RC(absmax_partials(P(plan, plan->i_enc_w[5]), 9L * 96 * 96, plan->ws + plan->o_wabs[0], s));
         RC(absmax_partials(P(plan, plan->i_enc_w[6]), 9L * 64 * 64, plan->ws + plan->o_wabs[1], s));
     }
-    if (repack && md.lstm_bf16 && md.lstm_planes == 1) {      // one bf16 plane: the seven packs in one launch
+    if (repack && md.precision == Operand::BF16) {      // one bf16 plane: the seven packs in one launch
         WeightPrepJob jobs[7];
         for (int i = 0; i < 7; ++i)
             jobs[i] = WeightPrepJob{1, P(plan, plan->i_lstm_w[i]), plan->ws + plan->o_wbf16[i], kLstm[i].cx + kLstm[i].C, 4 * kLstm[i].C, 4 * kLstm[i].C, 0};
         RC(weight_prep_batch(jobs, 7, s));
-    } else if (repack && md.lstm_bf16)
+    } else if (repack && md.packs())
         for (int i = 0; i < 7; ++i)
             RC(pack_lstm_bf16(P(plan, plan->i_lstm_w[i]), reinterpret_cast<unsigned short*>(plan->ws + plan->o_wbf16[i]),
-                              kLstm[i].cx + kLstm[i].C, 4 * kLstm[i].C, s, 0, md.lstm_planes, 0));
+                              kLstm[i].cx + kLstm[i].C, 4 * kLstm[i].C, s, md.precision));
     plan->packs_valid = 1;
     return PIVP_OK;
 }
@@ -1018,8 +1014,6 @@ static int backward_step(pivp_plan* p, int t, const float* prev, bool prev_has_g
         const size_t dG1 = (size_t)B * m.H * m.W * N;                      // floats of one timestep's dG
         float* ring = ws + g.dG[i] + (size_t)wg_ring * p->wg_cap * dG1;
         const float* h_prev = Sp ? ws + Sp->h[i] : nullptr;
-        // the piece modes' two-image tiles (data gradient, weight gradient) do not fit an 8-wide map with an odd batch: the fp32 kernels take the cell
-        const bool pieces_ok = pair_tile_serves(m.W, B);
         float* const absmax_ring = ws + g.dg_absmax + (size_t)(i * 2 + wg_ring) * p->wg_cap * 72;      // dG's partial maxima, 72 floats per ring slot
         SideFork f;
         if (wg_slot == 0) {     // a new batch: the ring's previous weight-gradient launch (two batches ago) must have read it
@@ -1035,12 +1029,12 @@ static int backward_step(pivp_plan* p, int t, const float* prev, bool prev_has_g
         a.dG = ring + (size_t)wg_slot * dG1; a.wt = ws + g.wt_lstm[i]; a.d_in = DIN(i, true);
         a.B = B; a.H = m.H; a.W = m.W;      // dW = null: the weight gradient is batched below; only the fork's `ready` (behind the gate math) is used
         a.wt_ready = 1;
-        if (md.lstm_bf16 && ((md.bwd_planes != 3 && md.bwd_planes != -2) || pieces_ok)) a.wt_bf16 = reinterpret_cast<unsigned short*>(ws + g.wtb_lstm[i]);
-        a.bf16_planes = md.bwd_planes;
+        a.operand = md.dgrad(m.W, B);      // (the L2-direct forms' two-image tiles do not fit an 8-wide map with an odd batch: the fp32 kernels take the cell)
+        if (a.operand != Operand::F32) a.wt_bf16 = reinterpret_cast<unsigned short*>(ws + g.wtb_lstm[i]);
         if (wg_flush) a.fork = fork_of(i, f);
         a.ln = &lf[i];
         a.dx_only = t == 0 ? 1 : 0;      // t = 0: nobody reads d h_{-1}
-        if (md.bwd_planes == -2 || md.x3_wgrad) a.dg_absmax = absmax_ring + (size_t)wg_slot * 72;
+        if (operand_needs_scale(md.precision)) a.dg_absmax = absmax_ring + (size_t)wg_slot * 72;
         a.ep = ep; a.det = p->det;
         RC(run_convlstm_backward(a, s));
         if (t == 0) RC(ln_finish(i + 1));       // the sweep's last timestep: the norm's partial parameter planes (written by the gate kernel) become its gradient
@@ -1064,15 +1058,16 @@ static int backward_step(pivp_plan* p, int t, const float* prev, bool prev_has_g
                 RC(lstm_wgrad_reduce(L.cx, L.C, 1, part, G(p, p->i_lstm_w[i]), G(p, p->i_lstm_b[i]), B, m.H, m.W, sw, 0, DET_SLOT_J));
             d.part = part; d.part_overwrite = (t == 0 || !p->lstm_started[i]) ? 1 : 0;
             d.slot_j = DET_SLOT_J;
-            RC(run_wgrad(d, sw, &bias_done, 0));
+            RC(run_wgrad(d, sw, &bias_done, Operand::F32));
             if (t == 0)
                 RC(lstm_wgrad_reduce(L.cx, L.C, p->wg_h[i] ? 1 : 0, part, G(p, p->i_lstm_w[i]), G(p, p->i_lstm_b[i]), B, m.H, m.W, sw, 0, DET_SLOT_J));
             else p->lstm_started[i] = true;
         } else {
-            if (md.x3_wgrad && pieces_ok) d.dy_absmax = absmax_ring;      // two fp16 pieces per operand
+            const Operand wform = md.wgrad(m.W, B);
+            if (operand_needs_scale(wform)) d.dy_absmax = absmax_ring;      // dG's partial maxima of the batch (run_convlstm_backward left them there)
             d.dy_absmax_stride = 72;
             d.form = (long)B * c.height * c.width > 32L * 64 * 64 ? 2 : 0;      // (frames above 64 x 64 x 32: the eight-wave weight gradient on every layer)
-            RC(run_wgrad(d, sw, &bias_done, md.bf16_all ? 1 : (md.x6_wgrad && pieces_ok) ? 3 : 0));
+            RC(run_wgrad(d, sw, &bias_done, wform));
         }
         if (!bias_done && p->det) return PIVP_ERR_STATE;      // (unreachable: see above)
         if (!bias_done)
@@ -1087,7 +1082,6 @@ static int backward_step(pivp_plan* p, int t, const float* prev, bool prev_has_g
     // timestep the side stream still has the previous timestep's last launches (lstm1's and enc0's weight gradients) in front of it, and the main stream
     // sat idle for ~40 us per timestep.
     SideFork fe;
-    const int encp = md.bf16_all ? 1 : 0;      // bf16 mode: enc1's data gradient (the transposed conv's tile kernel) on bf16 operands too
     // Weight gradients of the stride-2 3x3 layers (k = 0..4: enc6, enc5, enc4, enc2, enc1): a step adds itself to the layer's open batch -- its dY sits in slot
     // eg_slot of the ring, its forward input one slab below the previous step's -- and the step that closes the batch launches ONE weight gradient over all of
     // them on the side stream (wgrad3x3s2.hip: per launch a block pays 37-150 KB of partial planes, per timestep nothing).  run_conv_backward (dW = null) has
@@ -1114,7 +1108,7 @@ static int backward_step(pivp_plan* p, int t, const float* prev, bool prev_has_g
         d.x0 = p->enc_x0[k]; d.ld0 = E.ldx; d.dy = dy0; d.ldy = E.ldy; d.dw = G(p, p->i_enc_w[E.layer]); d.db = G(p, p->i_enc_b[E.layer]);
         d.tcount = cnt; d.ts_x0 = -slab_bytes; d.ts_dy = dy_step;
         d.part = ws + g.wg_part[k]; d.part_overwrite = p->enc_started[k] ? 0 : 1;
-        RC(run_wgrad(d, sw, &bias_done, 0));
+        RC(run_wgrad(d, sw, &bias_done, Operand::F32));
         if (!bias_done && p->det) return PIVP_ERR_STATE;      // (unreachable: set_deterministic admits only shapes wgrad3x3s2 serves, column sums included)
         if (!bias_done)
             for (int j = 0; j < cnt; ++j) RC(bias_grad(dy0 + (size_t)j * (dy_step / 4), E.ldy, E.c, B * d.Hy * d.Wy, G(p, p->i_enc_b[E.layer]), sw));
@@ -1136,7 +1130,7 @@ static int backward_step(pivp_plan* p, int t, const float* prev, bool prev_has_g
         a.wt_ready = 1;
         if (eg_flush) a.fork = fork_of(7 + k, fe);
         a.dy_add = dy_add; a.ld_add = ld_add;
-        a.prec = encp;
+        a.operand = md.enc_dgrad();
         RC(run_conv_backward(a, s));
         return eg_flush ? enc_flush(k, true) : PIVP_OK;
     };
@@ -1300,7 +1294,7 @@ static int rollout_backward_sweep(pivp_plan_t* plan, const float* images, const 
         // fetches every operand tile once per 32 x 64 output slice, and what a block pays per launch (205 KB of atomics, the first tile's
         // latency) is amortised over the batch (csrc/wgrad_bf16.hip).
         const int e = wgrad_batch_env();
-        int gb = e ? e : ((md.bf16_all || md.x3_wgrad || md.x6_wgrad) ? plan->wg_cap : 1);
+        int gb = e ? e : (md.wgrad_batches() ? plan->wg_cap : 1);
         if (gb < 1) gb = 1;
         if (gb > plan->wg_cap) gb = plan->wg_cap;
         plan->wg_batch = gb;
@@ -1329,18 +1323,18 @@ static int rollout_backward_sweep(pivp_plan_t* plan, const float* images, const 
             jobs[n++] = WeightPrepJob{0, P(plan, plan->i_enc_w[kEnc[k].layer]), ws + g.wt_enc[kEnc[k].layer], 9, kEnc[k].c, kEnc[k].c, 0};
         RC(weight_prep_batch(jobs, n, s));
     }
-    if (md.lstm_bf16 && md.bwd_planes == 1) {      // bf16 mode: the ConvLSTM data gradients run on one-plane bf16 packs of those: one launch
+    if (md.precision == Operand::BF16) {      // bf16 mode: the ConvLSTM data gradients run on one-plane bf16 packs of those: one launch
         WeightPrepJob jobs[7];
         for (int i = 0; i < 7; ++i) {
             const int cin = kLstm[i].cx + kLstm[i].C;
             jobs[i] = WeightPrepJob{1, ws + g.wt_lstm[i], ws + g.wtb_lstm[i], 4 * kLstm[i].C, cin, conv5x5_bf16_rows(cin), 0};
         }
         RC(weight_prep_batch(jobs, 7, s));
-    } else if (md.lstm_bf16)        // split modes: the hi / lo pair, the three pieces or the fp16 pieces (their own pack kernels, per layer)
+    } else if (md.packs())        // split modes: the hi / lo pair, the three pieces or the fp16 pieces (their own pack kernels, per layer)
         for (int i = 0; i < 7; ++i) {
             const int cin = kLstm[i].cx + kLstm[i].C;
-            RC(pack_lstm_bf16(ws + g.wt_lstm[i], reinterpret_cast<unsigned short*>(ws + g.wtb_lstm[i]), 4 * kLstm[i].C, cin, s,
-                              conv5x5_bf16_rows(cin), md.bwd_planes, 1));
+            RC(pack_lstm_bf16(ws + g.wt_lstm[i], reinterpret_cast<unsigned short*>(ws + g.wtb_lstm[i]), 4 * kLstm[i].C, cin, s, md.precision,
+                              conv5x5_bf16_rows(cin), 1));
         }
     bool has_go = false;
     int eq_next = 0;      // the enc dY ring slot of step t + 1 (unused at t = T - 2)
@@ -1454,7 +1448,7 @@ extern "C" long long pivp_get_tap(pivp_plan_t* plan, const char* name, int step,
         const F folded[] = {{"hidden2", 1, 2, S.n2, 32, HW2, 32}, {"hidden4", 3, 4, S.n4, 64, HW4, 64}, {"hidden6", 5, 6, S.cat6, 64, HW4, 96},
                             {"hidden7", 6, 7, S.cat7, 32, HW2, 64},
                             {"hidden1", 0, 1, S.n1, 32, HW2, 32, 1}, {"hidden3", 2, 3, S.n3, 64, HW4, 64, 1}};      // (the split modes: inside lstm2 / lstm4)
-        const bool split = plan->mode.lstm_planes == 3 || plan->mode.lstm_planes == -2;
+        const bool split = operand_l2_direct(plan->mode.precision);
         for (const F& f : folded)
             if (strcmp(f.n, name) == 0 && (!f.split_only || split)) {
                 int rc = run_layernorm(ws + S.h[f.layer], P(plan, plan->i_ln_g[f.norm]), P(plan, plan->i_ln_b[f.norm]), ws + f.dst,

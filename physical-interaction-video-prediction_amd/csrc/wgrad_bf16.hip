@@ -560,11 +560,14 @@ int wgrad5x5_bf16(const WgradDesc& d, hipStream_t s) {
     // A batch of timesteps goes to the 25-tap kernel (per timestep at B = 32, all seven layers: 168 us at 8 per launch, 225 us at 4); ONE
     // timestep to the kernel-row kernel below, whose 5 x cin/32 blocks per tile are then the better use of the chip (389 us against 580:
     // the sweep's t = 0 launches, sequences too short to batch).
-    if (d.dy_absmax) {       // two fp16 pieces per operand: the 25-tap kernel, whatever the batch
-        PIVP_CHECK_ARG(d.dy_absmax_stride >= 66 || d.tcount <= 1);
-        return launch_wgrad25<2>(d, s);
+    switch (d.operand) {
+        case Operand::F32: case Operand::BF16X3: return PIVP_ERR_BADARG;      // (the fp32 kernels' / no weight-gradient form)
+        case Operand::FP16X3:       // two fp16 pieces per operand: the 25-tap kernel, whatever the batch
+            PIVP_CHECK_ARG(d.dy_absmax && (d.dy_absmax_stride >= 66 || d.tcount <= 1));
+            return launch_wgrad25<2>(d, s);
+        case Operand::BF16X6: return launch_wgrad25<3>(d, s);      // three bf16 pieces per operand, likewise
+        case Operand::BF16: break;
     }
-    if (d.pieces == 3) return launch_wgrad25<3>(d, s);      // three bf16 pieces per operand, likewise
     // A batch of timesteps (WgradDesc::form): the four-wave form (co-resident with the main stream's small kernels) on maps of up to 32 x 32 x 32 pixels per
     // timestep, the eight-wave form (half the patch traffic per multiply-add) on larger ones; the plan asks for the eight-wave form on every layer of frames
     // above 64 x 64 x 32 -- config 5, whose main-stream kernels fill the chip by themselves: 68.2 ms with the four-wave form everywhere against 66.3.
