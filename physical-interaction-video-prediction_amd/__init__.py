@@ -17,10 +17,10 @@ from . import planning
 from . import metrics
 from .metrics import frame_metrics, StepCurves
 from .data import concat_examples
-from .optimizer import Adam
+from .optimizer import Adam, GradientClipping
 from .parallel import GradAllReduce, shard_batch
 
 __all__ = ['Model', 'config', 'using_config', 'reference_param_shapes', 'default_init',
            'scheduled_sampling_masks', 'save_npz', 'load_npz', 'to_internal', 'from_internal', 'concat_examples',
-           'Adam', 'GradAllReduce', 'shard_batch', 'save_optimizer_npz', 'load_optimizer_npz', 'dataset', 'planning',
+           'Adam', 'GradientClipping', 'GradAllReduce', 'shard_batch', 'save_optimizer_npz', 'load_optimizer_npz', 'dataset', 'planning',
            'metrics', 'frame_metrics', 'StepCurves', 'DeviceDataset', 'DeviceBatcher']

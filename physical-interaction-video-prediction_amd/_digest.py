@@ -2,7 +2,7 @@
 
 build.py embeds it in the library (`pivp_build_digest()`, include/pivp_hip.h) and `_lib.load()` recomputes it from the sources that
 travel with the package: a library older than the code it claims to implement refuses to load, so a GPU test can never pass on a stale
-build.  Sources only (csrc/*.hip, csrc/*.h, the two public headers): objects, the .so and compile flags are not part of it -- an
+build.  Sources only (csrc/*.hip, csrc/*.h, the three public headers): objects, the .so and compile flags are not part of it -- an
 instrumented build (PIVP_EXTRA_FLAGS) of the same sources is still the same code."""
 import hashlib
 import os
@@ -11,11 +11,12 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 HEADER = os.path.join(HERE, '..', 'include', 'pivp_hip.h')
 DATA_HEADER = os.path.join(HERE, '..', 'include', 'pivp_data.h')      # the data-feed entry points (pivp_gather_batch)
+OPTIM_HEADER = os.path.join(HERE, '..', 'include', 'pivp_optim.h')    # the guarded optimizer step (pivp_grad_stats, pivp_adam_step_guarded)
 
 
 def source_files():
     names = sorted(n for n in os.listdir(CSRC) if n.endswith('.hip') or n.endswith('.h'))
-    return [os.path.join(CSRC, n) for n in names] + [DATA_HEADER, HEADER]
+    return [os.path.join(CSRC, n) for n in names] + [DATA_HEADER, HEADER, OPTIM_HEADER]
 
 
 def source_digest():

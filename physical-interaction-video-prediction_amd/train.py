@@ -24,7 +24,7 @@ from . import dataset as ds
 from .checkpoint import load_npz, load_optimizer_npz, save_npz, save_optimizer_npz
 from .data import concat_examples
 from .model import Model, using_config
-from .optimizer import Adam
+from .optimizer import Adam, GradientClipping
 from .parallel import GradAllReduce
 
 
@@ -57,7 +57,20 @@ def build_parser():
     # frames are held there, uint8 only for frames on the k/255 grid (auto: decided from the first sequences)
     p.add_argument('--device_dataset', type=int, default=0, choices=(0, 1))
     p.add_argument('--device_storage', default='auto', choices=ds.STORAGES)
+    # the guarded Adam step (optimizer.py): --grad_clip t > 0 adds chainer's GradientClipping(t); --skip_nonfinite 1 leaves the parameters alone on a
+    # step whose gradient holds a NaN / inf and counts it; --log_grad_norm 1 only records the norm.  Any of them: the per-step global gradient norm
+    # stays on the device, is read once per epoch and saved as training-global_grad_norm.npy.  All off: the plain Adam launch, log and files as before
+    p.add_argument('--grad_clip', type=float, default=0.0)
+    p.add_argument('--skip_nonfinite', type=int, default=0, choices=(0, 1))
+    p.add_argument('--log_grad_norm', type=int, default=0, choices=(0, 1))
     return p
+
+
+def grad_norm_stat(norms, stat):
+    """[mean, std, min, max, median] of an epoch's per-step gradient norms.  The norm of a step with a NaN / inf gradient is itself non-finite: such
+    steps are left out (their number is the skipped-steps count when --skip_nonfinite is on); an epoch without a finite norm gives a row of NaN."""
+    finite = [v for v in norms if np.isfinite(v)]
+    return stat(finite) if finite else [float('nan')] * 5
 
 
 def _git_version():
@@ -98,7 +111,15 @@ def main(argv=None):
                   is_stp=args.model_type == 'STP', use_state=args.use_state, scheduled_sampling_k=args.schedsamp_k,
                   num_frame_before_prediction=args.context_frames, prefix='train', device=device, keep_activations=True,
                   deterministic=bool(args.deterministic))
-    optimizer = Adam(alpha=args.learning_rate).setup(model, data_parallel=dp)
+    if args.grad_clip < 0 or args.grad_clip != args.grad_clip:
+        raise SystemExit('--grad_clip must be >= 0 (0: off)')
+    guarded = bool(args.grad_clip > 0 or args.skip_nonfinite or args.log_grad_norm)
+    if guarded:
+        optimizer = Adam(alpha=args.learning_rate, skip_nonfinite=bool(args.skip_nonfinite), track_grad_norm=True).setup(model, data_parallel=dp)
+        if args.grad_clip > 0:
+            optimizer.add_hook(GradientClipping(args.grad_clip))
+    else:
+        optimizer = Adam(alpha=args.learning_rate).setup(model, data_parallel=dp)
     if args.pretrained_model:
         load_npz(args.pretrained_model, model)
     per_rank = args.batch_size // world
@@ -111,6 +132,7 @@ def main(argv=None):
     valid_iter = ds.SerialIterator(valid_set, args.batch_size, repeat=False, shuffle=True)
     save_dir = os.path.join(args.output_dir, '%s-%s-%d' % (time.strftime('%Y%m%d-%H%M%S'), args.model_type, args.batch_size))
     local_losses, local_psnr, g_loss, g_psnr, g_loss_v, g_psnr_v = [], [], [], [], [], []
+    local_gnorm, g_gnorm = [], []                     # guarded runs: the steps' gradient norms as device scalars, read at the epoch's end
     stat = lambda a: [float(np.mean(a)), float(np.std(a)), float(np.min(a)), float(np.max(a)), float(np.median(a))]
     state_loaded = False
     itr, start = 0, None
@@ -136,6 +158,8 @@ def main(argv=None):
                 model(x, 0)
             model.reset_state(); load_optimizer_npz(args.pretrained_state, optimizer); state_loaded = True
         optimizer.update(model, x, itr)             # enqueues the whole step; returns while the GPU is still working on it
+        if guarded:
+            local_gnorm.append(optimizer.grad_norm.clone())      # (a view of a buffer the next step overwrites; no synchronisation)
         if itr + 1 < args.num_iterations:
             feeder.prefetch()                       # ... so the next batch's host work and copy run underneath it
         stats = torch.stack([model.loss, model.psnr_all]).to(torch.float64)
@@ -148,7 +172,14 @@ def main(argv=None):
             logger.info('%d %s', epoch + 1, local_losses[-1])
         if is_new_epoch:
             g_loss.append(stat(local_losses)); g_psnr.append(stat(local_psnr))
-            if rank == 0:
+            if guarded:
+                g_gnorm.append(grad_norm_stat(torch.stack(local_gnorm).tolist(), stat))
+                skipped = optimizer.skipped_steps   # (reads the device counter)
+                if rank == 0:
+                    logger.info('[TRAIN] Epoch #: %d  elapsed %.2fs  loss %.6f  psnr %.3f  grad norm %.6g  skipped steps %d', epoch + 1,
+                                time.time() - start, g_loss[-1][0], g_psnr[-1][0], g_gnorm[-1][0], skipped)
+                local_gnorm = []
+            elif rank == 0:
                 logger.info('[TRAIN] Epoch #: %d  elapsed %.2fs  loss %.6f  psnr %.3f', epoch + 1, time.time() - start, g_loss[-1][0], g_psnr[-1][0])
             local_losses, local_psnr, start = [], [], None
             if (epoch + 1) % args.validation_interval == 0 and len(valid_set) > 0:
@@ -171,6 +202,8 @@ def main(argv=None):
                 np.save(os.path.join(save_dir, 'training-global_psnr_all'), np.array(g_psnr))
                 np.save(os.path.join(save_dir, 'training-global_losses_valid'), np.array(g_loss_v))
                 np.save(os.path.join(save_dir, 'training-global_psnr_all_valid'), np.array(g_psnr_v))
+                if guarded:
+                    np.save(os.path.join(save_dir, 'training-global_grad_norm'), np.array(g_gnorm))
         itr += 1
     if world > 1:
         import torch.distributed as dist
