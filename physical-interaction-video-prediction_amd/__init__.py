@@ -16,6 +16,8 @@ from .dataset import DeviceDataset, DeviceBatcher
 from . import planning
 from . import metrics
 from .metrics import frame_metrics, StepCurves
+from . import losses
+from .losses import ImageLoss, image_loss
 from .data import concat_examples
 from .optimizer import Adam, GradientClipping
 from .parallel import GradAllReduce, shard_batch
@@ -23,4 +25,4 @@ from .parallel import GradAllReduce, shard_batch
 __all__ = ['Model', 'config', 'using_config', 'reference_param_shapes', 'default_init',
            'scheduled_sampling_masks', 'save_npz', 'load_npz', 'to_internal', 'from_internal', 'concat_examples',
            'Adam', 'GradientClipping', 'GradAllReduce', 'shard_batch', 'save_optimizer_npz', 'load_optimizer_npz', 'dataset', 'planning',
-           'metrics', 'frame_metrics', 'StepCurves', 'DeviceDataset', 'DeviceBatcher']
+           'metrics', 'frame_metrics', 'StepCurves', 'DeviceDataset', 'DeviceBatcher', 'losses', 'ImageLoss', 'image_loss']

@@ -1,5 +1,5 @@
 """ctypes binding of libpivp_hip.so (the C ABI declared in include/pivp_hip.h, the data feed's entry points of include/pivp_data.h and the
-guarded optimizer step's of include/pivp_optim.h).
+guarded optimizer step's of include/pivp_optim.h, the image loss's and the seed hook of include/pivp_loss.h).
 
 There is no CPU fallback: if the library is missing or fails to load, `load()` raises."""
 import ctypes
@@ -160,6 +160,18 @@ OPTIM_SIGNATURES = {
     'pivp_grad_stats': (_i, [_vp, _ll, _vp, _vp, _i, _i, _d, _d, _vp, _vp, _vp]),
     'pivp_adam_step_guarded': (_i, [_vp, _vp, _vp, _vp, _ll, _d, _d, _d, _d, _d, _vp, _i, _vp, _vp]),
 }
+
+
+class PivpImageLoss(ctypes.Structure):      # pivp_image_loss_t
+    _fields_ = [('w_mse', _f), ('w_l1', _f), ('w_gdl', _f), ('w_dssim', _f), ('win', _i), ('sigma', _f), ('data_range', _f)]
+
+
+# ... and every symbol include/pivp_loss.h declares (the L1 / GDL / DSSIM image terms with their gradient; the backward sweep's seed hook)
+LOSS_SIGNATURES = {
+    'pivp_image_loss_ws_bytes': (_ll, [_i, _i, _i, _i, _c.POINTER(PivpImageLoss)]),
+    'pivp_image_loss': (_i, [_vp, _vp, _i, _i, _i, _i, _c.POINTER(PivpImageLoss), _vp, _vp, _vp, _vp, _vp]),
+    'pivp_plan_set_frame_grad': (_i, [_vp, _vp]),
+}
 OPTIM_MAX_SEGMENTS = 1024      # PIVP_OPTIM_MAX_SEGMENTS
 GRAD_GROUPS = 6                # PIVP_GRAD_GROUPS (include/pivp_hip.h)
 
@@ -176,7 +188,8 @@ def load():
             "libpivp_hip.so is missing (%s). Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "or `python physical-interaction-video-prediction_amd/build.py`. There is no CPU fallback." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(DATA_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()):
+    for name, (res, args) in (list(SIGNATURES.items()) + list(DATA_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items())
+                              + list(LOSS_SIGNATURES.items())):
         fn = getattr(lib, name)   # AttributeError if the ABI and the header drift apart
         fn.restype = res
         fn.argtypes = args
@@ -187,7 +200,7 @@ def load():
         shipped = _digest.source_digest()
     except OSError as e:      # a copied / installed package without csrc/ or the repo's include/: say what is missing instead of a bare open() error
         raise RuntimeError('cannot check libpivp_hip.so against its sources: %s is missing (the package needs csrc/*.hip, csrc/*.h and '
-                           '../include/pivp_hip.h, pivp_data.h and pivp_optim.h next to it; there is no CPU fallback)' % e.filename) from e
+                           '../include/pivp_hip.h, pivp_data.h, pivp_loss.h and pivp_optim.h next to it; there is no CPU fallback)' % e.filename) from e
     built = lib.pivp_build_digest().decode()
     if built != shipped:
         raise RuntimeError(

@@ -245,6 +245,9 @@ int cem_update(const float* cost, float* actions, float* mean, float* stdv, floa
 int frame_metrics(const float* pred, const float* truth, int N, int C, int H, int W, int win, float sigma, float data_range, float* mse,
                   float* ssim, hipStream_t s);
 
+// The caller's additional d loss / d gen_images joins the sweep's seed (csrc/image_loss.hip; pivp_plan_set_frame_grad): go[i] += seed[i].  One launch.
+int frame_seed_add(float* go, const float* seed, long n, hipStream_t s);
+
 // Batch gather out of a device-resident data set (csrc/batch_gather.hip): frames [N][T][H][W][3] (float32, or uint8 levels k = k / 255) + actions /
 // states [N][T][5], index [B] on the device -> images [T][B][3][H][W], actions / states [T][B][5].  One launch, bit-exact.
 int gather_batch(const void* frames, int frames_u8, const float* actions, const float* states, const int* index, int B, long long N, int T, int H,

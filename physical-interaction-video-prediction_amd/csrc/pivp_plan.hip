@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/pivp_hip.h"
+#include "../../include/pivp_loss.h"
 #include "pivp_host.h"
 
 using namespace pivp;
@@ -150,6 +151,7 @@ struct pivp_plan {
     int pack_cache = 0, packs_valid = 0;   // pivp_plan_set_pack_cache: keep the precision modes' weight packs across rollouts until pivp_plan_params_changed
     int main_prio = -1;               // pivp_plan_set_main_priority: -1 = on unless a gradient listener is registered (data parallelism), 0 / 1 = as said
     int det = 0;                      // pivp_plan_set_deterministic: fixed-order forms of every sum of the sweep (no float atomics)
+    const float* frame_seed = nullptr;   // pivp_plan_set_frame_grad: an additional d loss / d gen_images[ctx-1 .. T-2] for the sweep (null: the plan's own seed alone)
     bool lstm_started[7] = {};        // deterministic sweeps: the cell's weight-gradient slots hold this sweep's sums (before: stored, not added)
     pivp_grad_group_cb grad_cb = nullptr; void* grad_cb_user = nullptr;   // gradient-group-final notifications (t = 0 sweep)
     int loss_nparts;
@@ -472,6 +474,13 @@ extern "C" int pivp_plan_set_deterministic(pivp_plan_t* plan, int on) {
     return PIVP_OK;
 }
 extern "C" int pivp_plan_get_deterministic(const pivp_plan_t* plan) { return plan ? plan->det : PIVP_ERR_BADARG; }
+
+// include/pivp_loss.h: an additional d loss / d gen_images for every later sweep (null: none -- the sweep's launches are then exactly its own)
+extern "C" int pivp_plan_set_frame_grad(pivp_plan_t* plan, const float* seed) {
+    if (!plan || (reinterpret_cast<uintptr_t>(seed) & 3)) return PIVP_ERR_BADARG;
+    plan->frame_seed = seed;
+    return PIVP_OK;
+}
 // Inference with constant weights: keep the bf16 / fp16 weight packs across rollouts (on = 1) instead of rebuilding them at the start of each.  The
 // caller then owes pivp_plan_params_changed after EVERY modification of a parameter tensor (optimizer step, checkpoint load, host write); set_param,
 // set_precision and set_workspace invalidate by themselves.  Default off.
@@ -1313,6 +1322,8 @@ static int rollout_backward_sweep(pivp_plan_t* plan, const float* images, const 
     RC(scaled_diff(gen_states + (size_t)(ctx - 1) * B * 5, states + (size_t)ctx * B * 5, ws + g.dstate + (size_t)(ctx - 1) * B * 5, (long)(T - ctx) * B * 5, sscale, 0, s));
     // d loss / d gen[t], t = ctx-1 .. T-2 (gen[t] is compared with images[t + 1]); the sweep adds the feed-back terms of step t + 1 into frame t in place
     RC(scaled_diff(gen_images + (size_t)(ctx - 1) * fr, images + (size_t)ctx * fr, ws + g.go + (size_t)(ctx - 1) * fr, (long)(T - ctx) * (long)fr, fscale, 0, s));
+    // ... plus the caller's own d loss / d gen (pivp_plan_set_frame_grad): everything downstream of g.go is indifferent to where the seed came from
+    if (plan->frame_seed) RC(frame_seed_add(ws + g.go + (size_t)(ctx - 1) * fr, plan->frame_seed, (long)(T - ctx) * (long)fr, s));
     // weights are constant during the sweep: the transposed packs for the data gradients, all twelve in one launch (7 + 5 launches before round 5)
     {
         WeightPrepJob jobs[12];

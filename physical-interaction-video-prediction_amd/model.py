@@ -148,7 +148,7 @@ class Model(object):
     def __init__(self, num_masks, is_cdna=True, is_dna=False, is_stp=False, use_state=True,
                  scheduled_sampling_k=-1, num_frame_before_prediction=2, prefix=None,
                  device='cuda:0', ln_eps=1e-6, stp_border='clamp', keep_activations=False, precision='fp32', main_priority=None,
-                 deterministic=False):
+                 deterministic=False, image_loss=None):
         if is_cdna:                      # TM:531-542, precedence cdna > stp > dna
             self.model_type = 'CDNA'
         elif is_stp:
@@ -190,6 +190,17 @@ class Model(object):
             raise ValueError("deterministic=True is not served with precision=%r (only %s)"
                              % (precision, ', '.join(map(repr, self.DETERMINISTIC_PRECISIONS))))
         self.deterministic = deterministic
+        # image_loss: an `ImageLoss` (losses.py) -- L1 / gradient-difference / DSSIM terms (and another weight on the MSE) beside the reference's
+        # objective.  None, or the reference's weights (1, 0, 0, 0): nothing new is called and every output is what it is without the argument.
+        if image_loss is not None:
+            from .losses import ImageLoss
+            if not isinstance(image_loss, ImageLoss):
+                raise ValueError('image_loss must be an ImageLoss or None, not %r' % (image_loss,))
+        self.image_loss = image_loss
+        self._extra_loss = image_loss is not None and not image_loss.is_reference()
+        self.loss_terms = None         # with an image loss: device scalars mse / l1 / gdl / dssim (means over the scored frames) and extra (their weighted sum
+                                       # beyond the reference's loss) of the last call
+        self._loss_grad = None         # ... and d extra / d gen_images[ctx-1:], when the call kept what backward() needs
         self.main_priority = main_priority     # None / False / True: include/pivp_hip.h, pivp_plan_set_main_priority
         self._ref_pending = None       # reference-layout arrays loaded before the first call
         self._params = None            # name -> view into _flat_params (internal layout)
@@ -380,6 +391,8 @@ class Model(object):
         self.psnr_all = 0.0
         self._results = None
         self._imagined = False
+        self.loss_terms = None
+        self._loss_grad = None
         if self._active is not None:
             self._reset_plan(self._active)
 
@@ -449,7 +462,23 @@ class Model(object):
             self.gen_states = [gen_states[t] for t in range(T - 1)]
             self.loss = results[0]
             self.psnr_all = results[1]
+            self.loss_terms = None
+            self._loss_grad = None
+            if self._extra_loss:
+                self._add_image_loss(gen, images, ctx, config.train and self.keep_activations)
         return self.loss
+
+    def _add_image_loss(self, gen, images, ctx, want_grad):
+        """ONE pivp_image_loss call on the scored frames gen[ctx-1:] against images[ctx:] (both contiguous: N = (T-ctx) * B images), on the rollout's
+        stream and without a synchronisation.  The reference's loss already holds the MSE once, so the op's MSE weight is mse - 1."""
+        from .losses import _launch
+        spec = self.image_loss
+        T, B, C, H, W = images.shape
+        spec.check_frames((C, H, W))
+        out = _launch(gen[ctx - 1:], images[ctx:], (T - ctx) * B, C, H, W, spec._struct(extra_mse=spec.mse - 1.0), bool(want_grad), (T - ctx, B))
+        self.loss = self._results[0] + out.terms[4]
+        self.loss_terms = dict(mse=out.terms[0], l1=out.terms[1], gdl=out.terms[2], dssim=out.terms[3], extra=out.terms[4])
+        self._loss_grad = out.grad
 
     # ---- evaluation surface (no counterpart in the reference, whose only quality number is psnr_all: the PSNR of the batch-mean MSE) -------
     def evaluate(self, x, win=11, sigma=1.5, data_range=1.0):
@@ -574,6 +603,8 @@ class Model(object):
         self._gen_states = gen_states
         self._results = None
         self._imagined = True
+        self.loss_terms = None
+        self._loss_grad = None
         self.gen_images = [gen[t] for t in range(T - 1)]
         self.gen_states = [gen_states[t] for t in range(T - 1)]
         self.pixel_mass = None
@@ -592,9 +623,13 @@ class Model(object):
             raise RuntimeError('call the model first (parameters are lazily sized)')
         return list(self._group_ranges)
 
-    def backward(self, on_group=None):
+    def backward(self, on_group=None, frame_grad=None):
         """Back-propagate the loss of the LAST call through time (needs keep_activations=True).  Gradients
         accumulate into `model._flat_grads` (internal layouts); `grads_reference()` returns them in checkpoint layout.
+
+        frame_grad: an additional d loss / d gen_images[ctx-1:], a (T-ctx, B, 3, H, W) float32 tensor on the model's device -- the gradient of any
+        loss of the predicted frames the caller computed (in torch, say).  It joins the sweep's seed beside the reference loss's own gradient and
+        the model's image loss's, if it has one (pivp_plan_set_frame_grad, include/pivp_loss.h).
 
         on_group(i): optional host callback, invoked from inside the sweep as soon as every kernel that contributes to
         gradient group i (slice grad_group_ranges()[i]) has been enqueued on the model's stream -- the hook the
@@ -607,6 +642,15 @@ class Model(object):
         self._ensure_grads()
         images, actions, states = self._inputs
         gt_ptr = self._gt_mask.data_ptr() if self._gt_mask is not None else None
+        seed = self._loss_grad
+        if self._extra_loss and seed is None:
+            raise RuntimeError('the last call kept no gradient of the image loss (it ran under using_config(\'train\', False)): call the model in training mode')
+        if frame_grad is not None:
+            want = (images.shape[0] - self.num_frame_before_prediction,) + tuple(images.shape[1:])
+            if not torch.is_tensor(frame_grad) or tuple(frame_grad.shape) != want or frame_grad.dtype != torch.float32 or frame_grad.device != images.device:
+                raise ValueError('frame_grad must be a float32 tensor of shape %s on %s' % (want, images.device))
+            frame_grad = frame_grad.contiguous()
+            seed = frame_grad if seed is None else seed + frame_grad
         cb = None
         if on_group is not None:
             import ctypes
@@ -622,10 +666,14 @@ class Model(object):
         try:
             # the model's device must be the CURRENT one for the launches (and for the plan's own side stream, created on first use)
             with torch.cuda.device(self.device):
+                if seed is not None:      # (torch keeps the tensor's memory for the stream that is current here, the sweep's)
+                    _lib.check(plan.lib.pivp_plan_set_frame_grad(plan.h, seed.data_ptr()), 'pivp_plan_set_frame_grad')
                 _lib.check(plan.lib.pivp_rollout_backward(plan.h, images.data_ptr(), actions.data_ptr(), states.data_ptr(), gt_ptr,
                                                           self._gen.data_ptr(), self._gen_states.data_ptr(), self._stream()),
                            'pivp_rollout_backward')
         finally:
+            if seed is not None:
+                plan.lib.pivp_plan_set_frame_grad(plan.h, None)
             if cb is not None:
                 plan.lib.pivp_plan_set_grad_callback(plan.h, None, None)
         if cb is not None and errors:

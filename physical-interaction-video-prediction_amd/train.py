@@ -63,7 +63,24 @@ def build_parser():
     p.add_argument('--grad_clip', type=float, default=0.0)
     p.add_argument('--skip_nonfinite', type=int, default=0, choices=(0, 1))
     p.add_argument('--log_grad_norm', type=int, default=0, choices=(0, 1))
+    # the training objective's image terms (losses.ImageLoss): weights of the MSE, L1, gradient-difference and DSSIM = 1 - SSIM terms.  1 / 0 / 0 / 0 is
+    # the reference's objective: nothing new runs and the files are as before.  Anything else: validation scores the same loss, the per-step means
+    # of the four terms stay on the device, are read once per epoch and saved as training-global_loss_terms.npy (per-rank means, like the loss)
+    p.add_argument('--loss_mse', type=float, default=1.0)
+    p.add_argument('--loss_l1', type=float, default=0.0)
+    p.add_argument('--loss_gdl', type=float, default=0.0)
+    p.add_argument('--loss_dssim', type=float, default=0.0)
     return p
+
+
+def image_loss_from_args(args):
+    """-> the ImageLoss of --loss_*, or None for the reference's objective."""
+    from .losses import ImageLoss
+    try:
+        spec = ImageLoss(mse=args.loss_mse, l1=args.loss_l1, gdl=args.loss_gdl, dssim=args.loss_dssim)
+    except ValueError as e:
+        raise SystemExit('--loss_*: %s' % e)
+    return None if spec.is_reference() else spec
 
 
 def grad_norm_stat(norms, stat):
@@ -110,7 +127,8 @@ def main(argv=None):
     model = Model(num_masks=args.num_masks, is_cdna=args.model_type == 'CDNA', is_dna=args.model_type == 'DNA',
                   is_stp=args.model_type == 'STP', use_state=args.use_state, scheduled_sampling_k=args.schedsamp_k,
                   num_frame_before_prediction=args.context_frames, prefix='train', device=device, keep_activations=True,
-                  deterministic=bool(args.deterministic))
+                  deterministic=bool(args.deterministic), image_loss=image_loss_from_args(args))
+    extra_loss = model.image_loss is not None
     if args.grad_clip < 0 or args.grad_clip != args.grad_clip:
         raise SystemExit('--grad_clip must be >= 0 (0: off)')
     guarded = bool(args.grad_clip > 0 or args.skip_nonfinite or args.log_grad_norm)
@@ -132,6 +150,7 @@ def main(argv=None):
     valid_iter = ds.SerialIterator(valid_set, args.batch_size, repeat=False, shuffle=True)
     save_dir = os.path.join(args.output_dir, '%s-%s-%d' % (time.strftime('%Y%m%d-%H%M%S'), args.model_type, args.batch_size))
     local_losses, local_psnr, g_loss, g_psnr, g_loss_v, g_psnr_v = [], [], [], [], [], []
+    local_terms, g_terms = [], []                     # runs with an image loss: the steps' four term means as device tensors, read at the epoch's end
     local_gnorm, g_gnorm = [], []                     # guarded runs: the steps' gradient norms as device scalars, read at the epoch's end
     stat = lambda a: [float(np.mean(a)), float(np.std(a)), float(np.min(a)), float(np.max(a)), float(np.median(a))]
     state_loaded = False
@@ -160,6 +179,8 @@ def main(argv=None):
         optimizer.update(model, x, itr)             # enqueues the whole step; returns while the GPU is still working on it
         if guarded:
             local_gnorm.append(optimizer.grad_norm.clone())      # (a view of a buffer the next step overwrites; no synchronisation)
+        if extra_loss:
+            local_terms.append(torch.stack([model.loss_terms[k] for k in ('mse', 'l1', 'gdl', 'dssim')]))
         if itr + 1 < args.num_iterations:
             feeder.prefetch()                       # ... so the next batch's host work and copy run underneath it
         stats = torch.stack([model.loss, model.psnr_all]).to(torch.float64)
@@ -172,6 +193,11 @@ def main(argv=None):
             logger.info('%d %s', epoch + 1, local_losses[-1])
         if is_new_epoch:
             g_loss.append(stat(local_losses)); g_psnr.append(stat(local_psnr))
+            if extra_loss:                          # one row per epoch: the epoch's mean of each term
+                g_terms.append(torch.stack(local_terms).to(torch.float64).mean(dim=0).tolist())
+                if rank == 0:
+                    logger.info('[TRAIN] Epoch #: %d  loss terms  mse %.6f  l1 %.6f  gdl %.6f  dssim %.6f', epoch + 1, *g_terms[-1])
+                local_terms = []
             if guarded:
                 g_gnorm.append(grad_norm_stat(torch.stack(local_gnorm).tolist(), stat))
                 skipped = optimizer.skipped_steps   # (reads the device counter)
@@ -204,6 +230,8 @@ def main(argv=None):
                 np.save(os.path.join(save_dir, 'training-global_psnr_all_valid'), np.array(g_psnr_v))
                 if guarded:
                     np.save(os.path.join(save_dir, 'training-global_grad_norm'), np.array(g_gnorm))
+                if extra_loss:
+                    np.save(os.path.join(save_dir, 'training-global_loss_terms'), np.array(g_terms))
         itr += 1
     if world > 1:
         import torch.distributed as dist
