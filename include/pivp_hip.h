@@ -302,6 +302,22 @@ int pivp_conv5x5_bf16x6(const float* x, int cin, int ldx, const float* w, void* 
  * exactly.  x contiguous (ldx == cin), W % 16 == 0 (or W % 8 == 0 with an even batch); w_bf16 holds 2 * pivp_conv5x5_bf16_weight_elems(cin, cout) + 256 2-byte elements; scratch: 66 floats */
 int pivp_conv5x5_fp16x3(const float* x, int cin, int ldx, const float* w, void* w_bf16, float* out, int cout, int ldo, int accum,
                         int B, int H, int W, float* scratch, void* stream);
+/* Any of the four forms above, chosen by its precision code (PIVP_PRECISION_BF16 .. PIVP_PRECISION_FP16X3; w_bf16 and scratch sized as that form's entry asks,
+ * scratch may be NULL in the other three), with what the backward sweep adds to the launch:
+ *  - the epilogue hook: a second tensor ep_src[pixel * ep_ld + column] met on the output columns < min(ep_cols, cout) before they are stored.  ep_mode 1: the ReLU
+ *    mask out = ep_src > 0 ? out : 0 (a -0.0 or +0.0 source masks, the smallest positive one does not); ep_mode 2: out += ep_src.  Columns >= ep_cols, and the
+ *    columns cout .. ldo-1 of a strided destination, are written (or left) exactly as without the hook.  ep_src == NULL or ep_mode == 0: the plain conv.
+ *  - no_split != 0 (the deterministic sweeps): never split K, one block per output tile and plain stores.
+ * Only an unsplit grid takes the hook (a K split meets in `out` by atomic adds: nobody holds the whole sum): *applied (host, may be NULL) receives 1 when the launch
+ * applied it and 0 when it did not -- the output then is the plain conv's, bit for bit, and the separate pass is still the caller's to run.  A launch is unsplit
+ * when no_split is set, when accum != 0 or ldo != cout, when cin <= 64 (one K group), or when its tiles already fill the device: pivp_conv5x5_ep_ksplit (host only,
+ * no GPU work) returns the split the launch will use on the current device, 1 = unsplit.
+ * PIVP_ERR_BADARG, in front of the first launch: what the form's own entry refuses, a precision outside 1..4, an ep_mode outside 0..2, and a hook with
+ * ep_ld < min(ep_cols, cout). */
+int pivp_conv5x5_ep(int precision, const float* x, int cin, int ldx, const float* w, void* w_bf16, float* out, int cout, int ldo, int accum,
+                    const float* ep_src, int ep_ld, int ep_cols, int ep_mode, int no_split, float* scratch, int* applied,
+                    int B, int H, int W, void* stream);
+int pivp_conv5x5_ep_ksplit(int precision, int cin, int cout, int ldo, int accum, int no_split, int B, int H, int W);
 
 /* ConvLSTM weight gradient with bf16 operands and fp32 accumulation (bf16 mode): dW[tap][ci][n] += sum_m concat(x, h_prev)[m + tap][ci]
  * dG[m][n]; dW K-inner packed like the weight, ACCUMULATED; h_prev may be NULL (first timestep: only the x rows are touched);
@@ -386,6 +402,26 @@ int pivp_convlstm_backward_dx_only(const float* x, int cx, int ldx, const float*
                                    const float* c_old, const float* c_new, const float* dh_a, int lda, const float* dh_b, int ldb,
                                    float* dc, int dc_valid, float* dG, float* wt, float* d_in, float* dW, float* db,
                                    int B, int H, int W, void* stream);
+/* pivp_convlstm_backward (dx_only == 0) / pivp_convlstm_backward_dx_only (dx_only != 0) with the data gradient d_in = conv5x5(dG, flipped transposed w) in the
+ * form of a precision mode, as the backward sweep of that mode runs the cell.  precision PIVP_PRECISION_F32: exactly those two entries (scratch and the hook
+ * are not used; det is honoured).  Any other precision: the gate math stays fp32 (dG, dc do not depend on the form); the transposed pack is re-packed in that
+ * form (the fragment-major plain pack for BF16X6 / FP16X3) into `scratch`; FP16X3 takes dG's power-of-two scale from dG's partial maxima, also in `scratch`; when
+ * the data gradient will split K, the gate kernel clears d_in on the side.  The weight gradient runs on bf16 operands for PIVP_PRECISION_BF16 and in fp32 for
+ * every other precision.
+ *  scratch: pivp_convlstm_backward_form_scratch_floats(cx, C) floats = (3 * pivp_conv5x5_bf16_weight_elems(4C, cx+C) + 256) / 2 for the pack (three planes
+ *    and the fp16 pack's tail serve every form) + 72 for dG's partial maxima; 16-byte aligned.
+ *  ep_src / ep_ld / ep_cols / ep_mode / ep_applied: the data gradient's epilogue hook as in pivp_conv5x5_ep (cout = cx + C: the hook meets the d x columns first).
+ *  det != 0: the deterministic sweeps' unsplit data gradient -- every element of d_in is one block's plain store, bit-identical from run to run, and the hook is
+ *    always taken.
+ *  dx_only != 0: the d h_{t-1} columns of d_in are not needed; the fp32 form does not compute them (left as they are, or cleared), the other forms do.
+ * PIVP_ERR_BADARG, in front of the first launch: a precision outside 0..4, an ep_mode outside 0..2, a hook with ep_ld < min(ep_cols, cx + C), and BF16X6 / FP16X3
+ * on a map whose width is no multiple of 16 unless it is a multiple of 8 and B is even. */
+long long pivp_convlstm_backward_form_scratch_floats(int cx, int C);
+int pivp_convlstm_backward_form(int precision, const float* x, int cx, int ldx, const float* h_prev, int C, const float* w, const float* gates,
+                                const float* c_old, const float* c_new, const float* dh_a, int lda, const float* dh_b, int ldb,
+                                float* dc, int dc_valid, float* dG, float* wt, float* d_in, float* dW, float* db, float* scratch,
+                                const float* ep_src, int ep_ld, int ep_cols, int ep_mode, int* ep_applied, int det, int dx_only,
+                                int B, int H, int W, void* stream);
 /* LayerNorm forward keeping (mean, rstd) per sample in stat [B][2], and its backward (dgamma/dbeta accumulated). */
 int pivp_layernorm_train(const float* x, const float* gamma, const float* beta, float* out, float* partials, float* stat,
                          int B, int n, int C, int ldo, float eps, int relu, void* stream);

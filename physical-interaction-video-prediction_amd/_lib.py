@@ -75,6 +75,8 @@ SIGNATURES = {
     'pivp_conv5x5_bf16x3': (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     'pivp_conv5x5_bf16x6': (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     'pivp_conv5x5_fp16x3': (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    'pivp_conv5x5_ep': (_i, [_i, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _c.POINTER(_i), _i, _i, _i, _vp]),
+    'pivp_conv5x5_ep_ksplit': (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i]),
     'pivp_pack_lstm_bf16x3': (_i, [_vp, _vp, _i, _i, _vp]),
     'pivp_convlstm_bf16x3': (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp]),
     'pivp_pack_lstm_bf16x6': (_i, [_vp, _vp, _i, _i, _vp]),
@@ -99,6 +101,9 @@ SIGNATURES = {
     'pivp_conv_wgrad_partial_reduce': (_i, [_i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp]),
     'pivp_convlstm_backward_dx_only': (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp,
                                             _i, _i, _i, _vp]),
+    'pivp_convlstm_backward_form_scratch_floats': (_ll, [_i, _i]),
+    'pivp_convlstm_backward_form': (_i, [_i, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp,
+                                         _vp, _i, _i, _i, _c.POINTER(_i), _i, _i, _i, _i, _i, _vp]),
     'pivp_layernorm_train': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp]),
     'pivp_layernorm_backward_scratch_floats': (_ll, [_i, _i]),
     'pivp_layernorm_backward': (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),

@@ -449,6 +449,14 @@ extern "C" const char* pivp_build_digest(void) { return PIVP_BUILD_DIGEST; }
 extern "C" const char* pivp_build_flags(void) { return PIVP_BUILD_FLAGS; }
 extern "C" int pivp_abi_version(void) { return 17; }   // 9: + pivp_build_digest, pivp_grad_sum_shards, pivp_frame_head; 8: + pivp_gates_backward_ln (op entry of the norm + gate backward pair); 7: + bf16 gradient payload, batched bf16 weight gradient, partial-plane / dx-only op entries
 
+// the epilogue hook's arguments as the op entries take them: a mode of 0..2, and a source that covers the columns the hook is applied to
+static bool ep_args_ok(const float* ep_src, int ep_ld, int ep_cols, int ep_mode, int cout) {
+    if (ep_mode < 0 || ep_mode > 2) return false;
+    if (!ep_src || !ep_mode) return true;      // the plain conv
+    return ep_ld >= (ep_cols < cout ? ep_cols : cout);
+}
+// the L2-direct forms' tiles on an 8-wide map hold two images
+static bool form_serves_map(Operand form, int B, int W) { return !operand_l2_direct(form) || W % 16 == 0 || (W % 8 == 0 && B % 2 == 0); }
 extern "C" int pivp_convlstm(const float* x, int cx, int ldx, const float* h_prev, int C, const float* w, const float* bias,
                              const float* c_in, float* c_out, float* h_out, int B, int H, int W, void* stream) {
     if (!x || !w || !bias || !c_in || !c_out || !h_out) return PIVP_ERR_BADARG;
@@ -614,6 +622,40 @@ extern "C" int pivp_convlstm_backward_dx_only(const float* x, int cx, int ldx, c
                                               int B, int H, int W, void* stream) {
     return convlstm_backward_op(x, cx, ldx, h_prev, C, w, gates, c_old, c_new, dh_a, lda, dh_b, ldb, dc, dc_valid, dG, wt, d_in, dW, db, B, H, W, stream, 1);
 }
+// The cell backward with the data gradient in the form of a precision mode, as the sweep's lstmb (pivp_plan.hip) fills ConvLstmBwdArgs: the pack of wt in that
+// form and dG's partial maxima live in `scratch` (pivp_convlstm_backward_form_scratch_floats), the epilogue hook and det are passed through.  precision 0 is
+// pivp_convlstm_backward / _dx_only (scratch and the hook unused).  Everything that is refused is refused in front of the first launch.
+extern "C" long long pivp_convlstm_backward_form_scratch_floats(int cx, int C) {
+    if (cx <= 0 || C <= 0 || (cx + C) % 32) return PIVP_ERR_BADARG;
+    // up to three planes of the pack + the fp16 pack's tail (256 2-byte elements), then 72 floats of partial maxima
+    return (3 * (long long)lstm_bf16_weight_elems(4 * C, conv5x5_bf16_rows(cx + C)) + 256) / 2 + 72;
+}
+extern "C" int pivp_convlstm_backward_form(int precision, const float* x, int cx, int ldx, const float* h_prev, int C, const float* w, const float* gates,
+                                           const float* c_old, const float* c_new, const float* dh_a, int lda, const float* dh_b, int ldb,
+                                           float* dc, int dc_valid, float* dG, float* wt, float* d_in, float* dW, float* db, float* scratch,
+                                           const float* ep_src, int ep_ld, int ep_cols, int ep_mode, int* ep_applied, int det, int dx_only,
+                                           int B, int H, int W, void* stream) {
+    if (ep_applied) *ep_applied = 0;
+    if (precision < 0 || precision > 4 || !x || !w || !gates || !c_old || !c_new || !dc || !dG || !wt || !d_in || !dW || !db || cx <= 0 || C <= 0 ||
+        B <= 0 || H <= 0 || W <= 0)
+        return PIVP_ERR_BADARG;
+    const Operand form = (Operand)precision;
+    if ((form != Operand::F32 && (!scratch || (cx + C) % 32)) || !form_serves_map(form, B, W) || !ep_args_ok(ep_src, ep_ld, ep_cols, ep_mode, cx + C))
+        return PIVP_ERR_BADARG;
+    const EpSpec ep{ep_src, ep_ld, ep_cols, ep_mode, ep_applied};
+    ConvLstmBwdArgs a{};
+    a.x = x; a.cx = cx; a.ldx = ldx; a.h_prev = h_prev; a.C = C; a.w = w; a.gates = gates; a.c_old = c_old; a.c_new = c_new;
+    a.dh_a = dh_a; a.lda = lda; a.dh_b = dh_b; a.ldb = ldb; a.dc = dc; a.dc_valid = dc_valid; a.dG = dG; a.wt = wt; a.d_in = d_in;
+    a.dW = dW; a.db = db; a.B = B; a.H = H; a.W = W;
+    a.dx_only = dx_only ? 1 : 0; a.det = det ? 1 : 0;
+    a.operand = form;
+    if (form != Operand::F32) {
+        a.wt_bf16 = reinterpret_cast<unsigned short*>(scratch);
+        if (operand_needs_scale(form)) a.dg_absmax = scratch + pivp_convlstm_backward_form_scratch_floats(cx, C) - 72;
+        if (ep_src && ep_mode) a.ep = &ep;
+    }
+    return run_convlstm_backward(a, (hipStream_t)stream);
+}
 extern "C" int pivp_layernorm_train(const float* x, const float* gamma, const float* beta, float* out, float* partials, float* stat,
                                     int B, int n, int C, int ldo, float eps, int relu, void* stream) {
     if (!stat) return PIVP_ERR_BADARG;
@@ -728,6 +770,38 @@ extern "C" int pivp_conv5x5_fp16x3(const float* x, int cin, int ldx, const float
     Conv5x5Bf16Opts o{};
     o.operand = Operand::FP16X3; o.ascale_part = scratch;
     return run_conv5x5_bf16(x, cin, ldx, (const unsigned short*)w_bf16, out, cout, ldo, accum, B, H, W, (hipStream_t)stream, o);
+}
+// Any of the four forms above by its precision code, with the data gradient's epilogue hook (IgemmDesc::ep_*) and the deterministic sweeps' no_split: what
+// run_convlstm_backward launches, as an op.  Everything that is refused is refused in front of the first launch.
+extern "C" int pivp_conv5x5_ep(int precision, const float* x, int cin, int ldx, const float* w, void* w_bf16, float* out, int cout, int ldo, int accum,
+                               const float* ep_src, int ep_ld, int ep_cols, int ep_mode, int no_split, float* scratch, int* applied,
+                               int B, int H, int W, void* stream) {
+    if (applied) *applied = 0;
+    if (precision < 1 || precision > 4 || !x || !w || !w_bf16 || !out || cin <= 0 || cout <= 0 || B <= 0 || H <= 0 || W <= 0) return PIVP_ERR_BADARG;
+    const Operand form = (Operand)precision;
+    if (!form_serves_map(form, B, W) || (operand_needs_scale(form) && (!scratch || ldx != cin)) || !ep_args_ok(ep_src, ep_ld, ep_cols, ep_mode, cout))
+        return PIVP_ERR_BADARG;
+    int rc = pack_lstm_bf16(w, (unsigned short*)w_bf16, cin, cout, (hipStream_t)stream, form, conv5x5_bf16_rows(cout), operand_l2_direct(form) ? 1 : 0);
+    if (rc != PIVP_OK) return rc;
+    if (operand_needs_scale(form)) {
+        rc = absmax_partials(x, (long)B * H * W * cin, scratch, (hipStream_t)stream);
+        if (rc != PIVP_OK) return rc;
+    }
+    const EpSpec ep{ep_src, ep_ld, ep_cols, ep_mode, applied};
+    Conv5x5Bf16Opts o{};
+    o.operand = form; o.no_split = no_split ? 1 : 0;
+    if (operand_needs_scale(form)) o.ascale_part = scratch;
+    if (ep_src && ep_mode) o.ep = &ep;
+    return run_conv5x5_bf16(x, cin, ldx, (const unsigned short*)w_bf16, out, cout, ldo, accum, B, H, W, (hipStream_t)stream, o);
+}
+// host-only: the K split pivp_conv5x5_ep uses for these arguments on the current device (1: one block per output tile, the grid that takes the hook)
+extern "C" int pivp_conv5x5_ep_ksplit(int precision, int cin, int cout, int ldo, int accum, int no_split, int B, int H, int W) {
+    if (precision < 1 || precision > 4 || cin <= 0 || cout <= 0 || ldo < cout || B <= 0 || H <= 0 || W <= 0) return PIVP_ERR_BADARG;
+    IgemmDesc d;
+    static float dummy;
+    if (conv5x5_bf16_desc(d, &dummy, cin, cin, &dummy, cout, ldo, accum, B, H, W) != PIVP_OK) return PIVP_ERR_BADARG;
+    if (no_split) d.ksplit_ok = 0;
+    return conv5x5_bf16_ksplit(d, (Operand)precision);
 }
 // ConvLSTM weight gradient with bf16 operands: dW (K-inner packed like the weight, [25][(cx+C)/32][4C][32]) += x|h^T . dG per tap.
 extern "C" int pivp_wgrad5x5_bf16(const float* x, int cx, int ldx, const float* h_prev, int C, const float* dG, float* dW, float* db,

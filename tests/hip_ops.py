@@ -497,3 +497,57 @@ def wgrad5x5_f32_batch(launches, slots=True, h_is_zero=False, form=0):
     torch.cuda.synchronize()
     raw = dW.cpu().numpy().copy()
     return pivp_amd.from_internal('lstm1/conv/W', dW.cpu().numpy(), (4 * C, cx + C, 5, 5)), db.cpu().numpy(), raw
+
+
+FORMS = {'bf16': 1, 'bf16x3': 2, 'bf16x6': 3, 'fp16x3': 4}      # PIVP_PRECISION_* codes of the packed-operand forms
+_PIECES = {1: 1, 2: 2, 3: 3, 4: 2}
+
+
+def conv5x5_ep_ksplit(form, cin, cout, ldo, accum, no_split, B, H, Wd):
+    """The K split pivp_conv5x5_ep will use for these arguments on this device (host only; 1 = unsplit)."""
+    ks = _lib.load().pivp_conv5x5_ep_ksplit(FORMS.get(form, form), cin, cout, ldo, int(accum), int(no_split), B, H, Wd)
+    assert ks >= 1, ks
+    return ks
+
+
+def conv5x5_ep(x, W, form, ep=None, ep_cols=None, ep_ld=None, mode=0, no_split=False, ldo=None, accum_into=None):
+    """pivp_conv5x5_ep: the plain 5x5 convolution of conv5x5_bf16 in `form` (a FORMS name or code) with the epilogue hook.  x NCHW, W (Cout, Cin, 5, 5).
+    ep: the hook's source, NCHW with its own channel count c_ep; ep_cols (default c_ep) output columns meet it; ep_ld (default c_ep) is the pixel stride of the
+    device buffer it lives in -- with ep_ld > c_ep the source is the LAST c_ep channels of an ep_ld-wide NaN-filled buffer (a channel slice of a concat).
+    Returns (out NCHW float32, applied); with ldo > cout the destination is 7.0-prefilled and its columns cout .. ldo-1 (NHWC, [B, H, W, ldo - cout]) are returned third."""
+    import ctypes
+    lib = _lib.load()
+    prec = FORMS.get(form, form)
+    B, cin, H, Wd = x.shape
+    cout = W.shape[0]
+    ldo = cout if ldo is None else ldo
+    xd = nhwc(x)
+    wd = _t(pivp_amd.to_internal('lstm1/conv/W', W))          # [25][cin/32][cout][32]
+    wb = torch.empty(_PIECES[prec] * lib.pivp_conv5x5_bf16_weight_elems(cin, cout) + 256, dtype=torch.int16, device=DEV)
+    scratch = torch.zeros(128, dtype=torch.float32, device=DEV)
+    if accum_into is not None:
+        assert ldo == cout
+        out = nhwc(accum_into)
+    else:
+        out = torch.full((B, H, Wd, ldo), 7.0, dtype=torch.float32, device=DEV)
+    src_ptr, cols, ld = None, 0, 0
+    if ep is not None:
+        c_ep = ep.shape[1]
+        cols = c_ep if ep_cols is None else ep_cols
+        ld = c_ep if ep_ld is None else ep_ld
+        if ld >= c_ep:
+            buf = torch.full((B, H, Wd, ld), float('nan'), dtype=torch.float32, device=DEV)
+            buf[..., ld - c_ep:] = nhwc(ep)
+            src_ptr = buf.data_ptr() + (ld - c_ep) * 4
+        else:                                                  # (a stride the entry must refuse: nothing is read)
+            buf = nhwc(ep)
+            src_ptr = buf.data_ptr()
+    applied = ctypes.c_int(-1)
+    _lib.check(lib.pivp_conv5x5_ep(prec, xd.data_ptr(), cin, cin, wd.data_ptr(), wb.data_ptr(), out.data_ptr(), cout, ldo, 1 if accum_into is not None else 0,
+                                   src_ptr, ld, cols, mode, int(no_split), scratch.data_ptr(), ctypes.byref(applied), B, H, Wd, stream()), 'conv5x5_ep')
+    torch.cuda.synchronize()
+    full = out.cpu().numpy()
+    res = np.ascontiguousarray(full[..., :cout].transpose(0, 3, 1, 2))
+    if ldo > cout:
+        return res, applied.value, full[..., cout:]
+    return res, applied.value

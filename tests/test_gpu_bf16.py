@@ -703,7 +703,8 @@ def test_rollout_bf16x3_stays_inside_the_gate():
 
 
 def test_train_step_in_bf16x3_mode_matches_fp32_gradients():
-    # split forward + the fp32 backward: gradients agree with the fp32 path to the forward's 1e-5-level differences
+    # split forward; in the backward the ConvLSTM data gradients run in the split form too (Modes::dgrad, csrc/pivp_plan.hip), the weight gradients and everything
+    # else in fp32: gradients agree with the fp32 path to the 1e-5-level differences of the split products
     import pivp_amd
     outs = {}
     for prec in ('fp32', 'bf16x3'):
