@@ -9,15 +9,12 @@
  * Conventions
  *   - all pointers are DEVICE pointers to fp32 unless stated; the caller owns every buffer
  *   - return value: 0 = ok, <0 = error (PIVP_ERR_*); functions never throw and never synchronise
- *   - re-entrant per plan + stream.  Process-global state is limited to (a) write-once-per-DEVICE caches of kernel attributes and the
- *     CU count (csrc/pivp_common.h: a process may drive several devices) and (b) PIVP_* tuning knobs read once with getenv(); both
- *     are idempotent.  A plan that runs a backward sweep owns one internal low-priority stream and its events for the weight
- *     gradients (created on the first pivp_rollout_backward, destroyed with the plan); everything it enqueues there is fenced
- *     against the caller's stream with events, so the caller still only ever synchronises its own stream.  PIVP_SIDE_STREAM=0
- *     (read at pivp_plan_create) keeps all work on the caller's stream.  PIVP_FINISH_RIDER=0 (read there too) runs the motion head's finisher
- *     inside the frame-head launch instead of as extra blocks of enc5's launch: bit-identical results either way, it exists for A/B timing.
- *     PIVP_FUSE_ENC3=0 likewise keeps group 3 (smear + 1x1 conv) and the state predictor in a launch of their own instead of enc2's epilogue.
- *     PIVP_LN_FOLD_TRAIN=0: training plans apply the norms of hidden2 / hidden4 with ln_apply launches instead of inside enc1 / enc2's launches.
+ *   - re-entrant per plan + stream.  Process-global state is limited to write-once-per-DEVICE caches of kernel attributes and the CU count
+ *     (csrc/pivp_common.h: a process may drive several devices); they are idempotent.  The library never reads the environment: every
+ *     choice of a plan is an argument or a setter of this header (pivp_plan_set_option and its neighbours).  A plan that runs a backward
+ *     sweep owns one internal low-priority stream and its events for the weight gradients (created on the first pivp_rollout_backward,
+ *     destroyed with the plan); everything it enqueues there is fenced against the caller's stream with events, so the caller still only
+ *     ever synchronises its own stream.  PIVP_OPT_SIDE_STREAM = 0 keeps all work on the caller's stream.
  *   - feature maps are NHWC with an explicit pixel stride `ld` (floats); frames and mask planes are
  *     planar NCHW exactly as the reference holds them
  */
@@ -106,8 +103,8 @@ int pivp_plan_set_param(pivp_plan_t* plan, int idx, const float* dptr);
 int pivp_plan_set_precision(pivp_plan_t* plan, int precision);
 int pivp_plan_get_precision(const pivp_plan_t* plan);
 /* Deterministic training (on = 1; default 0).  A training step -- pivp_rollout_forward, pivp_rollout_backward, the optimizer's elementwise update -- then gives
- * the same bits every time for the same inputs, parameters, optimizer state, plan shape, precision, PIVP_WGRAD_BATCH and GPU model, whatever the side-stream
- * schedule (PIVP_SIDE_STREAM), the process or the workspace address: no float atomics are reached, and every sum runs in an order fixed by the problem shape.
+ * the same bits every time for the same inputs, parameters, optimizer state, plan shape, precision, PIVP_OPT_WGRAD_BATCH and GPU model, whatever the side-stream
+ * schedule (PIVP_OPT_SIDE_STREAM), the process or the workspace address: no float atomics are reached, and every sum runs in an order fixed by the problem shape.
  * The ConvLSTM data gradients never split K; the ConvLSTM weight gradients take the fp32 slot form (partial slots summed once per sweep, in every precision
  * mode); the bias, head, enc0 and enc3 / state-predictor gradients go through per-block rows summed in order behind each launch.  Served: PIVP_PRECISION_F32,
  * _BF16 and _BF16X3 (the ConvLSTM weight gradients then in fp32: deterministic BF16 is not default BF16's arithmetic there); CDNA, STP and DNA; shapes
@@ -119,6 +116,24 @@ int pivp_plan_get_precision(const pivp_plan_t* plan);
  * compatible, nothing else moved. */
 int pivp_plan_set_deterministic(pivp_plan_t* plan, int on);
 int pivp_plan_get_deterministic(const pivp_plan_t* plan);
+/* Plan options: the A/B levers of a plan, set per plan (the library reads no environment variable).
+ *   PIVP_OPT_SIDE_STREAM   (0 / 1, default 1)  0 = the backward sweep's weight gradients on the caller's stream too: one stream, additive kernel traces.
+ *   PIVP_OPT_FINISH_RIDER  (0 / 1, default 1)  0 = the motion head's finisher inside the frame-head launch instead of as extra blocks of enc5's launch;
+ *                                              bit-identical results either way, it exists for A/B timing.
+ *   PIVP_OPT_FUSE_ENC3     (0 / 1, default 1)  0 = group 3 (smear + 1x1 conv) and the state predictor in a launch of their own instead of enc2's epilogue
+ *                                              (inference plans); bit-identical either way.
+ *   PIVP_OPT_LN_FOLD_TRAIN (0 / 1, default 1)  0 = training plans apply the norms of hidden2 / hidden4 with ln_apply launches instead of inside enc1 /
+ *                                              enc2's launches.
+ *   PIVP_OPT_WGRAD_BATCH   (0 .. 8, default 0) timesteps per ConvLSTM weight-gradient launch, whatever the precision mode (never more than seq_len - 2);
+ *                                              0 = the mode's own choice: fp32 1, bf16 as many as the rings hold (8), fp16x3 and bf16x6 2.
+ * An unknown option or a value outside its range returns PIVP_ERR_BADARG and the plan is unchanged.
+ * ORDER: any time before pivp_plan_set_workspace, in any order relative to pivp_plan_set_precision / pivp_plan_set_deterministic; with a workspace bound
+ * the setter returns PIVP_ERR_STATE.  PIVP_OPT_WGRAD_BATCH sets the depth of the ConvLSTM gate-gradient rings, so pivp_plan_workspace_bytes changes with
+ * it (training plans).  pivp_plan_get_option returns the value as set (or the default), < 0 on error -- also when the plan could not create its side
+ * stream and runs on one.  Added in ABI 17 without a version change: backward compatible, nothing else moved. */
+enum { PIVP_OPT_SIDE_STREAM = 0, PIVP_OPT_FINISH_RIDER, PIVP_OPT_FUSE_ENC3, PIVP_OPT_LN_FOLD_TRAIN, PIVP_OPT_WGRAD_BATCH, PIVP_OPT_COUNT };
+int pivp_plan_set_option(pivp_plan_t* plan, int option, int value);
+int pivp_plan_get_option(const pivp_plan_t* plan, int option);
 /* The precision modes re-pack the ConvLSTM weights (bf16 / split pieces) at the start of every rollout, because the parameters may have changed.  With
  * constant weights (serving) pivp_plan_set_pack_cache(plan, 1) keeps the packs; the caller then calls pivp_plan_params_changed after EVERY modification of a
  * parameter tensor.  The Python Model does both by itself (torch's in-place version counter + its own optimizer steps). */

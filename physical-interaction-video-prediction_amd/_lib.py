@@ -65,6 +65,8 @@ SIGNATURES = {
     'pivp_plan_get_precision': (_i, [_vp]),
     'pivp_plan_set_deterministic': (_i, [_vp, _i]),
     'pivp_plan_get_deterministic': (_i, [_vp]),
+    'pivp_plan_set_option': (_i, [_vp, _i, _i]),
+    'pivp_plan_get_option': (_i, [_vp, _i]),
     'pivp_plan_set_pack_cache': (_i, [_vp, _i]),
     'pivp_plan_params_changed': (_i, [_vp]),
     'pivp_lstm_bf16_weight_elems': (_ll, [_i, _i]),

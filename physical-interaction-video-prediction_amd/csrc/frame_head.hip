@@ -8,7 +8,7 @@
 // 14 logit / enc7 / layer0 planes through HBM per timestep (425 us of a config-2 rollout).  Now the partial sums are the only launch in
 // front of this one.  Round 6: the finisher is per-SAMPLE work that every band of a sample repeated (128 KB of partial sums per block); the
 // plan now runs it as B "rider" blocks of enc5's launch (deconv_tile.hip) and this kernel reads the sample's kernels / parameters from a.aux
-// with its first loads.  The in-kernel finisher (a.partials != NULL) remains for callers without that launch in front (PIVP_FINISH_RIDER=0,
+// with its first loads.  The in-kernel finisher (a.partials != NULL) remains for callers without that launch in front (PIVP_OPT_FINISH_RIDER = 0,
 // the per-op API).  Round 6 also took the block's chain from 23 to 12.7 us: profiles/r06/NOTES.md 5.
 //
 // Block = one sample x FH_TR image rows.  The flat softmax groups of a band reach NP - 1 elements past either end of the band IN THE

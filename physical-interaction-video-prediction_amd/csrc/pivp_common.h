@@ -14,9 +14,9 @@
 
 // ---- per-device host-side caches -----------------------------------------------------------------------------------------------
 // hipFuncAttributeMaxDynamicSharedMemorySize and the CU count belong to a DEVICE, and one process may drive several (Model(device=
-// 'cuda:1') after 'cuda:0'): both are remembered per hipGetDevice() index.  These tables and the PIVP_* tuning knobs read once with
-// getenv() are the library's only process-global state; they are write-once per device / per process and idempotent, so concurrent
-// first calls from several host threads are benign.  Everything else lives in the plan or in the caller's buffers.
+// 'cuda:1') after 'cuda:0'): both are remembered per hipGetDevice() index.  These tables are the library's only process-global state
+// (it reads no environment variable: a plan's options arrive through pivp_plan_set_option); they are write-once per device and
+// idempotent, so concurrent first calls from several host threads are benign.  Everything else lives in the plan or in the caller's buffers.
 constexpr int PIVP_MAX_DEV = 64;
 inline int pivp_current_device() {
     int dev = 0;

@@ -1,6 +1,5 @@
 // The plan: Model.__init__ / reset_state / __call__ of the reference (TM:484-764) and the backward pass that
 // Chainer's autograd performs under optimizer.update (TM:950), sequenced in native code on one HIP stream.
-#include <stdlib.h>
 #include <string.h>
 #include <mutex>
 #include <string>
@@ -89,7 +88,7 @@ static int ln_partial_cap(int HW) {
 // timesteps alike; WgradDesc::tcount): a quarter of the block epilogues and grid ramps.  Measured at B = 32 it does not pay: alone
 // it is worth 0.4 ms of a 35.6 ms train step, and next to the side stream it LOSES 0.7 ms (34.1 vs 33.4 ms) because the weight
 // gradients then arrive in bursts instead of filling the gaps of every step.  So the default is one timestep per launch
-// (PIVP_WGRAD_BATCH=1), the dG rings then simply double-buffer; the batched path stays for larger per-GPU batches and is tested
+// (PIVP_OPT_WGRAD_BATCH 0 in fp32 = 1), the dG rings then simply double-buffer; the batched path stays for larger per-GPU batches and is tested
 // (tests/test_gpu_train.py).  Timestep 0 is always its own batch (its h_{-1} = 0 half is skipped).
 constexpr size_t ENC_RING_BYTES_MAX = (size_t)2 << 30;   // the five stride-2 3x3 layers' dY rings together (pivp_plan::eg_cap is cut to fit)
 // Deterministic sweeps: the fp32 slot form of the ConvLSTM weight gradients with this many blocks per XCD whatever the device reports (WgradDesc::slot_j;
@@ -164,13 +163,15 @@ struct pivp_plan {
     std::vector<int> prof_layer;
     size_t prof_used = 0;
     // Weight gradients run on a second, lower-priority stream next to the backward sweep's critical path (SideFork, pivp_host.h):
-    // slots 0..6 = the ConvLSTMs, 7..11 = enc6, enc5, enc4, enc2, enc1.  Created on first use; PIVP_SIDE_STREAM=0 (read when
-    // the plan is created) keeps everything on the caller's stream.
+    // slots 0..6 = the ConvLSTMs, 7..11 = enc6, enc5, enc4, enc2, enc1.  Created on first use; PIVP_OPT_SIDE_STREAM = 0 keeps everything on
+    // the caller's stream.
     static constexpr int NSLOT = 14;      // 12: enc0's weight gradient, 13: the motion head's Linear (cdna_kernels / stp_input)
-    bool use_side = true;
-    bool ln_fold_train = true;          // training: the norms of hidden2 / hidden4 applied (and written) by enc1 / enc2's launches (PIVP_LN_FOLD_TRAIN=0: ln_apply launches)
-    bool fuse_enc3 = true;              // inference: enc3 + state predictor in enc2's epilogue (PIVP_FUSE_ENC3=0: their own launch)
-    bool rider = true;                  // the motion head's finisher rides behind enc5's tiles (PIVP_FINISH_RIDER=0: inside frame_head, as rounds 4-5)
+    // pivp_plan_set_option (include/pivp_hip.h), by PIVP_OPT_*: SIDE_STREAM; FINISH_RIDER: the motion head's finisher rides behind enc5's tiles (0: inside
+    // frame_head, as rounds 4-5); FUSE_ENC3, inference: enc3 + state predictor in enc2's epilogue (0: their own launch); LN_FOLD_TRAIN, training: the norms of
+    // hidden2 / hidden4 applied (and written) by enc1 / enc2's launches (0: ln_apply launches); WGRAD_BATCH: timesteps per ConvLSTM weight-gradient launch
+    // (tests, measurements), whatever the precision mode; 0 = the mode's own choice
+    int opt[PIVP_OPT_COUNT] = {1, 1, 1, 1, 0};
+    bool side_failed = false;           // run-time state, not the option: the side stream could not be created, this plan's sweeps run on one stream
     hipStream_t side = nullptr;
     hipStream_t side_of(int) const { return side; }      // (a second side stream for the odd slots, round 3: fp32 no change, bf16 12.25 -> 12.05 ms, but with two
                                                          // processes on one GPU the step went from 65 ms to 78 SECONDS -- the hardware queues oversubscribe)
@@ -208,18 +209,12 @@ static const float* P(const pivp_plan* p, int idx) { return p->params[idx].ptr; 
 static float* G(const pivp_plan* p, int idx) { return p->params[idx].grad; }
 
 // ---- workspace carve (offsets in floats, 256-B aligned).  Runs at pivp_plan_create and again from pivp_plan_set_precision while no
-// workspace is bound: the ConvLSTM dG rings hold wg_cap timesteps per ring, and only the bf16 mode (or PIVP_WGRAD_BATCH) batches its weight
-// gradients -- an fp32 plan double-buffers with ONE slot per ring instead of 8 (2.5 GB less at 128 x 128, B = 32, T = 20). ----
-// PIVP_WGRAD_BATCH (tests, measurements): timesteps per ConvLSTM weight-gradient launch, whatever the precision mode; 0 = the mode's own choice
-static int wgrad_batch_env() {
-    static const int v = [] { const char* e = getenv("PIVP_WGRAD_BATCH"); return e ? atoi(e) : 0; }();
-    return v;
-}
+// workspace is bound, and from pivp_plan_set_option(PIVP_OPT_WGRAD_BATCH): the ConvLSTM dG rings hold wg_cap timesteps per ring, and only the bf16 mode
+// (or that option) batches its weight gradients -- an fp32 plan double-buffers with ONE slot per ring instead of 8 (2.5 GB less at 128 x 128, B = 32, T = 20). ----
 // dG ring slots per ring: timesteps t = T-2 .. 1 batch (t = 0, no h input, goes alone), as many slots as a launch may take timesteps.
 // (fp16-piece / three-piece weight gradients: TWO timesteps per launch on half the CUs -- measured grid, profiles/r04/fp16x3_train_wgrad_batch_slots.txt:
 // 8 per launch on every CU, what the bf16 mode does, leaves all of that work to the end of the sweep: 16.85 ms against 16.34)
-static int wg_cap_of(int T, const Modes& m) {
-    const int e = wgrad_batch_env();
+static int wg_cap_of(int T, const Modes& m, int e /* PIVP_OPT_WGRAD_BATCH */) {
     const int want = e ? e : m.precision == Operand::BF16 ? WG_BATCH_MAX : m.wgrad_batches() ? 2 : 1;
     int cap = T - 2 < 1 ? 1 : (T - 2 > WG_BATCH_MAX ? WG_BATCH_MAX : T - 2);
     if (want < cap) cap = want < 1 ? 1 : want;
@@ -245,7 +240,7 @@ static void plan_layout(pivp_plan* p) {
     for (int i = 0; i < 7; ++i)       // 2-byte elements in a float-counted workspace
         p->o_wbf16[i] = carve(lstm_bf16_weight_elems(kLstm[i].cx + kLstm[i].C, 4 * kLstm[i].C) * 3 / 2 + 64);   // room for the three planes of PIVP_PRECISION_BF16X6
     p->nslabs = train ? T - 1 : 2;
-    p->wg_cap = wg_cap_of(T, p->mode);
+    p->wg_cap = wg_cap_of(T, p->mode, p->opt[PIVP_OPT_WGRAD_BATCH]);
     p->eg_cap = T - 2 < 1 ? 1 : (T - 2 > WG_BATCH_MAX ? WG_BATCH_MAX : T - 2);      // whatever the precision mode: every mode batches these
     if (train) {
         // ... bounded by bytes: a ring slot holds the dY of all five layers (60 MB at B = 32 on 64 x 64 frames, 240 MB on 128 x 128), and there are
@@ -341,10 +336,6 @@ extern "C" int pivp_plan_create(const pivp_config_t* cfg, pivp_plan_t** out) {
     p->NE = cfg->model_type == PIVP_MODEL_DNA ? 25 : 3;
     p->K5 = 128 * p->H8 * p->W8;
     p->ws = nullptr; p->ws_floats = 0; p->last_steps = 0; p->last_sched = false;
-    { const char* e = getenv("PIVP_SIDE_STREAM"); p->use_side = !(e && e[0] == '0'); }
-    { const char* e = getenv("PIVP_FINISH_RIDER"); p->rider = !(e && e[0] == '0'); }
-    { const char* e = getenv("PIVP_FUSE_ENC3"); p->fuse_enc3 = !(e && e[0] == '0'); }
-    { const char* e = getenv("PIVP_LN_FOLD_TRAIN"); p->ln_fold_train = !(e && e[0] == '0'); }
 
     auto add = [&](const std::string& name, long long n) { p->params.push_back({name, n, nullptr, nullptr, grad_group_of(name)}); return (int)p->params.size() - 1; };
     for (int i = 0; i < 7; ++i) {
@@ -437,7 +428,7 @@ extern "C" int pivp_plan_set_precision(pivp_plan_t* plan, int precision_code) {
     // The dG rings' depth follows the precision, so the order is set_precision -> workspace_bytes -> set_workspace (include/pivp_hip.h).  With a
     // workspace already bound the layout it was sized for stays; a mode that needs deeper rings than it has is refused, not run short.
     const Modes cand{precision};
-    if (plan->ws && plan->has_grads && wg_cap_of(plan->cfg.seq_len, cand) > plan->wg_cap) return PIVP_ERR_STATE;
+    if (plan->ws && plan->has_grads && wg_cap_of(plan->cfg.seq_len, cand, plan->opt[PIVP_OPT_WGRAD_BATCH]) > plan->wg_cap) return PIVP_ERR_STATE;
     plan->mode = cand;
     plan->packs_valid = 0;
     if (!plan->ws) plan_layout(plan);
@@ -474,6 +465,18 @@ extern "C" int pivp_plan_set_deterministic(pivp_plan_t* plan, int on) {
     return PIVP_OK;
 }
 extern "C" int pivp_plan_get_deterministic(const pivp_plan_t* plan) { return plan ? plan->det : PIVP_ERR_BADARG; }
+// include/pivp_hip.h: the four switches 0 / 1, the weight-gradient batch 0 .. WG_BATCH_MAX; before a workspace is bound (the batch sets the dG rings' depth)
+extern "C" int pivp_plan_set_option(pivp_plan_t* plan, int option, int value) {
+    if (!plan || option < 0 || option >= PIVP_OPT_COUNT) return PIVP_ERR_BADARG;
+    if (value < 0 || value > (option == PIVP_OPT_WGRAD_BATCH ? WG_BATCH_MAX : 1)) return PIVP_ERR_BADARG;
+    if (plan->ws) return PIVP_ERR_STATE;
+    plan->opt[option] = value;
+    if (option == PIVP_OPT_WGRAD_BATCH) plan_layout(plan);
+    return PIVP_OK;
+}
+extern "C" int pivp_plan_get_option(const pivp_plan_t* plan, int option) {
+    return plan && option >= 0 && option < PIVP_OPT_COUNT ? plan->opt[option] : PIVP_ERR_BADARG;
+}
 
 // include/pivp_loss.h: an additional d loss / d gen_images for every later sweep (null: none -- the sweep's launches are then exactly its own)
 extern "C" int pivp_plan_set_frame_grad(pivp_plan_t* plan, const float* seed) {
@@ -513,11 +516,11 @@ extern "C" int pivp_reset_state(pivp_plan_t* plan, void* stream) {
 
 // the plan's second stream (lowest priority: the critical path wins the CUs it asks for) and its fork / join events
 static int ensure_side(pivp_plan* plan) {
-    if (!plan->use_side || plan->side) return PIVP_OK;
+    if (!plan->opt[PIVP_OPT_SIDE_STREAM] || plan->side_failed || plan->side) return PIVP_OK;
     int least = 0, greatest = 0;
     if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) least = 0;
     if (hipStreamCreateWithPriority(&plan->side, hipStreamNonBlocking, least) != hipSuccess) {
-        plan->side = nullptr; plan->use_side = false; (void)hipGetLastError();      // single-stream sweeps from here on
+        plan->side = nullptr; plan->side_failed = true; (void)hipGetLastError();      // single-stream sweeps from here on
         return PIVP_OK;
     }
     bool ok = true;
@@ -530,7 +533,7 @@ static int ensure_side(pivp_plan* plan) {
             ok = hipEventCreateWithFlags(&plan->ev_ring_done[i][r], hipEventDisableTiming) == hipSuccess;
     if (!ok) {      // never leave `side` set beside null events: back to "no side stream", and this plan runs its sweeps on one stream
         plan->destroy_side();
-        plan->use_side = false;
+        plan->side_failed = true;
         (void)hipGetLastError();
     }
     return PIVP_OK;
@@ -607,7 +610,7 @@ static int run_step(pivp_plan* p, int t, const float* prev, const float* action,
     // (run_conv3x3s2_ln) instead of by a launch of their own; training keeps the materialised tensors (the backward sweep reads them).
     // Training plans take the same launch (round 6) and have it WRITE the normalised hidden2 / hidden4 (every input pixel of a stride-2 3x3 conv is the
     // tap (1..2, 1..2) of exactly one anchor) and the samples' (mean, rstd) for the backward sweep: two ln_apply launches per timestep less.
-    if (np > 0 && (p->ln_fold_train || !train) && conv3x3s2_ln_ok(32, 32, B, p->H2, p->W2)) {
+    if (np > 0 && (p->opt[PIVP_OPT_LN_FOLD_TRAIN] || !train) && conv3x3s2_ln_ok(32, 32, B, p->H2, p->W2)) {
         Conv3x3LnOpts o{};
         if (train) o.keep = keep(2, ws + S.n2, 32);
         RC(run_conv3x3s2_ln(ws + S.h[1], 32, P(p, p->i_enc_w[1]), P(p, p->i_enc_b[1]), ws + S.cat6 + 64, 32, 96, 1, B, p->H2, p->W2, s, norm_in(2), o));
@@ -629,17 +632,17 @@ static int run_step(pivp_plan* p, int t, const float* prev, const float* action,
         RC(lstm(3, ws + S.n3, 64));
     }
     bool enc3_done = false;
-    if (train && np > 0 && p->ln_fold_train && conv3x3s2_ln_ok(64, 64, B, p->H4, p->W4)) {
+    if (train && np > 0 && p->opt[PIVP_OPT_LN_FOLD_TRAIN] && conv3x3s2_ln_ok(64, 64, B, p->H4, p->W4)) {
         Conv3x3LnOpts o{};
         o.keep = keep(4, ws + S.n4, 64);
         RC(run_conv3x3s2_ln(ws + S.h[3], 64, P(p, p->i_enc_w[2]), P(p, p->i_enc_b[2]), ws + S.e2, 64, 64, 1, B, p->H4, p->W4, s, norm_in(4), o));
     } else
     if (!train && np > 0 && conv3x3s2_ln_ok(64, 64, B, p->H4, p->W4)) {
         // Inference: group 3 (TM:598) and the state predictor (TM:730) in enc2's epilogue (round 6): enc3_state_kernel's launch
-        // disappears; bit-identical to it (the same fmaf chain on the matrix cores).  PIVP_FUSE_ENC3=0: two launches, as before.
+        // disappears; bit-identical to it (the same fmaf chain on the matrix cores).  PIVP_OPT_FUSE_ENC3 = 0: two launches, as before.
         Enc3Fuse f3;
         memset(&f3, 0, sizeof(f3));
-        if (p->fuse_enc3 && (p->H8 * p->W8) % 32 == 0) {
+        if (p->opt[PIVP_OPT_FUSE_ENC3] && (p->H8 * p->W8) % 32 == 0) {
             f3.w3 = P(p, p->i_enc_w[3]); f3.b3 = P(p, p->i_enc_b[3]); f3.action = action; f3.state = state_prev; f3.wcs = P(p, p->i_cs_w); f3.bcs = P(p, p->i_cs_b);
             f3.e3 = ws + S.e3; f3.state_out = state_out; f3.use_state = c.use_state;
             enc3_done = true;
@@ -691,7 +694,7 @@ static int run_step(pivp_plan* p, int t, const float* prev, const float* action,
     if (np > 0 && fold_small((long long)B * n4) && deconv3x3s2_ln_ok(64, 32, 96, B, p->H4, p->W4)) {
         MotionRider rd;
         memset(&rd, 0, sizeof(rd));
-        if (fh_fin && p->rider) {
+        if (fh_fin && p->opt[PIVP_OPT_FINISH_RIDER]) {
             if (!partials_done) { RC(motion_partials(ws + S.n5, P(p, p->i_head_w), ws + p->o_linpart, B, p->K5, c.model_type == PIVP_MODEL_STP ? 1 : 0, s)); partials_done = true; }
             rd.mode = c.model_type == PIVP_MODEL_STP ? 2 : 1; rd.KS = cdna_kernel_partials_slices(p->K5); rd.nout = 25 * c.num_masks;
             rd.partials = ws + p->o_linpart; rd.bias = P(p, p->i_head_b); rd.vpre = ws + S.vpre;
@@ -1298,11 +1301,11 @@ static int rollout_backward_sweep(pivp_plan_t* plan, const float* images, const 
     const Modes& md = plan->mode;
     RC(ensure_side(plan));
     RC(apply_main_prio(plan, s));
-    {   // Timesteps per ConvLSTM weight-gradient launch (PIVP_WGRAD_BATCH overrides, 1..wg_cap).  fp32: 1 (batches arrive in bursts and
+    {   // Timesteps per ConvLSTM weight-gradient launch (PIVP_OPT_WGRAD_BATCH overrides, 1..wg_cap).  fp32: 1 (batches arrive in bursts and
         // overlap the sweep worse: 29.9 / 30.3 ms for 1 / 2, profiles/r02).  bf16 mode: as many as the rings hold -- its 25-tap kernel
         // fetches every operand tile once per 32 x 64 output slice, and what a block pays per launch (205 KB of atomics, the first tile's
         // latency) is amortised over the batch (csrc/wgrad_bf16.hip).
-        const int e = wgrad_batch_env();
+        const int e = plan->opt[PIVP_OPT_WGRAD_BATCH];
         int gb = e ? e : (md.wgrad_batches() ? plan->wg_cap : 1);
         if (gb < 1) gb = 1;
         if (gb > plan->wg_cap) gb = plan->wg_cap;

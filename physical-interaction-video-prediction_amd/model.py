@@ -15,6 +15,8 @@ from __future__ import annotations
 import contextlib
 import ctypes
 import math
+import os
+import re
 from collections import OrderedDict
 
 import numpy as np
@@ -112,6 +114,42 @@ def scheduled_sampling_masks(batch_size, seq_len, context_frames, k, iter_num, r
     return mask
 
 
+# Plan options (include/pivp_hip.h, pivp_plan_set_option): `plan_options` key -> (PIVP_OPT_* id, the library's default, the environment variable this
+# package reads as ITS default -- the library reads none)
+PLAN_OPTIONS = OrderedDict(side_stream=(0, 1, 'PIVP_SIDE_STREAM'), finish_rider=(1, 1, 'PIVP_FINISH_RIDER'), fuse_enc3=(2, 1, 'PIVP_FUSE_ENC3'),
+                           ln_fold_train=(3, 1, 'PIVP_LN_FOLD_TRAIN'), wgrad_batch=(4, 0, 'PIVP_WGRAD_BATCH'))
+WGRAD_BATCH_MAX = 8
+
+
+def check_plan_options(given):
+    unknown = sorted(set(given or ()) - set(PLAN_OPTIONS))
+    if unknown:
+        raise ValueError('unknown plan option %s (known: %s)' % (', '.join(map(repr, unknown)), ', '.join(PLAN_OPTIONS)))
+
+
+def resolve_plan_options(given=None, environ=None):
+    """key -> value for every plan option: what `given` (Model(plan_options=...)) names, else the option's PIVP_* environment variable as it is now, else
+    the library's default.  A switch is off when its variable starts with '0'; PIVP_WGRAD_BATCH is its leading integer (0, unset or no number: the precision
+    mode's own choice), brought into 1 .. 8 when outside -- the plan cuts it to the rings' capacity either way, an exported value never raises.  Values
+    given by keyword are passed on as they are: the library refuses what is out of range."""
+    check_plan_options(given)
+    environ = os.environ if environ is None else environ
+    out = OrderedDict()
+    for key, (_, default, var) in PLAN_OPTIONS.items():
+        env = environ.get(var)
+        if given is not None and key in given:
+            out[key] = int(given[key])
+        elif env is None:
+            out[key] = default
+        elif key == 'wgrad_batch':
+            number = re.match(r'\s*[+-]?\d+', env)
+            v = int(number.group()) if number else 0
+            out[key] = v if v == 0 else min(max(v, 1), WGRAD_BATCH_MAX)
+        else:
+            out[key] = 0 if env.startswith('0') else 1
+    return out
+
+
 class _Plan(object):
     def __init__(self, lib, cfg):
         self.lib = lib
@@ -136,19 +174,24 @@ class Model(object):
     """MI355X drop-in for the reference's `Model` (TM:478-764).
 
     deterministic=True: a training step (forward, `backward()`, `Adam.update`) gives the same bits every time for the same inputs, parameters,
-    optimizer state, plan shape, precision, PIVP_WGRAD_BATCH and GPU model -- whatever the side-stream schedule, the process or the workspace
+    optimizer state, plan shape, precision, the 'wgrad_batch' plan option and GPU model -- whatever the side-stream schedule, the process or the workspace
     address (include/pivp_hip.h, pivp_plan_set_deterministic).  Served with precision 'fp32', 'bf16' and 'bf16x3', for CDNA, STP and DNA;
     other combinations raise ValueError.  Under the switch the ConvLSTM weight gradients are computed in fp32 in every precision mode, so
     deterministic 'bf16' differs from default 'bf16' there (it is the more precise of the two) and its step is slower (README).  A data-parallel
     run is deterministic only if its collective is: `algo='rs_ag'` sums the shards in rank order, the RCCL ring is not guaranteed to
-    (DESIGN.md 6)."""
+    (DESIGN.md 6).
+
+    plan_options: a dict of the plan's A/B levers (include/pivp_hip.h, pivp_plan_set_option) with keys 'side_stream', 'finish_rider', 'fuse_enc3',
+    'ln_fold_train' (0 / 1, default 1) and 'wgrad_batch' (0 .. 8 timesteps per ConvLSTM weight-gradient launch, default 0 = the precision mode's own
+    choice).  An option the dict does not name takes its default from PIVP_SIDE_STREAM, PIVP_FINISH_RIDER, PIVP_FUSE_ENC3, PIVP_LN_FOLD_TRAIN or
+    PIVP_WGRAD_BATCH, read when a plan is made (`resolve_plan_options`); `effective_plan_options()` reads the current plan's values back."""
 
     DETERMINISTIC_PRECISIONS = ('fp32', 'bf16', 'bf16x3')
 
     def __init__(self, num_masks, is_cdna=True, is_dna=False, is_stp=False, use_state=True,
                  scheduled_sampling_k=-1, num_frame_before_prediction=2, prefix=None,
                  device='cuda:0', ln_eps=1e-6, stp_border='clamp', keep_activations=False, precision='fp32', main_priority=None,
-                 deterministic=False, image_loss=None):
+                 deterministic=False, image_loss=None, plan_options=None):
         if is_cdna:                      # TM:531-542, precedence cdna > stp > dna
             self.model_type = 'CDNA'
         elif is_stp:
@@ -201,6 +244,8 @@ class Model(object):
         self.loss_terms = None         # with an image loss: device scalars mse / l1 / gdl / dssim (means over the scored frames) and extra (their weighted sum
                                        # beyond the reference's loss) of the last call
         self._loss_grad = None         # ... and d extra / d gen_images[ctx-1:], when the call kept what backward() needs
+        check_plan_options(plan_options)
+        self.plan_options = dict(plan_options or {})
         self.main_priority = main_priority     # None / False / True: include/pivp_hip.h, pivp_plan_set_main_priority
         self._ref_pending = None       # reference-layout arrays loaded before the first call
         self._params = None            # name -> view into _flat_params (internal layout)
@@ -357,6 +402,10 @@ class Model(object):
                                   keep_activations=1 if keep else 0,
                                   ln_eps=self.ln_eps, stp_zero_border=1 if self.stp_border == 'zeros' else 0)
             plan = _Plan(lib, cfg)
+            for name, value in resolve_plan_options(self.plan_options).items():
+                opt, default, _ = PLAN_OPTIONS[name]
+                if value != default:
+                    _lib.check(lib.pivp_plan_set_option(plan.h, opt, value), 'pivp_plan_set_option(%s, %d)' % (name, value))
             _lib.check(lib.pivp_plan_set_pack_cache(plan.h, 1), 'pivp_plan_set_pack_cache')
             if self.main_priority is not None:      # None: the library's rule (wave priority 3 for the sweep's kernels unless a gradient listener is registered)
                 _lib.check(lib.pivp_plan_set_main_priority(plan.h, 1 if self.main_priority else 0), 'pivp_plan_set_main_priority')
@@ -376,6 +425,13 @@ class Model(object):
             self._plans[key] = plan
             self._reset_plan(plan)
         return plan
+
+    def effective_plan_options(self):
+        """The options of the current plan, read back from the library (pivp_plan_get_option): key -> value as in `plan_options`."""
+        if self._active is None:
+            raise RuntimeError('no plan yet: plans are made by the first call')
+        lib, h = self._active.lib, self._active.h
+        return OrderedDict((name, int(lib.pivp_plan_get_option(h, opt))) for name, (opt, _, _) in PLAN_OPTIONS.items())
 
     def _stream(self):
         return torch.cuda.current_stream(self.device).cuda_stream

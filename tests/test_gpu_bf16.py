@@ -284,26 +284,27 @@ def test_wgrad5x5_fp16x3_batch_of_timesteps(ops, B, cx, C, H, T, gscale, mode):
         assert np.abs(got0[:, :cx] - ref[:, :cx]).max() < 2e-5 * unit and np.all(got0[:, cx:] == 0)
 
 
-def test_bf16_mode_batched_weight_gradients_match_per_step(monkeypatch):
+def test_bf16_mode_batched_weight_gradients_match_per_step():
     # the bf16 mode's plan batches the ConvLSTM weight gradients of up to 8 timesteps per launch (default) -- same products as one launch
-    # per timestep, other summation order
+    # per timestep, other summation order.  The batch is the plan option 'wgrad_batch' (None: not named, the mode's own choice); each Model must
+    # report the batch asked for, and its dG rings -- so its workspace -- the depth that goes with it (T - 2 = 5 slots hold the default's batches)
     import torch
     import pivp_amd
     from oracle import restatement as R
     assert torch.cuda.is_available()
     P = R.init_params_widened(seed=1, scale=1.0)
     imgs, acts, stas = R.synthetic_batch(2, 7)
-    outs = {}
+    outs, ws_bytes = {}, {}
     for batch in ('1', '3', None):
-        if batch is None:
-            monkeypatch.delenv('PIVP_WGRAD_BATCH', raising=False)
-        else:
-            monkeypatch.setenv('PIVP_WGRAD_BATCH', batch)
-        m = pivp_amd.Model(10, prefix='t', keep_activations=True, precision='bf16')
+        m = pivp_amd.Model(10, prefix='t', keep_activations=True, precision='bf16',
+                           plan_options={'wgrad_batch': 0 if batch is None else int(batch)})
         m.load_state_dict_reference(P)
         m([imgs, acts, stas], 0)
         m.cleargrads(); m.backward()
+        assert m.effective_plan_options()['wgrad_batch'] == (0 if batch is None else int(batch))
+        ws_bytes[batch] = m._active.lib.pivp_plan_workspace_bytes(m._active.h)
         outs[batch] = m._flat_grads.clone()
+    assert ws_bytes['1'] < ws_bytes['3'] < ws_bytes[None], ws_bytes      # ring depths 1, 3, 5
     for key, g in outs.items():
         rel = float((g - outs['1']).norm() / outs['1'].norm())
         # Two bf16 sweeps of the SAME configuration already differ by 1.5e-4 .. 6e-4 (the K-split data gradients' atomics reorder fp32 sums

@@ -40,15 +40,15 @@ def _fresh(pivp, P, x, n, kw):
     return [_sweep(m, x) for _ in range(n)], m
 
 
-def _determinism(pivp, monkeypatch, P, x, n_one=5, n_fresh=2, **kw):
+def _determinism(pivp, P, x, n_one=5, n_fresh=2, **kw):
     """n_one sweeps in one Model, n_fresh in a fresh one, one more each with the side stream off and on: all bit-identical"""
     runs, m = _fresh(pivp, P, x, n_one, kw)
     assert m.deterministic is True
     runs += _fresh(pivp, P, x, n_fresh, kw)[0]
-    for side in ('0', '1'):      # read when a plan is created
-        monkeypatch.setenv('PIVP_SIDE_STREAM', side)
-        runs += _fresh(pivp, P, x, 1, kw)[0]
-    monkeypatch.delenv('PIVP_SIDE_STREAM')
+    for side in (0, 1):
+        r, ms = _fresh(pivp, P, x, 1, dict(kw, plan_options={'side_stream': side}))
+        assert ms.effective_plan_options()['side_stream'] == side
+        runs += r
     g0, l0, i0 = runs[0]
     for j, (g, l, i) in enumerate(runs[1:], 1):
         assert torch.equal(g, g0), 'run %d: flat gradient differs in %d elements' % (j, int((g != g0).sum()))
@@ -101,9 +101,9 @@ def _config2():
     return P, [imgs, acts, stas]
 
 
-def test_config2_fp32_is_bit_identical_and_matches_golden(pivp, monkeypatch):
+def test_config2_fp32_is_bit_identical_and_matches_golden(pivp):
     P, x = _config2()
-    (g, loss, _), m = _determinism(pivp, monkeypatch, P, x)
+    (g, loss, _), m = _determinism(pivp, P, x)
     # the gates of test_config2_batch32_gradients_match_golden against the float64 autograd fixture
     gold = np.load(os.path.join(ROOT, 'tests', 'golden', 'cdna_b32_t10_grads.npz'))
     assert abs(float(loss) - float(gold['loss'])) < 1e-5
@@ -123,14 +123,14 @@ def test_config2_fp32_is_bit_identical_and_matches_golden(pivp, monkeypatch):
     print('config 2 fp32: deterministic vs default %.2e' % _agree(g, _default_grads(pivp, P, x), 1e-5))
 
 
-def test_config3_bf16_is_bit_identical(pivp, monkeypatch):
+def test_config3_bf16_is_bit_identical(pivp):
     P, x = _config2()
-    (g, _, _), _m = _determinism(pivp, monkeypatch, P, x, precision='bf16')
+    (g, _, _), _m = _determinism(pivp, P, x, precision='bf16')
     print('config 3 bf16: deterministic vs default %.2e' % _agree(g, _default_grads(pivp, P, x, precision='bf16'), 1e-3))
 
 
 @pytest.mark.parametrize('case', ['stp_b2_t4', 'stp_b32_t10', 'dna_b2_t4', 'cdna_b3_t4', 'cdna_128_b2_t3'])
-def test_other_models_and_shapes_are_bit_identical(pivp, monkeypatch, case):
+def test_other_models_and_shapes_are_bit_identical(pivp, case):
     if case.startswith('stp'):      # feed-self: d prev of the fed-back frames goes through the bilinear sampler's scatter
         kw = dict(is_cdna=False, is_stp=True)
         P = R.init_params_widened(seed=1, scale=1.0, model_type='STP')
@@ -147,7 +147,7 @@ def test_other_models_and_shapes_are_bit_identical(pivp, monkeypatch, case):
         kw = {}
         P = R.init_params_widened(seed=1, scale=1.0, height=128, width=128)
         x = list(R.synthetic_batch(2, 3, 128, 128))
-    _determinism(pivp, monkeypatch, P, x, n_one=3, n_fresh=1, **kw)
+    _determinism(pivp, P, x, n_one=3, n_fresh=1, **kw)
 
 
 def test_gradients_match_float64_autograd(pivp):

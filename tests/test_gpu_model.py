@@ -292,9 +292,9 @@ def test_other_mask_counts(pivp, mt, nm):
 
 @pytest.mark.parametrize('mt,nm', [('CDNA', 10), ('CDNA', 3), ('STP', 10)])
 @pytest.mark.parametrize('train', [False, True])
-def test_motion_finisher_behind_enc5_is_bit_identical(pivp, monkeypatch, mt, nm, train):
+def test_motion_finisher_behind_enc5_is_bit_identical(pivp, mt, nm, train):
     """Round 6: the motion head's finisher (sum of the Linear's K-slice partials, bias, activation, normalisation: TM:326-329 / 458-468) runs as B "rider"
-    blocks behind enc5's tiles instead of inside each of frame_head's 16 bands per sample (PIVP_FINISH_RIDER, read when the plan is made).
+    blocks behind enc5's tiles instead of inside each of frame_head's 16 bands per sample (plan option 'finish_rider').
     Same arithmetic in the same order: frames and loss are bit-identical with the switch off; in training mode the gradients agree to the
     last bits the sweep's atomics leave undetermined."""
     B, T = 3, 4
@@ -302,8 +302,8 @@ def test_motion_finisher_behind_enc5_is_bit_identical(pivp, monkeypatch, mt, nm,
     imgs, acts, stas = R.synthetic_batch(B, T)
     out = {}
     for rider in ('1', '0'):
-        monkeypatch.setenv('PIVP_FINISH_RIDER', rider)
-        m, loss, gen = _run(pivp, mt, nm, imgs, acts, stas, P, train=train, keep_activations=train)
+        m, loss, gen = _run(pivp, mt, nm, imgs, acts, stas, P, train=train, keep_activations=train, plan_options={'finish_rider': int(rider)})
+        assert m.effective_plan_options()['finish_rider'] == int(rider)
         grads = None
         if train:
             m.cleargrads(); m.backward()
@@ -317,9 +317,9 @@ def test_motion_finisher_behind_enc5_is_bit_identical(pivp, monkeypatch, mt, nm,
 
 
 @pytest.mark.parametrize('mt,nm,use_state', [('CDNA', 10, True), ('CDNA', 10, False), ('STP', 10, True), ('DNA', 1, True)])
-def test_group3_in_enc2s_epilogue_is_bit_identical(pivp, monkeypatch, mt, nm, use_state):
+def test_group3_in_enc2s_epilogue_is_bit_identical(pivp, mt, nm, use_state):
     """Round 6: in inference plans the smear + 1x1 conv + ReLU of group 3 (TM:598) and the state predictor (TM:730) run in the
-    epilogue of enc2's launch (PIVP_FUSE_ENC3, read when the plan is made) -- the same fmaf chain on the matrix cores: frames, predicted states and
+    epilogue of enc2's launch (plan option 'fuse_enc3') -- the same fmaf chain on the matrix cores: frames, predicted states and
     loss are bit-identical to the two-launch form."""
     import torch
     B, T = 3, 4
@@ -327,23 +327,23 @@ def test_group3_in_enc2s_epilogue_is_bit_identical(pivp, monkeypatch, mt, nm, us
     imgs, acts, stas = R.synthetic_batch(B, T)
     out = {}
     for fuse in ('1', '0'):
-        monkeypatch.setenv('PIVP_FUSE_ENC3', fuse)
-        m, loss, gen = _run(pivp, mt, nm, imgs, acts, stas, P, use_state=use_state)
+        m, loss, gen = _run(pivp, mt, nm, imgs, acts, stas, P, use_state=use_state, plan_options={'fuse_enc3': int(fuse)})
+        assert m.effective_plan_options()['fuse_enc3'] == int(fuse)
         out[fuse] = (loss, gen, torch.stack(m.gen_states).cpu().numpy())
     assert out['1'][0] == out['0'][0] and np.array_equal(out['1'][1], out['0'][1]) and np.array_equal(out['1'][2], out['0'][2])
 
 
-def test_training_plans_apply_the_norms_of_hidden2_and_hidden4_inside_enc1_and_enc2(pivp, monkeypatch):
+def test_training_plans_apply_the_norms_of_hidden2_and_hidden4_inside_enc1_and_enc2(pivp):
     """Round 6: in training plans too enc1 / enc2's launches apply the LayerNorm of their input while staging it -- and WRITE the normalised tensor and the
-    samples' (mean, rstd) that the backward sweep reads (PIVP_LN_FOLD_TRAIN=0: the two ln_apply launches per timestep, as before).  The expression is
+    samples' (mean, rstd) that the backward sweep reads (plan option 'ln_fold_train' 0: the two ln_apply launches per timestep, as before).  The expression is
     ln_apply's: frames and loss bit-identical, gradients equal to the last bits the sweep's atomics leave undetermined."""
     B, T = 3, 4
     P = R.init_params(seed=11, dtype=np.float32, scale=1.0)
     imgs, acts, stas = R.synthetic_batch(B, T)
     out = {}
     for fold in ('1', '0'):
-        monkeypatch.setenv('PIVP_LN_FOLD_TRAIN', fold)
-        m, loss, gen = _run(pivp, 'CDNA', 10, imgs, acts, stas, P, train=True, keep_activations=True)
+        m, loss, gen = _run(pivp, 'CDNA', 10, imgs, acts, stas, P, train=True, keep_activations=True, plan_options={'ln_fold_train': int(fold)})
+        assert m.effective_plan_options()['ln_fold_train'] == int(fold)
         m.cleargrads(); m.backward()
         out[fold] = (loss, gen, m.grads_reference())
     assert out['1'][0] == out['0'][0] and np.array_equal(out['1'][1], out['0'][1])

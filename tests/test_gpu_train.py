@@ -407,20 +407,23 @@ def test_bptt_gradients_128x128(pivp):
         assert rel_l2 < 1e-2 and med < 1e-3, '%s: relative L2 %.2e, median %.2e' % (kname, rel_l2, med)
 
 
-def test_batched_weight_gradients_match_per_step(pivp, monkeypatch):
-    # WgradDesc::tcount: the ConvLSTM weight gradients of up to 4 timesteps in one launch (PIVP_WGRAD_BATCH) must give the gradients of
-    # one launch per timestep (same products, other summation order), with and without the side stream
+def test_batched_weight_gradients_match_per_step(pivp):
+    # WgradDesc::tcount: the ConvLSTM weight gradients of up to 4 timesteps in one launch (plan option 'wgrad_batch') must give the gradients of
+    # one launch per timestep (same products, other summation order), with and without the side stream.  Each Model must report the options
+    # asked for, and its dG rings -- so its workspace -- the depth that goes with the batch
     P = R.init_params_widened(seed=1, scale=1.0)
     imgs, acts, stas = R.synthetic_batch(2, 8)             # 7 steps: batches [6,5,4,3] [2,1] [0]
-    outs = {}
+    outs, ws_bytes = {}, {}
     for batch, side in (('1', '1'), ('4', '1'), ('3', '0')):
-        monkeypatch.setenv('PIVP_WGRAD_BATCH', batch)
-        monkeypatch.setenv('PIVP_SIDE_STREAM', side)
-        m = pivp.Model(10, prefix='t', keep_activations=True)
+        m = pivp.Model(10, prefix='t', keep_activations=True, plan_options={'wgrad_batch': int(batch), 'side_stream': int(side)})
         m.load_state_dict_reference(P)
         m([imgs, acts, stas], 0)
         m.cleargrads(); m.backward()
+        eff = m.effective_plan_options()
+        assert (eff['wgrad_batch'], eff['side_stream']) == (int(batch), int(side))
+        ws_bytes[batch] = m._active.lib.pivp_plan_workspace_bytes(m._active.h)
         outs[(batch, side)] = m._flat_grads.clone()
+    assert ws_bytes['1'] < ws_bytes['3'] < ws_bytes['4'], ws_bytes      # ring depths 1, 3, 4
     ref = outs[('1', '1')]
     for key, g in outs.items():
         rel = float((g - ref).norm() / ref.norm())

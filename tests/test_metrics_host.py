@@ -197,7 +197,7 @@ def test_header_library_and_ctypes_table_agree_on_frame_metrics():
     declared = set(re.findall(r'\b(pivp_[a-z0-9_]+)\s*\(', header)) - {'pivp_config', 'pivp_plan'}
     exported = set(re.findall(r' T (pivp_[a-z0-9_]+)', subprocess.check_output(['nm', '-D', _lib.LIB_PATH]).decode()))
     assert 'pivp_frame_metrics' in declared and 'pivp_frame_metrics' in exported and 'pivp_frame_metrics' in _lib.SIGNATURES
-    assert declared == set(_lib.SIGNATURES) and declared <= exported and len(declared) == 116
+    assert declared == set(_lib.SIGNATURES) and declared <= exported and len(declared) == 118
     assert _lib.load().pivp_abi_version() == 17                       # added without a version change: nothing else moved
     res, args = _lib.SIGNATURES['pivp_frame_metrics']
     assert res is _lib._i and args == [_lib._vp, _lib._vp] + [_lib._i] * 5 + [_lib._f] * 2 + [_lib._vp] * 3

@@ -33,7 +33,7 @@ def test_optim_header_library_and_ctypes_table_agree():
     assert declared == set(_lib.OPTIM_SIGNATURES) == {'pivp_grad_stats_ws_bytes', 'pivp_grad_stats', 'pivp_adam_step_guarded'}
     assert declared <= exported
     assert not declared & set(_lib.SIGNATURES) and not declared & set(_lib.DATA_SIGNATURES)
-    assert len(_declared('pivp_hip.h') - {'pivp_config', 'pivp_plan'}) == 116 and _declared('pivp_data.h') == {'pivp_gather_batch'}
+    assert len(_declared('pivp_hip.h') - {'pivp_config', 'pivp_plan'}) == 118 and _declared('pivp_data.h') == {'pivp_gather_batch'}
     lib = _lib.load()
     assert lib.pivp_abi_version() == 17
     i, ll, vp, d = _lib._i, _lib._ll, _lib._vp, _lib._c.c_double
