@@ -1298,6 +1298,13 @@ int enc0_bwd(const float* img, const float* w, const float* d, float* dw, float*
     return PIVP_LAUNCH_STATUS();
 }
 
+int enc0_bwd_data(const float* w, const float* d, float* dimg, int dimg_accum, int B, int H, int W, hipStream_t s) {
+    PIVP_CHECK_ARG(w && d && dimg && B > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0);
+    const long tp = (long)B * (H / 2) * (W / 2);
+    hipLaunchKernelGGL(enc0_dgrad_kernel, dim3((unsigned)((tp + 63) / 64), 4), dim3(256), 0, s, d, w, dimg, dimg_accum, B, H, W);
+    return PIVP_LAUNCH_STATUS();
+}
+
 long long enc0_bwd_det_floats(int B, int H, int W) {
     const int total = B * (H / 2) * (W / 2);
     int blocks = (total + 63) / 64; if (blocks > 512) blocks = 512;

@@ -350,6 +350,11 @@ int enc0_bwd(const float* img, const float* w, const float* d, float* dw, float*
              hipStream_t s, const SideFork* fork = nullptr,   // fork: where the weight / bias gradient kernel runs
              float* det_part = nullptr);      // det_part (enc0_bwd_det_floats): per-block rows + det_rows_reduce instead of atomics
 long long enc0_bwd_det_floats(int B, int H, int W);
+// enc0_bwd's data gradient alone (sweeps without parameter gradients, pivp_plan_set_sweep_mode): the same launch, so the same d img
+int enc0_bwd_data(const float* w, const float* d, float* dimg, int dimg_accum, int B, int H, int W, hipStream_t s);
+// csrc/input_grad.hip: the action half of enc3's smeared-input gradient (include/pivp_input_grad.h, pivp_action_grad), one block per sample
+int action_grad(const float* e3, const float* de3, int ldd3, const float* w3, const float* wcs, const float* dsnew, float* dact, int B, int HW8,
+                int use_state, hipStream_t s);
 int add_strided(float* dst, int ldd, const float* src, int lds_, int C, long npix, hipStream_t s);
 
 // planar NCHW <-> NHWC helpers for taps (conv_res) and tests

@@ -7,6 +7,7 @@
 
 #include "../../include/pivp_hip.h"
 #include "../../include/pivp_loss.h"
+#include "../../include/pivp_input_grad.h"
 #include "pivp_host.h"
 
 using namespace pivp;
@@ -151,6 +152,8 @@ struct pivp_plan {
     int main_prio = -1;               // pivp_plan_set_main_priority: -1 = on unless a gradient listener is registered (data parallelism), 0 / 1 = as said
     int det = 0;                      // pivp_plan_set_deterministic: fixed-order forms of every sum of the sweep (no float atomics)
     const float* frame_seed = nullptr;   // pivp_plan_set_frame_grad: an additional d loss / d gen_images[ctx-1 .. T-2] for the sweep (null: the plan's own seed alone)
+    float* in_dact = nullptr; float* in_dstate0 = nullptr;   // pivp_plan_set_input_grad: d loss / d actions [T-1][B][5] and d loss / d states[0] [B][5] (null: not wanted)
+    int sweep_mode = 3;               // pivp_plan_set_sweep_mode: PIVP_SWEEP_PARAMS | PIVP_SWEEP_BUILTIN_LOSS (include/pivp_input_grad.h)
     bool lstm_started[7] = {};        // deterministic sweeps: the cell's weight-gradient slots hold this sweep's sums (before: stored, not added)
     pivp_grad_group_cb grad_cb = nullptr; void* grad_cb_user = nullptr;   // gradient-group-final notifications (t = 0 sweep)
     int loss_nparts;
@@ -484,6 +487,18 @@ extern "C" int pivp_plan_set_frame_grad(pivp_plan_t* plan, const float* seed) {
     plan->frame_seed = seed;
     return PIVP_OK;
 }
+// include/pivp_input_grad.h: where the sweep leaves d loss / d actions and d loss / d states[0] (null: nowhere -- no launch is added), and what it computes
+extern "C" int pivp_plan_set_input_grad(pivp_plan_t* plan, float* dactions, float* dstate0) {
+    if (!plan || ((reinterpret_cast<uintptr_t>(dactions) | reinterpret_cast<uintptr_t>(dstate0)) & 3)) return PIVP_ERR_BADARG;
+    plan->in_dact = dactions; plan->in_dstate0 = dstate0;
+    return PIVP_OK;
+}
+extern "C" int pivp_plan_set_sweep_mode(pivp_plan_t* plan, int flags) {
+    if (!plan || flags < 0 || flags > (PIVP_SWEEP_PARAMS | PIVP_SWEEP_BUILTIN_LOSS)) return PIVP_ERR_BADARG;
+    plan->sweep_mode = flags;
+    return PIVP_OK;
+}
+extern "C" int pivp_plan_get_sweep_mode(const pivp_plan_t* plan) { return plan ? plan->sweep_mode : PIVP_ERR_BADARG; }
 // Inference with constant weights: keep the bf16 / fp16 weight packs across rollouts (on = 1) instead of rebuilding them at the start of each.  The
 // caller then owes pivp_plan_params_changed after EVERY modification of a parameter tensor (optimizer step, checkpoint load, host write); set_param,
 // set_precision and set_workspace invalidate by themselves.  Default off.
@@ -977,8 +992,11 @@ static int backward_step(pivp_plan* p, int t, const float* prev, bool prev_has_g
     const int n2 = 32 * p->H2 * p->W2, n4 = 64 * p->H4 * p->W4, n8 = 128 * p->H8 * p->W8;
     float* lnpart = ws + g.lnpart;
     const Modes& md = p->mode;
+    // sweeps without parameter gradients (pivp_plan_set_sweep_mode): p->side is null for their duration, so no fork, join or side launch below happens;
+    // what is left to skip are the launches that form nothing but parameter gradients
+    const bool params = (p->sweep_mode & PIVP_SWEEP_PARAMS) != 0;
     auto ln_finish = [&](int j) -> int {
-        if (!p->ln_touched[j]) return PIVP_OK;
+        if (!p->ln_touched[j] || !params) return PIVP_OK;
         p->ln_touched[j] = false;
         return ln_bwd_params_reduce(ws + g.ln_ppart[j], G(p, p->i_ln_g[j]), G(p, p->i_ln_b[j]), B, (int)ln_numel(c, j), s);
     };
@@ -1050,7 +1068,7 @@ static int backward_step(pivp_plan* p, int t, const float* prev, bool prev_has_g
         a.ep = ep; a.det = p->det;
         RC(run_convlstm_backward(a, s));
         if (t == 0) RC(ln_finish(i + 1));       // the sweep's last timestep: the norm's partial parameter planes (written by the gate kernel) become its gradient
-        if (!wg_flush) return PIVP_OK;
+        if (!wg_flush || !params) return PIVP_OK;
         // weight + bias gradient of the whole batch: timestep j of it reads slab (first - j) and ring slot j; on the side stream it
         // starts as soon as this step's dG exists, next to this step's own data gradient
         hipStream_t sw = p->side ? p->side_of(i) : s;
@@ -1133,7 +1151,7 @@ static int backward_step(pivp_plan* p, int t, const float* prev, bool prev_has_g
     auto encb = [&](int k, const float* x, float* dy, const float* y, float* dx, int accum_dx, const float* dy_add = nullptr, int ld_add = 0) -> int {
         const EncSpec& E = kEnc[k];
         const MapSize m = level_map(c, E.level);
-        enc_add(k, x);
+        if (params) enc_add(k, x);      // (an empty batch: enc_flush launches nothing)
         ConvBwdArgs a{};
         a.mode = E.mode; a.x = x; a.cin = E.c; a.ldx = E.ldx; a.w = P(p, p->i_enc_w[E.layer]); a.dy = dy; a.cout = E.c; a.ldy = E.ldy;
         a.y = y; a.ldyy = E.ldo;
@@ -1192,6 +1210,7 @@ static int backward_step(pivp_plan* p, int t, const float* prev, bool prev_has_g
     };
     // t = 0 is the sweep's final timestep: a gradient group is final once the side stream's weight gradients of its layers are in too
     auto done = [&](int group) -> int {
+        if (!params) return PIVP_OK;      // nothing becomes final, nobody is told
         if (t == 0 && !p->grad_cb) {       // no listener: still turn the group's partial sums into gradients
             static const int encs[6][1] = {{0}, {-1}, {1}, {2}, {3}, {4}};
             if (encs[group][0] >= 0) RC(reduce_enc(encs[group][0]));
@@ -1234,6 +1253,14 @@ static int backward_step(pivp_plan* p, int t, const float* prev, bool prev_has_g
                       ws + g.dstate + (size_t)t * B * 5, d_e2, G(p, p->i_enc_w[3]), G(p, p->i_enc_b[3]), G(p, p->i_cs_w),
                       G(p, p->i_cs_b), t > 0 ? ws + g.dstate + (size_t)(t - 1) * B * 5 : ws + g.dstate + (size_t)(c.seq_len - 1) * B * 5,
                       B, p->H8 * p->W8, c.use_state, s, 1, p->det ? ws + g.det_enc3 : nullptr));      // d e2 comes out masked by enc2's ReLU
+    // d action[t]: the other half of the smeared-input gradient, from the tensors enc3_state_bwd has just read (it wrote d e2 and gradients only)
+    if (p->in_dact)
+        RC(action_grad(ws + S.e3, DIN(4, true), 192, P(p, p->i_enc_w[3]), P(p, p->i_cs_w), ws + g.dstate + (size_t)t * B * 5,
+                       p->in_dact + (size_t)t * B * 5, B, p->H8 * p->W8, c.use_state, s));
+    // d states[0]: the state chain ends in slot T-1 of g.dstate (this launch's d state_prev at t = 0; behind its det_rows_reduce in deterministic plans)
+    if (t == 0 && p->in_dstate0 &&
+        hipMemcpyAsync(p->in_dstate0, ws + g.dstate + (size_t)(c.seq_len - 1) * B * 5, (size_t)B * 5 * 4, hipMemcpyDeviceToDevice, s) != hipSuccess)
+        return PIVP_ERR_LAUNCH;
     // group 2 (TM:597): enc2 conv (ReLU) <- hidden4 <- lstm4 <- hidden3 <- lstm3 <- enc1
     RC(encb(3, ws + S.n4, d_e2, nullptr, ws + g.n4, 0));
     RC(lnb_cell(3, ws + g.n4, 64, n4, 64));
@@ -1250,6 +1277,11 @@ static int backward_step(pivp_plan* p, int t, const float* prev, bool prev_has_g
     if (!ep_ok0) RC(add_strided(ws + g.cat7 + 32, 64, DIN(0, true), 64, 32, px2, s));          // d enc0: from enc6's concat + from lstm1
     // group 0 (TM:595): norm_enc0 (+relu) <- enc0 conv <- frame
     RC(join(12));          // d e0raw
+    if (!params) {      // enc0's weight gradient is a launch of its own: only the frame gradient of a feed-self step is left, and norm_enc0's dx feeds nothing else
+        if (!prev_has_grad) return PIVP_OK;
+        RC(lnb(0, ep_ok0 ? DIN(0, true) : ws + g.cat7 + 32, 64, ws + S.cat7 + 32, 64, ws + S.e0raw, ws + g.e0raw[par], n2, 32, 1));
+        return enc0_bwd_data(P(p, p->i_enc_w[0]), ws + g.e0raw[par], go_prev, 1, B, H, W, s);
+    }
     RC(lnb(0, ep_ok0 ? DIN(0, true) : ws + g.cat7 + 32, 64, ws + S.cat7 + 32, 64, ws + S.e0raw, ws + g.e0raw[par], n2, 32, 1));
     RC(enc0_bwd(prev, P(p, p->i_enc_w[0]), ws + g.e0raw[par], G(p, p->i_enc_w[0]), G(p, p->i_enc_b[0]), prev_has_grad ? go_prev : nullptr, 1,
                 B, H, W, s, fork_of(12, fe), p->det ? ws + g.det_enc0 : nullptr));
@@ -1262,7 +1294,14 @@ static int rollout_backward_sweep(pivp_plan_t* plan, const float* images, const 
 extern "C" int pivp_rollout_backward(pivp_plan_t* plan, const float* images, const float* actions, const float* states,
                                      const unsigned char* gt_select, const float* gen_images, const float* gen_states, void* stream) {
     if (!plan) return PIVP_ERR_BADARG;
+    // A sweep without parameter gradients has nothing for the side stream: the plan has none while it runs, so nothing forks, nothing is joined below
+    // and no event of an earlier sweep is waited for (those sweeps joined their own work into the caller's stream before they returned)
+    const bool params = (plan->sweep_mode & PIVP_SWEEP_PARAMS) != 0;
+    hipStream_t const kept_side = plan->side;
+    if (!params) plan->side = nullptr;
     const int rc = rollout_backward_sweep(plan, images, actions, states, gt_select, gen_images, gen_states, stream);
+    if (!params) plan->side = kept_side;
+    if (!params) return rc;
     // The side stream's weight gradients are joined whatever the sweep returned: on success the caller's stream is made to wait for
     // them (what it enqueues next -- the all-reduce, Adam -- sees every gradient); after a failure half-way the host waits for both
     // streams, so nothing is still reading the workspace or writing gradients when the caller clears, reuses or frees them.
@@ -1290,6 +1329,8 @@ static int rollout_backward_sweep(pivp_plan_t* plan, const float* images, const 
     if (plan->last_predict) return PIVP_ERR_STATE;      // pivp_rollout_predict keeps no loss to differentiate
     if ((gt_select != nullptr) != plan->last_sched) return PIVP_ERR_STATE;
     for (const ParamInfo& pi : plan->params) if (!pi.ptr || !pi.grad) return PIVP_ERR_STATE;
+    const bool params = (plan->sweep_mode & PIVP_SWEEP_PARAMS) != 0, own_loss = (plan->sweep_mode & PIVP_SWEEP_BUILTIN_LOSS) != 0;
+    if (!own_loss && !plan->frame_seed) return PIVP_ERR_STATE;      // nothing to differentiate
     hipStream_t s = (hipStream_t)stream;
     const pivp_config_t& c = plan->cfg;
     const int B = c.batch, T = c.seq_len, ctx = c.context_frames;
@@ -1299,7 +1340,7 @@ static int rollout_backward_sweep(pivp_plan_t* plan, const float* images, const 
     const float fscale = 2.0f / ((float)fr * (float)(T - ctx));              // d/d gen of mean-squared error / (T - ctx)
     const float sscale = 2.0f * 1e-4f / ((float)(B * 5) * (float)(T - ctx));
     const Modes& md = plan->mode;
-    RC(ensure_side(plan));
+    if (params) RC(ensure_side(plan));
     RC(apply_main_prio(plan, s));
     {   // Timesteps per ConvLSTM weight-gradient launch (PIVP_OPT_WGRAD_BATCH overrides, 1..wg_cap).  fp32: 1 (batches arrive in bursts and
         // overlap the sweep worse: 29.9 / 30.3 ms for 1 / 2, profiles/r02).  bf16 mode: as many as the rings hold -- its 25-tap kernel
@@ -1313,7 +1354,7 @@ static int rollout_backward_sweep(pivp_plan_t* plan, const float* images, const 
     }
     // the norms' partial parameter gradients start from zero every sweep; the enc convs' partial planes are STORED by each layer's first launch of the
     // sweep (WgradDesc::part_overwrite; 240 MB of planes at B = 32: a memset of them would cost what the weight gradients do)
-    if (hipMemsetAsync(ws + g.ln_ppart[0], 0, g.ln_ppart_floats * 4, s) != hipSuccess) return PIVP_ERR_LAUNCH;
+    if (params && hipMemsetAsync(ws + g.ln_ppart[0], 0, g.ln_ppart_floats * 4, s) != hipSuccess) return PIVP_ERR_LAUNCH;
     for (int j = 0; j < 9; ++j) plan->ln_touched[j] = false;
     for (int k = 0; k < 5; ++k) { plan->enc_desc_valid[k] = false; plan->enc_cnt[k] = 0; plan->enc_started[k] = false; }
     for (int i = 0; i < 7; ++i) plan->lstm_started[i] = false;
@@ -1322,9 +1363,13 @@ static int rollout_backward_sweep(pivp_plan_t* plan, const float* images, const 
     // d loss / d gen_states[t] for every t (zero before ctx-1), later accumulated with the state recurrence
     if (hipMemsetAsync(ws + g.dstate, 0, (size_t)T * B * 5 * 4, s) != hipSuccess) return PIVP_ERR_LAUNCH;
     // (gen_states[t] against states[t + 1], t = ctx-1 .. T-2: contiguous in t, one launch; likewise the frames' loss terms below -- 16 launches per sweep before)
-    RC(scaled_diff(gen_states + (size_t)(ctx - 1) * B * 5, states + (size_t)ctx * B * 5, ws + g.dstate + (size_t)(ctx - 1) * B * 5, (long)(T - ctx) * B * 5, sscale, 0, s));
+    // (without the plan's own loss, pivp_plan_set_sweep_mode: the memset above is the state seed, a zero fill the frames')
+    if (own_loss)
+        RC(scaled_diff(gen_states + (size_t)(ctx - 1) * B * 5, states + (size_t)ctx * B * 5, ws + g.dstate + (size_t)(ctx - 1) * B * 5, (long)(T - ctx) * B * 5, sscale, 0, s));
     // d loss / d gen[t], t = ctx-1 .. T-2 (gen[t] is compared with images[t + 1]); the sweep adds the feed-back terms of step t + 1 into frame t in place
-    RC(scaled_diff(gen_images + (size_t)(ctx - 1) * fr, images + (size_t)ctx * fr, ws + g.go + (size_t)(ctx - 1) * fr, (long)(T - ctx) * (long)fr, fscale, 0, s));
+    if (own_loss)
+        RC(scaled_diff(gen_images + (size_t)(ctx - 1) * fr, images + (size_t)ctx * fr, ws + g.go + (size_t)(ctx - 1) * fr, (long)(T - ctx) * (long)fr, fscale, 0, s));
+    else if (hipMemsetAsync(ws + g.go + (size_t)(ctx - 1) * fr, 0, (size_t)(T - ctx) * fr * 4, s) != hipSuccess) return PIVP_ERR_LAUNCH;
     // ... plus the caller's own d loss / d gen (pivp_plan_set_frame_grad): everything downstream of g.go is indifferent to where the seed came from
     if (plan->frame_seed) RC(frame_seed_add(ws + g.go + (size_t)(ctx - 1) * fr, plan->frame_seed, (long)(T - ctx) * (long)fr, s));
     // weights are constant during the sweep: the transposed packs for the data gradients, all twelve in one launch (7 + 5 launches before round 5)

@@ -244,6 +244,8 @@ class Model(object):
         self.loss_terms = None         # with an image loss: device scalars mse / l1 / gdl / dssim (means over the scored frames) and extra (their weighted sum
                                        # beyond the reference's loss) of the last call
         self._loss_grad = None         # ... and d extra / d gen_images[ctx-1:], when the call kept what backward() needs
+        self.action_grad = None        # backward(input_grad=True): d loss / d actions[:T-1] (T-1, B, 5) and ...
+        self.state_grad = None         # ... d loss / d states[0] (B, 5), device tensors
         check_plan_options(plan_options)
         self.plan_options = dict(plan_options or {})
         self.main_priority = main_priority     # None / False / True: include/pivp_hip.h, pivp_plan_set_main_priority
@@ -679,7 +681,7 @@ class Model(object):
             raise RuntimeError('call the model first (parameters are lazily sized)')
         return list(self._group_ranges)
 
-    def backward(self, on_group=None, frame_grad=None):
+    def backward(self, on_group=None, frame_grad=None, input_grad=False, params=True, builtin_loss=True):
         """Back-propagate the loss of the LAST call through time (needs keep_activations=True).  Gradients
         accumulate into `model._flat_grads` (internal layouts); `grads_reference()` returns them in checkpoint layout.
 
@@ -689,7 +691,20 @@ class Model(object):
 
         on_group(i): optional host callback, invoked from inside the sweep as soon as every kernel that contributes to
         gradient group i (slice grad_group_ranges()[i]) has been enqueued on the model's stream -- the hook the
-        data-parallel all-reduce uses to overlap communication with the rest of the sweep."""
+        data-parallel all-reduce uses to overlap communication with the rest of the sweep.
+
+        input_grad=True: the sweep also leaves d loss / d actions[:T-1] in `model.action_grad` (T-1, B, 5) and d loss / d states[0] in
+        `model.state_grad` (B, 5), float32 tensors on the model's device (pivp_plan_set_input_grad, include/pivp_input_grad.h).  They are overwritten, not
+        accumulated; the buffers are reused by the next such call of the same shape, and nothing synchronises.
+        params=False: the sweep skips every launch that only forms parameter gradients (pivp_plan_set_sweep_mode) -- for callers who want the input
+        gradients alone.  `_flat_grads` then holds unspecified values: `cleargrads()` before the next full sweep.  `on_group` must be None.
+        builtin_loss=False: the sweep differentiates `frame_grad` (and the model's image loss, if it has one) alone, without the reference's frame and
+        state MSE; without either there is nothing to differentiate and the call raises ValueError.
+        Both switches hold for this call only."""
+        if not params and on_group is not None:
+            raise ValueError('backward(params=False) announces no gradient group: on_group must be None')
+        if not builtin_loss and frame_grad is None and self._loss_grad is None:
+            raise ValueError('backward(builtin_loss=False) needs frame_grad (or a model with an image loss): there is nothing to differentiate')
         plan = self._active
         if plan is None or self._results is None:
             raise RuntimeError('call the model first')
@@ -719,15 +734,29 @@ class Model(object):
                     errors.append(e)
             cb = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int)(_trampoline)
             _lib.check(plan.lib.pivp_plan_set_grad_callback(plan.h, ctypes.cast(cb, ctypes.c_void_p), None), 'pivp_plan_set_grad_callback')
+        mode = (_lib.SWEEP_PARAMS if params else 0) | (_lib.SWEEP_BUILTIN_LOSS if builtin_loss else 0)
+        if input_grad:
+            shape = (images.shape[0] - 1, images.shape[1], 5)
+            if self.action_grad is None or tuple(self.action_grad.shape) != shape or self.action_grad.device != images.device:
+                self.action_grad = torch.empty(shape, dtype=torch.float32, device=images.device)
+                self.state_grad = torch.empty(shape[1:], dtype=torch.float32, device=images.device)
         try:
             # the model's device must be the CURRENT one for the launches (and for the plan's own side stream, created on first use)
             with torch.cuda.device(self.device):
+                if input_grad:
+                    _lib.check(plan.lib.pivp_plan_set_input_grad(plan.h, self.action_grad.data_ptr(), self.state_grad.data_ptr()), 'pivp_plan_set_input_grad')
+                if mode != 3:
+                    _lib.check(plan.lib.pivp_plan_set_sweep_mode(plan.h, mode), 'pivp_plan_set_sweep_mode')
                 if seed is not None:      # (torch keeps the tensor's memory for the stream that is current here, the sweep's)
                     _lib.check(plan.lib.pivp_plan_set_frame_grad(plan.h, seed.data_ptr()), 'pivp_plan_set_frame_grad')
                 _lib.check(plan.lib.pivp_rollout_backward(plan.h, images.data_ptr(), actions.data_ptr(), states.data_ptr(), gt_ptr,
                                                           self._gen.data_ptr(), self._gen_states.data_ptr(), self._stream()),
                            'pivp_rollout_backward')
         finally:
+            if input_grad:
+                plan.lib.pivp_plan_set_input_grad(plan.h, None, None)
+            if mode != 3:
+                plan.lib.pivp_plan_set_sweep_mode(plan.h, 3)
             if seed is not None:
                 plan.lib.pivp_plan_set_frame_grad(plan.h, None)
             if cb is not None:

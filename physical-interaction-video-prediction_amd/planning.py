@@ -8,6 +8,9 @@ tracked planes) and pivp_plan_cost (expected distance to the goals, each plane r
 synchronisation and no host-to-device copy inside it.  It knows about PAST actions: the steps before the last observed frame are fixed, only the
 horizon is optimised (the MPC case).
 
+`refine_actions` is the gradient-based counterpart: Adam on an action sequence, with d cost / d actions from the model's own backward sweep
+(`Model.backward(input_grad=True, params=False, builtin_loss=False)`, include/pivp_input_grad.h) and any torch cost of the predicted frames.
+
 `score_actions` scores a given set of candidates with one `imagine` and plain torch (`one_hot_planes`, `expected_position`,
 `expected_distance`); it is kept as it was for callers that bring their own optimiser."""
 import contextlib
@@ -19,7 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .model import Model
+from .model import Model, using_config
 
 
 def one_hot_planes(coords, H, W, device=None):
@@ -314,3 +317,173 @@ def _cem_iterate(model, a, b, trace=False):
         records[-1]['elites'] = b.elite_idx.clone()
     return SimpleNamespace(actions=b.best_actions, cost=b.best_cost[0], mean=b.mean, std=b.std, best_cost_per_iteration=b.per_iter,
                            trace=records if trace else None)
+
+
+# ---- gradient-based refinement of an action sequence ---------------------------------------------------------------------------------------
+ADAM_BETA1, ADAM_BETA2, ADAM_EPS = 0.9, 0.999, 1e-8      # refine_actions' Adam: the optimizer's defaults (optimizer.Adam)
+
+
+def _adam_lr_t(lr, t, beta1=ADAM_BETA1, beta2=ADAM_BETA2):
+    """The bias-corrected step size of Adam's update t = 1, 2, ... (optimizer.Adam.lr), formed on the host in double."""
+    return lr * math.sqrt(1.0 - math.pow(beta2, t)) / (1.0 - math.pow(beta1, t))
+
+
+def _adam_launch(model, p, g, m, v, lr_t):
+    """ONE pivp_adam_step on the flat buffers p, g, m, v (same numel), on the model's stream."""
+    _lib.check(_lib.load().pivp_adam_step(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), lr_t, ADAM_BETA1, ADAM_BETA2, ADAM_EPS,
+                                          1.0, model._stream()), 'pivp_adam_step')
+
+
+def _check_refine_args(model, context_images, state, actions, goal_image, cost_fn, steps, lr, past_actions, bounds):
+    """Every complaint of `refine_actions` is a ValueError raised here, before the GPU or the library is needed.  -> the checked host-side values."""
+    ctx = int(model.num_frame_before_prediction)
+    si = Model._host_shape(context_images)
+    if len(si) != 5 or si[2] != 3 or si[1] < 1:
+        raise ValueError('context_images must be (ctx, B, 3, H, W), got shape %s' % (si,))
+    if ctx < 1 or si[0] != ctx:
+        raise ValueError('context_images holds %d frames, the model was built with num_frame_before_prediction=%d' % (si[0], ctx))
+    B, H, W = si[1], si[3], si[4]
+    if H < 2 or W < 2:
+        raise ValueError('context_images is empty: shape %s' % (si,))
+    if Model._host_shape(state) != (B, 5):
+        raise ValueError('state must be (%d, 5), got shape %s' % (B, Model._host_shape(state)))
+    sa = Model._host_shape(actions)
+    if len(sa) != 3 or sa[1] != B or sa[2] != 5 or sa[0] < ctx:
+        raise ValueError('actions must be (T-1, %d, 5) with T-1 >= %d (one action per rollout step, the steps between the context frames included), '
+                         'got shape %s' % (B, ctx, sa))
+    if not getattr(model, 'keep_activations', False):
+        raise ValueError('refine_actions back-propagates through the rollout: the model needs keep_activations=True')
+    if getattr(model, '_extra_loss', False):
+        raise ValueError('refine_actions differentiates its own cost alone: the model must not carry an image loss')
+    if (goal_image is None) == (cost_fn is None):
+        raise ValueError('exactly one of goal_image and cost_fn must be given')
+    if cost_fn is not None and not callable(cost_fn):
+        raise ValueError('cost_fn must be callable: cost_fn(gen (T-ctx, B, 3, H, W)) -> (B,)')
+    if goal_image is not None:
+        sg = Model._host_shape(goal_image)
+        if sg not in ((3, H, W), (B, 3, H, W)):
+            raise ValueError('goal_image must be (3, %d, %d) or (%d, 3, %d, %d), got shape %s' % (H, W, B, H, W, sg))
+    if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or steps < 1:
+        raise ValueError('steps must be an integer >= 1, not %r' % (steps,))
+    if isinstance(lr, bool) or not isinstance(lr, (int, float, np.integer, np.floating)) or not math.isfinite(lr) or lr < 0:
+        raise ValueError('lr must be a finite non-negative number, not %r' % (lr,))
+    n_past = 0
+    if past_actions is not None:
+        sp = Model._host_shape(past_actions)
+        if ctx < 2 or sp not in ((ctx - 1, 5), (ctx - 1, B, 5)):
+            raise ValueError('past_actions must be (%d, 5) or (%d, %d, 5): the actions taken between the %d observed frames, got shape %s'
+                             % (ctx - 1, ctx - 1, B, ctx, sp))
+        n_past = ctx - 1
+    low = high = None
+    if bounds is not None:
+        if not isinstance(bounds, (tuple, list)) or len(bounds) != 2:
+            raise ValueError('bounds must be a pair (low, high)')
+        pair = []
+        for name, v, default in (('bounds[0]', bounds[0], -np.inf), ('bounds[1]', bounds[1], np.inf)):
+            a = np.full(5, default) if v is None else _host_array(v, name)
+            if a.shape not in ((), (5,)) or np.isnan(a).any():
+                raise ValueError('%s must be a scalar or (5,) without NaN, got shape %s' % (name, a.shape))
+            pair.append(np.ascontiguousarray(np.broadcast_to(a, (5,))))
+        if (pair[0] > pair[1]).any():
+            raise ValueError('bounds: low exceeds high')
+        low, high = pair
+    return SimpleNamespace(ctx=ctx, B=B, H=H, W=W, steps_T=sa[0], n_past=n_past, iters=int(steps), lr=float(lr), low=low, high=high)
+
+
+def refine_actions(model, context_images, state, actions, goal_image=None, cost_fn=None, steps=10, lr=0.05, past_actions=None, bounds=None):
+    """Gradient descent (Adam) on an action sequence, with the gradient from the model's own backward sweep.
+
+    context_images (ctx, B, 3, H, W), state (B, 5): what each of B robots sees now; actions (T-1, B, 5): the sequence to start from, one action per
+    rollout step (rows t < ctx-1 are the steps between the context frames).  past_actions (ctx-1, 5) or (ctx-1, B, 5): when given, those first rows
+    are set to it and held fixed (the MPC case: they have been executed); None: every row is free (explaining an observed video).
+
+    Per iteration: ONE feed-self training-mode rollout (`model(...)` under config.train with scheduled sampling off, whatever the model's
+    scheduled_sampling_k is; the frames after the context are zeros and play no part), the cost of the predictions gen = gen_images[ctx-1:]
+    (T-ctx, B, 3, H, W) in torch -- cost_fn(gen) -> (B,), differentiated by autograd, or, with goal_image (3, H, W) / (B, 3, H, W), the squared error
+    to it averaged over steps and pixels --, `backward(frame_grad=d sum(cost) / d gen, input_grad=True, params=False, builtin_loss=False)`, the past
+    rows of the gradient zeroed, ONE pivp_adam_step on the flat action buffer (beta1 0.9, beta2 0.999, eps 1e-8, its own moments, the bias-corrected
+    step size formed on the host) and the clamp to bounds = (low, high), each a scalar, (5,) or None.  Stream-ordered launches only: nothing
+    synchronises with the host.  A last rollout scores the returned sequence.
+
+    -> (actions (T-1, B, 5), costs (steps + 1, B)): the refined sequence and the cost of every sample in front of each update and behind the last;
+    device tensors.  lr = 0 returns the input's bits.
+
+    It knows nothing of `cem_plan`; refining CEM's plan is the caller's three lines:
+
+        plan = cem_plan(model, context, state, designated_rc, goal_rc, horizon, past_actions=past)
+        seq = torch.cat((torch.as_tensor(past, dtype=torch.float32, device=plan.actions.device).view(-1, 5), plan.actions)).unsqueeze(1)
+        refined, costs = refine_actions(train_model, context, state, seq, goal_image=goal, past_actions=past)
+
+    (`train_model`: the same weights with keep_activations=True.)  Side effect: the model holds the last rollout; its parameter gradients are
+    unspecified afterwards (`cleargrads()` before training on)."""
+    a = _check_refine_args(model, context_images, state, actions, goal_image, cost_fn, steps, lr, past_actions, bounds)
+    with torch.cuda.device(model.device) if torch.cuda.is_available() else contextlib.nullcontext():
+        return _refine_iterate(model, a, _refine_upload(model, a, context_images, state, actions, goal_image, past_actions), cost_fn)
+
+
+def _refine_upload(model, a, context_images, state, actions, goal_image, past_actions):
+    """Everything the loop reads or writes, uploaded or built ONCE: -> the device buffers of one `refine_actions` call."""
+    model._require_gpu()
+    dev = model.device
+    T = a.steps_T + 1
+    b = SimpleNamespace()
+    b.images = torch.zeros((T, a.B, 3, a.H, a.W), dtype=torch.float32, device=dev)
+    b.images[:a.ctx] = model._as_device(context_images, ())
+    b.states = torch.zeros((T, a.B, 5), dtype=torch.float32, device=dev)
+    b.states[0] = model._as_device(state, (5,))
+    b.actions = torch.zeros((T, a.B, 5), dtype=torch.float32, device=dev)      # (the rollout's action tensor is (T, B, 5); row T-1 is never read)
+    b.actions[:T - 1] = model._as_device(actions, (5,))
+    if a.n_past:
+        past = model._as_device(past_actions, (5,))
+        b.actions[:a.n_past] = past if past.dim() == 3 else past.unsqueeze(1)
+    b.goal = None if goal_image is None else model._as_device(goal_image, ())
+    to_dev = lambda v: None if v is None else torch.from_numpy(np.asarray(v, dtype=np.float32)).to(dev)
+    b.low, b.high = to_dev(a.low), to_dev(a.high)
+    return b
+
+
+def _refine_iterate(model, a, b, cost_fn=None, adam=_adam_launch):
+    """The loop of `refine_actions` on its device buffers: rollout, cost, sweep, Adam -- stream-ordered work only (tests/test_gpu_input_grad.py runs it
+    under torch's sync debug mode)."""
+    T1, t0 = a.steps_T, a.n_past
+    p = b.actions[:T1]                    # the optimised buffer: a contiguous prefix
+    m, v = torch.zeros_like(p), torch.zeros_like(p)
+    costs = torch.empty((a.iters + 1, a.B), dtype=torch.float32, device=p.device)
+    nf = T1 + 1 - a.ctx
+
+    def rollout_cost(want_grad):
+        k = model.scheduled_sampling_k
+        model.scheduled_sampling_k = -1
+        try:
+            with using_config('train', True):
+                model([b.images, b.actions, b.states])
+        finally:
+            model.scheduled_sampling_k = k
+        gen = model._gen[a.ctx - 1:]
+        if cost_fn is None:      # mean over steps and pixels of the squared error, per sample; its gradient in closed form
+            diff = gen - b.goal
+            return (diff * diff).mean(dim=(0, 2, 3, 4)), (diff * (2.0 / (nf * 3 * a.H * a.W)) if want_grad else None)
+        if not want_grad:
+            with torch.no_grad():
+                return cost_fn(gen), None
+        leaf = gen.detach().requires_grad_(True)
+        c = cost_fn(leaf)
+        if not torch.is_tensor(c) or tuple(c.shape) != (a.B,):
+            raise ValueError('cost_fn must return a (%d,) tensor, got %s' % (a.B, tuple(c.shape) if torch.is_tensor(c) else type(c).__name__))
+        grad, = torch.autograd.grad(c.sum(), leaf)
+        return c.detach(), grad
+
+    for it in range(a.iters):
+        c, grad = rollout_cost(True)
+        costs[it].copy_(c)
+        model.backward(frame_grad=grad.to(torch.float32).contiguous(), input_grad=True, params=False, builtin_loss=False)
+        g = model.action_grad
+        if t0:
+            g[:t0].zero_()
+        adam(model, p, g, m, v, _adam_lr_t(a.lr, it + 1))
+        if b.low is not None:
+            free = p[t0:]
+            torch.maximum(free, b.low, out=free)
+            torch.minimum(free, b.high, out=free)
+    costs[a.iters].copy_(rollout_cost(False)[0])
+    return p, costs
