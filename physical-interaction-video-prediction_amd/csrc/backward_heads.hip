@@ -719,14 +719,12 @@ int cdna_kernels_bwd(const float* hidden5, const float* wt, const float* vpre, c
         if (rr != PIVP_OK) return rr;
     }
     hipLaunchKernelGGL(skinny_linear_bwd_x_kernel, dim3((K + 31) / 32, (B + 31) / 32), dim3(256), 0, s, wt, dv, dhidden5, B, K, accum_dx);
-    hipStream_t sw = s;      // the weight gradient needs dv only: on the fork's stream it runs beside the rest of the sweep
-    if (fork && fork->side) {
-        // `ready` sits behind skinny_linear_bwd_x too: one kernel later than strictly needed, and the side stream never reads dv early
-        if (hipEventRecord(fork->ready, s) != hipSuccess || hipStreamWaitEvent(fork->side, fork->ready, 0) != hipSuccess) return PIVP_ERR_LAUNCH;
-        sw = fork->side;
-    }
+    // the weight gradient needs dv only: on the fork's stream it runs beside the rest of the sweep
+    // (`ready` sits behind skinny_linear_bwd_x too: one kernel later than strictly needed, and the side stream never reads dv early)
+    hipStream_t sw;
+    if (fork_begin(fork, s, &sw) != PIVP_OK) return PIVP_ERR_LAUNCH;
     hipLaunchKernelGGL(skinny_linear_bwd_w_kernel, dim3((K + 7) / 8), dim3(256), 0, sw, hidden5, dv, dwt, B, K);
-    if (fork && fork->side && hipEventRecord(fork->done, fork->side) != hipSuccess) return PIVP_ERR_LAUNCH;
+    if (fork_end(fork) != PIVP_OK) return PIVP_ERR_LAUNCH;
     return PIVP_LAUNCH_STATUS();
 }
 
@@ -1275,11 +1273,8 @@ int enc0_bwd(const float* img, const float* w, const float* d, float* dw, float*
              hipStream_t s, const SideFork* fork, float* det_part) {
     PIVP_CHECK_ARG(img && w && d && dw && db && B > 0 && H > 0 && W > 0);
     PIVP_CHECK_ARG(!dimg || (H % 2 == 0 && W % 2 == 0));       // the parity-class data gradient: checked before anything is enqueued
-    hipStream_t sw = s;
-    if (fork && fork->side) {
-        if (hipEventRecord(fork->ready, s) != hipSuccess || hipStreamWaitEvent(fork->side, fork->ready, 0) != hipSuccess) return PIVP_ERR_LAUNCH;
-        sw = fork->side;
-    }
+    hipStream_t sw;
+    if (fork_begin(fork, s, &sw) != PIVP_OK) return PIVP_ERR_LAUNCH;
     const int total = B * (H / 2) * (W / 2);
     int blocks = (total + 63) / 64; if (blocks > 512) blocks = 512;
     hipLaunchKernelGGL(enc0_wgrad_kernel, dim3(blocks), dim3(256), 0, sw, img, d, dw, db, B, H, W, det_part);
@@ -1290,7 +1285,7 @@ int enc0_bwd(const float* img, const float* w, const float* d, float* dw, float*
         const int rr = det_rows_reduce(det_part, blocks, 1, sg, sw);
         if (rr != PIVP_OK) return rr;
     }
-    if (fork && fork->side && hipEventRecord(fork->done, fork->side) != hipSuccess) return PIVP_ERR_LAUNCH;
+    if (fork_end(fork) != PIVP_OK) return PIVP_ERR_LAUNCH;
     if (dimg) {
         const long tp = (long)B * (H / 2) * (W / 2);           // pixels per parity class, 64 per block
         hipLaunchKernelGGL(enc0_dgrad_kernel, dim3((unsigned)((tp + 63) / 64), 4), dim3(256), 0, s, d, w, dimg, dimg_accum, B, H, W);

@@ -314,19 +314,6 @@ int lstm_wgrad_reduce(int cx, int C, int has_h, float* part, float* dW, float* d
 }
 
 // ---- backward ----
-static int fork_begin(const SideFork* f, hipStream_t s, hipStream_t* sw) {
-    *sw = s;
-    if (!f || !f->side) return PIVP_OK;
-    if (hipEventRecord(f->ready, s) != hipSuccess || hipStreamWaitEvent(f->side, f->ready, 0) != hipSuccess) return PIVP_ERR_LAUNCH;
-    *sw = f->side;
-    return PIVP_OK;
-}
-static int fork_end(const SideFork* f) {
-    if (!f || !f->side) return PIVP_OK;
-    return hipEventRecord(f->done, f->side) == hipSuccess ? PIVP_OK : PIVP_ERR_LAUNCH;
-}
-
-
 int run_convlstm_backward(const ConvLstmBwdArgs& a, hipStream_t s) {
     const int B = a.B, H = a.H, W = a.W, cx = a.cx, C = a.C, det = a.det;
     const int M = B * H * W, cin = cx + C, N = 4 * C;

@@ -4,6 +4,8 @@
 // Value-initialised means every field zero / null; an operand form (Operand, pivp_kernels.h) then is F32.
 #pragma once
 #include "pivp_kernels.h"
+#include "side_lane.h"
+#include "sweep_schedule.h"
 
 namespace pivp {
 

@@ -103,6 +103,18 @@ struct SideFork {
     hipStream_t side;
     hipEvent_t ready, done;
 };
+// dY is final on s: *sw = where the weight-gradient kernels go (no fork: s itself); fork_end behind the last of them
+inline int fork_begin(const SideFork* f, hipStream_t s, hipStream_t* sw) {
+    *sw = s;
+    if (!f || !f->side) return PIVP_OK;
+    if (hipEventRecord(f->ready, s) != hipSuccess || hipStreamWaitEvent(f->side, f->ready, 0) != hipSuccess) return PIVP_ERR_LAUNCH;
+    *sw = f->side;
+    return PIVP_OK;
+}
+inline int fork_end(const SideFork* f) {
+    if (!f || !f->side) return PIVP_OK;
+    return hipEventRecord(f->done, f->side) == hipSuccess ? PIVP_OK : PIVP_ERR_LAUNCH;
+}
 
 struct WgradDesc {
     const float* x0; const float* x1;    // forward input sources (channel-concatenated), NHWC

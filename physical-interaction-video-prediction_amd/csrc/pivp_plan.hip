@@ -165,21 +165,12 @@ struct pivp_plan {
     std::vector<hipEvent_t> prof_ev;
     std::vector<int> prof_layer;
     size_t prof_used = 0;
-    // Weight gradients run on a second, lower-priority stream next to the backward sweep's critical path (SideFork, pivp_host.h):
-    // slots 0..6 = the ConvLSTMs, 7..11 = enc6, enc5, enc4, enc2, enc1.  Created on first use; PIVP_OPT_SIDE_STREAM = 0 keeps everything on
-    // the caller's stream.
-    static constexpr int NSLOT = 14;      // 12: enc0's weight gradient, 13: the motion head's Linear (cdna_kernels / stp_input)
     // pivp_plan_set_option (include/pivp_hip.h), by PIVP_OPT_*: SIDE_STREAM; FINISH_RIDER: the motion head's finisher rides behind enc5's tiles (0: inside
     // frame_head, as rounds 4-5); FUSE_ENC3, inference: enc3 + state predictor in enc2's epilogue (0: their own launch); LN_FOLD_TRAIN, training: the norms of
     // hidden2 / hidden4 applied (and written) by enc1 / enc2's launches (0: ln_apply launches); WGRAD_BATCH: timesteps per ConvLSTM weight-gradient launch
     // (tests, measurements), whatever the precision mode; 0 = the mode's own choice
     int opt[PIVP_OPT_COUNT] = {1, 1, 1, 1, 0};
-    bool side_failed = false;           // run-time state, not the option: the side stream could not be created, this plan's sweeps run on one stream
-    hipStream_t side = nullptr;
-    hipStream_t side_of(int) const { return side; }      // (a second side stream for the odd slots, round 3: fp32 no change, bf16 12.25 -> 12.05 ms, but with two
-                                                         // processes on one GPU the step went from 65 ms to 78 SECONDS -- the hardware queues oversubscribe)
-    hipEvent_t ev_ready[NSLOT][2] = {}, ev_done[NSLOT][2] = {};      // slots 7..11 (the stride-2 3x3 layers): by dY ring; 12, 13: by timestep parity (Grads::cat6, e0raw)
-    hipEvent_t ev_ring_done[7][2] = {};        // ConvLSTM slots: one `done` per dG ring (slots 0..6 of ev_done are unused)
+    SideLane lane;                             // the weight gradients' stream and its events (side_lane.h); a sweep reads it, only create / the destructor change it
     int wg_cap = 1;                            // dG ring slots per ring = min(T - 2, WG_BATCH_MAX), fixed when the workspace is laid out
     int wg_batch = 1;                          // timesteps per weight-gradient launch (<= wg_cap)
     const float* wg_x[7] = {}; const float* wg_h[7] = {};   // operands of the first timestep of the open batch
@@ -190,21 +181,10 @@ struct pivp_plan {
     int enc_cnt[5] = {};                                    // timesteps in each layer's open batch (enc6 only counts the steps a frame gradient reaches)
     const float* enc_x0[5] = {};                            // ... and the forward input of the batch's first timestep
     bool enc_started[5] = {};                               // the layer has launched in this sweep: its partial planes hold sums (before: stored, not added)
-    // the side stream(s) and every fork / join event, back to "never created" (the destructor; ensure_side's partial-failure path)
-    void destroy_side() {
-        for (int i = 0; i < 7; ++i) for (int r = 0; r < 2; ++r) if (ev_ring_done[i][r]) { (void)hipEventDestroy(ev_ring_done[i][r]); ev_ring_done[i][r] = nullptr; }
-        for (int i = 0; i < NSLOT; ++i) {
-            for (int r = 0; r < 2; ++r) {
-                if (ev_ready[i][r]) { (void)hipEventDestroy(ev_ready[i][r]); ev_ready[i][r] = nullptr; }
-                if (ev_done[i][r]) { (void)hipEventDestroy(ev_done[i][r]); ev_done[i][r] = nullptr; }
-            }
-        }
-        if (side) { (void)hipStreamDestroy(side); side = nullptr; }
-    }
     ~pivp_plan() {
-        if (side) (void)hipStreamSynchronize(side);      // a sweep that failed half-way may have left weight-gradient kernels in flight
+        lane.sync();
         for (hipEvent_t e : prof_ev) (void)hipEventDestroy(e);
-        destroy_side();
+        lane.destroy();
     }
 };
 
@@ -528,31 +508,6 @@ extern "C" int pivp_reset_state(pivp_plan_t* plan, void* stream) {
 }
 
 #define RC(call) do { int rc_ = (call); if (rc_ != PIVP_OK) return rc_; } while (0)
-
-// the plan's second stream (lowest priority: the critical path wins the CUs it asks for) and its fork / join events
-static int ensure_side(pivp_plan* plan) {
-    if (!plan->opt[PIVP_OPT_SIDE_STREAM] || plan->side_failed || plan->side) return PIVP_OK;
-    int least = 0, greatest = 0;
-    if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) least = 0;
-    if (hipStreamCreateWithPriority(&plan->side, hipStreamNonBlocking, least) != hipSuccess) {
-        plan->side = nullptr; plan->side_failed = true; (void)hipGetLastError();      // single-stream sweeps from here on
-        return PIVP_OK;
-    }
-    bool ok = true;
-    for (int i = 0; i < pivp_plan::NSLOT && ok; ++i)
-        for (int r = 0; r < 2 && ok; ++r)
-            ok = hipEventCreateWithFlags(&plan->ev_ready[i][r], hipEventDisableTiming) == hipSuccess &&
-                 hipEventCreateWithFlags(&plan->ev_done[i][r], hipEventDisableTiming) == hipSuccess;
-    for (int i = 0; i < 7 && ok; ++i)
-        for (int r = 0; r < 2 && ok; ++r)
-            ok = hipEventCreateWithFlags(&plan->ev_ring_done[i][r], hipEventDisableTiming) == hipSuccess;
-    if (!ok) {      // never leave `side` set beside null events: back to "no side stream", and this plan runs its sweeps on one stream
-        plan->destroy_side();
-        plan->side_failed = true;
-        (void)hipGetLastError();
-    }
-    return PIVP_OK;
-}
 
 // ------------------------------------------------------------------------------------------------------------
 // forward, one timestep (TM:659-731)
@@ -927,16 +882,11 @@ extern "C" int pivp_rollout_predict(pivp_plan_t* plan, const float* context_imag
 // backward through time (what loss.backward() does inside Chainer's optimizer.update, TM:950), all three heads.
 // Gradients are ACCUMULATED into the buffers registered with pivp_plan_set_grad (same layouts as the parameters).
 // ------------------------------------------------------------------------------------------------------------
-// side-stream slots whose weight gradients belong to gradient group g (pivp_plan::NSLOT numbering)
-static const int kGroupSlots[6][4] = {{7, 13, -1, -1}, {6, -1, -1, -1}, {8, 5, -1, -1}, {9, 4, -1, -1}, {10, 3, 2, -1}, {11, 1, 0, 12}};
-// make `stream` wait for the side stream's latest work of one slot (no side stream: nothing to do).  NB: a null hipStream_t is the
-// legacy default stream, a perfectly good stream to wait on -- never a "no stream" marker.
-static int wait_slot(pivp_plan* p, int sl, hipStream_t stream) {
-    if (!p->side) return PIVP_OK;
-    for (int r = 0; r < 2; ++r)
-        if (hipStreamWaitEvent(stream, sl >= 7 ? p->ev_done[sl][r] : p->ev_ring_done[sl][r], 0) != hipSuccess) return PIVP_ERR_LAUNCH;
-    return PIVP_OK;
-}
+// side-lane slots whose weight gradients belong to gradient group g (-1: none); a slot of the stride-2 range also names the layer whose partial sums
+// the group reduces
+static const int kGroupSlots[6][4] = {{SLOT_ENC + 0, SLOT_HEAD, -1, -1}, {SLOT_LSTM + 6, -1, -1, -1}, {SLOT_ENC + 1, SLOT_LSTM + 5, -1, -1},
+                                      {SLOT_ENC + 2, SLOT_LSTM + 4, -1, -1}, {SLOT_ENC + 3, SLOT_LSTM + 3, SLOT_LSTM + 2, -1},
+                                      {SLOT_ENC + 4, SLOT_LSTM + 1, SLOT_LSTM + 0, SLOT_ENC0_W}};
 // Wave priority of the main stream's kernels during this plan's calls (csrc/pivp_common.h): the device word is rewritten only when the wanted value
 // differs from what this process last wrote on the device.
 // The cache of what the device words hold is process-wide (the words are per device, not per plan): guarded by a mutex, marked unknown while the
@@ -967,15 +917,17 @@ extern "C" int pivp_plan_set_group_join(pivp_plan_t* plan, int join) {
 }
 extern "C" int pivp_plan_group_wait(pivp_plan_t* plan, int group, void* stream) {
     if (!plan || group < 0 || group >= 6) return PIVP_ERR_BADARG;
-    for (int k = 0; k < 4; ++k) if (kGroupSlots[group][k] >= 0) RC(wait_slot(plan, kGroupSlots[group][k], (hipStream_t)stream));
+    if (!plan->lane.live()) return PIVP_OK;      // no side stream: nothing to wait for
+    for (int k = 0; k < 4; ++k) if (kGroupSlots[group][k] >= 0) RC(plan->lane.wait_slot(kGroupSlots[group][k], (hipStream_t)stream));
     return PIVP_OK;
 }
 
-// wg_ring / wg_slot: where this step's gate gradients go in the ConvLSTMs' dG rings; wg_flush: this step closes its batch.
-// eg_ring / eg_slot / eg_flush: the same for the dY rings of the five stride-2 3x3 layers (Grads::cat6); eq_next: the ring slot step t + 1 used.
+// ss: this step's place in the dG / dY rings (sweep_schedule.h).  lane: where this sweep's weight gradients fork to; null = everything on s (the plan
+// has no side stream, or the sweep forms no parameter gradients)
 static int backward_step(pivp_plan* p, int t, const float* prev, bool prev_has_grad, const float* action, const float* state_prev,
-                         bool has_go, float* go, float* go_prev, bool last_step, int wg_ring, int wg_slot, bool wg_flush,
-                         int eg_ring, int eg_slot, bool eg_flush, int eq_next, hipStream_t s) {
+                         bool has_go, float* go, float* go_prev, bool last_step, const StepSlots& ss, const SideLane* lane, hipStream_t s) {
+    const int wg_ring = ss.wg_ring, wg_slot = ss.wg_slot, eg_ring = ss.eg_ring, eg_slot = ss.eg_slot, eq_next = ss.eq_next;
+    const bool wg_flush = ss.wg_flush, eg_flush = ss.eg_flush;
     const pivp_config_t& c = p->cfg;
     const int B = c.batch, H = c.height, W = c.width, HW = H * W;
     float* ws = p->ws;
@@ -992,7 +944,7 @@ static int backward_step(pivp_plan* p, int t, const float* prev, bool prev_has_g
     const int n2 = 32 * p->H2 * p->W2, n4 = 64 * p->H4 * p->W4, n8 = 128 * p->H8 * p->W8;
     float* lnpart = ws + g.lnpart;
     const Modes& md = p->mode;
-    // sweeps without parameter gradients (pivp_plan_set_sweep_mode): p->side is null for their duration, so no fork, join or side launch below happens;
+    // sweeps without parameter gradients (pivp_plan_set_sweep_mode): `lane` is null, so no fork, join or side launch below happens;
     // what is left to skip are the launches that form nothing but parameter gradients
     const bool params = (p->sweep_mode & PIVP_SWEEP_PARAMS) != 0;
     auto ln_finish = [&](int j) -> int {
@@ -1007,20 +959,20 @@ static int backward_step(pivp_plan* p, int t, const float* prev, bool prev_has_g
         if (t == 0) RC(ln_finish(j));       // the sweep's last timestep: the partial planes become the gradient
         return PIVP_OK;
     };
-    // weight-gradient slots (pivp_plan::NSLOT): join = the main stream waits for the slot's last weight-gradient kernels
+    // weight-gradient slots (side_lane.h): which of a slot's two events this step uses, its fork, and join = the main stream waits for the slot's last
+    // weight-gradient kernels on the buffer this step rewrites
+    auto ring_of = [&](int slot) { return slot < SLOT_ENC ? wg_ring : slot_is_ring(slot) ? eg_ring : par; };
     auto fork_of = [&](int slot, SideFork& f) -> const SideFork* {
-        if (!p->side) return nullptr;
-        const int r = slot >= 7 && slot < 12 ? eg_ring : par;
-        f.side = p->side_of(slot); f.ready = p->ev_ready[slot][r]; f.done = p->ev_done[slot][r];
+        if (!lane) return nullptr;
+        f = lane->fork(slot, ring_of(slot));
         return &f;
     };
     auto join = [&](int slot) -> int {
-        if (!p->side) return PIVP_OK;
-        if (slot >= 7 && slot < 12) {      // an enc layer's dY ring: only a batch's first step meets a slot the ring's previous launch (two batches ago) read
-            if (eg_slot) return PIVP_OK;
-            return hipStreamWaitEvent(s, p->ev_done[slot][eg_ring], 0) == hipSuccess ? PIVP_OK : PIVP_ERR_LAUNCH;
-        }
-        return hipStreamWaitEvent(s, p->ev_done[slot][par], 0) == hipSuccess ? PIVP_OK : PIVP_ERR_LAUNCH;   // this parity's last use: two timesteps ago (never recorded: returns at once)
+        if (!lane) return PIVP_OK;
+        // a dY ring: only a batch's first step meets a slot the ring's previous launch (two batches ago) read.  A parity buffer: its last use was two
+        // timesteps ago (never recorded: returns at once)
+        if (slot_is_ring(slot) && (slot < SLOT_ENC ? wg_slot : eg_slot)) return PIVP_OK;
+        return lane->wait_done(slot, ring_of(slot), s);
     };
     const long long slab_bytes = p->nslabs > 1 ? ((long long)p->slabs[1].cat7 - (long long)p->slabs[0].cat7) * 4 : 0;
     // LayerNorm behind ConvLSTM i (hidden<i+1>): one launch leaves the two sums per sample and the norm's partial parameter planes
@@ -1046,10 +998,8 @@ static int backward_step(pivp_plan* p, int t, const float* prev, bool prev_has_g
         const float* h_prev = Sp ? ws + Sp->h[i] : nullptr;
         float* const absmax_ring = ws + g.dg_absmax + (size_t)(i * 2 + wg_ring) * p->wg_cap * 72;      // dG's partial maxima, 72 floats per ring slot
         SideFork f;
-        if (wg_slot == 0) {     // a new batch: the ring's previous weight-gradient launch (two batches ago) must have read it
-            if (p->side && hipStreamWaitEvent(s, p->ev_ring_done[i][wg_ring], 0) != hipSuccess) return PIVP_ERR_LAUNCH;
-            p->wg_x[i] = x; p->wg_h[i] = h_prev;
-        }
+        RC(join(SLOT_LSTM + i));      // a new batch: the ring's previous weight-gradient launch (two batches ago) must have read it
+        if (wg_slot == 0) { p->wg_x[i] = x; p->wg_h[i] = h_prev; }
         ConvLstmBwdArgs a{};
         a.x = x; a.cx = L.cx; a.ldx = ldx; a.h_prev = h_prev; a.C = L.C; a.w = P(p, p->i_lstm_w[i]); a.gates = ws + S.gates[i];
         a.c_old = Sp ? ws + Sp->c[i] : ws + p->o_zero; a.c_new = ws + S.c[i];
@@ -1061,7 +1011,7 @@ static int backward_step(pivp_plan* p, int t, const float* prev, bool prev_has_g
         a.wt_ready = 1;
         a.operand = md.dgrad(m.W, B);      // (the L2-direct forms' two-image tiles do not fit an 8-wide map with an odd batch: the fp32 kernels take the cell)
         if (a.operand != Operand::F32) a.wt_bf16 = reinterpret_cast<unsigned short*>(ws + g.wtb_lstm[i]);
-        if (wg_flush) a.fork = fork_of(i, f);
+        if (wg_flush) a.fork = fork_of(SLOT_LSTM + i, f);
         a.ln = &lf[i];
         a.dx_only = t == 0 ? 1 : 0;      // t = 0: nobody reads d h_{-1}
         if (operand_needs_scale(md.precision)) a.dg_absmax = absmax_ring + (size_t)wg_slot * 72;
@@ -1071,7 +1021,7 @@ static int backward_step(pivp_plan* p, int t, const float* prev, bool prev_has_g
         if (!wg_flush || !params) return PIVP_OK;
         // weight + bias gradient of the whole batch: timestep j of it reads slab (first - j) and ring slot j; on the side stream it
         // starts as soon as this step's dG exists, next to this step's own data gradient
-        hipStream_t sw = p->side ? p->side_of(i) : s;
+        hipStream_t sw = lane ? lane->stream : s;
         const int cnt = wg_slot + 1;
         int bias_done = 0;
         WgradDesc d;
@@ -1102,8 +1052,7 @@ static int backward_step(pivp_plan* p, int t, const float* prev, bool prev_has_g
         if (!bias_done && p->det) return PIVP_ERR_STATE;      // (unreachable: see above)
         if (!bias_done)
             for (int j = 0; j < cnt; ++j) RC(bias_grad(ring + (size_t)j * dG1, N, N, B * m.H * m.W, G(p, p->i_lstm_b[i]), sw));
-        if (p->side && hipEventRecord(p->ev_ring_done[i][wg_ring], p->side_of(i)) != hipSuccess) return PIVP_ERR_LAUNCH;
-        return PIVP_OK;
+        return lane ? lane->record_done(SLOT_LSTM + i, wg_ring) : PIVP_OK;
     };
     const long px2 = (long)B * p->H2 * p->W2, px8 = (long)B * p->H8 * p->W8;
 
@@ -1126,10 +1075,9 @@ static int backward_step(pivp_plan* p, int t, const float* prev, bool prev_has_g
                          : k == 3 ? ws + g.e2 + ring0 * g.e2_sz : ws + g.cat6 + ring0 * g.cat6_sz + 64;
         const long long dy_step = 4LL * (long long)(k == 0 ? g.e6raw_sz : k == 1 ? g.din_sz[6] : k == 2 ? g.din_sz[5] : k == 3 ? g.e2_sz : g.cat6_sz);
         hipStream_t sw = s;
-        if (p->side) {
-            if (!forked && (hipEventRecord(p->ev_ready[7 + k][eg_ring], s) != hipSuccess ||
-                            hipStreamWaitEvent(p->side, p->ev_ready[7 + k][eg_ring], 0) != hipSuccess)) return PIVP_ERR_LAUNCH;
-            sw = p->side_of(7 + k);
+        if (lane) {
+            const SideFork f = lane->fork(SLOT_ENC + k, eg_ring);
+            if (forked) sw = f.side; else RC(fork_begin(&f, s, &sw));
         }
         const MapSize m = level_map(c, E.level);
         int bias_done = 0;
@@ -1142,7 +1090,7 @@ static int backward_step(pivp_plan* p, int t, const float* prev, bool prev_has_g
         if (!bias_done && p->det) return PIVP_ERR_STATE;      // (unreachable: set_deterministic admits only shapes wgrad3x3s2 serves, column sums included)
         if (!bias_done)
             for (int j = 0; j < cnt; ++j) RC(bias_grad(dy0 + (size_t)j * (dy_step / 4), E.ldy, E.c, B * d.Hy * d.Wy, G(p, p->i_enc_b[E.layer]), sw));
-        if (p->side && hipEventRecord(p->ev_done[7 + k][eg_ring], sw) != hipSuccess) return PIVP_ERR_LAUNCH;
+        if (lane) RC(lane->record_done(SLOT_ENC + k, eg_ring));
         p->enc_started[k] = true; p->enc_desc_valid[k] = true; p->enc_cnt[k] = 0;
         return PIVP_OK;
     };
@@ -1158,7 +1106,7 @@ static int backward_step(pivp_plan* p, int t, const float* prev, bool prev_has_g
         a.wt = ws + g.wt_enc[E.layer]; a.dx = dx; a.lddx = E.c; a.accum_dx = accum_dx;
         a.B = B; a.Hin = m.H; a.Win = m.W;
         a.wt_ready = 1;
-        if (eg_flush) a.fork = fork_of(7 + k, fe);
+        if (eg_flush) a.fork = fork_of(SLOT_ENC + k, fe);
         a.dy_add = dy_add; a.ld_add = ld_add;
         a.operand = md.enc_dgrad();
         RC(run_conv_backward(a, s));
@@ -1179,17 +1127,17 @@ static int backward_step(pivp_plan* p, int t, const float* prev, bool prev_has_g
         RC(mask_softmax_bwd(ws + S.logits, ws + g.dmk, B, HW, p->NP, s));
         RC(heads_bwd(ws + S.e6, P(p, p->i_masks_w), P(p, p->i_enc7_w), ws + g.dmk, ws + g.dz, ws + g.e6, G(p, p->i_masks_w),
                      G(p, p->i_masks_b), G(p, p->i_enc7_w), G(p, p->i_enc7_b), B, HW, p->NP, p->NE, s, p->det ? ws + g.det_heads : nullptr));
-        RC(join(13));      // d v (the kernel generator's weight gradient reads it)
+        RC(join(SLOT_HEAD));      // d v (the kernel generator's weight gradient reads it)
         if (c.model_type == PIVP_MODEL_CDNA)
             RC(cdna_kernels_bwd(ws + S.n5, P(p, p->i_head_w), ws + S.vpre, ws + g.dkpart, composite_bwd_tiles(H, W), ws + g.dv[par], ws + g.n5, 0,
-                                G(p, p->i_head_w), G(p, p->i_head_b), B, p->K5, c.num_masks, s, fork_of(13, fe), p->det ? ws + g.det_dv : nullptr));
+                                G(p, p->i_head_w), G(p, p->i_head_b), B, p->K5, c.num_masks, s, fork_of(SLOT_HEAD, fe), p->det ? ws + g.det_dv : nullptr));
         else if (c.model_type == PIVP_MODEL_STP)
             RC(stp_params_bwd(ws + S.n5, P(p, p->i_head_w), ws + S.vpre, P(p, p->i_head2_w), ws + g.dkpart, composite_bwd_tiles(H, W),
                               ws + g.dv[par], ws + g.n5, G(p, p->i_head_w), G(p, p->i_head_b), G(p, p->i_head2_w), G(p, p->i_head2_b),
                               B, p->K5, s, p->det ? ws + g.det_stp : nullptr));
         else if (hipMemsetAsync(ws + g.n5, 0, (size_t)px8 * 128 * 4, s) != hipSuccess) return PIVP_ERR_LAUNCH;   // DNA: no hidden5 head
         // group 6 (TM:601), reversed: norm_enc6 (+relu) <- enc6 deconv <- [hidden7 | enc0]
-        RC(join(7));       // d e6raw
+        RC(join(SLOT_ENC + 0));       // d e6raw
         RC(lnb(8, ws + g.e6, 64, ws + S.e6, 64, ws + S.e6raw, d_e6raw, 64 * HW, 64, 1));
         RC(encb(0, ws + S.cat7, d_e6raw, nullptr, ws + g.cat7, 0));
     } else {
@@ -1203,31 +1151,25 @@ static int backward_step(pivp_plan* p, int t, const float* prev, bool prev_has_g
     auto reduce_enc = [&](int k) -> int {
         if (!p->enc_desc_valid[k]) return PIVP_OK;
         p->enc_desc_valid[k] = false;
-        hipStream_t sw = p->side ? p->side_of(7 + k) : s;
-        RC(igemm_wgrad_reduce(p->enc_desc[k], sw));
-        if (p->side && hipEventRecord(p->ev_done[7 + k][eg_ring], sw) != hipSuccess) return PIVP_ERR_LAUNCH;      // (t = 0: behind this step's own launch, same ring)
-        return PIVP_OK;
+        RC(igemm_wgrad_reduce(p->enc_desc[k], lane ? lane->stream : s));
+        return lane ? lane->record_done(SLOT_ENC + k, eg_ring) : PIVP_OK;      // (t = 0: behind this step's own launch, same ring)
     };
     // t = 0 is the sweep's final timestep: a gradient group is final once the side stream's weight gradients of its layers are in too
     auto done = [&](int group) -> int {
-        if (!params) return PIVP_OK;      // nothing becomes final, nobody is told
-        if (t == 0 && !p->grad_cb) {       // no listener: still turn the group's partial sums into gradients
-            static const int encs[6][1] = {{0}, {-1}, {1}, {2}, {3}, {4}};
-            if (encs[group][0] >= 0) RC(reduce_enc(encs[group][0]));
-        }
-        if (t != 0 || !p->grad_cb) return PIVP_OK;
-        const int (&slots)[6][4] = kGroupSlots;
+        if (!params || t != 0) return PIVP_OK;      // nothing becomes final, nobody is told
         for (int k = 0; k < 4; ++k) {
-            const int sl = slots[group][k];
-            if (sl >= 7 && sl < 12) RC(reduce_enc(sl - 7));          // behind the conv's last weight-gradient launch, on the same stream
-            if (sl >= 0 && p->group_join) RC(wait_slot(p, sl, s));
+            const int sl = kGroupSlots[group][k];
+            if (sl < 0) continue;
+            // the group's partial sums become gradients, listener or not: behind the conv's last weight-gradient launch, on the same stream
+            if (slot_enc_layer(sl) >= 0) RC(reduce_enc(slot_enc_layer(sl)));
+            if (p->grad_cb && p->group_join && lane) RC(lane->wait_slot(sl, s));
         }
-        p->grad_cb(p->grad_cb_user, group);
+        if (p->grad_cb) p->grad_cb(p->grad_cb_user, group);
         return PIVP_OK;
     };
     RC(done(0));
     RC(lnb_cell(6, ws + g.cat7, 64, n2, 32));
-    RC(join(8));           // enc5's dY = the x part of lstm7's d_in: a ring slot (a batch's first step waits for the ring's previous weight-gradient launch)
+    RC(join(SLOT_ENC + 1));           // enc5's dY = the x part of lstm7's d_in: a ring slot (a batch's first step waits for the ring's previous weight-gradient launch)
     // The x columns of a cell's input gradient are the dY of the enc conv in front of the cell: its ReLU mask (enc5, enc4) or the second gradient path into
     // the same tensor (enc0: + enc6's concat part) is met in the data gradient's epilogue where that kernel has the hook and its grid is unsplit (the bf16 /
     // split-precision forms: 27 relu_mask / add_strided launches fewer per train step at B = 32); otherwise the separate pass runs as before.
@@ -1235,11 +1177,11 @@ static int backward_step(pivp_plan* p, int t, const float* prev, bool prev_has_g
     const EpSpec ep6{ws + S.e5, 96, 96, 1, &ep_ok6}, ep5{ws + S.e4, 128, 128, 1, &ep_ok5}, ep0{ws + g.cat7 + 32, 64, 32, 2, &ep_ok0};
     RC(lstmb(6, ws + S.e5, 96, &ep6));
     RC(done(1));
-    RC(join(11));          // enc1's dY lives in d cat6, which enc5's data gradient rewrites
+    RC(join(SLOT_ENC + 4));          // enc1's dY lives in d cat6, which enc5's data gradient rewrites
     // group 5 (TM:600): d e5 = x-part of lstm7's d_in (ReLU fused in enc5) <- enc5 deconv <- [hidden6 | enc1]
     RC(encb(1, ws + S.cat6, DIN(6, true), ep_ok6 ? nullptr : ws + S.e5, d_cat6, 0));
     RC(lnb_cell(5, d_cat6, 96, n4, 64));
-    RC(join(9));           // enc4's dY = the x part of lstm6's d_in, likewise
+    RC(join(SLOT_ENC + 2));           // enc4's dY = the x part of lstm6's d_in, likewise
     RC(lstmb(5, ws + S.e4, 128, &ep5));
     RC(done(2));
     // group 4 (TM:599): d e4 = x-part of lstm6's d_in <- enc4 deconv <- hidden5 (also read by the CDNA kernel generator)
@@ -1248,7 +1190,7 @@ static int backward_step(pivp_plan* p, int t, const float* prev, bool prev_has_g
     RC(lstmb(4, ws + S.e3, 64));
     RC(done(3));
     // group 3 (TM:598) + state predictor (TM:730): d e3 = x-part of lstm5's d_in (ld 192)
-    RC(join(10));          // d e2
+    RC(join(SLOT_ENC + 3));          // d e2
     RC(enc3_state_bwd(ws + S.e2, ws + S.e3, DIN(4, true), 192, action, state_prev, P(p, p->i_enc_w[3]), P(p, p->i_cs_w),
                       ws + g.dstate + (size_t)t * B * 5, d_e2, G(p, p->i_enc_w[3]), G(p, p->i_enc_b[3]), G(p, p->i_cs_w),
                       G(p, p->i_cs_b), t > 0 ? ws + g.dstate + (size_t)(t - 1) * B * 5 : ws + g.dstate + (size_t)(c.seq_len - 1) * B * 5,
@@ -1276,7 +1218,7 @@ static int backward_step(pivp_plan* p, int t, const float* prev, bool prev_has_g
     RC(lstmb(0, ws + S.cat7 + 32, 64, &ep0));
     if (!ep_ok0) RC(add_strided(ws + g.cat7 + 32, 64, DIN(0, true), 64, 32, px2, s));          // d enc0: from enc6's concat + from lstm1
     // group 0 (TM:595): norm_enc0 (+relu) <- enc0 conv <- frame
-    RC(join(12));          // d e0raw
+    RC(join(SLOT_ENC0_W));          // d e0raw
     if (!params) {      // enc0's weight gradient is a launch of its own: only the frame gradient of a feed-self step is left, and norm_enc0's dx feeds nothing else
         if (!prev_has_grad) return PIVP_OK;
         RC(lnb(0, ep_ok0 ? DIN(0, true) : ws + g.cat7 + 32, 64, ws + S.cat7 + 32, 64, ws + S.e0raw, ws + g.e0raw[par], n2, 32, 1));
@@ -1284,7 +1226,7 @@ static int backward_step(pivp_plan* p, int t, const float* prev, bool prev_has_g
     }
     RC(lnb(0, ep_ok0 ? DIN(0, true) : ws + g.cat7 + 32, 64, ws + S.cat7 + 32, 64, ws + S.e0raw, ws + g.e0raw[par], n2, 32, 1));
     RC(enc0_bwd(prev, P(p, p->i_enc_w[0]), ws + g.e0raw[par], G(p, p->i_enc_w[0]), G(p, p->i_enc_b[0]), prev_has_grad ? go_prev : nullptr, 1,
-                B, H, W, s, fork_of(12, fe), p->det ? ws + g.det_enc0 : nullptr));
+                B, H, W, s, fork_of(SLOT_ENC0_W, fe), p->det ? ws + g.det_enc0 : nullptr));
     RC(done(5));
     return PIVP_OK;
 }
@@ -1294,33 +1236,18 @@ static int rollout_backward_sweep(pivp_plan_t* plan, const float* images, const 
 extern "C" int pivp_rollout_backward(pivp_plan_t* plan, const float* images, const float* actions, const float* states,
                                      const unsigned char* gt_select, const float* gen_images, const float* gen_states, void* stream) {
     if (!plan) return PIVP_ERR_BADARG;
-    // A sweep without parameter gradients has nothing for the side stream: the plan has none while it runs, so nothing forks, nothing is joined below
-    // and no event of an earlier sweep is waited for (those sweeps joined their own work into the caller's stream before they returned)
-    const bool params = (plan->sweep_mode & PIVP_SWEEP_PARAMS) != 0;
-    hipStream_t const kept_side = plan->side;
-    if (!params) plan->side = nullptr;
     const int rc = rollout_backward_sweep(plan, images, actions, states, gt_select, gen_images, gen_states, stream);
-    if (!params) plan->side = kept_side;
-    if (!params) return rc;
+    // A sweep without parameter gradients forked nothing (rollout_backward_sweep): nothing is joined, and no event of an earlier sweep is waited for
+    // (those sweeps joined their own work into the caller's stream before they returned)
+    if (!(plan->sweep_mode & PIVP_SWEEP_PARAMS) || !plan->lane.live()) return rc;
     // The side stream's weight gradients are joined whatever the sweep returned: on success the caller's stream is made to wait for
     // them (what it enqueues next -- the all-reduce, Adam -- sees every gradient); after a failure half-way the host waits for both
     // streams, so nothing is still reading the workspace or writing gradients when the caller clears, reuses or frees them.
-    if (plan->side) {
-        hipStream_t s = (hipStream_t)stream;
-        bool joined = rc == PIVP_OK;
-        if (joined) {
-            for (int i = 7; i < pivp_plan::NSLOT && joined; ++i)
-                for (int r = 0; r < 2 && joined; ++r) joined = hipStreamWaitEvent(s, plan->ev_done[i][r], 0) == hipSuccess;
-            for (int i = 0; i < 7 && joined; ++i)
-                for (int r = 0; r < 2 && joined; ++r) joined = hipStreamWaitEvent(s, plan->ev_ring_done[i][r], 0) == hipSuccess;
-        }
-        if (!joined) {
-            (void)hipStreamSynchronize(plan->side);
-            (void)hipStreamSynchronize(s);
-            return rc != PIVP_OK ? rc : PIVP_ERR_LAUNCH;
-        }
-    }
-    return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (rc == PIVP_OK && plan->lane.join_all(s) == PIVP_OK) return PIVP_OK;
+    plan->lane.sync();
+    (void)hipStreamSynchronize(s);
+    return rc != PIVP_OK ? rc : PIVP_ERR_LAUNCH;
 }
 static int rollout_backward_sweep(pivp_plan_t* plan, const float* images, const float* actions, const float* states,
                                   const unsigned char* gt_select, const float* gen_images, const float* gen_states, void* stream) {
@@ -1340,7 +1267,9 @@ static int rollout_backward_sweep(pivp_plan_t* plan, const float* images, const 
     const float fscale = 2.0f / ((float)fr * (float)(T - ctx));              // d/d gen of mean-squared error / (T - ctx)
     const float sscale = 2.0f * 1e-4f / ((float)(B * 5) * (float)(T - ctx));
     const Modes& md = plan->mode;
-    if (params) RC(ensure_side(plan));
+    // the lane this sweep forks its weight gradients to, decided once: none when the sweep forms no parameter gradients, the option is off or creation failed
+    if (params && plan->opt[PIVP_OPT_SIDE_STREAM]) plan->lane.create();
+    const SideLane* const lane = params && plan->lane.live() ? &plan->lane : nullptr;
     RC(apply_main_prio(plan, s));
     {   // Timesteps per ConvLSTM weight-gradient launch (PIVP_OPT_WGRAD_BATCH overrides, 1..wg_cap).  fp32: 1 (batches arrive in bursts and
         // overlap the sweep worse: 29.9 / 30.3 ms for 1 / 2, profiles/r02).  bf16 mode: as many as the rings hold -- its 25-tap kernel
@@ -1407,24 +1336,13 @@ static int rollout_backward_sweep(pivp_plan_t* plan, const float* images, const 
         const bool next_loss = (t - 1) >= ctx - 1 && t >= 1;
         const float* prev = step_input(plan, t, images, gt_select, gen_images, fr);
         const float* st_prev = t == 0 ? states : gen_states + (size_t)(t - 1) * B * 5;
-        // the ConvLSTM weight gradients: batches of wg_batch timesteps counted from the top of the sweep; t = 0 on its own
-        // With deep batches (G > 2: the bf16 mode's 8) the LAST TWO batched timesteps (t = 2, 1) form a batch of their own: one batch of everything
-        // is launched at t = 1, when two timesteps of main-stream work are left for 1.4 ms of weight gradients to hide behind -- the sweep then ended with
-        // the main stream waiting ~0.2 ms per step for the side stream (profiles/r05/NOTES.md).
-        auto sched = [&](int G, int& b, int& slot, bool& flush) {
-            const int k = T - 2 - t, n = T - 2;
-            const int tail = (G > 2 && n > 2) ? 2 : 0, body = n - tail, nb_body = (body + G - 1) / G;
-            if (t == 0) { b = nb_body + (tail ? 1 : 0); slot = 0; flush = true; }
-            else if (k < body) { b = k / G; slot = k % G; flush = slot == G - 1 || k == body - 1; }
-            else { b = nb_body; slot = k - body; flush = k == n - 1; }
-        };
-        int wg_b, wg_slot, eg_b, eg_slot; bool wg_flush, eg_flush;
-        sched(plan->wg_batch, wg_b, wg_slot, wg_flush);
+        // the ConvLSTM weight gradients: batches of wg_batch timesteps (sweep_schedule.h)
+        const BatchSlot wg = batch_slot(T, t, plan->wg_batch);
         // (1 / 2 / 4 timesteps per launch instead of the rings' 8, r05_c23: config 3 11.63 / 11.24 / 11.22 ms against 11.10, fp32 train 28.08 / 27.90 / 27.67 against 27.41)
-        sched(plan->eg_cap, eg_b, eg_slot, eg_flush);      // the stride-2 3x3 layers' weight gradients: as many timesteps per launch as their rings hold, every mode
-        RC(backward_step(plan, t, prev, prev_has_grad && has_go, actions + (size_t)t * B * 5, st_prev, has_go, go, go_prev, last,
-                         wg_b & 1, wg_slot, wg_flush, eg_b & 1, eg_slot, eg_flush, eq_next, s));
-        eq_next = (eg_b & 1) * plan->eg_cap + eg_slot;
+        const BatchSlot eg = batch_slot(T, t, plan->eg_cap);      // the stride-2 3x3 layers' weight gradients: as many timesteps per launch as their rings hold, every mode
+        const StepSlots ss{wg.batch & 1, wg.slot, wg.flush, eg.batch & 1, eg.slot, eg.flush, eq_next};
+        RC(backward_step(plan, t, prev, prev_has_grad && has_go, actions + (size_t)t * B * 5, st_prev, has_go, go, go_prev, last, ss, lane, s));
+        eq_next = ss.eg_ring * plan->eg_cap + ss.eg_slot;
         has_go = next_loss || (prev_has_grad && has_go);
     }
     return PIVP_OK;      // the side stream is joined by the caller, pivp_rollout_backward, on every path
