@@ -265,6 +265,13 @@ int frame_seed_add(float* go, const float* seed, long n, hipStream_t s);
 int gather_batch(const void* frames, int frames_u8, const float* actions, const float* states, const int* index, int B, long long N, int T, int H,
                  int W, float* out_images, float* out_actions, float* out_states, hipStream_t s);
 
+// The recurrent state as one buffer (csrc/state.hip; include/pivp_state.h): fourteen segments (c, h of the seven cells), n floats per sample each.
+// state_copy: sample b < B_dst of every dst segment = sample index[b] (index null: b) of its src segment.  One launch, bit-exact, 64-bit offsets.
+constexpr int STATE_SEGMENTS = 14;
+struct StateSeg { const float* src; float* dst; long long n; };
+struct StateCopyArgs { StateSeg seg[STATE_SEGMENTS]; int first_run[STATE_SEGMENTS]; int pieces[STATE_SEGMENTS]; };   // the kernel's argument: seg + where each segment's runs start
+int state_copy(const StateSeg seg[STATE_SEGMENTS], const int* index, int B_dst, hipStream_t s);
+
 // One launch for the output side of a timestep (csrc/frame_head.hip): norm_enc6 + ReLU + the 1x1 heads + the motion head's finisher +
 // flat softmax + transform + compositing; bit-identical to heads_1x1 + cdna_kernels / stp_params + composite.
 struct FrameHeadArgs {

@@ -8,6 +8,7 @@
 #include "../../include/pivp_hip.h"
 #include "../../include/pivp_loss.h"
 #include "../../include/pivp_input_grad.h"
+#include "../../include/pivp_state.h"
 #include "pivp_host.h"
 
 using namespace pivp;
@@ -22,6 +23,15 @@ const LstmSpec kLstm[7] = {
     {"lstm1", 32, 32, 2}, {"lstm2", 32, 32, 2}, {"lstm3", 32, 64, 4}, {"lstm4", 64, 64, 4},
     {"lstm5", 64, 128, 8}, {"lstm6", 128, 64, 4}, {"lstm7", 96, 32, 2}};
 static MapSize lstm_map(const pivp_config_t& c, int i) { return level_map(c, kLstm[i].level); }   // cell i's (H, W)
+// The recurrent state as one buffer (include/pivp_state.h): segment g = 2 i is cell i's c, 2 i + 1 its h; floats per sample, and where the segment
+// starts in the state of a batch c.batch
+static_assert(STATE_SEGMENTS == PIVP_STATE_SEGMENTS && STATE_SEGMENTS == 2 * 7, "c and h of the seven cells");
+static long long state_seg_floats(const pivp_config_t& c, int g) { const MapSize m = lstm_map(c, g / 2); return (long long)m.H * m.W * kLstm[g / 2].C; }
+static size_t state_seg_offset(const pivp_config_t& c, int g) {
+    long long at = 0;
+    for (int k = 0; k < g; ++k) at += state_seg_floats(c, k);
+    return (size_t)at * c.batch;
+}
 // The five stride-2 3x3 layers in the order of their side-stream slots 7..11 and of Grads::wg_part: enc6, enc5, enc4 (transposed: anchors = their INPUT maps),
 // enc2, enc1 (convs).  c: channels in = out; ldx / ldo: pixel strides of the forward input / output (enc1 writes into cat6); ldy: of dY in the backward sweep
 // (a ring slot of its own, or the x columns of the next cell's input gradient); level: of the input map.
@@ -154,6 +164,10 @@ struct pivp_plan {
     const float* frame_seed = nullptr;   // pivp_plan_set_frame_grad: an additional d loss / d gen_images[ctx-1 .. T-2] for the sweep (null: the plan's own seed alone)
     float* in_dact = nullptr; float* in_dstate0 = nullptr;   // pivp_plan_set_input_grad: d loss / d actions [T-1][B][5] and d loss / d states[0] [B][5] (null: not wanted)
     int sweep_mode = 3;               // pivp_plan_set_sweep_mode: PIVP_SWEEP_PARAMS | PIVP_SWEEP_BUILTIN_LOSS (include/pivp_input_grad.h)
+    // pivp_plan_set_rollout_state (include/pivp_state.h): where the next rollouts read their initial (c, h) of the seven cells and leave their final ones
+    // (null: zeros / nowhere), and how many leading steps pivp_rollout_predict feeds from context_images (0: cfg.context_frames)
+    const float* state_in = nullptr; float* state_out = nullptr; int observed = 0;
+    bool last_carried = false;        // the last rollout started from state_in: the sweep's t = 0 forms without h do not describe it
     bool lstm_started[7] = {};        // deterministic sweeps: the cell's weight-gradient slots hold this sweep's sums (before: stored, not added)
     pivp_grad_group_cb grad_cb = nullptr; void* grad_cb_user = nullptr;   // gradient-group-final notifications (t = 0 sweep)
     int loss_nparts;
@@ -473,6 +487,44 @@ extern "C" int pivp_plan_set_input_grad(pivp_plan_t* plan, float* dactions, floa
     plan->in_dact = dactions; plan->in_dstate0 = dstate0;
     return PIVP_OK;
 }
+// include/pivp_state.h: the recurrent state across rollouts
+extern "C" int pivp_state_layout(const pivp_config_t* cfg, long long seg_floats_per_sample[PIVP_STATE_SEGMENTS], long long* floats_per_sample) {
+    if (!cfg || cfg->height < 16 || cfg->width < 16 || cfg->height % 8 || cfg->width % 8) return PIVP_ERR_BADARG;
+    long long total = 0;
+    for (int g = 0; g < PIVP_STATE_SEGMENTS; ++g) {
+        const long long n = state_seg_floats(*cfg, g);
+        if (seg_floats_per_sample) seg_floats_per_sample[g] = n;
+        total += n;
+    }
+    if (floats_per_sample) *floats_per_sample = total;
+    return PIVP_OK;
+}
+extern "C" int pivp_plan_set_rollout_state(pivp_plan_t* plan, const float* state_in, float* state_out, int observed) {
+    if (!plan || ((reinterpret_cast<uintptr_t>(state_in) | reinterpret_cast<uintptr_t>(state_out)) & 15)) return PIVP_ERR_BADARG;
+    if (observed < 0 || observed > plan->cfg.seq_len - 1) return PIVP_ERR_BADARG;
+    plan->state_in = state_in; plan->state_out = state_out; plan->observed = observed;
+    return PIVP_OK;
+}
+extern "C" int pivp_plan_get_rollout_state(const pivp_plan_t* plan, const float** state_in, float** state_out, int* observed) {
+    if (!plan) return PIVP_ERR_BADARG;
+    if (state_in) *state_in = plan->state_in;
+    if (state_out) *state_out = plan->state_out;
+    if (observed) *observed = plan->observed;
+    return PIVP_OK;
+}
+extern "C" int pivp_state_copy(const pivp_config_t* cfg, const float* src, int B_src, float* dst, int B_dst, const int* index, void* stream) {
+    if (!cfg || !src || !dst || B_src < 1 || B_dst < 1 || (!index && B_src != B_dst)) return PIVP_ERR_BADARG;
+    if (cfg->height < 16 || cfg->width < 16 || cfg->height % 8 || cfg->width % 8) return PIVP_ERR_BADARG;
+    if ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(index)) & 3) return PIVP_ERR_BADARG;
+    StateSeg seg[STATE_SEGMENTS];
+    long long at = 0;      // floats per sample in front of the segment: it starts at B * at on either side
+    for (int g = 0; g < STATE_SEGMENTS; ++g) {
+        const long long n = state_seg_floats(*cfg, g);
+        seg[g] = StateSeg{src + at * B_src, dst + at * B_dst, n};
+        at += n;
+    }
+    return state_copy(seg, index, B_dst, (hipStream_t)stream);
+}
 extern "C" int pivp_plan_set_sweep_mode(pivp_plan_t* plan, int flags) {
     if (!plan || flags < 0 || flags > (PIVP_SWEEP_PARAMS | PIVP_SWEEP_BUILTIN_LOSS)) return PIVP_ERR_BADARG;
     plan->sweep_mode = flags;
@@ -522,8 +574,11 @@ static int run_step(pivp_plan* p, int t, const float* prev, const float* action,
     float* lnp = ws + p->o_lnpart;
     const float eps = c.ln_eps;
     const bool train = c.keep_activations != 0;
-    auto hp = [&](int i) -> const float* { return Sp ? ws + Sp->h[i] : nullptr; };   // t = 0: h == 0, skipped
-    auto cp = [&](int i) { return Sp ? ws + Sp->c[i] : ws + p->o_zero; };
+    // t = 0: h == 0, skipped, and c from the zero buffer -- unless the rollout starts from a registered state (pivp_plan_set_rollout_state): then the
+    // ordinary two-operand launch on the caller's (c, h)
+    const float* const sin = t == 0 ? p->state_in : nullptr;
+    auto hp = [&](int i) -> const float* { return Sp ? ws + Sp->h[i] : sin ? sin + state_seg_offset(c, 2 * i + 1) : nullptr; };
+    auto cp = [&](int i) -> const float* { return Sp ? ws + Sp->c[i] : sin ? sin + state_seg_offset(c, 2 * i) : ws + p->o_zero; };
     const int ln_cap = ln_partial_cap(H * W);   // partial slots per sample in lnp (see the workspace carve)
     int np = 0;
     const Modes& md = p->mode;
@@ -542,7 +597,7 @@ static int run_step(pivp_plan* p, int t, const float* prev, const float* action,
                               cp(i), ws + S.c[i], ws + S.h[i], B, m.H, m.W, s, o);
         if (prof) {
             (void)hipEventRecord(p->prof_ev[p->prof_used + 1], s);
-            p->prof_layer[p->prof_used / 2] = i + (Sp ? 0 : 8);   // +8: first-step launch without the h half of K
+            p->prof_layer[p->prof_used / 2] = i + (hp(i) ? 0 : 8);   // +8: first-step launch without the h half of K
             p->prof_used += 2;
         }
         return rc;
@@ -800,6 +855,17 @@ static int rollout_prepare_packs(pivp_plan* plan, hipStream_t s) {
     return PIVP_OK;
 }
 
+// behind a rollout's last timestep: the last slab's (c, h) of the seven cells -> the registered state_out, ONE launch (csrc/state.hip)
+static int rollout_pack_state(pivp_plan* plan, hipStream_t s) {
+    if (!plan->state_out) return PIVP_OK;
+    const pivp_config_t& c = plan->cfg;
+    const Slab& S = plan->slabs[(c.seq_len - 2) % plan->nslabs];
+    StateSeg seg[STATE_SEGMENTS];
+    for (int g = 0; g < STATE_SEGMENTS; ++g)
+        seg[g] = StateSeg{plan->ws + (g % 2 ? S.h[g / 2] : S.c[g / 2]), plan->state_out + state_seg_offset(c, g), state_seg_floats(c, g)};
+    return state_copy(seg, nullptr, c.batch, s);
+}
+
 extern "C" int pivp_rollout_forward(pivp_plan_t* plan, const float* images, const float* actions, const float* states,
                                     const unsigned char* gt_select, float* gen_images, float* gen_states, float* results,
                                     void* stream) {
@@ -819,9 +885,11 @@ extern "C" int pivp_rollout_forward(pivp_plan_t* plan, const float* images, cons
         const float* st_prev = t == 0 ? states : gen_states + (size_t)(t - 1) * B * 5;   // TM:646, TM:730
         RC(run_step(plan, t, prev, actions + (size_t)t * B * 5, st_prev, gen_images + t * fr, gen_states + (size_t)t * B * 5, s));
     }
+    RC(rollout_pack_state(plan, s));
     plan->last_steps = T - 1;
     plan->last_sched = gt_select != nullptr;
     plan->last_predict = false;
+    plan->last_carried = plan->state_in != nullptr;
     // loss (TM:737-759): frames ctx..T-1 vs gen[ctx-1..T-2]
     const int nf = T - ctx;
     float* lp = plan->ws + plan->o_losspart;
@@ -847,7 +915,8 @@ extern "C" int pivp_rollout_predict(pivp_plan_t* plan, const float* context_imag
                                     float* gen_images, float* gen_states, float* track_out, void* stream) {
     if (!plan || !context_images || !actions || !state0 || !gen_images || !gen_states) return PIVP_ERR_BADARG;
     const pivp_config_t& c = plan->cfg;
-    const int B = c.batch, T = c.seq_len, ctx = c.context_frames, P = track_planes, f = track_frame;
+    // the leading steps fed from context_images: the configuration's, or what pivp_plan_set_rollout_state registered (include/pivp_state.h)
+    const int B = c.batch, T = c.seq_len, ctx = plan->observed > 0 ? plan->observed : c.context_frames, P = track_planes, f = track_frame;
     if (ctx < 1 || T - 1 < ctx) return PIVP_ERR_BADARG;
     if (track_in ? (P < 1 || P > 8 || !track_out || f < 0 || f > ctx - 1) : P != 0) return PIVP_ERR_BADARG;
     if (!plan->ws) return PIVP_ERR_STATE;
@@ -873,8 +942,10 @@ extern "C" int pivp_rollout_predict(pivp_plan_t* plan, const float* context_imag
     }
     plan->masks_every_step = false;
     if (rc != PIVP_OK) return rc;
+    RC(rollout_pack_state(plan, s));
     plan->last_steps = T - 1;
     plan->last_sched = false;
+    plan->last_carried = plan->state_in != nullptr;
     return PIVP_OK;
 }
 
@@ -1254,6 +1325,7 @@ static int rollout_backward_sweep(pivp_plan_t* plan, const float* images, const 
     if (!plan || !images || !actions || !states || !gen_images || !gen_states) return PIVP_ERR_BADARG;
     if (!plan->ws || !plan->has_grads || plan->last_steps != plan->cfg.seq_len - 1) return PIVP_ERR_STATE;
     if (plan->last_predict) return PIVP_ERR_STATE;      // pivp_rollout_predict keeps no loss to differentiate
+    if (plan->last_carried) return PIVP_ERR_STATE;      // the rollout started from a registered state: truncated BPTT across calls is not served (include/pivp_state.h)
     if ((gt_select != nullptr) != plan->last_sched) return PIVP_ERR_STATE;
     for (const ParamInfo& pi : plan->params) if (!pi.ptr || !pi.grad) return PIVP_ERR_STATE;
     const bool params = (plan->sweep_mode & PIVP_SWEEP_PARAMS) != 0, own_loss = (plan->sweep_mode & PIVP_SWEEP_BUILTIN_LOSS) != 0;

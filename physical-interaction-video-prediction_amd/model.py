@@ -24,6 +24,7 @@ import torch
 
 from . import _lib
 from . import checkpoint as ckpt
+from .state import RecurrentState, is_recurrent_state
 
 
 class _Config(object):
@@ -184,14 +185,21 @@ class Model(object):
     plan_options: a dict of the plan's A/B levers (include/pivp_hip.h, pivp_plan_set_option) with keys 'side_stream', 'finish_rider', 'fuse_enc3',
     'ln_fold_train' (0 / 1, default 1) and 'wgrad_batch' (0 .. 8 timesteps per ConvLSTM weight-gradient launch, default 0 = the precision mode's own
     choice).  An option the dict does not name takes its default from PIVP_SIDE_STREAM, PIVP_FINISH_RIDER, PIVP_FUSE_ENC3, PIVP_LN_FOLD_TRAIN or
-    PIVP_WGRAD_BATCH, read when a plan is made (`resolve_plan_options`); `effective_plan_options()` reads the current plan's values back."""
+    PIVP_WGRAD_BATCH, read when a plan is made (`resolve_plan_options`); `effective_plan_options()` reads the current plan's values back.
+
+    carry_state=True: the seven ConvLSTM (c, h) pairs live on between calls, as the reference's do until `reset_state()` (TM:230-232, 254-257): a call
+    continues from the state the last one left -- `__call__`, `evaluate` and `imagine` alike, whatever their T -- and `reset_state()` clears it.  The
+    model then owns one state buffer for its (B, H, W); a call at another batch or frame size while a state is carried raises ValueError (the
+    reference fails in F.concat).  `recurrent_state()` / `set_recurrent_state()` snapshot and restore it (state.RecurrentState).  `backward()` after a
+    call that started from a carried state raises: truncated back-propagation through time across calls is not served (include/pivp_state.h).
+    With the default False every call starts from zeros and nothing of this runs."""
 
     DETERMINISTIC_PRECISIONS = ('fp32', 'bf16', 'bf16x3')
 
     def __init__(self, num_masks, is_cdna=True, is_dna=False, is_stp=False, use_state=True,
                  scheduled_sampling_k=-1, num_frame_before_prediction=2, prefix=None,
                  device='cuda:0', ln_eps=1e-6, stp_border='clamp', keep_activations=False, precision='fp32', main_priority=None,
-                 deterministic=False, image_loss=None, plan_options=None):
+                 deterministic=False, image_loss=None, plan_options=None, carry_state=False):
         if is_cdna:                      # TM:531-542, precedence cdna > stp > dna
             self.model_type = 'CDNA'
         elif is_stp:
@@ -246,6 +254,11 @@ class Model(object):
         self._loss_grad = None         # ... and d extra / d gen_images[ctx-1:], when the call kept what backward() needs
         self.action_grad = None        # backward(input_grad=True): d loss / d actions[:T-1] (T-1, B, 5) and ...
         self.state_grad = None         # ... d loss / d states[0] (B, 5), device tensors
+        if not isinstance(carry_state, bool):
+            raise ValueError('carry_state must be a bool, not %r' % (carry_state,))
+        self.carry_state = carry_state
+        self._state = None             # carry_state: the RecurrentState the next call starts from (None: zeros, as after reset_state())
+        self._carried_start = False    # the last __call__ started from a carried state: backward() is not served
         check_plan_options(plan_options)
         self.plan_options = dict(plan_options or {})
         self.main_priority = main_priority     # None / False / True: include/pivp_hip.h, pivp_plan_set_main_priority
@@ -391,16 +404,19 @@ class Model(object):
             if self._grads is not None:
                 _lib.check(lib.pivp_plan_set_grad(plan.h, i, self._grads[name].data_ptr()), 'pivp_plan_set_grad(%s)' % name)
 
-    def _plan_for(self, B, T, H, W, keep_activations=None):
+    def _plan_for(self, B, T, H, W, keep_activations=None, observed=None):
         keep = self.keep_activations if keep_activations is None else bool(keep_activations)
-        key = (B, T, H, W, keep)
+        # a rollout told how many frames it observes (imagine(observed=...)) may be shorter than the configured context: its plan is then made with
+        # the context cut to T-1 -- the registration overrides it anyway -- and kept under a key of its own
+        ctx = self.num_frame_before_prediction if observed is None else min(self.num_frame_before_prediction, T - 1)
+        key = (B, T, H, W, keep) if ctx == self.num_frame_before_prediction else (B, T, H, W, keep, ctx)
         plan = self._plans.get(key)
         if plan is None:
             lib = self._require_gpu()
             cfg = _lib.PivpConfig(batch=B, seq_len=T, height=H, width=W, num_masks=self.num_masks,
                                   model_type={'CDNA': 0, 'STP': 1, 'DNA': 2}[self.model_type],
                                   use_state=1 if self.use_state else 0,
-                                  context_frames=self.num_frame_before_prediction,
+                                  context_frames=ctx,
                                   keep_activations=1 if keep else 0,
                                   ln_eps=self.ln_eps, stp_zero_border=1 if self.stp_border == 'zeros' else 0)
             plan = _Plan(lib, cfg)
@@ -442,9 +458,73 @@ class Model(object):
         with torch.cuda.device(self.device):
             _lib.check(plan.lib.pivp_reset_state(plan.h, self._stream()), 'pivp_reset_state')
 
+    # ---- the recurrent state across calls (carry_state=True; include/pivp_state.h) -----------------------------------------------------
+    def _check_carried_shape(self, B, H, W):
+        s = self._state
+        if self.carry_state and s is not None and (s.batch, s.hw) != (B, (H, W)):
+            raise ValueError('the model carries the recurrent state of batch %d at %dx%d frames, this call has batch %d at %dx%d: reset_state() first'
+                             % (s.batch, s.hw[0], s.hw[1], B, H, W))
+
+    @contextlib.contextmanager
+    def _carried(self, plan, B, H, W, advance=True, observed=0):
+        """Around ONE rollout of `plan`: registers where it reads its initial recurrent state (the carried one, if any) and leaves its final one (the
+        model's buffer, unless advance=False), and clears the registration behind it, as backward() does with its seed.  With carry_state=False and
+        no `observed` the library's setter is never called.  Yields whether the rollout starts from a carried state."""
+        if not self.carry_state and not observed:
+            yield False
+            return
+        cur = self._state if self.carry_state else None
+        out = None
+        if self.carry_state and advance:
+            out = cur if cur is not None else RecurrentState.empty(B, (H, W), self.device)
+        lib = plan.lib
+        try:
+            _lib.check(lib.pivp_plan_set_rollout_state(plan.h, cur.data.data_ptr() if cur is not None else None,
+                                                       out.data.data_ptr() if out is not None else None, int(observed)), 'pivp_plan_set_rollout_state')
+            yield cur is not None
+            if out is not None:
+                self._state = out      # (only behind a rollout that was enqueued whole)
+        finally:
+            lib.pivp_plan_set_rollout_state(plan.h, None, None, 0)
+
+    def recurrent_state(self):
+        """A snapshot (copy) of the carried recurrent state as a `RecurrentState`, or None when the next call starts from zeros (nothing was called
+        since `reset_state()`).  Needs carry_state=True."""
+        if not self.carry_state:
+            raise RuntimeError('recurrent_state() needs Model(..., carry_state=True): without it no state exists between calls')
+        return None if self._state is None else self._state.clone()
+
+    def set_recurrent_state(self, s):
+        """The next call starts from `s` (a `RecurrentState` on the model's device; it is copied, so later calls leave `s` itself untouched), or from
+        zeros with None.  Loss, PSNR and the other results of the last call stay."""
+        if not self.carry_state:
+            raise RuntimeError('set_recurrent_state() needs Model(..., carry_state=True)')
+        if s is None:
+            self._state = None
+            return
+        self._checked_state(s)
+        self._state = s.clone()
+
+    def _checked_state(self, s):
+        if not is_recurrent_state(s):
+            raise ValueError('a RecurrentState (or None) is expected, not %r' % (type(s).__name__,))
+        if self._hw is not None and s.hw != self._hw:
+            raise ValueError('the model was sized for %dx%d frames, the state is of %dx%d' % (self._hw + s.hw))
+        if s.data.device != self.device and not (s.data.is_cuda and self.device.type == 'cuda' and self.device.index is None):
+            raise ValueError('the state lives on %s, the model on %s' % (s.data.device, self.device))
+        return True
+
+    def _adopt_state(self, s):
+        """set_recurrent_state without the copy: the model takes `s` itself and later calls write into it."""
+        self._checked_state(s)
+        self._state = s
+
     # ---- reference surface ----------------------------------------------------------------
     def reset_state(self):
-        """TM:604-618: clears loss/PSNR/summaries/conv_res and the seven ConvLSTM (c, h) pairs."""
+        """TM:604-618: clears loss/PSNR/summaries/conv_res and the seven ConvLSTM (c, h) pairs: with carry_state=True the carried state is dropped and
+        the next call starts from zeros; without it every call does, and only the plan's zero buffer is cleared."""
+        self._state = None
+        self._carried_start = False
         self.loss = 0.0
         self.psnr_all = 0.0
         self._results = None
@@ -478,6 +558,10 @@ class Model(object):
         if actions is None or states is None:
             # the reference dereferences states[0] (TM:646) and fails the same way
             raise TypeError("'NoneType' object is not subscriptable")
+        if self._state is not None:      # a carried state of another batch or frame size: refused before any GPU work
+            shp = self._host_shape(images)
+            if len(shp) == 5:
+                self._check_carried_shape(shp[1], shp[3], shp[4])
         with torch.cuda.device(self.device) if torch.cuda.is_available() else contextlib.nullcontext():
             self._require_gpu()
             images = self._as_device(images, ())
@@ -507,9 +591,11 @@ class Model(object):
             if getattr(plan, 'packed_key', None) != pkey:
                 _lib.check(plan.lib.pivp_plan_params_changed(plan.h), 'pivp_plan_params_changed')
                 plan.packed_key = pkey
-            _lib.check(plan.lib.pivp_rollout_forward(plan.h, images.data_ptr(), actions.data_ptr(), states.data_ptr(),
-                                                     gt_ptr, gen.data_ptr(), gen_states.data_ptr(), results.data_ptr(),
-                                                     self._stream()), 'pivp_rollout_forward')
+            with self._carried(plan, B, H, W) as carried:
+                _lib.check(plan.lib.pivp_rollout_forward(plan.h, images.data_ptr(), actions.data_ptr(), states.data_ptr(),
+                                                         gt_ptr, gen.data_ptr(), gen_states.data_ptr(), results.data_ptr(),
+                                                         self._stream()), 'pivp_rollout_forward')
+            self._carried_start = carried
             self._inputs = (images, actions, states)   # keep alive until the stream has consumed them
             self._gen = gen
             self._gen_states = gen_states
@@ -572,17 +658,31 @@ class Model(object):
             return (len(a),) + tuple(a[0].shape)
         return tuple(np.shape(a))
 
-    def _check_imagine_args(self, context_images, actions, state, designated, designated_frame):
-        """-> (ctx, T, B, H, W, P, f); every complaint is a ValueError raised before the GPU or the library is needed."""
+    def _check_imagine_args(self, context_images, actions, state, designated, designated_frame, observed=None, advance=True):
+        """-> (ctx, T, B, H, W, P, f); every complaint is a ValueError raised before the GPU or the library is needed.  ctx: the number of observed
+        frames -- `observed`, or num_frame_before_prediction with None."""
         ctx = int(self.num_frame_before_prediction)
+        if observed is not None:
+            if isinstance(observed, bool) or not isinstance(observed, (int, np.integer)) or observed < 1:
+                raise ValueError('observed must be a positive integer (the number of frames in context_images) or None, not %r' % (observed,))
+            if not self.carry_state:
+                raise ValueError('observed is for continuing from a carried recurrent state: the model needs carry_state=True')
+            ctx = int(observed)
+        if not isinstance(advance, bool):
+            raise ValueError('advance must be a bool, not %r' % (advance,))
+        if not advance and not self.carry_state:
+            raise ValueError('advance=False leaves a carried recurrent state untouched: the model needs carry_state=True')
         si, sa, ss = self._host_shape(context_images), self._host_shape(actions), self._host_shape(state)
         if len(si) != 5 or si[2] != 3:
             raise ValueError('context_images must be time-major (ctx, B, 3, H, W), got shape %s' % (si,))
+        if observed is not None and si[0] != ctx:
+            raise ValueError('context_images holds %d frames, observed=%d was given' % (si[0], ctx))
         if ctx < 1 or si[0] != ctx:
             raise ValueError('context_images holds %d frames, the model was built with num_frame_before_prediction=%d' % (si[0], ctx))
         _, B, _, H, W = si
         if B < 1 or H < 1 or W < 1:
             raise ValueError('context_images is empty: shape %s' % (si,))
+        self._check_carried_shape(B, H, W)
         if len(sa) != 3 or sa[1] != B or sa[2] != 5:
             raise ValueError('actions must be (T-1, %d, 5), got shape %s' % (B, sa))
         if sa[0] < ctx:
@@ -609,7 +709,7 @@ class Model(object):
                 raise ValueError('designated_frame %d is not an observed frame (0 .. %d)' % (f, ctx - 1))
         return ctx, T, B, H, W, P, f
 
-    def imagine(self, context_images, actions, state, designated=None, designated_frame=None, normalize=False):
+    def imagine(self, context_images, actions, state, designated=None, designated_frame=None, normalize=False, observed=None, advance=True):
         """Open-loop prediction for planning: roll the model forward from `context_images` (ctx, B, 3, H, W) -- the observed frames --, the robot
         `state` (B, 5) of frame 0 and candidate `actions` (T-1, B, 5), feeding its own predictions back after the context.  No ground truth beyond
         the context, no loss: `loss` / `psnr_all` are left alone, `summaries` is [] and `backward()` raises until the model is called again.  Always
@@ -621,29 +721,41 @@ class Model(object):
         compositing masks are a linear map, applied here to the planes with the synthesised layer set to zero (painted-from-scratch pixels carry
         no mass) -- giving the predicted distribution of the designated pixels: `pixel_distrib` (T-1-f, B, P, H, W), entry i on predicted frame
         f+1+i, and `pixel_mass` (T-1-f, B, P), always the raw plane sums.  normalize=True divides each plane by its sum; the raw mass is
-        informative (how much of the pixel the model explains by motion), so this is optional."""
-        ctx, T, B, H, W, P, f = self._check_imagine_args(context_images, actions, state, designated, designated_frame)
+        informative (how much of the pixel the model explains by motion), so this is optional.
+
+        With carry_state=True the rollout starts from the carried recurrent state (zeros after `reset_state()`) and leaves its own behind.
+        observed: the number of frames in `context_images` when it is not num_frame_before_prediction (None: that one, as ever): 1 <= observed <= T-1,
+        and designated_frame <= observed-1 (default observed-1).  advance=False reads the carried state and leaves it untouched -- K what-ifs from one
+        belief.  To CONTINUE an open-loop prediction, pass the last predicted frame as the one observed frame and the last predicted robot state:
+
+            gen = model.imagine(context, actions[:n], state0)                                                  # steps 0 .. n-1
+            more = model.imagine(gen[-1:], actions[n:], model.gen_states[-1], observed=1)                      # steps n ..: torch.cat((gen, more)) is
+                                                                                                               # the one rollout over all of actions, bit for bit
+
+        (tracked planes continue the same way: designated=model.pixel_distrib[-1] of an un-normalised first call, on frame 0 of the second)."""
+        ctx, T, B, H, W, P, f = self._check_imagine_args(context_images, actions, state, designated, designated_frame, observed, advance)
         with torch.cuda.device(self.device) if torch.cuda.is_available() else contextlib.nullcontext():
             self._require_gpu()
             images = self._as_device(context_images, ())
             actions = self._as_device(actions, (5,))
             state = self._as_device(state, (5,))
             planes = self._as_device(designated, ()) if P else None
-            gen, track = self._rollout_predict(images, actions, state, planes, f)
+            gen, track = self._rollout_predict(images, actions, state, planes, f, observed=observed, advance=advance)
             if P:
                 mass = track.sum(dim=(3, 4))
                 self.pixel_mass = mass
                 self.pixel_distrib = track / mass[..., None, None] if normalize else track
         return gen
 
-    def _rollout_predict(self, images, actions, state, planes, f):
+    def _rollout_predict(self, images, actions, state, planes, f, observed=None, advance=True):
         """pivp_rollout_predict on checked, contiguous fp32 tensors of this device (the caller holds the device context): -> (frames, raw tracked
-        planes or None).  Sets what `imagine` sets, with `pixel_distrib` / `pixel_mass` cleared; no torch pass over the planes."""
+        planes or None).  Sets what `imagine` sets, with `pixel_distrib` / `pixel_mass` cleared; no torch pass over the planes.  observed / advance:
+        as `imagine`'s (carry_state=True only)."""
         _, B, _, H, W = images.shape
         T = actions.shape[0] + 1
         P = planes.shape[1] if planes is not None else 0
         self._ensure_params(H, W)
-        plan = self._plan_for(B, T, H, W, keep_activations=False)
+        plan = self._plan_for(B, T, H, W, keep_activations=False, observed=observed)
         self._active = plan
         gen = torch.empty((T - 1, B, 3, H, W), dtype=torch.float32, device=self.device)
         gen_states = torch.empty((T - 1, B, 5), dtype=torch.float32, device=self.device)
@@ -652,9 +764,10 @@ class Model(object):
         if getattr(plan, 'packed_key', None) != pkey:
             _lib.check(plan.lib.pivp_plan_params_changed(plan.h), 'pivp_plan_params_changed')
             plan.packed_key = pkey
-        _lib.check(plan.lib.pivp_rollout_predict(plan.h, images.data_ptr(), actions.data_ptr(), state.data_ptr(),
-                                                 planes.data_ptr() if P else None, P, f, gen.data_ptr(), gen_states.data_ptr(),
-                                                 track.data_ptr() if P else None, self._stream()), 'pivp_rollout_predict')
+        with self._carried(plan, B, H, W, advance=advance, observed=observed or 0):
+            _lib.check(plan.lib.pivp_rollout_predict(plan.h, images.data_ptr(), actions.data_ptr(), state.data_ptr(),
+                                                     planes.data_ptr() if P else None, P, f, gen.data_ptr(), gen_states.data_ptr(),
+                                                     track.data_ptr() if P else None, self._stream()), 'pivp_rollout_predict')
         self._inputs = (images, actions, state, planes)   # keep alive until the stream has consumed them
         self._gt_mask = None
         self._gen = gen
@@ -710,6 +823,9 @@ class Model(object):
             raise RuntimeError('call the model first')
         if not self.keep_activations:
             raise RuntimeError('backward() needs Model(..., keep_activations=True)')
+        if self._carried_start:
+            raise RuntimeError('the last call started from a carried recurrent state: truncated BPTT across calls is not served (reset_state() in front of '
+                               'every call that is back-propagated)')
         self._ensure_grads()
         images, actions, states = self._inputs
         gt_ptr = self._gt_mask.data_ptr() if self._gt_mask is not None else None

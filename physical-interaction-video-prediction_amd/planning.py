@@ -12,7 +12,11 @@ horizon is optimised (the MPC case).
 (`Model.backward(input_grad=True, params=False, builtin_loss=False)`, include/pivp_input_grad.h) and any torch cost of the predicted frames.
 
 `score_actions` scores a given set of candidates with one `imagine` and plain torch (`one_hot_planes`, `expected_position`,
-`expected_distance`); it is kept as it was for callers that bring their own optimiser."""
+`expected_distance`); it is kept as it was for callers that bring their own optimiser.
+
+Closed-loop control: `cem_plan(..., belief=)` and `score_actions(..., belief=)` start every candidate from ONE recurrent state (`state.RecurrentState`,
+what a `Model(carry_state=True)` holds after it has seen the frames so far) and the newest frame, instead of re-encoding the observed frames for every
+candidate in every iteration."""
 import contextlib
 import ctypes
 import math
@@ -23,6 +27,7 @@ import torch
 
 from . import _lib
 from .model import Model, using_config
+from .state import is_recurrent_state
 
 
 def one_hot_planes(coords, H, W, device=None):
@@ -77,8 +82,51 @@ def expected_distance(distrib, goal_rc):
     return (d * dist).sum(dim=(-2, -1))
 
 
-def score_actions(model, context_images, state, candidates, designated_rc, goal_rc):
+def _check_belief(model, belief, ctx_shape, past_actions=None):
+    """The complaints about `belief` (a batch-1 RecurrentState of the frames' size on a carry_state model, with ONE context frame and no past actions)."""
+    if not is_recurrent_state(belief):
+        raise ValueError('belief must be a RecurrentState (Model.recurrent_state()), not %r' % (type(belief).__name__,))
+    if not getattr(model, 'carry_state', False):
+        raise ValueError('belief: the model must be built with carry_state=True')
+    if belief.batch != 1:
+        raise ValueError('belief must be a batch-1 state (what the robot believes now), this one holds %d samples' % belief.batch)
+    if ctx_shape[0] != 1:
+        raise ValueError('with a belief, context_images is (1, 1, 3, H, W): the newest frame only (the belief holds the frames before it), got shape %s'
+                         % (ctx_shape,))
+    if belief.hw != tuple(ctx_shape[3:]):
+        raise ValueError('belief is of %dx%d frames, context_images of %dx%d' % (belief.hw + tuple(ctx_shape[3:])))
+    if past_actions is not None and _host_array(past_actions, 'past_actions').size:
+        raise ValueError('past_actions given with a belief: the belief has consumed the past steps, past_actions must be empty')
+
+
+@contextlib.contextmanager
+def _starting_from(model, state):
+    """Inside: the model's carried recurrent state is `state` (taken as it is, not copied); behind it: what it was before.  None: the rollouts inside
+    start from zeros and leave no state behind, on a carry_state model too -- planning from the context frames is the same with and without the flag."""
+    if state is None:
+        carries = getattr(model, 'carry_state', False)
+        if carries:
+            model.carry_state = False
+        try:
+            yield
+        finally:
+            if carries:
+                model.carry_state = True
+        return
+    kept = model._state
+    model._adopt_state(state)
+    try:
+        yield
+    finally:
+        model._state = kept
+
+
+def score_actions(model, context_images, state, candidates, designated_rc, goal_rc, belief=None):
     """Cost of K candidate action sequences for moving one designated pixel to a goal.
+
+    belief: a batch-1 `RecurrentState` (carry_state=True models).  context_images is then (1, 1, 3, H, W), the newest frame only; `state` its robot
+    state; candidates (K, horizon, 5).  The belief is expanded to K and every candidate runs `horizon` steps from it (`imagine(observed=1,
+    advance=False)`); the model's own carried state is what it was afterwards.  None: the path below, with the bits it always had.
 
     context_images (ctx, 1, 3, H, W), state (1, 5): what the robot sees now; candidates (K, T-1, 5); designated_rc, goal_rc: (row, col) on the
     last context frame.  The context is replicated K times and ONE `imagine` runs at batch K with normalised distributions; the cost of
@@ -86,6 +134,8 @@ def score_actions(model, context_images, state, candidates, designated_rc, goal_
     ctx_shape = Model._host_shape(context_images)
     if len(ctx_shape) != 5 or ctx_shape[1] != 1:
         raise ValueError('context_images must be (ctx, 1, 3, H, W), got shape %s' % (ctx_shape,))
+    if belief is not None:
+        _check_belief(model, belief, ctx_shape)
     cand_shape = Model._host_shape(candidates)
     if len(cand_shape) != 3 or cand_shape[2] != 5 or cand_shape[0] < 1:
         raise ValueError('candidates must be (K, T-1, 5), got shape %s' % (cand_shape,))
@@ -99,7 +149,11 @@ def score_actions(model, context_images, state, candidates, designated_rc, goal_
     actions = to_t(candidates).transpose(0, 1)
     rc = np.asarray(designated_rc).reshape(1, 1, 2)
     planes = one_hot_planes(np.broadcast_to(rc, (K, 1, 2)), H, W)
-    model.imagine(ctx_k, actions, state_k, designated=planes, normalize=True)
+    with _starting_from(model, belief.expand(K) if belief is not None else None):
+        if belief is not None:
+            model.imagine(ctx_k, actions, state_k, designated=planes, normalize=True, observed=1, advance=False)
+        else:
+            model.imagine(ctx_k, actions, state_k, designated=planes, normalize=True)
     return expected_distance(model.pixel_distrib[:, :, 0], goal_rc).sum(dim=0)
 
 
@@ -144,12 +198,15 @@ def _per_step(a, what, horizon, default):
 
 
 def _check_cem_args(model, context_images, state, designated_rc, goal_rc, horizon, past_actions, iterations, samples, elites, init_mean, init_std,
-                    min_std, alpha, action_low, action_high, step_weights, plane_weights, miss_cost, chunk, seed):
+                    min_std, alpha, action_low, action_high, step_weights, plane_weights, miss_cost, chunk, seed, belief=None):
     """Every complaint of `cem_plan` is a ValueError raised here, before the GPU or the library is needed.  -> the checked host-side values."""
     ctx = int(model.num_frame_before_prediction)
     si = Model._host_shape(context_images)
     if len(si) != 5 or si[1] != 1 or si[2] != 3:
         raise ValueError('context_images must be (ctx, 1, 3, H, W), got shape %s' % (si,))
+    if belief is not None:      # one observed frame on top of the belief, whatever the model's context length
+        _check_belief(model, belief, si, past_actions)
+        ctx = 1
     if ctx < 1 or si[0] != ctx:
         raise ValueError('context_images holds %d frames, the model was built with num_frame_before_prediction=%d' % (si[0], ctx))
     H, W = si[3:]
@@ -214,12 +271,13 @@ def _check_cem_args(model, context_images, state, designated_rc, goal_rc, horizo
         raise ValueError('seed must be an integer in [0, 2**64), not %r' % (seed,))
     return SimpleNamespace(ctx=ctx, H=H, W=W, P=P, K=int(samples), M=int(elites), chunk=int(chunk), horizon=int(horizon), iterations=int(iterations),
                            designated=designated, goals=goals, past=past, mean=mean, std=std, low=bounds[0], high=bounds[1],
-                           step_w=weights[0], plane_w=weights[1], miss_cost=float(miss_cost), min_std=float(min_std), alpha=float(alpha), seed=int(seed))
+                           step_w=weights[0], plane_w=weights[1], miss_cost=float(miss_cost), min_std=float(min_std), alpha=float(alpha), seed=int(seed),
+                           belief=belief)
 
 
 def cem_plan(model, context_images, state, designated_rc, goal_rc, horizon, past_actions=None, iterations=3, samples=32, elites=8, init_mean=None,
              init_std=1.0, min_std=1e-3, alpha=0.0, action_low=None, action_high=None, step_weights=None, plane_weights=None, miss_cost=None,
-             chunk=None, seed=0, trace=False):
+             chunk=None, seed=0, trace=False, belief=None):
     """Cross-entropy-method planning of `horizon` actions that move P designated pixels to their goals, entirely on the model's device.
 
     context_images (ctx, 1, 3, H, W), state (1, 5): what the robot sees now; designated_rc (P, 2) whole (row, col) pixels of the LAST context frame,
@@ -236,11 +294,17 @@ def cem_plan(model, context_images, state, designated_rc, goal_rc, horizon, past
     `best_cost_per_iteration` (iterations,); and, with trace=True, `trace`: per iteration a dict of `actions` (T-1, samples, 5), `cost` (samples,),
     `elites` (elites,) int32 best first, `mass` and `edist` (horizon, samples, P).  All device tensors; nothing is synchronised.
 
+    belief: a batch-1 `RecurrentState` -- what a `Model(carry_state=True)` holds after the frames observed so far (`model.recurrent_state()`).
+    context_images is then (1, 1, 3, H, W), the newest frame only, `state` its robot state, and past_actions must be empty: the belief has consumed the
+    past.  It is expanded ONCE to the chunk size, in front of the loop, and every rollout runs `horizon` steps from it (`imagine`'s observed=1,
+    advance=False) instead of ctx-1 + horizon from zeros; the model's own carried state is what it was afterwards.  None: the path and the bits of
+    a call without the argument.  (Belief and no-belief planning agree to rounding, not bit for bit: the observing steps ran at another batch size.)
+
     Side effect: the rollouts run on `model` as `imagine` does, so afterwards `model.gen_images` / `gen_states` hold the LAST rollout (the last
     chunk of the last iteration), `pixel_distrib` / `pixel_mass` are None and `backward()` raises until the model is called again.  With
     chunk < samples every rollout copies its slice of the action buffer and allocates its own frames, on the stream, without a host round trip."""
     a = _check_cem_args(model, context_images, state, designated_rc, goal_rc, horizon, past_actions, iterations, samples, elites, init_mean,
-                        init_std, min_std, alpha, action_low, action_high, step_weights, plane_weights, miss_cost, chunk, seed)
+                        init_std, min_std, alpha, action_low, action_high, step_weights, plane_weights, miss_cost, chunk, seed, belief)
     with torch.cuda.device(model.device) if torch.cuda.is_available() else contextlib.nullcontext():
         return _cem_iterate(model, a, _cem_upload(model, a, context_images, state), trace)
 
@@ -275,7 +339,11 @@ def _cem_upload(model, a, context_images, state):
     b.part = (new(Hh, C, P), new(Hh, C, P)) if C != K else None      # a chunk's moments: [Hh][C][P] is not a slice of [Hh][K][P]
     b.elite_idx = torch.empty((M,), dtype=torch.int32, device=dev)
     model._ensure_params(H, W)
-    model._plan_for(C, steps + 1, H, W, keep_activations=False)      # sized and bound here, not inside the loop
+    b.belief = None
+    if getattr(a, 'belief', None) is not None:      # ONE expansion to the chunk size (pivp_state_copy); every rollout of the loop reads it and leaves it untouched
+        model._checked_state(a.belief)
+        b.belief = a.belief.expand(C)
+    model._plan_for(C, steps + 1, H, W, keep_activations=False, observed=1 if b.belief is not None else None)      # sized and bound here, not inside the loop
     return b
 
 
@@ -293,28 +361,32 @@ def _cem_iterate(model, a, b, trace=False):
                                        b.elite_idx.data_ptr(), K, steps, t0, M, a.alpha, a.min_std, ctypes.c_ulonglong(a.seed), it, stream),
                    'pivp_cem_update')
 
+    belief = getattr(b, 'belief', None)
+    from_belief = dict(observed=1, advance=False) if belief is not None else {}
     records = []
-    for it in range(a.iterations):
-        update(it > 0, it)
-        if it > 0:
-            b.per_iter[it - 1:it].copy_(b.best_cost)
+    with _starting_from(model, belief):      # (the expanded belief, read by every rollout and written by none; None: every rollout from zeros)
+        for it in range(a.iterations):
+            update(it > 0, it)
+            if it > 0:
+                b.per_iter[it - 1:it].copy_(b.best_cost)
+                if trace:
+                    records[-1]['elites'] = b.elite_idx.clone()
+            for k0 in range(0, K, C):
+                _, track = model._rollout_predict(b.context, b.actions if C == K else b.actions[:, k0:k0 + C].contiguous(), b.state, b.planes, t0,
+                                                  **from_belief)
+                m_out, e_out = (b.mass, b.edist) if C == K else b.part
+                _lib.check(lib.pivp_plan_cost(track.data_ptr(), b.goals.data_ptr(), b.step_w.data_ptr(), b.plane_w.data_ptr(), a.miss_cost,
+                                              b.cost.data_ptr() + 4 * k0, m_out.data_ptr(), e_out.data_ptr(), Hh, C, P, a.H, a.W, stream),
+                           'pivp_plan_cost')
+                if C != K and trace:
+                    b.mass[:, k0:k0 + C].copy_(m_out)
+                    b.edist[:, k0:k0 + C].copy_(e_out)
             if trace:
-                records[-1]['elites'] = b.elite_idx.clone()
-        for k0 in range(0, K, C):
-            _, track = model._rollout_predict(b.context, b.actions if C == K else b.actions[:, k0:k0 + C].contiguous(), b.state, b.planes, t0)
-            m_out, e_out = (b.mass, b.edist) if C == K else b.part
-            _lib.check(lib.pivp_plan_cost(track.data_ptr(), b.goals.data_ptr(), b.step_w.data_ptr(), b.plane_w.data_ptr(), a.miss_cost,
-                                          b.cost.data_ptr() + 4 * k0, m_out.data_ptr(), e_out.data_ptr(), Hh, C, P, a.H, a.W, stream),
-                       'pivp_plan_cost')
-            if C != K and trace:
-                b.mass[:, k0:k0 + C].copy_(m_out)
-                b.edist[:, k0:k0 + C].copy_(e_out)
+                records.append(dict(actions=b.actions.clone(), cost=b.cost.clone(), mass=b.mass.clone(), edist=b.edist.clone()))
+        update(True, a.iterations)      # the last candidates count too: best_*, mean and std reflect them (the resampled rows are not used)
+        b.per_iter[a.iterations - 1:].copy_(b.best_cost)
         if trace:
-            records.append(dict(actions=b.actions.clone(), cost=b.cost.clone(), mass=b.mass.clone(), edist=b.edist.clone()))
-    update(True, a.iterations)      # the last candidates count too: best_*, mean and std reflect them (the resampled rows are not used)
-    b.per_iter[a.iterations - 1:].copy_(b.best_cost)
-    if trace:
-        records[-1]['elites'] = b.elite_idx.clone()
+            records[-1]['elites'] = b.elite_idx.clone()
     return SimpleNamespace(actions=b.best_actions, cost=b.best_cost[0], mean=b.mean, std=b.std, best_cost_per_iteration=b.per_iter,
                            trace=records if trace else None)
 
