@@ -9,9 +9,10 @@
  * with (H_i, W_i) = (H, W) / {2, 2, 4, 4, 8, 4, 2} and C_i = {32, 32, 64, 64, 128, 64, 32}: fourteen segments, exactly the values the plan's own
  * step buffers hold, in every precision mode (the cell state and output are fp32 in all of them).
  *
- * NOT served here: the backward sweep through a rollout that started from a given state (truncated back-propagation through time across the call
- * boundary).  The sweep's first timestep has forms of its own for "no recurrent input" -- in the batched weight gradients, in the deterministic slot
- * form and in the data-gradient-only kernel -- and giving them a carried h is a change of its own.  pivp_rollout_backward refuses (PIVP_ERR_STATE). */
+ * NOT served by this header alone: the backward sweep through a rollout that started from a given state (truncated back-propagation through time
+ * across the call boundary).  The sweep's first timestep has forms of its own for "no recurrent input" -- in the batched weight gradients, in the
+ * deterministic slot form and in the data-gradient-only kernel.  pivp_rollout_backward refuses such a rollout (PIVP_ERR_STATE) unless the sweep has been
+ * enabled for it through include/pivp_state_grad.h, which also gives the gradient with respect to the initial state and takes one on the final state. */
 #ifndef PIVP_STATE_H
 #define PIVP_STATE_H
 
@@ -39,7 +40,7 @@ int pivp_state_layout(const pivp_config_t* cfg, long long seg_floats_per_sample[
  *     <= observed - 1 (pivp_rollout_predict returns PIVP_ERR_BADARG otherwise).  This is how a prediction is continued: observed = 1, the one
  *     frame being the last predicted one.
  * The memory must stay valid until the rollouts that use it have run.  After a rollout that started from state_in != NULL, pivp_rollout_backward
- * returns PIVP_ERR_STATE (see the head of this file).
+ * returns PIVP_ERR_STATE unless enabled (see the head of this file); an enabled sweep reads state_in again, so it must then stay unmodified until that sweep.
  * PIVP_ERR_BADARG: a null plan, a pointer off 16 bytes, observed < 0 or > T-1. */
 int pivp_plan_set_rollout_state(pivp_plan_t* plan, const float* state_in, float* state_out, int observed);
 /* Reads the registration back; any output may be null.  PIVP_ERR_BADARG: a null plan. */

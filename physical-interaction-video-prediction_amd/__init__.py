@@ -20,6 +20,8 @@ from . import losses
 from .losses import ImageLoss, image_loss
 from . import state
 from .state import RecurrentState
+from . import tbptt
+from .tbptt import chunked_backward
 from .data import concat_examples
 from .optimizer import Adam, GradientClipping
 from .parallel import GradAllReduce, shard_batch
@@ -27,4 +29,5 @@ from .parallel import GradAllReduce, shard_batch
 __all__ = ['Model', 'config', 'using_config', 'reference_param_shapes', 'default_init',
            'scheduled_sampling_masks', 'save_npz', 'load_npz', 'to_internal', 'from_internal', 'concat_examples',
            'Adam', 'GradientClipping', 'GradAllReduce', 'shard_batch', 'save_optimizer_npz', 'load_optimizer_npz', 'dataset', 'planning',
-           'metrics', 'frame_metrics', 'StepCurves', 'DeviceDataset', 'DeviceBatcher', 'losses', 'ImageLoss', 'image_loss', 'state', 'RecurrentState']
+           'metrics', 'frame_metrics', 'StepCurves', 'DeviceDataset', 'DeviceBatcher', 'losses', 'ImageLoss', 'image_loss', 'state', 'RecurrentState',
+           'tbptt', 'chunked_backward']

@@ -1,6 +1,6 @@
 """ctypes binding of libpivp_hip.so (the C ABI declared in include/pivp_hip.h, the data feed's entry points of include/pivp_data.h and the
 guarded optimizer step's of include/pivp_optim.h, the image loss's and the seed hook of include/pivp_loss.h, the
-sweep's input gradients and mode of include/pivp_input_grad.h, the recurrent state across rollouts of include/pivp_state.h).
+sweep's input gradients and mode of include/pivp_input_grad.h, the recurrent state across rollouts of include/pivp_state.h, the gradients through it of include/pivp_state_grad.h).
 
 There is no CPU fallback: if the library is missing or fails to load, `load()` raises."""
 import ctypes
@@ -194,6 +194,14 @@ STATE_SIGNATURES = {
     'pivp_plan_get_rollout_state': (_i, [_vp, _c.POINTER(_vp), _c.POINTER(_vp), _c.POINTER(_i)]),
     'pivp_state_copy': (_i, [_c.POINTER(PivpConfig), _vp, _i, _vp, _i, _vp, _vp]),
 }
+# ... and every symbol include/pivp_state_grad.h declares (the sweep through a rollout that started from a state; d loss / d that state; the seed on the final one)
+_cells = _vp * 7               # a table of the seven cells' device pointers
+STATE_GRAD_SIGNATURES = {
+    'pivp_plan_set_state_grad': (_i, [_vp, _i, _vp, _vp]),
+    'pivp_plan_get_state_grad': (_i, [_vp, _c.POINTER(_i), _c.POINTER(_vp), _c.POINTER(_vp)]),
+    'pivp_state_grad_gather': (_i, [_c.POINTER(PivpConfig), _cells, _cells, _vp, _vp]),
+    'pivp_state_grad_scatter': (_i, [_c.POINTER(PivpConfig), _vp, _cells, _vp]),
+}
 STATE_SEGMENTS = 14            # PIVP_STATE_SEGMENTS (include/pivp_state.h)
 SWEEP_PARAMS, SWEEP_BUILTIN_LOSS = 1, 2      # PIVP_SWEEP_* (include/pivp_input_grad.h)
 OPTIM_MAX_SEGMENTS = 1024      # PIVP_OPTIM_MAX_SEGMENTS
@@ -213,7 +221,8 @@ def load():
             "or `python physical-interaction-video-prediction_amd/build.py`. There is no CPU fallback." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(DATA_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items())
-                              + list(LOSS_SIGNATURES.items()) + list(INPUT_GRAD_SIGNATURES.items()) + list(STATE_SIGNATURES.items())):
+                              + list(LOSS_SIGNATURES.items()) + list(INPUT_GRAD_SIGNATURES.items()) + list(STATE_SIGNATURES.items())
+                              + list(STATE_GRAD_SIGNATURES.items())):
         fn = getattr(lib, name)   # AttributeError if the ABI and the header drift apart
         fn.restype = res
         fn.argtypes = args
@@ -224,7 +233,7 @@ def load():
         shipped = _digest.source_digest()
     except OSError as e:      # a copied / installed package without csrc/ or the repo's include/: say what is missing instead of a bare open() error
         raise RuntimeError('cannot check libpivp_hip.so against its sources: %s is missing (the package needs csrc/*.hip, csrc/*.h and '
-                           '../include/pivp_hip.h, pivp_data.h, pivp_input_grad.h, pivp_loss.h, pivp_state.h and pivp_optim.h next to it; there is no CPU fallback)' % e.filename) from e
+                           '../include/pivp_hip.h, pivp_data.h, pivp_input_grad.h, pivp_loss.h, pivp_state.h, pivp_state_grad.h and pivp_optim.h next to it; there is no CPU fallback)' % e.filename) from e
     built = lib.pivp_build_digest().decode()
     if built != shipped:
         raise RuntimeError(

@@ -271,6 +271,12 @@ constexpr int STATE_SEGMENTS = 14;
 struct StateSeg { const float* src; float* dst; long long n; };
 struct StateCopyArgs { StateSeg seg[STATE_SEGMENTS]; int first_run[STATE_SEGMENTS]; int pieces[STATE_SEGMENTS]; };   // the kernel's argument: seg + where each segment's runs start
 int state_copy(const StateSeg seg[STATE_SEGMENTS], const int* index, int B_dst, hipStream_t s);
+// Gradients through the state (csrc/state_grad.hip; include/pivp_state_grad.h): up to fourteen ROW segments in one launch -- `rows` rows of C floats,
+// row strides lds / ldd floats (>= C) -- for the gather of d loss / d state_in (the h halves are strided columns of the cells' input gradients) and
+// the scatter of a seed's c segments.  Bit-exact, 64-bit offsets, every destination element written once.
+struct StateRowSeg { const float* src; float* dst; long long rows; int C, lds, ldd; };
+struct StateRowsArgs { StateRowSeg seg[STATE_SEGMENTS]; int first_run[STATE_SEGMENTS]; int vec[STATE_SEGMENTS]; int nseg; };   // vec: the segment takes 16-byte accesses
+int state_rows_copy(const StateRowSeg* seg, int nseg, hipStream_t s);
 
 // One launch for the output side of a timestep (csrc/frame_head.hip): norm_enc6 + ReLU + the 1x1 heads + the motion head's finisher +
 // flat softmax + transform + compositing; bit-identical to heads_1x1 + cdna_kernels / stp_params + composite.

@@ -9,6 +9,7 @@
 #include "../../include/pivp_loss.h"
 #include "../../include/pivp_input_grad.h"
 #include "../../include/pivp_state.h"
+#include "../../include/pivp_state_grad.h"
 #include "pivp_host.h"
 
 using namespace pivp;
@@ -168,6 +169,11 @@ struct pivp_plan {
     // (null: zeros / nowhere), and how many leading steps pivp_rollout_predict feeds from context_images (0: cfg.context_frames)
     const float* state_in = nullptr; float* state_out = nullptr; int observed = 0;
     bool last_carried = false;        // the last rollout started from state_in: the sweep's t = 0 forms without h do not describe it
+    // pivp_plan_set_state_grad (include/pivp_state_grad.h): the sweep serves a rollout that started from a state (sg_enable), is seeded with d / d (its final
+    // state) (sg_seed) and leaves d loss / d (its initial state) (sg_dstate_in); null / 0: none of it
+    int sg_enable = 0; const float* sg_seed = nullptr; float* sg_dstate_in = nullptr;
+    const float* fwd_state_in = nullptr;   // the state_in the last pivp_rollout_forward read (null: zeros): the sweep's t = 0 reads it again
+    bool fwd_state_lost = false;           // ... which that rollout overwrote with its own final state (state_in == state_out)
     bool lstm_started[7] = {};        // deterministic sweeps: the cell's weight-gradient slots hold this sweep's sums (before: stored, not added)
     pivp_grad_group_cb grad_cb = nullptr; void* grad_cb_user = nullptr;   // gradient-group-final notifications (t = 0 sweep)
     int loss_nparts;
@@ -524,6 +530,65 @@ extern "C" int pivp_state_copy(const pivp_config_t* cfg, const float* src, int B
         at += n;
     }
     return state_copy(seg, index, B_dst, (hipStream_t)stream);
+}
+// include/pivp_state_grad.h: gradients through the recurrent state
+static size_t state_bytes(const pivp_config_t& c) { return (state_seg_offset(c, STATE_SEGMENTS - 1) + (size_t)state_seg_floats(c, STATE_SEGMENTS - 1) * c.batch) * 4; }
+static bool ranges_overlap(const void* a, const void* b, size_t bytes) {
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return a && b && x < y + bytes && y < x + bytes;
+}
+extern "C" int pivp_plan_set_state_grad(pivp_plan_t* plan, int enable, const float* d_state_out, float* d_state_in) {
+    if (!plan || (enable != 0 && enable != 1)) return PIVP_ERR_BADARG;
+    if ((reinterpret_cast<uintptr_t>(d_state_out) | reinterpret_cast<uintptr_t>(d_state_in)) & 15) return PIVP_ERR_BADARG;
+    if (d_state_in && !enable) return PIVP_ERR_BADARG;
+    const size_t bytes = state_bytes(plan->cfg);
+    if (ranges_overlap(d_state_out, d_state_in, bytes)) return PIVP_ERR_BADARG;
+    if (plan->last_carried && ranges_overlap(d_state_in, plan->fwd_state_in, bytes)) return PIVP_ERR_BADARG;
+    plan->sg_enable = enable; plan->sg_seed = d_state_out; plan->sg_dstate_in = d_state_in;
+    return PIVP_OK;
+}
+extern "C" int pivp_plan_get_state_grad(const pivp_plan_t* plan, int* enable, const float** d_state_out, float** d_state_in) {
+    if (!plan) return PIVP_ERR_BADARG;
+    if (enable) *enable = plan->sg_enable;
+    if (d_state_out) *d_state_out = plan->sg_seed;
+    if (d_state_in) *d_state_in = plan->sg_dstate_in;
+    return PIVP_OK;
+}
+// d loss / d state_in <- the cells' d c (contiguous) and the h columns of their input gradients (rows of C floats at stride cx + C, cx floats in): ONE launch
+static int state_grad_gather(const pivp_config_t& c, const float* const dc[7], const float* const din[7], float* d_state_in, hipStream_t s) {
+    StateRowSeg seg[STATE_SEGMENTS];
+    for (int i = 0; i < 7; ++i) {
+        const MapSize m = lstm_map(c, i);
+        const long long rows = (long long)c.batch * m.H * m.W;
+        const int C = kLstm[i].C, cx = kLstm[i].cx;
+        seg[2 * i] = StateRowSeg{dc[i], d_state_in + state_seg_offset(c, 2 * i), rows, C, C, C};
+        seg[2 * i + 1] = StateRowSeg{din[i] + cx, d_state_in + state_seg_offset(c, 2 * i + 1), rows, C, cx + C, C};
+    }
+    return state_rows_copy(seg, STATE_SEGMENTS, s);
+}
+// the seed's seven c segments -> the cells' d c buffers: the same kernel the other way, ONE launch
+static int state_grad_scatter(const pivp_config_t& c, const float* d_state_out, float* const dc[7], hipStream_t s) {
+    StateRowSeg seg[7];
+    for (int i = 0; i < 7; ++i) {
+        const MapSize m = lstm_map(c, i);
+        seg[i] = StateRowSeg{d_state_out + state_seg_offset(c, 2 * i), dc[i], (long long)c.batch * m.H * m.W, kLstm[i].C, kLstm[i].C, kLstm[i].C};
+    }
+    return state_rows_copy(seg, 7, s);
+}
+static bool state_grad_cfg_ok(const pivp_config_t* cfg) {
+    return cfg && cfg->batch >= 1 && cfg->height >= 16 && cfg->width >= 16 && cfg->height % 8 == 0 && cfg->width % 8 == 0;
+}
+extern "C" int pivp_state_grad_gather(const pivp_config_t* cfg, const float* const dc[7], const float* const din[7], float* d_state_in, void* stream) {
+    if (!state_grad_cfg_ok(cfg) || !dc || !din || !d_state_in || (reinterpret_cast<uintptr_t>(d_state_in) & 3)) return PIVP_ERR_BADARG;
+    for (int i = 0; i < 7; ++i)
+        if (!dc[i] || !din[i] || ((reinterpret_cast<uintptr_t>(dc[i]) | reinterpret_cast<uintptr_t>(din[i])) & 3)) return PIVP_ERR_BADARG;
+    return state_grad_gather(*cfg, dc, din, d_state_in, (hipStream_t)stream);
+}
+extern "C" int pivp_state_grad_scatter(const pivp_config_t* cfg, const float* d_state_out, float* const dc[7], void* stream) {
+    if (!state_grad_cfg_ok(cfg) || !dc || !d_state_out || (reinterpret_cast<uintptr_t>(d_state_out) & 3)) return PIVP_ERR_BADARG;
+    for (int i = 0; i < 7; ++i)
+        if (!dc[i] || (reinterpret_cast<uintptr_t>(dc[i]) & 3)) return PIVP_ERR_BADARG;
+    return state_grad_scatter(*cfg, d_state_out, dc, (hipStream_t)stream);
 }
 extern "C" int pivp_plan_set_sweep_mode(pivp_plan_t* plan, int flags) {
     if (!plan || flags < 0 || flags > (PIVP_SWEEP_PARAMS | PIVP_SWEEP_BUILTIN_LOSS)) return PIVP_ERR_BADARG;
@@ -890,6 +955,9 @@ extern "C" int pivp_rollout_forward(pivp_plan_t* plan, const float* images, cons
     plan->last_sched = gt_select != nullptr;
     plan->last_predict = false;
     plan->last_carried = plan->state_in != nullptr;
+    // what the sweep's t = 0 will read again when it is enabled (pivp_plan_set_state_grad) -- gone if this rollout wrote its final state over it
+    plan->fwd_state_in = plan->state_in;
+    plan->fwd_state_lost = plan->state_in && plan->state_in == plan->state_out;
     // loss (TM:737-759): frames ctx..T-1 vs gen[ctx-1..T-2]
     const int nf = T - ctx;
     float* lp = plan->ws + plan->o_losspart;
@@ -1018,6 +1086,10 @@ static int backward_step(pivp_plan* p, int t, const float* prev, bool prev_has_g
     // sweeps without parameter gradients (pivp_plan_set_sweep_mode): `lane` is null, so no fork, join or side launch below happens;
     // what is left to skip are the launches that form nothing but parameter gradients
     const bool params = (p->sweep_mode & PIVP_SWEEP_PARAMS) != 0;
+    // a rollout that started from a state (the sweep has checked that it is served, include/pivp_state_grad.h): what t = 0 reads, and whether
+    // d loss / d (that state) is wanted behind it
+    const float* const sin = t == 0 && p->last_carried ? p->fwd_state_in : nullptr;
+    const bool want_dstate = sin && p->sg_dstate_in;
     auto ln_finish = [&](int j) -> int {
         if (!p->ln_touched[j] || !params) return PIVP_OK;
         p->ln_touched[j] = false;
@@ -1066,17 +1138,20 @@ static int backward_step(pivp_plan* p, int t, const float* prev, bool prev_has_g
         const int cin = L.cx + L.C, N = 4 * L.C;
         const size_t dG1 = (size_t)B * m.H * m.W * N;                      // floats of one timestep's dG
         float* ring = ws + g.dG[i] + (size_t)wg_ring * p->wg_cap * dG1;
-        const float* h_prev = Sp ? ws + Sp->h[i] : nullptr;
+        // t = 0: no recurrent input and c_{-1} = 0 -- unless the rollout started from a state (sin: the one it read, a constant of this sweep)
+        const float* h_prev = Sp ? ws + Sp->h[i] : sin ? sin + state_seg_offset(c, 2 * i + 1) : nullptr;
         float* const absmax_ring = ws + g.dg_absmax + (size_t)(i * 2 + wg_ring) * p->wg_cap * 72;      // dG's partial maxima, 72 floats per ring slot
         SideFork f;
         RC(join(SLOT_LSTM + i));      // a new batch: the ring's previous weight-gradient launch (two batches ago) must have read it
         if (wg_slot == 0) { p->wg_x[i] = x; p->wg_h[i] = h_prev; }
         ConvLstmBwdArgs a{};
         a.x = x; a.cx = L.cx; a.ldx = ldx; a.h_prev = h_prev; a.C = L.C; a.w = P(p, p->i_lstm_w[i]); a.gates = ws + S.gates[i];
-        a.c_old = Sp ? ws + Sp->c[i] : ws + p->o_zero; a.c_new = ws + S.c[i];
+        a.c_old = Sp ? ws + Sp->c[i] : sin ? sin + state_seg_offset(c, 2 * i) : ws + p->o_zero; a.c_new = ws + S.c[i];
         a.lda = L.C;      // (dh_a = null: formed from the norm behind the cell, a.ln)
-        if (!last_step) { a.dh_b = DIN(i, false) + L.cx; a.dc_valid = 1; }
         a.ldb = cin; a.dc = ws + g.dc[i];
+        if (!last_step) { a.dh_b = DIN(i, false) + L.cx; a.dc_valid = 1; }
+        // the sweep's first visited step with a seed (pivp_plan_set_state_grad): d h of the final state read in place, d c scattered into g.dc in front of the sweep
+        else if (p->sg_seed) { a.dh_b = p->sg_seed + state_seg_offset(c, 2 * i + 1); a.ldb = L.C; a.dc_valid = 1; }
         a.dG = ring + (size_t)wg_slot * dG1; a.wt = ws + g.wt_lstm[i]; a.d_in = DIN(i, true);
         a.B = B; a.H = m.H; a.W = m.W;      // dW = null: the weight gradient is batched below; only the fork's `ready` (behind the gate math) is used
         a.wt_ready = 1;
@@ -1084,7 +1159,7 @@ static int backward_step(pivp_plan* p, int t, const float* prev, bool prev_has_g
         if (a.operand != Operand::F32) a.wt_bf16 = reinterpret_cast<unsigned short*>(ws + g.wtb_lstm[i]);
         if (wg_flush) a.fork = fork_of(SLOT_LSTM + i, f);
         a.ln = &lf[i];
-        a.dx_only = t == 0 ? 1 : 0;      // t = 0: nobody reads d h_{-1}
+        a.dx_only = t == 0 && !want_dstate ? 1 : 0;      // t = 0: nobody reads d h_{-1} -- unless d loss / d state_in is wanted
         if (operand_needs_scale(md.precision)) a.dg_absmax = absmax_ring + (size_t)wg_slot * 72;
         a.ep = ep; a.det = p->det;
         RC(run_convlstm_backward(a, s));
@@ -1101,13 +1176,14 @@ static int backward_step(pivp_plan* p, int t, const float* prev, bool prev_has_g
         d.tcount = cnt; d.ts_x0 = -slab_bytes; d.ts_x1 = -slab_bytes; d.ts_dy = (long long)dG1 * 4;
         if (p->det) {
             // deterministic sweeps: the fp32 slot form (wgrad5x5p) in every precision mode -- each launch adds into the cell's slots (the sweep's first
-            // stores), the slots are summed in a fixed order once: t = 0 has no h operand and cuts the slots another way, so the batches with h are
-            // reduced in front of it and its own launch behind it
+            // stores), the slots are summed in a fixed order once: a t = 0 without h operand cuts the slots another way, so the batches with h are
+            // reduced in front of it and its own launch behind it.  After a start from a state t = 0 has the K of the other batches and simply joins them.
             // (the slot form takes every shape pivp_plan_set_deterministic admits, and it sums the columns of dG itself: bias_done is always set)
             float* part = ws + g.lstm_part[i];
-            if (t == 0 && p->lstm_started[i])
+            const bool cut = t == 0 && !p->wg_h[i];
+            if (cut && p->lstm_started[i])
                 RC(lstm_wgrad_reduce(L.cx, L.C, 1, part, G(p, p->i_lstm_w[i]), G(p, p->i_lstm_b[i]), B, m.H, m.W, sw, 0, DET_SLOT_J));
-            d.part = part; d.part_overwrite = (t == 0 || !p->lstm_started[i]) ? 1 : 0;
+            d.part = part; d.part_overwrite = (cut || !p->lstm_started[i]) ? 1 : 0;
             d.slot_j = DET_SLOT_J;
             RC(run_wgrad(d, sw, &bias_done, Operand::F32));
             if (t == 0)
@@ -1288,6 +1364,11 @@ static int backward_step(pivp_plan* p, int t, const float* prev, bool prev_has_g
     RC(lnb_cell(0, DIN(1, true), 64, n2, 32));
     RC(lstmb(0, ws + S.cat7 + 32, 64, &ep0));
     if (!ep_ok0) RC(add_strided(ws + g.cat7 + 32, 64, DIN(0, true), 64, 32, px2, s));          // d enc0: from enc6's concat + from lstm1
+    if (want_dstate) {      // every cell's gate backward and data gradient of t = 0 is enqueued: d c_{-1} sits in g.dc, d h_{-1} in the h columns of this step's d_in
+        const float* dcs[7]; const float* dins[7];
+        for (int i = 0; i < 7; ++i) { dcs[i] = ws + g.dc[i]; dins[i] = DIN(i, true); }
+        RC(state_grad_gather(c, dcs, dins, p->sg_dstate_in, s));
+    }
     // group 0 (TM:595): norm_enc0 (+relu) <- enc0 conv <- frame
     RC(join(SLOT_ENC0_W));          // d e0raw
     if (!params) {      // enc0's weight gradient is a launch of its own: only the frame gradient of a feed-self step is left, and norm_enc0's dx feeds nothing else
@@ -1325,11 +1406,14 @@ static int rollout_backward_sweep(pivp_plan_t* plan, const float* images, const 
     if (!plan || !images || !actions || !states || !gen_images || !gen_states) return PIVP_ERR_BADARG;
     if (!plan->ws || !plan->has_grads || plan->last_steps != plan->cfg.seq_len - 1) return PIVP_ERR_STATE;
     if (plan->last_predict) return PIVP_ERR_STATE;      // pivp_rollout_predict keeps no loss to differentiate
-    if (plan->last_carried) return PIVP_ERR_STATE;      // the rollout started from a registered state: truncated BPTT across calls is not served (include/pivp_state.h)
+    // the rollout started from a registered state: served only when enabled (include/pivp_state_grad.h), and only while that state still exists
+    if (plan->last_carried && (!plan->sg_enable || plan->fwd_state_lost)) return PIVP_ERR_STATE;
+    if (plan->sg_dstate_in && !(plan->sg_enable && plan->last_carried)) return PIVP_ERR_STATE;      // d loss / d (a state the rollout did not start from)
+    if (plan->last_carried && ranges_overlap(plan->sg_dstate_in, plan->fwd_state_in, state_bytes(plan->cfg))) return PIVP_ERR_STATE;
     if ((gt_select != nullptr) != plan->last_sched) return PIVP_ERR_STATE;
     for (const ParamInfo& pi : plan->params) if (!pi.ptr || !pi.grad) return PIVP_ERR_STATE;
     const bool params = (plan->sweep_mode & PIVP_SWEEP_PARAMS) != 0, own_loss = (plan->sweep_mode & PIVP_SWEEP_BUILTIN_LOSS) != 0;
-    if (!own_loss && !plan->frame_seed) return PIVP_ERR_STATE;      // nothing to differentiate
+    if (!own_loss && !plan->frame_seed && !plan->sg_seed) return PIVP_ERR_STATE;      // nothing to differentiate
     hipStream_t s = (hipStream_t)stream;
     const pivp_config_t& c = plan->cfg;
     const int B = c.batch, T = c.seq_len, ctx = c.context_frames;
@@ -1396,6 +1480,11 @@ static int rollout_backward_sweep(pivp_plan_t* plan, const float* images, const 
             RC(pack_lstm_bf16(ws + g.wt_lstm[i], reinterpret_cast<unsigned short*>(ws + g.wtb_lstm[i]), 4 * kLstm[i].C, cin, s, md.precision,
                               conv5x5_bf16_rows(cin), 1));
         }
+    if (plan->sg_seed) {      // the seed's c segments start every cell's d c (its h segments are read in place by the first visited step's gate backward)
+        float* dcs[7];
+        for (int i = 0; i < 7; ++i) dcs[i] = ws + g.dc[i];
+        RC(state_grad_scatter(c, plan->sg_seed, dcs, s));
+    }
     bool has_go = false;
     int eq_next = 0;      // the enc dY ring slot of step t + 1 (unused at t = T - 2)
     for (int t = T - 2; t >= 0; --t) {

@@ -191,15 +191,21 @@ class Model(object):
     continues from the state the last one left -- `__call__`, `evaluate` and `imagine` alike, whatever their T -- and `reset_state()` clears it.  The
     model then owns one state buffer for its (B, H, W); a call at another batch or frame size while a state is carried raises ValueError (the
     reference fails in F.concat).  `recurrent_state()` / `set_recurrent_state()` snapshot and restore it (state.RecurrentState).  `backward()` after a
-    call that started from a carried state raises: truncated back-propagation through time across calls is not served (include/pivp_state.h).
-    With the default False every call starts from zeros and nothing of this runs."""
+    call that started from a carried state raises unless the model was built with state_backward=True (below).
+    With the default False every call starts from zeros and nothing of this runs.
+
+    state_backward=True (needs carry_state=True and keep_activations=True): `backward()` serves a call that started from a carried state, with that
+    state as a constant -- truncated back-propagation through time across calls (include/pivp_state_grad.h).  `backward(initial_state_grad=True)`
+    also leaves d loss / d (that state) in `model.initial_state_grad`, and `backward(final_state_grad=rs)` seeds the sweep with d (a later loss) /
+    d (the state the call left): chained over consecutive windows that is the exact gradient in the memory of one window
+    (`pivp_amd.chunked_backward`).  The model then alternates two state buffers instead of advancing one in place -- same frames, same states."""
 
     DETERMINISTIC_PRECISIONS = ('fp32', 'bf16', 'bf16x3')
 
     def __init__(self, num_masks, is_cdna=True, is_dna=False, is_stp=False, use_state=True,
                  scheduled_sampling_k=-1, num_frame_before_prediction=2, prefix=None,
                  device='cuda:0', ln_eps=1e-6, stp_border='clamp', keep_activations=False, precision='fp32', main_priority=None,
-                 deterministic=False, image_loss=None, plan_options=None, carry_state=False):
+                 deterministic=False, image_loss=None, plan_options=None, state_backward=False, carry_state=False):
         if is_cdna:                      # TM:531-542, precedence cdna > stp > dna
             self.model_type = 'CDNA'
         elif is_stp:
@@ -258,7 +264,17 @@ class Model(object):
             raise ValueError('carry_state must be a bool, not %r' % (carry_state,))
         self.carry_state = carry_state
         self._state = None             # carry_state: the RecurrentState the next call starts from (None: zeros, as after reset_state())
-        self._carried_start = False    # the last __call__ started from a carried state: backward() is not served
+        self._carried_start = False    # the last __call__ started from a carried state: backward() needs state_backward=True
+        # state_backward: backward() also serves a call that started from a carried state (include/pivp_state_grad.h).  The sweep reads that state
+        # again, so the model no longer advances its state in place: it alternates two buffers, and the one a call started from is intact until the next call
+        if not isinstance(state_backward, bool):
+            raise ValueError('state_backward must be a bool, not %r' % (state_backward,))
+        if state_backward and not (carry_state and self.keep_activations):
+            raise ValueError('state_backward=True back-propagates through a carried recurrent state: the model needs carry_state=True and keep_activations=True')
+        self.state_backward = state_backward
+        self._spare_state = None       # state_backward: the other of the two state buffers = the state the last call started from
+        self.initial_state_grad = None   # backward(initial_state_grad=True): d loss / d (the state the last call started from), a RecurrentState
+        self._spare_state_grad = None    # ... and the buffer it alternates with when the next sweep is seeded with it
         check_plan_options(plan_options)
         self.plan_options = dict(plan_options or {})
         self.main_priority = main_priority     # None / False / True: include/pivp_hip.h, pivp_plan_set_main_priority
@@ -476,13 +492,22 @@ class Model(object):
         cur = self._state if self.carry_state else None
         out = None
         if self.carry_state and advance:
-            out = cur if cur is not None else RecurrentState.empty(B, (H, W), self.device)
+            if self.state_backward:      # the final state goes to the OTHER buffer: a sweep reads the one this rollout starts from again
+                spare = self._spare_state      # (a start from zeros reuses it too: what it held belonged to a call this one supersedes)
+                fits = spare is not None and spare is not cur and (spare.batch, spare.hw) == (B, (H, W))
+                out = spare if fits else RecurrentState.empty(B, (H, W), self.device)
+            else:
+                out = cur if cur is not None else RecurrentState.empty(B, (H, W), self.device)
         lib = plan.lib
         try:
             _lib.check(lib.pivp_plan_set_rollout_state(plan.h, cur.data.data_ptr() if cur is not None else None,
                                                        out.data.data_ptr() if out is not None else None, int(observed)), 'pivp_plan_set_rollout_state')
             yield cur is not None
             if out is not None:
+                if out is not cur and cur is not None:
+                    self._spare_state = cur      # (kept alive and unmodified until the next rollout)
+                elif self._spare_state is out:
+                    self._spare_state = None
                 self._state = out      # (only behind a rollout that was enqueued whole)
         finally:
             lib.pivp_plan_set_rollout_state(plan.h, None, None, 0)
@@ -794,7 +819,45 @@ class Model(object):
             raise RuntimeError('call the model first (parameters are lazily sized)')
         return list(self._group_ranges)
 
-    def backward(self, on_group=None, frame_grad=None, input_grad=False, params=True, builtin_loss=True):
+    def _state_grad_args(self, initial_state_grad, final_state_grad):
+        """The argument checks of backward()'s two state keywords: every complaint is a ValueError raised before the GPU or the library is needed."""
+        if not isinstance(initial_state_grad, bool):
+            raise ValueError('initial_state_grad must be a bool, not %r' % (initial_state_grad,))
+        if (initial_state_grad or final_state_grad is not None) and not self.state_backward:
+            raise ValueError('initial_state_grad / final_state_grad need Model(..., carry_state=True, keep_activations=True, state_backward=True)')
+        if initial_state_grad and not self._carried_start:
+            raise ValueError('initial_state_grad=True: the last call started from zeros (after reset_state()), not from a carried state')
+        if final_state_grad is not None:
+            if not is_recurrent_state(final_state_grad):
+                raise ValueError('final_state_grad must be a RecurrentState (or None), not %r' % (type(final_state_grad).__name__,))
+            self._checked_state(final_state_grad)
+            swept = self._swept_shape()
+            if swept is not None and (final_state_grad.batch, final_state_grad.hw) != swept:
+                raise ValueError('final_state_grad is of batch %d at %dx%d frames, the last call ran batch %d at %dx%d'
+                                 % ((final_state_grad.batch,) + final_state_grad.hw + (swept[0],) + swept[1]))
+
+    def _swept_shape(self):
+        """(batch, (H, W)) of the last training call -- what its plan was made for and the sweep will run at, whatever was done to the carried state
+        since -- or None before any call."""
+        inputs = getattr(self, '_inputs', None)
+        if inputs is None or self._hw is None:
+            return None
+        return int(inputs[1].shape[1]), tuple(self._hw)
+
+    def _state_grad_buffer(self, seed):
+        """Where the sweep leaves d loss / d (initial state), sized for the call that is swept: `initial_state_grad` again when it fits -- or, when that
+        very buffer seeds this sweep (chunked_backward hands one window's result to the next sweep), the buffer it alternates with."""
+        batch, hw = self._swept_shape()
+        fits = lambda g: g is not None and (g.batch, g.hw) == (batch, hw)
+        dst = self.initial_state_grad if fits(self.initial_state_grad) else None
+        if dst is not None and seed is not None and dst.data.data_ptr() == seed.data.data_ptr():
+            dst, self._spare_state_grad = (self._spare_state_grad if fits(self._spare_state_grad) else None), dst
+        if dst is None:
+            dst = RecurrentState.empty(batch, hw, self.device)
+        self.initial_state_grad = dst
+        return dst
+
+    def backward(self, on_group=None, frame_grad=None, input_grad=False, params=True, builtin_loss=True, initial_state_grad=False, final_state_grad=None):
         """Back-propagate the loss of the LAST call through time (needs keep_activations=True).  Gradients
         accumulate into `model._flat_grads` (internal layouts); `grads_reference()` returns them in checkpoint layout.
 
@@ -813,19 +876,26 @@ class Model(object):
         gradients alone.  `_flat_grads` then holds unspecified values: `cleargrads()` before the next full sweep.  `on_group` must be None.
         builtin_loss=False: the sweep differentiates `frame_grad` (and the model's image loss, if it has one) alone, without the reference's frame and
         state MSE; without either there is nothing to differentiate and the call raises ValueError.
-        Both switches hold for this call only."""
+        Both switches hold for this call only.
+
+        On a model built with state_backward=True (otherwise a call that started from a carried state is refused: truncated BPTT needs the flag):
+        the state the last call started from is a constant of the sweep.  initial_state_grad=True: the sweep also leaves d loss / d (that state) in
+        `model.initial_state_grad`, a `RecurrentState`; it is overwritten by each such call and reused by the next one of the same shape.
+        final_state_grad: a `RecurrentState` of the model's batch and frame size, d (some later loss) / d (the state the last call left); it joins the
+        sweep at its first visited timestep and alone counts as something to differentiate under builtin_loss=False.  Both hold for this call only."""
         if not params and on_group is not None:
             raise ValueError('backward(params=False) announces no gradient group: on_group must be None')
-        if not builtin_loss and frame_grad is None and self._loss_grad is None:
+        self._state_grad_args(initial_state_grad, final_state_grad)
+        if not builtin_loss and frame_grad is None and self._loss_grad is None and final_state_grad is None:
             raise ValueError('backward(builtin_loss=False) needs frame_grad (or a model with an image loss): there is nothing to differentiate')
         plan = self._active
         if plan is None or self._results is None:
             raise RuntimeError('call the model first')
         if not self.keep_activations:
             raise RuntimeError('backward() needs Model(..., keep_activations=True)')
-        if self._carried_start:
-            raise RuntimeError('the last call started from a carried recurrent state: truncated BPTT across calls is not served (reset_state() in front of '
-                               'every call that is back-propagated)')
+        if self._carried_start and not self.state_backward:
+            raise RuntimeError('the last call started from a carried recurrent state: truncated BPTT across calls needs Model(..., state_backward=True) '
+                               '(or reset_state() in front of every call that is back-propagated)')
         self._ensure_grads()
         images, actions, states = self._inputs
         gt_ptr = self._gt_mask.data_ptr() if self._gt_mask is not None else None
@@ -856,9 +926,13 @@ class Model(object):
             if self.action_grad is None or tuple(self.action_grad.shape) != shape or self.action_grad.device != images.device:
                 self.action_grad = torch.empty(shape, dtype=torch.float32, device=images.device)
                 self.state_grad = torch.empty(shape[1:], dtype=torch.float32, device=images.device)
+        state_dst = self._state_grad_buffer(final_state_grad) if initial_state_grad else None
         try:
             # the model's device must be the CURRENT one for the launches (and for the plan's own side stream, created on first use)
             with torch.cuda.device(self.device):
+                if self.state_backward:      # the sweep may start at a carried state; the seed on the final state and where d / d (initial state) goes
+                    _lib.check(plan.lib.pivp_plan_set_state_grad(plan.h, 1, final_state_grad.data.data_ptr() if final_state_grad is not None else None,
+                                                                 state_dst.data.data_ptr() if state_dst is not None else None), 'pivp_plan_set_state_grad')
                 if input_grad:
                     _lib.check(plan.lib.pivp_plan_set_input_grad(plan.h, self.action_grad.data_ptr(), self.state_grad.data_ptr()), 'pivp_plan_set_input_grad')
                 if mode != 3:
@@ -869,6 +943,8 @@ class Model(object):
                                                           self._gen.data_ptr(), self._gen_states.data_ptr(), self._stream()),
                            'pivp_rollout_backward')
         finally:
+            if self.state_backward:
+                plan.lib.pivp_plan_set_state_grad(plan.h, 0, None, None)
             if input_grad:
                 plan.lib.pivp_plan_set_input_grad(plan.h, None, None)
             if mode != 3:

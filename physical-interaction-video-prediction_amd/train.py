@@ -70,7 +70,32 @@ def build_parser():
     p.add_argument('--loss_l1', type=float, default=0.0)
     p.add_argument('--loss_gdl', type=float, default=0.0)
     p.add_argument('--loss_dssim', type=float, default=0.0)
+    # truncated back-propagation through time: every drawn sequence is cut into N consecutive windows (T divisible by N); each window is one forward,
+    # one backward with the state it started from as a constant, and one Adam step, the ConvLSTM state carried from window to window and cleared
+    # between sequences (Model(carry_state=True, state_backward=True)).  1, the default: the sequence is one window and nothing new runs
+    p.add_argument('--tbptt_windows', type=int, default=1)
     return p
+
+
+def model_state_flags(args):
+    """-> the Model keywords --tbptt_windows adds: none for 1 (the model is built exactly as before)."""
+    if args.tbptt_windows < 1:
+        raise SystemExit('--tbptt_windows must be >= 1 (1: off)')
+    return dict(carry_state=True, state_backward=True) if args.tbptt_windows > 1 else {}
+
+
+def train_step(optimizer, model, x, itr, windows=1):
+    """One drawn batch: optimizer.update on the whole sequence (windows = 1, the path as it always was), or on each of its consecutive windows in
+    turn with the state carried across them.  The caller clears the state between sequences.  -> [(loss, psnr_all)] device scalars, one per update."""
+    if windows == 1:
+        optimizer.update(model, x, itr)
+        return [(model.loss, model.psnr_all)]
+    from .tbptt import split_windows
+    out = []
+    for w in split_windows(x, windows):
+        optimizer.update(model, w, itr)
+        out.append((model.loss, model.psnr_all))
+    return out
 
 
 def image_loss_from_args(args):
@@ -127,7 +152,7 @@ def main(argv=None):
     model = Model(num_masks=args.num_masks, is_cdna=args.model_type == 'CDNA', is_dna=args.model_type == 'DNA',
                   is_stp=args.model_type == 'STP', use_state=args.use_state, scheduled_sampling_k=args.schedsamp_k,
                   num_frame_before_prediction=args.context_frames, prefix='train', device=device, keep_activations=True,
-                  deterministic=bool(args.deterministic), image_loss=image_loss_from_args(args))
+                  deterministic=bool(args.deterministic), image_loss=image_loss_from_args(args), **model_state_flags(args))
     extra_loss = model.image_loss is not None
     if args.grad_clip < 0 or args.grad_clip != args.grad_clip:
         raise SystemExit('--grad_clip must be >= 0 (0: off)')
@@ -176,7 +201,7 @@ def main(argv=None):
             with using_config('train', False):
                 model(x, 0)
             model.reset_state(); load_optimizer_npz(args.pretrained_state, optimizer); state_loaded = True
-        optimizer.update(model, x, itr)             # enqueues the whole step; returns while the GPU is still working on it
+        steps = train_step(optimizer, model, x, itr, args.tbptt_windows)      # enqueues the whole step; returns while the GPU is still working on it
         if guarded:
             local_gnorm.append(optimizer.grad_norm.clone())      # (a view of a buffer the next step overwrites; no synchronisation)
         if extra_loss:
@@ -184,7 +209,9 @@ def main(argv=None):
         if itr + 1 < args.num_iterations:
             feeder.prefetch()                       # ... so the next batch's host work and copy run underneath it
         stats = torch.stack([model.loss, model.psnr_all]).to(torch.float64)
-        if world > 1:                               # the logged statistics are those of the GLOBAL batch (mean over the ranks' shards)
+        if len(steps) > 1:                          # --tbptt_windows: the mean over the sequence's windows (gradient norm and loss terms: the last window's)
+            stats = torch.stack([torch.stack(s) for s in steps]).to(torch.float64).mean(dim=0)
+        if world > 1:                              # the logged statistics are those of the GLOBAL batch (mean over the ranks' shards)
             dist.all_reduce(stats); stats /= world
         lv, pv = stats.tolist()                     # the step's one host synchronisation
         local_losses.append(lv); local_psnr.append(pv)
