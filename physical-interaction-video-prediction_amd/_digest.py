@@ -23,9 +23,10 @@ def source_files():
     return [os.path.join(CSRC, n) for n in names] + [DATA_HEADER, HEADER, OPTIM_HEADER, LOSS_HEADER, INPUT_GRAD_HEADER, STATE_HEADER, STATE_GRAD_HEADER]
 
 
-def source_digest():
+def source_digest(paths=None):
+    """The digest of `paths` (default: every source file); build.py takes the headers' alone, as its key for recompiling every object."""
     h = hashlib.sha256()
-    for path in source_files():
+    for path in source_files() if paths is None else paths:
         h.update(os.path.basename(path).encode())
         with open(path, 'rb') as f:
             h.update(f.read())

@@ -9,7 +9,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
-SOURCES = ['igemm_f32.hip', 'igemm_small.hip', 'deconv_tile.hip', 'convlstm_bf16.hip', 'conv5x5_bf16.hip', 'igemm_wgrad.hip', 'wgrad3x3s2.hip', 'wgrad5x5p.hip', 'wgrad_bf16.hip', 'small_kernels.hip', 'heads.hip', 'frame_head.hip', 'pixel_track.hip', 'cem.hip', 'metrics.hip', 'batch_gather.hip', 'optim.hip', 'image_loss.hip', 'input_grad.hip', 'state.hip', 'state_grad.hip', 'backward.hip', 'backward_heads.hip', 'pivp_c_api.hip', 'pivp_plan.hip']
+SOURCES = ['igemm_f32.hip', 'igemm_small.hip', 'deconv_tile.hip', 'convlstm_bf16.hip', 'conv5x5_bf16.hip', 'igemm_wgrad.hip', 'wgrad3x3s2.hip', 'wgrad5x5p.hip', 'wgrad_bf16.hip', 'small_kernels.hip', 'heads.hip', 'frame_head.hip', 'pixel_track.hip', 'cem.hip', 'metrics.hip', 'batch_gather.hip', 'optim.hip', 'image_loss.hip', 'input_grad.hip', 'state.hip', 'state_grad.hip', 'backward.hip', 'backward_heads.hip', 'pivp_c_api.hip', 'plan_setup.hip', 'plan_forward.hip', 'plan_backward.hip']
 LIB = os.path.join(HERE, 'libpivp_hip.so')
 STAMP = os.path.join(HERE, '.libpivp_hip.stamp')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=off', '-Wall', '-Wno-unused-function']
@@ -29,25 +29,23 @@ def _load_digest_module():
 
 
 def _digest():
-    """-> (source digest: what the library embeds and `_lib.load()` checks, stamp: source digest + compile flags, the rebuild key)."""
-    src = _load_digest_module().source_digest()
-    return src, hashlib.sha256((src + ' ' + ' '.join(FLAGS)).encode()).hexdigest()
+    """-> (source digest: what the library embeds and `_lib.load()` checks, stamp: source digest + compile flags, the rebuild key,
+    header digest: the same function of the same file list cut down to the headers)."""
+    mod = _load_digest_module()
+    src = mod.source_digest()
+    headers = [p for p in mod.source_files() if p.endswith('.h')]
+    return src, hashlib.sha256((src + ' ' + ' '.join(FLAGS)).encode()).hexdigest(), mod.source_digest(headers)
 
 
 def build(force=False, verbose=False):
     """Compile every HIP source for gfx950 into libpivp_hip.so (no-op when up to date)."""
-    src_dig, dig = _digest()
+    src_dig, dig, hdr_dig = _digest()
     if not force and os.path.exists(LIB) and os.path.exists(STAMP) and open(STAMP).read().strip() == dig:
         return LIB
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
     objs = []
     procs = []
-    # every header any source may include: a change there recompiles everything, a change in one .hip only that object
-    hdr = hashlib.sha256()
-    for n in sorted(os.listdir(CSRC)) + ['../../include/pivp_hip.h', '../../include/pivp_data.h', '../../include/pivp_optim.h', '../../include/pivp_loss.h', '../../include/pivp_input_grad.h', '../../include/pivp_state.h', '../../include/pivp_state_grad.h']:
-        if n.endswith('.h'):
-            with open(os.path.join(CSRC, n), 'rb') as f:
-                hdr.update(n.encode() + f.read())
+    # hdr_dig covers every header any source may include: a change there recompiles everything, a change in one .hip only that object
     for src in SOURCES:
         obj = os.path.join(CSRC, src.replace('.hip', '.o'))
         cmd = [hipcc] + FLAGS + ['-c', os.path.join(CSRC, src), '-o', obj]
@@ -56,7 +54,7 @@ def build(force=False, verbose=False):
             cmd.insert(-4, '-DPIVP_BUILD_FLAGS="%s"' % ' '.join(EXTRA).replace('"', "'"))
         objs.append(obj)
         with open(os.path.join(CSRC, src), 'rb') as f:
-            key = hashlib.sha256(hdr.digest() + f.read() + ' '.join(cmd).encode()).hexdigest()
+            key = hashlib.sha256(hdr_dig.encode() + f.read() + ' '.join(cmd).encode()).hexdigest()
         ostamp = obj + '.stamp'
         if not force and os.path.exists(obj) and os.path.exists(ostamp) and open(ostamp).read().strip() == key:
             continue

@@ -1,6 +1,6 @@
 // C-ABI layer: the host-side launch helpers of pivp_host.h and the per-op entry points declared in include/pivp_hip.h.
 // The plan (Model.__init__ / reset_state / __call__ of the reference, TM:484-764), which sequences the whole per-timestep
-// op program in native code on one HIP stream, lives in pivp_plan.hip.
+// op program in native code on one HIP stream, lives in plan_setup.hip / plan_forward.hip / plan_backward.hip (plan.h).
 #include <string.h>
 #include <string>
 #include <vector>
@@ -356,7 +356,7 @@ int run_convlstm_backward(const ConvLstmBwdArgs& a, hipStream_t s) {
         rc = run_conv_s1(a.dG, N, N, a.wt, a.d_in, a.dx_only ? cx : cin, cin, 5, B, H, W, s, o);
     }
     if (rc != PIVP_OK) return rc;
-    if (!a.dW) return PIVP_OK;   // the caller batches this layer's weight gradient over several timesteps itself (pivp_plan.hip)
+    if (!a.dW) return PIVP_OK;   // the caller batches this layer's weight gradient over several timesteps itself (plan_backward.hip)
     int bias_done = 0;   // the 5x5 weight-gradient kernel sums dG's columns on the side
     // (a single timestep's weight gradient: bf16 operands in that form, the fp32 kernel in every other)
     WgradDesc d;
@@ -413,7 +413,7 @@ int run_conv_backward(const ConvBwdArgs& a, hipStream_t s) {
                   : run_deconv3x3s2(a.dy, a.cout, a.ldy, a.wt, nullptr, a.dx, a.cin, a.lddx, 0, B, Hout, Wout, s, o);
         if (rc != PIVP_OK) return rc;
     }
-    if (!a.dW) return PIVP_OK;     // the caller batches this layer's weight gradient over several timesteps itself (pivp_plan.hip); the fork's `ready` is recorded
+    if (!a.dW) return PIVP_OK;     // the caller batches this layer's weight gradient over several timesteps itself (plan_backward.hip); the fork's `ready` is recorded
     int bias_done = 0;     // the weight-gradient kernel sums dY's columns on the side when it can
     WgradDesc d;
     conv3x3s2_wgrad_geom(d, mode, a.cin, a.cout, B, Hin, Win);
@@ -609,7 +609,7 @@ extern "C" int pivp_convlstm_backward_dx_only(const float* x, int cx, int ldx, c
                                               int B, int H, int W, void* stream) {
     return convlstm_backward_op(x, cx, ldx, h_prev, C, w, gates, c_old, c_new, dh_a, lda, dh_b, ldb, dc, dc_valid, dG, wt, d_in, dW, db, B, H, W, stream, 1);
 }
-// The cell backward with the data gradient in the form of a precision mode, as the sweep's lstmb (pivp_plan.hip) fills ConvLstmBwdArgs: the pack of wt in that
+// The cell backward with the data gradient in the form of a precision mode, as the sweep's lstmb (plan_backward.hip) fills ConvLstmBwdArgs: the pack of wt in that
 // form and dG's partial maxima live in `scratch` (pivp_convlstm_backward_form_scratch_floats), the epilogue hook and det are passed through.  precision 0 is
 // pivp_convlstm_backward / _dx_only (scratch and the hook unused).  Everything that is refused is refused in front of the first launch.
 extern "C" long long pivp_convlstm_backward_form_scratch_floats(int cx, int C) {
@@ -874,7 +874,7 @@ extern "C" int pivp_layernorm_backward(const float* dy, int lddy, const float* y
                                        int B, int n, int C, int relu, void* stream) {
     return ln_backward(dy, lddy, y, ldy, x, stat, gamma, partials, dx, dgamma, dbeta, B, n, C, relu, (hipStream_t)stream);
 }
-// LayerNorm backward of the norm behind a ConvLSTM + the cell's gate backward, the way the BPTT sweep runs the pair (pivp_plan.hip:
+// LayerNorm backward of the norm behind a ConvLSTM + the cell's gate backward, the way the BPTT sweep runs the pair (plan_backward.hip:
 // lnb_cell + lstmb): sums + parameter planes in one launch (ln_bwd_sums_params_kernel), then the gate kernel forms the norm's dx from the sums on the fly.
 extern "C" long long pivp_gates_backward_ln_scratch_floats(int B, int n) {
     if (B <= 0 || n <= 0) return PIVP_ERR_BADARG;
@@ -901,7 +901,7 @@ extern "C" int pivp_gates_backward_ln(const float* gates, const float* c_old, co
     if (rc != PIVP_OK) return rc;
     return ln_bwd_params_reduce(part, dgamma, dbeta, B, n, s);
 }
-// Op entries of the head-side backward kernels (backward_heads.hip), one launcher each: what the BPTT sweep of pivp_plan.hip calls, reachable one at a
+// Op entries of the head-side backward kernels (backward_heads.hip), one launcher each: what the BPTT sweep of plan_backward.hip calls, reachable one at a
 // time (tests/test_gpu_backward_heads.py).  The SideFork of the sweep (a second stream for the weight gradients) is not exposed: everything on `stream`.
 extern "C" int pivp_composite_backward_tiles(int H, int W) {
     if (H <= 0 || W <= 0) return PIVP_ERR_BADARG;

@@ -1,4 +1,4 @@
-// Host-side launch helpers shared by the per-op C ABI (pivp_c_api.hip) and the plan (pivp_plan.hip).
+// Host-side launch helpers shared by the per-op C ABI (pivp_c_api.hip) and the plan (plan.h, plan_setup.hip, plan_forward.hip, plan_backward.hip).
 // A helper takes its required core positionally (tensors, channel counts, strides, B, H, W, stream) and everything optional as named fields of ONE
 // options struct behind it: callers value-initialise the struct (`T o{};`), assign what they use by name and pass it by reference.
 // Value-initialised means every field zero / null; an operand form (Operand, pivp_kernels.h) then is F32.
@@ -124,7 +124,7 @@ struct ConvLstmBwdArgs {
     float* dc; int dc_valid;      // updated in place to d c_{t-1}
     float* dG; float* wt;
     float* d_in;                  // [M][cx+C]: d x (first cx channels) and d h_{t-1} (last C)
-    float* dW; float* db;         // dW == null: the caller batches this layer's weight gradient over several timesteps itself (pivp_plan.hip)
+    float* dW; float* db;         // dW == null: the caller batches this layer's weight gradient over several timesteps itself (plan_backward.hip)
     int B, H, W;
     // optional
     int wt_ready;                 // 1: wt (and wt_bf16) already hold the transposed pack

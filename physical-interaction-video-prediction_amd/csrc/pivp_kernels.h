@@ -1,4 +1,4 @@
-// Internal launcher interface between the host layer (the launch helpers and per-op C ABI of pivp_c_api.hip, the plan of pivp_plan.hip) and the gfx950 kernels.
+// Internal launcher interface between the host layer (the launch helpers and per-op C ABI of pivp_c_api.hip, the plan of plan_*.hip) and the gfx950 kernels.
 // Internal data layout (DESIGN.md "Data layout in HBM"):
 //   * feature maps: NHWC fp32, `ld` = floats between consecutive pixels (lets a producer write
 //     straight into a channel slice of a skip-concat buffer; TM:569-576 never materialises a copy)
@@ -13,7 +13,7 @@
 
 namespace pivp {
 
-// How an fp32 operand travels into the matrix pipe.  The values are the precision modes' (PIVP_PRECISION_*, include/pivp_hip.h; pinned in pivp_plan.hip).
+// How an fp32 operand travels into the matrix pipe.  The values are the precision modes' (PIVP_PRECISION_*, include/pivp_hip.h; pinned in plan.h).
 enum class Operand : int {
     F32 = 0,       // as it is (the fp32 kernels)
     BF16 = 1,      // rounded to bf16

@@ -1,0 +1,216 @@
+// The plan (Model.__init__ / reset_state / __call__ of the reference, TM:484-764, and the backward pass that Chainer's autograd performs under
+// optimizer.update, TM:950, sequenced in native code on one HIP stream): its layer tables and types, shared by plan_setup.hip (create, setters, layout,
+// taps), plan_forward.hip (the rollouts) and plan_backward.hip (the sweep).  Internal: nothing here is part of the C ABI but the name `pivp_plan`.
+#pragma once
+#include <string.h>
+#include <string>
+#include <vector>
+
+#include "../../include/pivp_hip.h"
+#include "../../include/pivp_loss.h"
+#include "../../include/pivp_input_grad.h"
+#include "../../include/pivp_state.h"
+#include "../../include/pivp_state_grad.h"
+#include "pivp_host.h"
+
+#pragma GCC visibility push(hidden)      // internal names: none of them joins the library's exports
+namespace pivp {
+
+// ---- the layer tables: every per-layer size of the plan comes from here ----
+struct MapSize { int H, W; };
+inline MapSize level_map(const pivp_config_t& c, int level) { return {c.height / level, c.width / level}; }   // pyramid level: 1 = the frame, 2 -> H/2, 4 -> H/4, 8 -> H/8
+struct LstmSpec { const char* name; int cx; int C; int level; };
+inline const LstmSpec kLstm[7] = {
+    {"lstm1", 32, 32, 2}, {"lstm2", 32, 32, 2}, {"lstm3", 32, 64, 4}, {"lstm4", 64, 64, 4},
+    {"lstm5", 64, 128, 8}, {"lstm6", 128, 64, 4}, {"lstm7", 96, 32, 2}};
+inline MapSize lstm_map(const pivp_config_t& c, int i) { return level_map(c, kLstm[i].level); }   // cell i's (H, W)
+// The recurrent state as one buffer (include/pivp_state.h): segment g = 2 i is cell i's c, 2 i + 1 its h; floats per sample, and where the segment
+// starts in the state of a batch c.batch
+static_assert(STATE_SEGMENTS == PIVP_STATE_SEGMENTS && STATE_SEGMENTS == 2 * 7, "c and h of the seven cells");
+inline long long state_seg_floats(const pivp_config_t& c, int g) { const MapSize m = lstm_map(c, g / 2); return (long long)m.H * m.W * kLstm[g / 2].C; }
+inline size_t state_seg_offset(const pivp_config_t& c, int g) {
+    long long at = 0;
+    for (int k = 0; k < g; ++k) at += state_seg_floats(c, k);
+    return (size_t)at * c.batch;
+}
+// The five stride-2 3x3 layers in the order of their side-stream slots 7..11 and of Grads::wg_part: enc6, enc5, enc4 (transposed: anchors = their INPUT maps),
+// enc2, enc1 (convs).  c: channels in = out; ldx / ldo: pixel strides of the forward input / output (enc1 writes into cat6); ldy: of dY in the backward sweep
+// (a ring slot of its own, or the x columns of the next cell's input gradient); level: of the input map.
+struct EncSpec { int mode, layer, c, ldx, ldo, ldy, level; };
+inline const EncSpec kEnc[5] = {{1, 6, 64, 64, 64, 64, 2}, {1, 5, 96, 96, 96, 128, 4}, {1, 4, 128, 128, 128, 192, 8}, {0, 2, 64, 64, 64, 64, 4}, {0, 1, 32, 32, 96, 96, 2}};
+// parameter sizes: enc0 5x5 on 3 channels, enc3 1x1 on e2 (+ the smeared action / state), the others 3x3 with as many channels in as out
+inline const int kEncB[7] = {32, 32, 64, 64, 128, 96, 64};
+inline long long enc_w_numel(const pivp_config_t& c, int i) {
+    return i == 0 ? 75 * 32 : i == 3 ? (64 + (c.use_state ? 10 : 0)) * 64LL : 9LL * kEncB[i] * kEncB[i];
+}
+// elements per sample of the nine LayerNorms: norm_enc0, hidden1..hidden7 (behind cell j - 1), norm_enc6
+inline long long ln_numel(const pivp_config_t& c, int j) {
+    if (j == 0) return 32LL * (c.height / 2) * (c.width / 2);
+    if (j == 8) return 64LL * c.height * c.width;
+    const MapSize m = lstm_map(c, j - 1);
+    return (long long)kLstm[j - 1].C * m.H * m.W;
+}
+
+// ---- the precision mode: everything the plan derives from it ----
+static_assert((int)Operand::F32 == PIVP_PRECISION_F32 && (int)Operand::BF16 == PIVP_PRECISION_BF16 && (int)Operand::BF16X3 == PIVP_PRECISION_BF16X3 &&
+              (int)Operand::BF16X6 == PIVP_PRECISION_BF16X6 && (int)Operand::FP16X3 == PIVP_PRECISION_FP16X3, "Operand is the PIVP_PRECISION_* code");
+// the two-image tile of the L2-direct forms' kernels serves this map (an 8-wide map needs an even batch; otherwise the fp32 kernel takes it)
+inline bool pair_tile_serves(int W, int B) { return W % 16 == 0 || B % 2 == 0; }
+struct Modes {
+    Operand precision;      // the mode = the form of the ConvLSTM forward's operands
+    // the ConvLSTM forward runs on weight packs (of the form `precision`)
+    bool packs() const { return precision != Operand::F32; }
+    // the ConvLSTM data gradient on a W-wide map at batch B: the forward's form where its tiles serve the map
+    Operand dgrad(int W, int B) const { return operand_l2_direct(precision) && !pair_tile_serves(W, B) ? Operand::F32 : precision; }
+    // ... and the weight gradient of a batch of timesteps: the split mode has no form of its own and stays fp32
+    Operand wgrad(int W, int B) const { return precision == Operand::BF16X3 ? Operand::F32 : dgrad(W, B); }
+    // ... which those forms batch: BF16 as many timesteps per launch as the rings hold, the L2-direct forms two; fp32 none
+    bool wgrad_batches() const { return precision == Operand::BF16 || operand_l2_direct(precision); }
+    // a transposed conv.  has_wabs: the layer keeps its weights' absmax partials (enc5 / enc6: pivp_plan::o_wabs), which the fp16-piece form needs -- a layer
+    // without them (enc4) stays fp32 in that mode, as every layer does in the three-piece mode (the tile kernel has no such form)
+    Operand deconv(bool has_wabs) const { return precision == Operand::BF16X6 || (operand_needs_scale(precision) && !has_wabs) ? Operand::F32 : precision; }
+    // the stride-2 convs' data gradient (enc1's is a transposed conv the tile kernel takes): bf16 operands in that mode only
+    Operand enc_dgrad() const { return precision == Operand::BF16 ? Operand::BF16 : Operand::F32; }
+};
+
+struct ParamInfo { std::string name; long long numel; const float* ptr; float* grad; int group; };
+
+// LayerNorm partial slots per sample: the ln_stats slices of the largest map (64 channels at full resolution) or the tiles
+// of the producers that write partials themselves (enc6 through igemm_small: HW/4 anchors / 32 x 2 column blocks x 4 parities)
+inline int ln_partial_cap(int HW) {
+    const int a = ln_stats_slices(64 * HW), b = (HW / 4 / 32 + 1) * 2 * 4;
+    return a > b ? a : b;
+}
+
+// Deterministic sweeps: the fp32 slot form of the ConvLSTM weight gradients with this many blocks per XCD whatever the device reports (WgradDesc::slot_j;
+// two per CU on a 256-CU MI355X), so that the order of its sums follows the problem shape alone -- not the CU count of a partition mode
+constexpr int DET_SLOT_J = 64;
+
+// Per-timestep activations (offsets in floats from the workspace base).  Two rolling slabs for inference, T-1 slabs
+// when keep_activations (BPTT needs every step).
+struct Slab {
+    size_t cat7, n1, n2, cat6, n3, n4, e2, e3, n5, e4, e5, e6;   // NHWC feature maps (cat7 = [hidden7|enc0], cat6 = [hidden6|enc1])
+    size_t h[7], c[7];                                           // ConvLSTM states
+    size_t e0raw, e6raw;                                         // LayerNorm inputs of norm_enc0 / norm_enc6
+    size_t gates[7];                                             // gate activations [M][4C] (training)
+    size_t lnstat;                                               // [9][B][2] mean, rstd (training)
+    size_t logits, enc7, layer0, kerns, vpre, theta;             // head tensors of the step
+    size_t prevsel;                                              // scheduled-sampling input frame of the step
+};
+
+struct Grads {   // gradient workspace (single copy, reused by every timestep of the backward sweep)
+    size_t cat7, n2, n4, n5, e6;
+    size_t e0raw[2], dv[2];   // dY tensors the side stream's weight gradients read, by timestep parity: a step rewrites the buffer the weight gradients of
+                              // TWO steps ago read, so the main stream never waits for the previous step's (round 5)
+    // The dY tensors of the five stride-2 3x3 layers live in RINGS like the ConvLSTMs' dG: 2 rings x eg_cap timesteps, one weight-gradient launch per
+    // batch (wgrad3x3s2.hip).  enc6: d e6raw; enc2: d e2; enc1: columns 64.. of d cat6; enc5 / enc4: the x columns of lstm7's / lstm6's input gradient,
+    // din[6] / din[5] -- so those two hold ring slots as well (the other cells' din: two buffers by timestep parity).  *_sz: floats per slot.
+    size_t cat6, e2, e6raw, cat6_sz, e2_sz, e6raw_sz;
+    size_t din[7], din_sz[7], dc[7];
+    size_t dG[7], go, dmk, dz, dkpart, dstate, lnpart;   // dG: gate pre-activation gradients per ConvLSTM: 2 rings x wg_cap timesteps (batched weight gradients)
+                                                             // go: d loss / d gen[t] for every t ([T-1] frames: the loss terms of all of them come from ONE launch)
+    size_t wt_lstm[7], wt_enc[7];   // re-packed (transposed) weights for the data gradients, rebuilt once per backward
+    size_t ln_ppart[9], ln_ppart_floats;   // per-norm partial parameter gradients (ln_backward's param_part), one contiguous region
+    size_t wg_part[5], wg_part_floats;   // per-block partial weight gradients of enc6, enc5, enc4, enc2, enc1 (WgradDesc::part), one contiguous region
+    size_t wtb_lstm[7];             // ... and their bf16 packs (bf16 precision mode)
+    size_t dg_absmax;               // fp16-piece data gradients: the partial maxima of the dG in front of the launch (absmax_partials; stream-ordered, one buffer)
+    // deterministic sweeps only (pivp_plan_set_deterministic; 0 otherwise): the ConvLSTM weight gradients' segment slots (wgrad5x5p, one region per cell,
+    // summed once per sweep), and the per-block rows of the output side's small gradients (heads_bwd, the CDNA generator's bias, enc3 + state
+    // predictor, enc0, the STP regressor), summed in order behind each launch; STP's d prev as exact 64-bit integer sums (det_stp_acc)
+    size_t lstm_part[7], det_heads, det_dv, det_enc3, det_enc0, det_stp, det_stp_acc;
+};
+
+// What the last rollout of a plan was: what pivp_rollout_backward, pivp_get_tap and pivp_plan_set_state_grad may assume about the slabs.  A rollout resets it
+// to {} in front of its first launch and assigns it whole behind its last, so one that failed half-way leaves "no rollout".
+struct LastRollout {
+    int steps;                  // timesteps whose slabs are whole (0: none)
+    bool sched;                 // scheduled sampling was on (frames detached, TM:669-670)
+    bool predict;               // it was pivp_rollout_predict: nothing to back-propagate
+    bool carried;               // it started from a registered state: the sweep's t = 0 forms without h do not describe it
+    const float* state_in;      // pivp_rollout_forward: the state it read (null: zeros) -- the sweep's t = 0 reads it again
+    bool state_lost;            // ... which that rollout overwrote with its own final state (state_in == state_out)
+};
+
+}  // namespace pivp
+#pragma GCC visibility pop
+
+struct pivp_plan {
+    // ---- fixed at pivp_plan_create ----
+    pivp_config_t cfg;
+    std::vector<pivp::ParamInfo> params;      // (ptr / grad: pivp_plan_set_param / pivp_plan_set_grad)
+    int i_enc_w[7], i_enc_b[7], i_lstm_w[7], i_lstm_b[7];
+    int i_ln_g[9], i_ln_b[9];   // order: norm_enc0, hidden1..hidden7, norm_enc6
+    int i_masks_w, i_masks_b, i_cs_w, i_cs_b, i_enc7_w, i_enc7_b;
+    int i_head_w, i_head_b, i_head2_w, i_head2_b;
+    int H2, W2, H4, W4, H8, W8, NP, NE, K5;
+    // ---- fixed before the workspace is bound: the switches the layout follows, and the layout (plan_layout) ----
+    pivp::Modes mode{pivp::Operand::F32};   // pivp_plan_set_precision
+    int det = 0;                      // pivp_plan_set_deterministic: fixed-order forms of every sum of the sweep (no float atomics)
+    // pivp_plan_set_option (include/pivp_hip.h), by PIVP_OPT_*: SIDE_STREAM; FINISH_RIDER: the motion head's finisher rides behind enc5's tiles (0: inside
+    // frame_head, as rounds 4-5); FUSE_ENC3, inference: enc3 + state predictor in enc2's epilogue (0: their own launch); LN_FOLD_TRAIN, training: the norms of
+    // hidden2 / hidden4 applied (and written) by enc1 / enc2's launches (0: ln_apply launches); WGRAD_BATCH: timesteps per ConvLSTM weight-gradient launch
+    // (tests, measurements), whatever the precision mode; 0 = the mode's own choice
+    int opt[PIVP_OPT_COUNT] = {1, 1, 1, 1, 0};
+    int wg_cap = 1;                   // dG ring slots per ring = min(T - 2, WG_BATCH_MAX), fixed when the workspace is laid out
+    int eg_cap = 1;                   // slots per enc dY ring (Grads::cat6): min(T - 2, WG_BATCH_MAX), cut to ENC_RING_BYTES_MAX
+    float* ws; long long ws_floats;
+    int nslabs;
+    std::vector<pivp::Slab> slabs;
+    pivp::Grads g;
+    bool has_grads;
+    size_t o_zero, o_lnpart, o_lnpart2, o_linpart, o_masks, o_losspart;   // o_lnpart2: enc6 reads hidden7's partials while writing its own
+    size_t o_wabs[2];                 // precision mode FP16X3: absmax_partials of the enc5 / enc6 weights (rebuilt at the start of a rollout)
+    size_t o_wbf16[7];                // bf16 packs of the ConvLSTM weights (pivp_plan_set_precision), rebuilt at the start of a rollout
+    int loss_nparts;
+    // ---- registered for the next calls ----
+    int pack_cache = 0, packs_valid = 0;   // pivp_plan_set_pack_cache: keep the precision modes' weight packs across rollouts until pivp_plan_params_changed
+    int main_prio = -1;               // pivp_plan_set_main_priority: -1 = on unless a gradient listener is registered (data parallelism), 0 / 1 = as said
+    pivp_grad_group_cb grad_cb = nullptr; void* grad_cb_user = nullptr;   // gradient-group-final notifications (t = 0 sweep)
+    bool group_join = true;           // pivp_plan_set_group_join
+    const float* frame_seed = nullptr;   // pivp_plan_set_frame_grad: an additional d loss / d gen_images[ctx-1 .. T-2] for the sweep (null: the plan's own seed alone)
+    float* in_dact = nullptr; float* in_dstate0 = nullptr;   // pivp_plan_set_input_grad: d loss / d actions [T-1][B][5] and d loss / d states[0] [B][5] (null: not wanted)
+    int sweep_mode = 3;               // pivp_plan_set_sweep_mode: PIVP_SWEEP_PARAMS | PIVP_SWEEP_BUILTIN_LOSS (include/pivp_input_grad.h)
+    // pivp_plan_set_rollout_state (include/pivp_state.h): where the next rollouts read their initial (c, h) of the seven cells and leave their final ones
+    // (null: zeros / nowhere), and how many leading steps pivp_rollout_predict feeds from context_images (0: cfg.context_frames)
+    const float* state_in = nullptr; float* state_out = nullptr; int observed = 0;
+    // pivp_plan_set_state_grad (include/pivp_state_grad.h): the sweep serves a rollout that started from a state (sg_enable), is seeded with d / d (its final
+    // state) (sg_seed) and leaves d loss / d (its initial state) (sg_dstate_in); null / 0: none of it
+    int sg_enable = 0; const float* sg_seed = nullptr; float* sg_dstate_in = nullptr;
+    // ---- written by the rollouts ----
+    pivp::LastRollout last = {};
+    bool masks_every_step = false;    // pivp_rollout_predict with tracked planes: the head writes its softmaxed masks at every step
+    bool prof_on = false;             // pivp_plan_set_profiling; run_step records into prof_ev
+    std::vector<hipEvent_t> prof_ev;
+    std::vector<int> prof_layer;
+    size_t prof_used = 0;
+    // ---- the weight gradients' stream and its events (side_lane.h): a sweep reads it, only create / the destructor change it.  (What a sweep mutates
+    // is its own: Sweep, plan_backward.hip) ----
+    pivp::SideLane lane;
+    ~pivp_plan() {
+        lane.sync();
+        for (hipEvent_t e : prof_ev) (void)hipEventDestroy(e);
+        lane.destroy();
+    }
+};
+
+#pragma GCC visibility push(hidden)
+namespace pivp {
+
+inline const float* P(const pivp_plan* p, int idx) { return p->params[idx].ptr; }
+inline float* G(const pivp_plan* p, int idx) { return p->params[idx].grad; }
+
+// the frame sizes every entry point takes: three stride-2 levels under 5x5 ConvLSTMs.  (Each caller adds its own condition on batch and seq_len.)
+inline bool frame_size_ok(const pivp_config_t& c) { return c.height >= 16 && c.width >= 16 && c.height % 8 == 0 && c.width % 8 == 0; }
+
+// ---- what crosses the units ----
+void plan_layout(pivp_plan* p);                              // plan_setup.hip: the workspace carve
+size_t state_bytes(const pivp_config_t& c);                  // ... bytes of the recurrent state at batch c.batch
+bool ranges_overlap(const void* a, const void* b, size_t bytes);
+const float* step_input(const pivp_plan* plan, int t, const float* images, const unsigned char* gt_select, const float* gen_images, size_t fr);   // plan_forward.hip
+int state_grad_gather(const pivp_config_t& c, const float* const dc[7], const float* const din[7], float* d_state_in, hipStream_t s);             // plan_backward.hip
+int state_grad_scatter(const pivp_config_t& c, const float* d_state_out, float* const dc[7], hipStream_t s);
+
+#define RC(call) do { int rc_ = (call); if (rc_ != PIVP_OK) return rc_; } while (0)
+
+}  // namespace pivp
+#pragma GCC visibility pop

@@ -27,7 +27,7 @@
 // 32 x 32 x 5-tap wave tile costs; the 64-column tile (NTW = 2, 0.7 x both) needs 256 VGPRs with 45 spilled to keep two waves per SIMD and two LDS buffers:
 // 4-17 % slower on every cell.  In the backward sweep the slots cost 0.7 ms per train step (27.3 -> 28.0 ms): 42 MB of slot traffic per launch stream through
 // HBM beside the main stream's memory-bound kernels, where the round-2 kernel's atomics hit a gradient that stays in L2.  So the SWEEP keeps the round-2 kernel
-// (pivp_plan.hip), and this one is the bit-reproducible form behind pivp_wgrad5x5_f32_batch (part != NULL) and the deterministic sweep
+// (plan_backward.hip), and this one is the bit-reproducible form behind pivp_wgrad5x5_f32_batch (part != NULL) and the deterministic sweep
 // (pivp_plan_set_deterministic: every precision mode's ConvLSTM weight gradients, one reduction per cell and sweep).
 #include <type_traits>
 

@@ -704,7 +704,7 @@ def test_rollout_bf16x3_stays_inside_the_gate():
 
 
 def test_train_step_in_bf16x3_mode_matches_fp32_gradients():
-    # split forward; in the backward the ConvLSTM data gradients run in the split form too (Modes::dgrad, csrc/pivp_plan.hip), the weight gradients and everything
+    # split forward; in the backward the ConvLSTM data gradients run in the split form too (Modes::dgrad, csrc/plan.h), the weight gradients and everything
     # else in fp32: gradients agree with the fp32 path to the 1e-5-level differences of the split products
     import pivp_amd
     outs = {}
