@@ -1,6 +1,6 @@
 """ctypes binding of libpivp_hip.so (the C ABI declared in include/pivp_hip.h, the data feed's entry points of include/pivp_data.h and the
 guarded optimizer step's of include/pivp_optim.h, the image loss's and the seed hook of include/pivp_loss.h, the
-sweep's input gradients and mode of include/pivp_input_grad.h, the recurrent state across rollouts of include/pivp_state.h, the gradients through it of include/pivp_state_grad.h).
+sweep's input gradients and mode of include/pivp_input_grad.h, the recurrent state across rollouts of include/pivp_state.h, the gradients through it of include/pivp_state_grad.h, the planner's goal-image cost of include/pivp_goal_cost.h).
 
 There is no CPU fallback: if the library is missing or fails to load, `load()` raises."""
 import ctypes
@@ -202,6 +202,10 @@ STATE_GRAD_SIGNATURES = {
     'pivp_state_grad_gather': (_i, [_c.POINTER(PivpConfig), _cells, _cells, _vp, _vp]),
     'pivp_state_grad_scatter': (_i, [_c.POINTER(PivpConfig), _vp, _cells, _vp]),
 }
+# ... and the symbol include/pivp_goal_cost.h declares (the cost of predicted frames against a goal image, with its gradient: CEM, scoring and refinement share it)
+GOAL_COST_SIGNATURES = {
+    'pivp_goal_image_cost': (_i, [_vp, _vp, _i, _vp, _f, _vp, _f, _f, _f, _f, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+}
 STATE_SEGMENTS = 14            # PIVP_STATE_SEGMENTS (include/pivp_state.h)
 SWEEP_PARAMS, SWEEP_BUILTIN_LOSS = 1, 2      # PIVP_SWEEP_* (include/pivp_input_grad.h)
 OPTIM_MAX_SEGMENTS = 1024      # PIVP_OPTIM_MAX_SEGMENTS
@@ -222,7 +226,7 @@ def load():
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(DATA_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items())
                               + list(LOSS_SIGNATURES.items()) + list(INPUT_GRAD_SIGNATURES.items()) + list(STATE_SIGNATURES.items())
-                              + list(STATE_GRAD_SIGNATURES.items())):
+                              + list(STATE_GRAD_SIGNATURES.items()) + list(GOAL_COST_SIGNATURES.items())):
         fn = getattr(lib, name)   # AttributeError if the ABI and the header drift apart
         fn.restype = res
         fn.argtypes = args
@@ -233,7 +237,7 @@ def load():
         shipped = _digest.source_digest()
     except OSError as e:      # a copied / installed package without csrc/ or the repo's include/: say what is missing instead of a bare open() error
         raise RuntimeError('cannot check libpivp_hip.so against its sources: %s is missing (the package needs csrc/*.hip, csrc/*.h and '
-                           '../include/pivp_hip.h, pivp_data.h, pivp_input_grad.h, pivp_loss.h, pivp_state.h, pivp_state_grad.h and pivp_optim.h next to it; there is no CPU fallback)' % e.filename) from e
+                           '../include/pivp_hip.h, pivp_data.h, pivp_input_grad.h, pivp_loss.h, pivp_state.h, pivp_state_grad.h, pivp_goal_cost.h and pivp_optim.h next to it; there is no CPU fallback)' % e.filename) from e
     built = lib.pivp_build_digest().decode()
     if built != shipped:
         raise RuntimeError(

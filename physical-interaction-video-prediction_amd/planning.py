@@ -16,9 +16,15 @@ horizon is optimised (the MPC case).
 
 Closed-loop control: `cem_plan(..., belief=)` and `score_actions(..., belief=)` start every candidate from ONE recurrent state (`state.RecurrentState`,
 what a `Model(carry_state=True)` holds after it has seen the frames so far) and the newest frame, instead of re-encoding the observed frames for every
-candidate in every iteration."""
+candidate in every iteration.
+
+Planning on a goal image: `GoalImageCost` specifies the task as a frame to reach (weighted squared / absolute error of the predicted frames, with an
+optional region of interest and step weights); `goal_image_cost` is one call of pivp_goal_image_cost (include/pivp_goal_cost.h), value and gradient
+on the device.  `cem_plan(goal_image=)`, `score_actions(goal_image=)` and `refine_actions(goal_image=)` share it, and `cem_refine` composes the two
+optimisers on that one cost: CEM chooses a plan, gradient descent polishes it, the cheapest sequence is returned."""
 import contextlib
 import ctypes
+import inspect
 import math
 from types import SimpleNamespace
 
@@ -121,7 +127,7 @@ def _starting_from(model, state):
         model._state = kept
 
 
-def score_actions(model, context_images, state, candidates, designated_rc, goal_rc, belief=None):
+def score_actions(model, context_images, state, candidates, designated_rc, goal_rc, belief=None, goal_image=None):
     """Cost of K candidate action sequences for moving one designated pixel to a goal.
 
     belief: a batch-1 `RecurrentState` (carry_state=True models).  context_images is then (1, 1, 3, H, W), the newest frame only; `state` its robot
@@ -130,7 +136,11 @@ def score_actions(model, context_images, state, candidates, designated_rc, goal_
 
     context_images (ctx, 1, 3, H, W), state (1, 5): what the robot sees now; candidates (K, T-1, 5); designated_rc, goal_rc: (row, col) on the
     last context frame.  The context is replicated K times and ONE `imagine` runs at batch K with normalised distributions; the cost of
-    candidate k is the sum over the predicted frames of `expected_distance` to the goal.  -> (K,) tensor on the model's device."""
+    candidate k is the sum over the predicted frames of `expected_distance` to the goal.  -> (K,) tensor on the model's device.
+
+    goal_image: a `GoalImageCost` or a bare (3, H, W) array (its defaults): `goal_image_cost` of the predicted frames -- the cost `cem_plan(goal_image=)`
+    ranks by -- is added to the pixel term, or, with designated_rc and goal_rc both None, returned instead of it (the rollout then runs without
+    planes).  None: the path and the bits of a call without the argument."""
     ctx_shape = Model._host_shape(context_images)
     if len(ctx_shape) != 5 or ctx_shape[1] != 1:
         raise ValueError('context_images must be (ctx, 1, 3, H, W), got shape %s' % (ctx_shape,))
@@ -143,18 +153,33 @@ def score_actions(model, context_images, state, candidates, designated_rc, goal_
         raise ValueError('state must be (1, 5), got shape %s' % (Model._host_shape(state),))
     K = cand_shape[0]
     H, W = ctx_shape[3:]
+    image = _as_goal_cost(goal_image)
+    pixels = designated_rc is not None or goal_rc is not None
+    if image is not None:
+        n_ctx = 1 if belief is not None else int(model.num_frame_before_prediction)
+        if cand_shape[1] < n_ctx:
+            raise ValueError('candidates cover %d steps; at least the %d context steps are needed' % (cand_shape[1], n_ctx))
+        image.check_frames(cand_shape[1] - (n_ctx - 1), K, H, W)
+    elif not pixels:
+        raise ValueError('no goal: give designated_rc and goal_rc (a pixel to move), goal_image (a frame to reach), or both')
     to_t = lambda a: a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float32)))
     ctx_k = to_t(context_images).expand(-1, K, -1, -1, -1)
     state_k = to_t(state).expand(K, -1)
     actions = to_t(candidates).transpose(0, 1)
-    rc = np.asarray(designated_rc).reshape(1, 1, 2)
-    planes = one_hot_planes(np.broadcast_to(rc, (K, 1, 2)), H, W)
+    planes = None
+    if pixels:
+        rc = np.asarray(designated_rc).reshape(1, 1, 2)
+        planes = one_hot_planes(np.broadcast_to(rc, (K, 1, 2)), H, W)
     with _starting_from(model, belief.expand(K) if belief is not None else None):
         if belief is not None:
-            model.imagine(ctx_k, actions, state_k, designated=planes, normalize=True, observed=1, advance=False)
+            gen = model.imagine(ctx_k, actions, state_k, designated=planes, normalize=True, observed=1, advance=False)
         else:
-            model.imagine(ctx_k, actions, state_k, designated=planes, normalize=True)
-    return expected_distance(model.pixel_distrib[:, :, 0], goal_rc).sum(dim=0)
+            gen = model.imagine(ctx_k, actions, state_k, designated=planes, normalize=True)
+    cost = expected_distance(model.pixel_distrib[:, :, 0], goal_rc).sum(dim=0) if pixels else None
+    if image is not None:
+        c_image = goal_image_cost(gen[n_ctx - 1:], image)[0]
+        cost = c_image if cost is None else cost + c_image
+    return cost
 
 
 MAX_CEM_SAMPLES = 1024
@@ -197,8 +222,154 @@ def _per_step(a, what, horizon, default):
     return np.ascontiguousarray(np.broadcast_to(a, (horizon, 5)))
 
 
+# ---- the goal-image cost (include/pivp_goal_cost.h): one op on the device for CEM, scoring and refinement -----------------------------------
+def _finite_number(v, what, low=None):
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v) \
+            or abs(float(v)) > float(np.finfo(np.float32).max):      # (the library takes float32 scalars)
+        raise ValueError('%s must be a finite number, not %r' % (what, v))
+    if low is not None and v < low:
+        raise ValueError('%s must be >= %g, not %r' % (what, low, v))
+    return float(v)
+
+
+class GoalImageCost(object):
+    """The cost of predicted frames against a goal image, the other standard task specification of visual MPC (Finn & Levine 2017; Ebert et al. 2018):
+
+        per_step[s][k] = sum_c sum_i pixel_weight[i] * (mse * d*d + l1 * |d|) / (3 * sum(pixel_weight)),   d = frame[s][k][c][i] - goal[c][i]
+        cost[k]        = weight * sum_s step_weights[s] * per_step[s][k]
+
+    (include/pivp_goal_cost.h).  A host-validated spec: every complaint is a ValueError raised here, before the GPU or the library is needed.
+    goal_image: (3, H, W) -- or (B, 3, H, W), one goal per sample, for `refine_actions`; an array, or a tensor (taken where it lies).  mse, l1:
+    finite, non-negative, not both zero.  pixel_weight: (H, W), finite, non-negative with a positive sum -- the region of interest; None: all ones.
+    step_weights: (horizon,), finite; None: 1 / horizon each (the mean over the steps).  weight: the factor on the whole cost (what `cem_plan` adds
+    to the pixel cost when both goals are given).  bad_cost: what a frame that is not finite (a diverged rollout) costs per step; default mse + l1,
+    the cost of a frame that is off by 1 everywhere.  The defaults are `refine_actions`' bare goal_image cost."""
+
+    def __init__(self, goal_image, mse=1.0, l1=0.0, pixel_weight=None, step_weights=None, weight=1.0, bad_cost=None):
+        shape = Model._host_shape(goal_image)
+        if len(shape) not in (3, 4) or shape[-3] != 3 or shape[-2] < 2 or shape[-1] < 2 or shape[0] < 1:
+            raise ValueError('goal_image must be (3, H, W) or (B, 3, H, W), got shape %s' % (shape,))
+        if torch.is_tensor(goal_image):
+            if not goal_image.is_floating_point():
+                raise ValueError('goal_image must be a floating-point tensor, not %s' % (goal_image.dtype,))
+            self.goal_image = goal_image.detach()
+        else:
+            g = _host_array(goal_image, 'goal_image')
+            if not np.isfinite(g).all():
+                raise ValueError('goal_image must be finite')
+            self.goal_image = np.ascontiguousarray(g, dtype=np.float32)
+        self.shape = tuple(int(n) for n in shape)
+        self.hw = self.shape[-2:]
+        self.batch = self.shape[0] if len(shape) == 4 else None
+        self.mse, self.l1 = _finite_number(mse, 'mse', 0.0), _finite_number(l1, 'l1', 0.0)
+        if self.mse == 0.0 and self.l1 == 0.0:
+            raise ValueError('mse and l1 are both zero: the cost is empty')
+        self.pixel_weight = None
+        if pixel_weight is not None:
+            w = _host_array(pixel_weight, 'pixel_weight')
+            if w.shape != self.hw:
+                raise ValueError('pixel_weight must be (%d, %d), got shape %s' % (self.hw + (w.shape,)))
+            if not np.isfinite(w).all() or (w < 0).any():
+                raise ValueError('pixel_weight must be finite and non-negative')
+            w = np.ascontiguousarray(w, dtype=np.float32)
+            if not float(w.sum(dtype=np.float64)) > 0.0:
+                raise ValueError('pixel_weight sums to zero: no pixel counts')
+            self.pixel_weight = w
+        self.step_weights = None
+        if step_weights is not None:
+            sw = _host_array(step_weights, 'step_weights')
+            if sw.ndim != 1 or sw.shape[0] < 1 or not np.isfinite(sw).all():
+                raise ValueError('step_weights must be finite and (horizon,), got shape %s' % (sw.shape,))
+            self.step_weights = np.ascontiguousarray(sw, dtype=np.float32)
+        self.weight = _finite_number(weight, 'weight')
+        self.bad_cost = self.mse + self.l1 if bad_cost is None else _finite_number(bad_cost, 'bad_cost')
+        if not math.isfinite(self.inv_norm()) or not np.float32(self.inv_norm()) > 0:
+            raise ValueError('pixel_weight is too large or too small to normalise by in float32: its sum is %r' % (1.0 / (3.0 * self.inv_norm()),))
+
+    def inv_norm(self):
+        """1 / (3 * sum(pixel_weight)), in double (the weights as the device sees them, float32)."""
+        if self.pixel_weight is None:
+            return 1.0 / (3.0 * self.hw[0] * self.hw[1])
+        return 1.0 / (3.0 * float(self.pixel_weight.sum(dtype=np.float64)))
+
+    def steps(self, horizon):
+        """-> the (horizon,) float32 step weights; ValueError if step_weights was given for another horizon."""
+        if self.step_weights is None:
+            return np.full(horizon, 1.0 / horizon, dtype=np.float32)
+        if self.step_weights.shape != (horizon,):
+            raise ValueError('the goal image\'s step_weights must be (%d,), got shape %s' % (horizon, self.step_weights.shape))
+        return self.step_weights
+
+    def check_frames(self, horizon, K, H, W, per_sample=False):
+        """ValueError if (horizon, K, 3, H, W) frames cannot be scored against this goal.  per_sample: a (K, 3, H, W) goal is served."""
+        if self.hw != (H, W):
+            raise ValueError('goal_image is of %dx%d frames, the frames are %dx%d' % (self.hw + (H, W)))
+        if self.batch is not None and not (per_sample and self.batch == K):
+            raise ValueError('goal_image must be (3, %d, %d)%s, got shape %s' % (H, W, ' or (%d, 3, %d, %d)' % (K, H, W) if per_sample else '', self.shape))
+        if W + 4 > 256 or H > 32768:
+            raise ValueError('%dx%d frames: the goal-image cost serves widths up to 252 and heights up to 32768' % (H, W))
+        self.steps(horizon)
+
+    def __repr__(self):
+        return 'GoalImageCost(goal_image=%s, mse=%g, l1=%g, pixel_weight=%s, step_weights=%s, weight=%g, bad_cost=%g)' % (
+            self.shape, self.mse, self.l1, None if self.pixel_weight is None else self.hw,
+            None if self.step_weights is None else self.step_weights.shape, self.weight, self.bad_cost)
+
+
+def _as_goal_cost(goal_image, what='goal_image'):
+    """None | GoalImageCost | a bare (3, H, W) array (the defaults) -> None | GoalImageCost."""
+    if goal_image is None or isinstance(goal_image, GoalImageCost):
+        return goal_image
+    spec = GoalImageCost(goal_image)
+    if spec.batch is not None:
+        raise ValueError('%s must be (3, H, W), got shape %s' % (what, spec.shape))
+    return spec
+
+
+def _goal_upload(spec, horizon, dev):
+    """The goal, the pixel weights and the step weights of `spec` on the device: uploaded ONCE, in front of whatever loop launches the op."""
+    to_dev = lambda v: v.to(device=dev, dtype=torch.float32).contiguous() if torch.is_tensor(v) else torch.from_numpy(v).to(dev)
+    return SimpleNamespace(spec=spec, goal=to_dev(spec.goal_image), G=spec.batch if spec.batch is not None else 1,
+                           pixel_w=None if spec.pixel_weight is None else to_dev(spec.pixel_weight), step_w=to_dev(spec.steps(horizon)),
+                           inv_norm=spec.inv_norm())
+
+
+def _goal_launch(d, frames_ptr, S, K, H, W, cost_ptr, per_step_ptr, grad_ptr, accumulate, stream):
+    """ONE pivp_goal_image_cost on the buffers of `_goal_upload` (the caller holds the device context)."""
+    sp = d.spec
+    _lib.check(_lib.load().pivp_goal_image_cost(frames_ptr, d.goal.data_ptr(), d.G, None if d.pixel_w is None else d.pixel_w.data_ptr(), d.inv_norm,
+                                                d.step_w.data_ptr(), sp.mse, sp.l1, sp.bad_cost, sp.weight, int(accumulate), cost_ptr, per_step_ptr,
+                                                grad_ptr, S, K, H, W, stream), 'pivp_goal_image_cost')
+
+
+def goal_image_cost(frames, spec, want_grad=False):
+    """The cost of predicted frames (S, K, 3, H, W), a float32 tensor on the device (`imagine`'s return value from the first predicted frame on),
+    under the `GoalImageCost` spec: one pivp_goal_image_cost call (include/pivp_goal_cost.h), a thin wrapper as `losses.image_loss` is for its op.
+    -> (cost (K,), per_step (S, K), grad (S, K, 3, H, W) = d cost[k] / d frames, or None).  The goal is (3, H, W) or (K, 3, H, W).  Stream-ordered
+    on the frames' device; no host synchronisation (the spec's arrays are uploaded by this call: `cem_plan` and `refine_actions` do that once)."""
+    if not isinstance(spec, GoalImageCost):
+        raise ValueError('spec must be a GoalImageCost, not %r' % (spec,))
+    if not torch.is_tensor(frames) or frames.dim() != 5 or frames.shape[2] != 3 or frames.dtype != torch.float32 or frames.shape[0] < 1 or frames.shape[1] < 1:
+        raise ValueError('frames must be a float32 tensor (S, K, 3, H, W), got %s' % (tuple(frames.shape) if torch.is_tensor(frames) else type(frames).__name__,))
+    S, K, _, H, W = frames.shape
+    spec.check_frames(S, K, H, W, per_sample=True)
+    if not frames.is_cuda:
+        raise RuntimeError('frames must be on the GPU: this path has no CPU fallback')
+    _lib.load()
+    dev = frames.device
+    with torch.cuda.device(dev):
+        frames = frames.contiguous()
+        d = _goal_upload(spec, S, dev)
+        cost = torch.empty((K,), dtype=torch.float32, device=dev)
+        per_step = torch.empty((S, K), dtype=torch.float32, device=dev)
+        grad = torch.empty_like(frames) if want_grad else None
+        _goal_launch(d, frames.data_ptr(), S, K, H, W, cost.data_ptr(), per_step.data_ptr(), grad.data_ptr() if want_grad else None, 0,
+                     torch.cuda.current_stream(dev).cuda_stream)
+    return cost, per_step, grad
+
+
 def _check_cem_args(model, context_images, state, designated_rc, goal_rc, horizon, past_actions, iterations, samples, elites, init_mean, init_std,
-                    min_std, alpha, action_low, action_high, step_weights, plane_weights, miss_cost, chunk, seed, belief=None):
+                    min_std, alpha, action_low, action_high, step_weights, plane_weights, miss_cost, chunk, seed, belief=None, goal_image=None):
     """Every complaint of `cem_plan` is a ValueError raised here, before the GPU or the library is needed.  -> the checked host-side values."""
     ctx = int(model.num_frame_before_prediction)
     si = Model._host_shape(context_images)
@@ -225,11 +396,23 @@ def _check_cem_args(model, context_images, state, designated_rc, goal_rc, horizo
         chunk = samples
     if isinstance(chunk, bool) or not isinstance(chunk, (int, np.integer)) or chunk < 1 or chunk > samples or samples % chunk:
         raise ValueError('chunk must divide samples = %d, not %r' % (samples, chunk))
-    designated = _pixel_coords(designated_rc, 'designated_rc', H, W, whole=True)
-    goals = _pixel_coords(goal_rc, 'goal_rc', H, W, whole=False)
-    P = designated.shape[0]
-    if goals.shape[0] != P:
-        raise ValueError('goal_rc holds %d goals for %d designated pixels' % (goals.shape[0], P))
+    image = _as_goal_cost(goal_image)
+    if image is not None:
+        image.check_frames(int(horizon), int(samples), H, W)
+    pixels = designated_rc is not None or goal_rc is not None
+    if not pixels and image is None:
+        raise ValueError('no goal: give designated_rc and goal_rc (pixels to move), goal_image (a frame to reach), or both')
+    if pixels:
+        designated = _pixel_coords(designated_rc, 'designated_rc', H, W, whole=True)
+        goals = _pixel_coords(goal_rc, 'goal_rc', H, W, whole=False)
+        P = designated.shape[0]
+        if goals.shape[0] != P:
+            raise ValueError('goal_rc holds %d goals for %d designated pixels' % (goals.shape[0], P))
+    else:      # a goal image alone: the rollouts run without planes and pivp_plan_cost is not called
+        if plane_weights is not None or miss_cost is not None or step_weights is not None:
+            raise ValueError('plane_weights, miss_cost and step_weights belong to the designated pixels: without designated_rc / goal_rc they must be '
+                             'None (the goal image has its own step_weights, in its GoalImageCost)')
+        designated, goals, P = np.zeros((0, 2)), np.zeros((0, 2)), 0
     if ctx > 1:
         if past_actions is None:
             raise ValueError('past_actions (%d, 5) is required with %d context frames: the actions taken between the observed frames' % (ctx - 1, ctx))
@@ -272,12 +455,12 @@ def _check_cem_args(model, context_images, state, designated_rc, goal_rc, horizo
     return SimpleNamespace(ctx=ctx, H=H, W=W, P=P, K=int(samples), M=int(elites), chunk=int(chunk), horizon=int(horizon), iterations=int(iterations),
                            designated=designated, goals=goals, past=past, mean=mean, std=std, low=bounds[0], high=bounds[1],
                            step_w=weights[0], plane_w=weights[1], miss_cost=float(miss_cost), min_std=float(min_std), alpha=float(alpha), seed=int(seed),
-                           belief=belief)
+                           belief=belief, image=image)
 
 
 def cem_plan(model, context_images, state, designated_rc, goal_rc, horizon, past_actions=None, iterations=3, samples=32, elites=8, init_mean=None,
              init_std=1.0, min_std=1e-3, alpha=0.0, action_low=None, action_high=None, step_weights=None, plane_weights=None, miss_cost=None,
-             chunk=None, seed=0, trace=False, belief=None):
+             chunk=None, seed=0, trace=False, belief=None, goal_image=None):
     """Cross-entropy-method planning of `horizon` actions that move P designated pixels to their goals, entirely on the model's device.
 
     context_images (ctx, 1, 3, H, W), state (1, 5): what the robot sees now; designated_rc (P, 2) whole (row, col) pixels of the LAST context frame,
@@ -300,11 +483,19 @@ def cem_plan(model, context_images, state, designated_rc, goal_rc, horizon, past
     advance=False) instead of ctx-1 + horizon from zeros; the model's own carried state is what it was afterwards.  None: the path and the bits of
     a call without the argument.  (Belief and no-belief planning agree to rounding, not bit for bit: the observing steps ran at another batch size.)
 
+    goal_image: a `GoalImageCost`, or a bare (3, H, W) array which gets its defaults -- the task as a frame to reach.  Each chunk's frames are then
+    scored by ONE pivp_goal_image_cost call (include/pivp_goal_cost.h) behind the rollout, on the stream.  designated_rc and goal_rc may then both be
+    None: the rollouts run without planes, pivp_plan_cost is not called, cost = the image cost (plane_weights, miss_cost and step_weights must be None; `mass` /
+    `edist` are (horizon, samples, 0)).  With both kinds of goal pivp_plan_cost writes cost first and the image cost accumulates weight * its value
+    onto it; `step_weights` weighs the pixel term, the image term has its own in the spec.  trace=True: each record also holds `image_cost`
+    (horizon, samples), the per-step image costs.  The goal and its weights are uploaded once, in front of the loop.  None: the launches and the bits
+    of a call without the argument.
+
     Side effect: the rollouts run on `model` as `imagine` does, so afterwards `model.gen_images` / `gen_states` hold the LAST rollout (the last
     chunk of the last iteration), `pixel_distrib` / `pixel_mass` are None and `backward()` raises until the model is called again.  With
     chunk < samples every rollout copies its slice of the action buffer and allocates its own frames, on the stream, without a host round trip."""
     a = _check_cem_args(model, context_images, state, designated_rc, goal_rc, horizon, past_actions, iterations, samples, elites, init_mean,
-                        init_std, min_std, alpha, action_low, action_high, step_weights, plane_weights, miss_cost, chunk, seed, belief)
+                        init_std, min_std, alpha, action_low, action_high, step_weights, plane_weights, miss_cost, chunk, seed, belief, goal_image)
     with torch.cuda.device(model.device) if torch.cuda.is_available() else contextlib.nullcontext():
         return _cem_iterate(model, a, _cem_upload(model, a, context_images, state), trace)
 
@@ -327,9 +518,16 @@ def _cem_upload(model, a, context_images, state):
     for name, v in parts:
         setattr(b, name, packed[at:at + np.size(v)].view(np.shape(v)))
         at += np.size(v)
-    b.planes = torch.zeros((C, P, H * W), dtype=torch.float32, device=dev)
-    b.planes.scatter_(2, b.pixel.to(torch.int64).view(1, P, 1).expand(C, P, 1), 1.0)      # one-hot planes, built on the device (H * W < 2^24: exact)
-    b.planes = b.planes.view(C, P, H, W)
+    b.planes = None
+    if P:
+        b.planes = torch.zeros((C, P, H * W), dtype=torch.float32, device=dev)
+        b.planes.scatter_(2, b.pixel.to(torch.int64).view(1, P, 1).expand(C, P, 1), 1.0)      # one-hot planes, built on the device (H * W < 2^24: exact)
+        b.planes = b.planes.view(C, P, H, W)
+    b.image = None
+    if getattr(a, 'image', None) is not None:      # the goal image and its weights: uploaded here, read by every pivp_goal_image_cost of the loop
+        b.image = _goal_upload(a.image, Hh, dev)
+        b.image_cost = new(Hh, K)
+        b.image_part = new(Hh, C) if C != K else None      # a chunk's per-step costs: [Hh][C] is not a slice of [Hh][K]
     b.actions = torch.zeros((steps, K, 5), dtype=torch.float32, device=dev)
     if t0:
         b.actions[:t0] = b.past.unsqueeze(1)
@@ -348,8 +546,8 @@ def _cem_upload(model, a, context_images, state):
 
 
 def _cem_iterate(model, a, b, trace=False):
-    """The loop of `cem_plan` on the buffers of `_cem_upload`: pivp_cem_update, the rollout, pivp_plan_cost -- stream-ordered launches and
-    device-to-device copies only (tests/test_gpu_planning.py runs it under torch's sync debug mode)."""
+    """The loop of `cem_plan` on the buffers of `_cem_upload`: pivp_cem_update, the rollout, pivp_plan_cost and / or pivp_goal_image_cost --
+    stream-ordered launches and device-to-device copies only (tests/test_gpu_planning.py runs it under torch's sync debug mode)."""
     lib = _lib.load()
     P, K, M, C, Hh = a.P, a.K, a.M, a.chunk, a.horizon
     t0, steps = a.ctx - 1, a.ctx - 1 + Hh
@@ -361,7 +559,7 @@ def _cem_iterate(model, a, b, trace=False):
                                        b.elite_idx.data_ptr(), K, steps, t0, M, a.alpha, a.min_std, ctypes.c_ulonglong(a.seed), it, stream),
                    'pivp_cem_update')
 
-    belief = getattr(b, 'belief', None)
+    belief, image = getattr(b, 'belief', None), getattr(b, 'image', None)
     from_belief = dict(observed=1, advance=False) if belief is not None else {}
     records = []
     with _starting_from(model, belief):      # (the expanded belief, read by every rollout and written by none; None: every rollout from zeros)
@@ -372,17 +570,25 @@ def _cem_iterate(model, a, b, trace=False):
                 if trace:
                     records[-1]['elites'] = b.elite_idx.clone()
             for k0 in range(0, K, C):
-                _, track = model._rollout_predict(b.context, b.actions if C == K else b.actions[:, k0:k0 + C].contiguous(), b.state, b.planes, t0,
+                gen, track = model._rollout_predict(b.context, b.actions if C == K else b.actions[:, k0:k0 + C].contiguous(), b.state, b.planes, t0,
                                                   **from_belief)
-                m_out, e_out = (b.mass, b.edist) if C == K else b.part
-                _lib.check(lib.pivp_plan_cost(track.data_ptr(), b.goals.data_ptr(), b.step_w.data_ptr(), b.plane_w.data_ptr(), a.miss_cost,
-                                              b.cost.data_ptr() + 4 * k0, m_out.data_ptr(), e_out.data_ptr(), Hh, C, P, a.H, a.W, stream),
-                           'pivp_plan_cost')
-                if C != K and trace:
-                    b.mass[:, k0:k0 + C].copy_(m_out)
-                    b.edist[:, k0:k0 + C].copy_(e_out)
+                if P:
+                    m_out, e_out = (b.mass, b.edist) if C == K else b.part
+                    _lib.check(lib.pivp_plan_cost(track.data_ptr(), b.goals.data_ptr(), b.step_w.data_ptr(), b.plane_w.data_ptr(), a.miss_cost,
+                                                  b.cost.data_ptr() + 4 * k0, m_out.data_ptr(), e_out.data_ptr(), Hh, C, P, a.H, a.W, stream),
+                               'pivp_plan_cost')
+                    if C != K and trace:
+                        b.mass[:, k0:k0 + C].copy_(m_out)
+                        b.edist[:, k0:k0 + C].copy_(e_out)
+                if image is not None:      # the frames from the first predicted one on; onto the pixel cost where there is one
+                    i_out = b.image_cost if C == K else b.image_part
+                    _goal_launch(image, gen[t0:].data_ptr(), Hh, C, a.H, a.W, b.cost.data_ptr() + 4 * k0, i_out.data_ptr(), None, 1 if P else 0, stream)
+                    if C != K and trace:
+                        b.image_cost[:, k0:k0 + C].copy_(i_out)
             if trace:
                 records.append(dict(actions=b.actions.clone(), cost=b.cost.clone(), mass=b.mass.clone(), edist=b.edist.clone()))
+                if image is not None:
+                    records[-1]['image_cost'] = b.image_cost.clone()
         update(True, a.iterations)      # the last candidates count too: best_*, mean and std reflect them (the resampled rows are not used)
         b.per_iter[a.iterations - 1:].copy_(b.best_cost)
         if trace:
@@ -431,7 +637,9 @@ def _check_refine_args(model, context_images, state, actions, goal_image, cost_f
         raise ValueError('exactly one of goal_image and cost_fn must be given')
     if cost_fn is not None and not callable(cost_fn):
         raise ValueError('cost_fn must be callable: cost_fn(gen (T-ctx, B, 3, H, W)) -> (B,)')
-    if goal_image is not None:
+    if isinstance(goal_image, GoalImageCost):
+        goal_image.check_frames(sa[0] + 1 - ctx, B, H, W, per_sample=True)
+    elif goal_image is not None:
         sg = Model._host_shape(goal_image)
         if sg not in ((3, H, W), (B, 3, H, W)):
             raise ValueError('goal_image must be (3, %d, %d) or (%d, 3, %d, %d), got shape %s' % (H, W, B, H, W, sg))
@@ -472,7 +680,8 @@ def refine_actions(model, context_images, state, actions, goal_image=None, cost_
     Per iteration: ONE feed-self training-mode rollout (`model(...)` under config.train with scheduled sampling off, whatever the model's
     scheduled_sampling_k is; the frames after the context are zeros and play no part), the cost of the predictions gen = gen_images[ctx-1:]
     (T-ctx, B, 3, H, W) in torch -- cost_fn(gen) -> (B,), differentiated by autograd, or, with goal_image (3, H, W) / (B, 3, H, W), the squared error
-    to it averaged over steps and pixels --, `backward(frame_grad=d sum(cost) / d gen, input_grad=True, params=False, builtin_loss=False)`, the past
+    to it averaged over steps and pixels; a `GoalImageCost` as goal_image takes value and gradient from one pivp_goal_image_cost call instead (the
+    cost `cem_plan(goal_image=)` ranks by; its defaults are the bare array's cost, to rounding) --, `backward(frame_grad=d sum(cost) / d gen, input_grad=True, params=False, builtin_loss=False)`, the past
     rows of the gradient zeroed, ONE pivp_adam_step on the flat action buffer (beta1 0.9, beta2 0.999, eps 1e-8, its own moments, the bias-corrected
     step size formed on the host) and the clamp to bounds = (low, high), each a scalar, (5,) or None.  Stream-ordered launches only: nothing
     synchronises with the host.  A last rollout scores the returned sequence.
@@ -480,13 +689,14 @@ def refine_actions(model, context_images, state, actions, goal_image=None, cost_
     -> (actions (T-1, B, 5), costs (steps + 1, B)): the refined sequence and the cost of every sample in front of each update and behind the last;
     device tensors.  lr = 0 returns the input's bits.
 
-    It knows nothing of `cem_plan`; refining CEM's plan is the caller's three lines:
+    It knows nothing of `cem_plan`; refining CEM's plan on the cost that chose it is `cem_refine`, in short
 
-        plan = cem_plan(model, context, state, designated_rc, goal_rc, horizon, past_actions=past)
+        spec = GoalImageCost(goal)
+        plan = cem_plan(model, context, state, None, None, horizon, past_actions=past, goal_image=spec)
         seq = torch.cat((torch.as_tensor(past, dtype=torch.float32, device=plan.actions.device).view(-1, 5), plan.actions)).unsqueeze(1)
-        refined, costs = refine_actions(train_model, context, state, seq, goal_image=goal, past_actions=past)
+        refined, costs = refine_actions(model, context, state, seq, goal_image=spec, past_actions=past)
 
-    (`train_model`: the same weights with keep_activations=True.)  Side effect: the model holds the last rollout; its parameter gradients are
+    (`model`: built with keep_activations=True.)  Side effect: the model holds the last rollout; its parameter gradients are
     unspecified afterwards (`cleargrads()` before training on)."""
     a = _check_refine_args(model, context_images, state, actions, goal_image, cost_fn, steps, lr, past_actions, bounds)
     with torch.cuda.device(model.device) if torch.cuda.is_available() else contextlib.nullcontext():
@@ -508,7 +718,11 @@ def _refine_upload(model, a, context_images, state, actions, goal_image, past_ac
     if a.n_past:
         past = model._as_device(past_actions, (5,))
         b.actions[:a.n_past] = past if past.dim() == 3 else past.unsqueeze(1)
-    b.goal = None if goal_image is None else model._as_device(goal_image, ())
+    b.goal, b.goal_cost = None, None
+    if isinstance(goal_image, GoalImageCost):      # the spec's goal and weights: uploaded here, read by the loop's one pivp_goal_image_cost per iteration
+        b.goal_cost = _goal_upload(goal_image, T - a.ctx, dev)
+    elif goal_image is not None:
+        b.goal = model._as_device(goal_image, ())
     to_dev = lambda v: None if v is None else torch.from_numpy(np.asarray(v, dtype=np.float32)).to(dev)
     b.low, b.high = to_dev(a.low), to_dev(a.high)
     return b
@@ -532,6 +746,14 @@ def _refine_iterate(model, a, b, cost_fn=None, adam=_adam_launch):
         finally:
             model.scheduled_sampling_k = k
         gen = model._gen[a.ctx - 1:]
+        spec = getattr(b, 'goal_cost', None)
+        if cost_fn is None and spec is not None:      # a GoalImageCost: value and d sum(cost) / d gen from ONE op call (include/pivp_goal_cost.h)
+            c = torch.empty((a.B,), dtype=torch.float32, device=gen.device)
+            per_step = torch.empty((nf, a.B), dtype=torch.float32, device=gen.device)
+            grad = torch.empty_like(gen) if want_grad else None
+            _goal_launch(spec, gen.data_ptr(), nf, a.B, a.H, a.W, c.data_ptr(), per_step.data_ptr(), grad.data_ptr() if want_grad else None, 0,
+                         torch.cuda.current_stream(gen.device).cuda_stream)
+            return c, grad
         if cost_fn is None:      # mean over steps and pixels of the squared error, per sample; its gradient in closed form
             diff = gen - b.goal
             return (diff * diff).mean(dim=(0, 2, 3, 4)), (diff * (2.0 / (nf * 3 * a.H * a.W)) if want_grad else None)
@@ -559,3 +781,82 @@ def _refine_iterate(model, a, b, cost_fn=None, adam=_adam_launch):
             torch.minimum(free, b.high, out=free)
     costs[a.iters].copy_(rollout_cost(False)[0])
     return p, costs
+
+
+def cem_refine(model, context_images, state, horizon, goal_image, past_actions=None, refine_steps=10, lr=0.05, **cem_arguments):
+    """CEM on a goal image, then gradient refinement of its plan on the SAME cost: `cem_plan(goal_image=)` and `refine_actions(goal_image=)` share one
+    `GoalImageCost`, so the polish descends the objective that chose the plan.
+
+    model: built with keep_activations=True (the rollouts of CEM run on its inference plan, refinement on its training plan); context_images
+    (ctx, 1, 3, H, W), state (1, 5), past_actions (ctx-1, 5) as `cem_plan` takes them; goal_image: a `GoalImageCost` or a bare (3, H, W) array.
+    cem_arguments: `cem_plan`'s keywords (iterations, samples, elites, init_mean, init_std, min_std, alpha, action_low, action_high, chunk, seed,
+    trace).  The pixel goals and a belief are not served here.
+
+    After CEM, `refine_actions` runs `refine_steps` Adam steps of size `lr` at batch 2, from CEM's best sequence and from its final mean, the past
+    actions held fixed and CEM's action bounds passed as `bounds`.  The cheapest of the three sequences -- CEM's best (0), the refined best (1), the
+    refined mean (2) -- is returned, picked by argmin / index_select on the device: nothing synchronises with the host.
+
+    -> an object with `actions` (horizon, 5), `cost`, `source` (0 / 1 / 2, an int64 scalar tensor), `cem` (what `cem_plan` returned) and
+    `refine_costs` (refine_steps + 1, 2).  `cost` is never above `cem.cost`.  (The refined costs come from training-plan rollouts, CEM's from
+    inference-plan rollouts of the same weights: the two agree to rounding, so does `score_actions(goal_image=)` on the returned actions.)"""
+    a = _check_cem_refine_args(model, context_images, state, horizon, goal_image, past_actions, refine_steps, lr, cem_arguments)
+    with torch.cuda.device(model.device) if torch.cuda.is_available() else contextlib.nullcontext():
+        return _cem_refine_iterate(model, a, _cem_refine_upload(model, a, context_images, state))
+
+
+def _check_cem_refine_args(model, context_images, state, horizon, goal_image, past_actions, refine_steps, lr, cem_arguments):
+    """Every complaint of `cem_refine` is a ValueError (an unknown keyword: a TypeError) raised here, before the GPU or the library is needed.
+    -> the checked values of its two stages: `cem` (`_check_cem_args`) and `refine` (`_check_refine_args` at batch 2)."""
+    if not getattr(model, 'keep_activations', False):
+        raise ValueError('cem_refine back-propagates through the rollout: the model needs keep_activations=True')
+    for name in ('designated_rc', 'goal_rc', 'step_weights', 'plane_weights', 'miss_cost'):
+        if cem_arguments.get(name) is not None:
+            raise ValueError('cem_refine plans and refines on the goal image alone: %s is not served' % name)
+    if cem_arguments.get('belief') is not None:
+        raise ValueError('cem_refine does not plan from a belief: refinement re-encodes the context frames')
+    if goal_image is None:
+        raise ValueError('cem_refine needs a goal_image')
+    spec = _as_goal_cost(goal_image)
+    if spec.batch is not None:
+        raise ValueError('goal_image must be (3, H, W), got shape %s' % (spec.shape,))
+    kw = {n: q.default for n, q in inspect.signature(cem_plan).parameters.items() if q.default is not q.empty}
+    unknown = sorted(set(cem_arguments) - set(kw))
+    if unknown:
+        raise TypeError('cem_refine got unexpected keyword arguments %s' % (unknown,))
+    kw.update(cem_arguments)
+    trace = kw.pop('trace')
+    cem = _check_cem_args(model, context_images, state, None, None, horizon, past_actions, kw['iterations'], kw['samples'], kw['elites'], kw['init_mean'],
+                          kw['init_std'], kw['min_std'], kw['alpha'], kw['action_low'], kw['action_high'], None, None, None, kw['chunk'], kw['seed'],
+                          None, spec)
+    shaped = lambda *shape: np.broadcast_to(np.float32(0), shape)      # the refinement's arguments exist on the device only: their shapes are checked
+    low, high = kw['action_low'], kw['action_high']
+    refine = _check_refine_args(model, shaped(cem.ctx, 2, 3, cem.H, cem.W), shaped(2, 5), shaped(cem.ctx - 1 + cem.horizon, 2, 5), spec, None, refine_steps,
+                                lr, cem.past if cem.ctx > 1 else None, None if low is None and high is None else (low, high))
+    return SimpleNamespace(cem=cem, refine=refine, spec=spec, trace=bool(trace))
+
+
+def _cem_refine_upload(model, a, context_images, state):
+    """Everything both stages read or write, uploaded or built ONCE: `_cem_upload`'s buffers and `_refine_upload`'s at batch 2 (the two starting
+    sequences are written by the loop; the past rows are set here)."""
+    cem = _cem_upload(model, a.cem, context_images, state)
+    context2 = model._as_device(context_images, ()).expand(-1, 2, -1, -1, -1)
+    state2 = model._as_device(state, (5,)).expand(2, -1)
+    starts = torch.zeros((a.refine.steps_T, 2, 5), dtype=torch.float32, device=model.device)
+    refine = _refine_upload(model, a.refine, context2, state2, starts, a.spec, cem.past if a.refine.n_past else None)
+    return SimpleNamespace(cem=cem, refine=refine)
+
+
+def _cem_refine_iterate(model, a, b):
+    """`cem_refine` on its device buffers: `_cem_iterate`, two device-to-device copies of the starting sequences, `_refine_iterate`, the choice --
+    stream-ordered work only."""
+    plan = _cem_iterate(model, a.cem, b.cem, a.trace)
+    t0, T1 = a.cem.ctx - 1, a.refine.steps_T
+    b.refine.actions[t0:T1, 0].copy_(plan.actions)
+    b.refine.actions[t0:T1, 1].copy_(plan.mean)
+    refined, costs = _refine_iterate(model, a.refine, b.refine)
+    three_costs = torch.cat((plan.cost.view(1), costs[-1]))
+    three = torch.cat((plan.actions.unsqueeze(0), refined[t0:].transpose(0, 1)))      # (3, horizon, 5)
+    source = torch.argmin(three_costs)
+    pick = source.view(1)
+    return SimpleNamespace(actions=three.index_select(0, pick)[0], cost=three_costs.index_select(0, pick)[0], source=source, cem=plan,
+                           refine_costs=costs)
