@@ -69,6 +69,16 @@ typedef struct pivp_config {
     int stp_zero_border;   /* 0: clamp sampling coords (Chainer 2.0.x), 1: zero outside          */
 } pivp_config_t;
 
+/* The accepted domain.  pivp_plan_create returns PIVP_ERR_BADARG for everything outside it, before it allocates anything; what it accepts rolls out
+ * (pivp_rollout_forward / _predict) without a refusal half-way:
+ *   batch >= 1, seq_len >= 2, 1 <= context_frames < seq_len;
+ *   height, width >= 16 and multiples of 8, width <= 248 (the compositing kernels give a frame row padded by 4 the 256 threads of a block);
+ *   num_masks: CDNA 1 .. 10 (the motion head's finishers give each of its 25 * num_masks kernel taps a thread of one 256-thread block),
+ *              STP 1 .. 11, DNA 1 (TM:389-390).
+ * Training is narrower: pivp_rollout_backward serves CDNA with 1 .. 10 masks, STP with 2 .. 10 (the STP composite backward has no one-mask form; eleven
+ * masks pass the forward alone) and DNA, on frames whose composite-backward tile fits in LDS -- every mask count on frames up to 128 wide, which is as far as
+ * the sweep is validated; fewer masks on wider frames (csrc/backward_heads.hip, composite_bwd_serves).  A plan outside that is refused with PIVP_ERR_BADARG
+ * at the ENTRY of pivp_rollout_backward: nothing is enqueued, the gradients and the workspace keep their contents, and the plan stays usable for rollouts. */
 int pivp_plan_create(const pivp_config_t* cfg, pivp_plan_t** out);
 void pivp_plan_destroy(pivp_plan_t* plan);
 
@@ -211,6 +221,7 @@ int pivp_plan_set_grad_callback(pivp_plan_t* plan, pivp_grad_group_cb cb, void* 
  * sweep (the optimizer step) is ordered behind every gradient either way. */
 int pivp_plan_set_group_join(pivp_plan_t* plan, int join);
 int pivp_plan_group_wait(pivp_plan_t* plan, int group, void* stream);
+/* The backward sweep of the last pivp_rollout_forward.  PIVP_ERR_BADARG before the first launch for a plan outside the training domain (pivp_plan_create). */
 int pivp_rollout_backward(pivp_plan_t* plan, const float* images, const float* actions, const float* states,
                           const unsigned char* gt_select, const float* gen_images, const float* gen_states, void* stream);
 

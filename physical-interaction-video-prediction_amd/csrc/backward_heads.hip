@@ -247,15 +247,26 @@ __global__ __launch_bounds__(CBC_NT) void composite_bwd_cdna_kernel(const float*
 
 int composite_bwd_tiles(int H, int W) { const int tr = composite_bwd_rows(W); return (H + tr - 1) / tr; }
 
-int composite_bwd_cdna(const float* prev, const float* logits, const float* layer0, const float* kerns, const float* go,
-                       float* dmk, float* dz, float* dkpart, float* dprev, int dprev_accum, int B, int H, int W, int NM, hipStream_t s) {
-    PIVP_CHECK_ARG(prev && logits && layer0 && kerns && go && dmk && dz && dkpart && B > 0 && H > 1 && W > 1 && NM >= 1 && NM <= 10);
+// bytes of LDS a block of the CDNA composite backward stages
+static size_t composite_bwd_cdna_lds(int W, int NM) {
     const int CB_TR = composite_bwd_rows(W);
     const int NP = NM + 1, PR = CB_TR + 4;
     const int enp = PR * W, win = enp + 2 * (NP - 1), G = enp / NP + 2;
-    const size_t lds = sizeof(float) * ((size_t)NP * win + 2 * NP * G + (size_t)NP * PR * W + 3 * PR * W + 3 * PR * (W + 4) + ((NM * 25 + 3) & ~3) +
-                                        (size_t)CB_TR * CBC_NT);      // ... + the kernel-gradient row partials
-    PIVP_CHECK_ARG(lds <= 160 * 1024 && W + 4 <= 256 && NM * 25 <= 256 && win <= 2 * CBC_NT && PR * (W + 4) <= 2 * CBC_NT);
+    return sizeof(float) * ((size_t)NP * win + 2 * NP * G + (size_t)NP * PR * W + 3 * PR * W + 3 * PR * (W + 4) + ((NM * 25 + 3) & ~3) +
+                            (size_t)CB_TR * CBC_NT);      // ... + the kernel-gradient row partials
+}
+// the frames and mask counts it takes (composite_bwd_serves below: what a sweep asks in front of its first launch)
+static bool composite_bwd_cdna_serves(int H, int W, int NM) {
+    if (H <= 1 || W <= 1 || NM < 1 || NM > 10) return false;
+    const int PR = composite_bwd_rows(W) + 4, win = PR * W + 2 * NM;
+    return composite_bwd_cdna_lds(W, NM) <= 160 * 1024 && W + 4 <= 256 && NM * 25 <= 256 && win <= 2 * CBC_NT && PR * (W + 4) <= 2 * CBC_NT;
+}
+
+int composite_bwd_cdna(const float* prev, const float* logits, const float* layer0, const float* kerns, const float* go,
+                       float* dmk, float* dz, float* dkpart, float* dprev, int dprev_accum, int B, int H, int W, int NM, hipStream_t s) {
+    PIVP_CHECK_ARG(prev && logits && layer0 && kerns && go && dmk && dz && dkpart && B > 0 && composite_bwd_cdna_serves(H, W, NM));
+    const int CB_TR = composite_bwd_rows(W);
+    const size_t lds = composite_bwd_cdna_lds(W, NM);
     if (CB_TR == 8 && NM == 10 && W == 64 && H == 64) {      // the reference's geometry: the constant-folded instance
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&composite_bwd_cdna_kernel<8, 10, 64, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         hipLaunchKernelGGL((composite_bwd_cdna_kernel<8, 10, 64, 64>), dim3(composite_bwd_tiles(H, W), B), dim3(CBC_NT), lds, s, prev, logits, layer0, kerns, go,
@@ -375,13 +386,17 @@ __global__ __launch_bounds__(256) void composite_bwd_dna_kernel(const float* __r
     }
 }
 
+static size_t composite_bwd_dna_lds(int W) {
+    const int PR = composite_bwd_rows(W) + 4;
+    return sizeof(float) * ((size_t)29 * PR * W + 3 * PR * (W + 4));
+}
+static bool composite_bwd_dna_serves(int H, int W) { return H > 1 && W > 1 && composite_bwd_dna_lds(W) <= 160 * 1024; }
+
 int composite_bwd_dna(const float* prev, const float* logits, const float* e7, const float* go, float* dmk, float* dz,
                       float* dprev, int dprev_accum, int B, int H, int W, hipStream_t s) {
-    PIVP_CHECK_ARG(prev && logits && e7 && go && dmk && dz && B > 0 && H > 1 && W > 1);
+    PIVP_CHECK_ARG(prev && logits && e7 && go && dmk && dz && B > 0 && composite_bwd_dna_serves(H, W));
     const int CB_TR = composite_bwd_rows(W);
-    const int PR = CB_TR + 4;
-    const size_t lds = sizeof(float) * ((size_t)29 * PR * W + 3 * PR * (W + 4));
-    PIVP_CHECK_ARG(lds <= 160 * 1024);
+    const size_t lds = composite_bwd_dna_lds(W);
     if (CB_TR == 8) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&composite_bwd_dna_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         hipLaunchKernelGGL(composite_bwd_dna_kernel<8>, dim3(composite_bwd_tiles(H, W), B), dim3(256), lds, s, prev, logits, e7, go, dmk, dz, dprev,
@@ -930,6 +945,25 @@ __global__ __launch_bounds__(256) void stp_dprev_finish_kernel(unsigned long lon
     }
 }
 
+// bytes of LDS of the STP composite backward in front of its d prev window: the masks' windows and groups
+static size_t composite_bwd_stp_lds_head(int W, int NM) {
+    const int CB_TR = composite_bwd_rows(W);
+    const int NP = NM + 1, np = CB_TR * W, win = np + 2 * (NP - 1), G = np / NP + 2;
+    return sizeof(float) * ((size_t)NP * win + 2 * NP * G);
+}
+// The frames and mask counts it takes, in the form every launch may need: the +-CBS_R-row window of d prev (floats, or 64-bit integers in a deterministic
+// sweep).  The whole-frame form is only chosen where it is the smaller one.
+static bool composite_bwd_stp_serves(int H, int W, int NM, bool det) {
+    if (H <= 1 || W <= 1 || NM < 2 || NM > 10) return false;
+    const size_t wn = 3 * (size_t)(composite_bwd_rows(W) + 2 * CBS_R) * W;
+    return composite_bwd_stp_lds_head(W, NM) + (det ? 8 + sizeof(unsigned long long) * wn : sizeof(float) * wn) <= 150 * 1024;
+}
+// can the sweep's composite backward serve this head (PIVP_MODEL_*) on this frame?  The launchers' own limits: plan_serves_backward (plan.h) asks them at the
+// entry of pivp_rollout_backward, so that a configuration the forward takes and these kernels do not is refused before anything is enqueued
+bool composite_bwd_serves(int mode, int H, int W, int NM, bool det) {
+    return mode == 0 ? composite_bwd_cdna_serves(H, W, NM) : mode == 1 ? composite_bwd_stp_serves(H, W, NM, det) : mode == 2 && NM == 1 && composite_bwd_dna_serves(H, W);
+}
+
 int composite_bwd_stp(const float* prev, const float* logits, const float* layer0, const float* theta, const float* go,
                       float* dmk, float* dz, float* dthpart, float* dprev, int B, int H, int W, int NM, int stp_zero, hipStream_t s,
                       unsigned long long* det_acc) {
@@ -939,6 +973,7 @@ int composite_bwd_stp(const float* prev, const float* logits, const float* layer
     constexpr int whole_on = 8;      // at most this many blocks per sample, each with the whole frame's d prev in LDS (B = 32: 29.3 / 29.3 / 28.6 / 28.2 / 28.0 ms per STP
                                      // train step for one block per tile with a +-12-row window / 1 / 2 / 4 / 8)
     const size_t lds_head = sizeof(float) * ((size_t)NP * win + 2 * NP * G);
+    PIVP_CHECK_ARG(lds_head == composite_bwd_stp_lds_head(W, NM));      // (the predicate above and this launch size the same staging)
     const int whole = (!det_acc && whole_on > 0 && dprev && lds_head + sizeof(float) * 3 * (size_t)H * W <= 96 * 1024) ? 1 : 0;
     const size_t wn = 3 * (size_t)(whole ? H : CB_TR + 2 * CBS_R) * W;
     const size_t lds = lds_head + (det_acc ? 8 + sizeof(unsigned long long) * wn : sizeof(float) * wn);     // (+8: the integer window's alignment)

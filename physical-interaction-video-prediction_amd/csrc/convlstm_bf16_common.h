@@ -93,10 +93,10 @@ template <int N, class F> __device__ __forceinline__ void static_for(F&& f) { st
 }  // namespace
 
 inline bool bf16_geometry_ok(const IgemmDesc& d) {
-    if (d.ksize != 5 || d.pad != 2 || d.in_step != 1 || d.Hin % TH) return false;
+    static_assert(TH == 8, "packed_tiles_serve (pivp_kernels.h) states the tile's depth");
+    if (d.ksize != 5 || d.pad != 2 || d.in_step != 1) return false;
     if (d.c0 % 8 || d.c1 % 8 || d.ld0 % 4 || d.ld1 % 4) return false;
-    if (d.Win % 16 == 0) return true;
-    return d.Win % 8 == 0 && d.B % 2 == 0;
+    return packed_tiles_serve(d.Hin, d.Win, d.B);
 }
 
 #ifdef PIVP_BF16_STAMPS   // in-kernel phase stamps of every block's wave 0, constant-rate 100 MHz counter (scripts/bf16_stamps.py)

@@ -151,9 +151,12 @@ __global__ __launch_bounds__(256) void cdna_kernels_finish_kernel(const float* _
     cdna_finish_block(partials, bias, kerns, B, KS, nout, vpre, blockIdx.x, v);
 }
 
+// the mask counts cdna_kernels() takes: its finisher is one block of 256 threads, a thread per kernel tap (asked by plan_serves_forward / _backward, plan.h)
+bool cdna_kernels_serves(int num_masks) { return num_masks >= 1 && num_masks * 25 <= 256; }
+
 int cdna_kernels(const float* hidden5, const float* wt, const float* bias, float* partials, float* kerns,
                  int B, int K, int num_masks, hipStream_t s, float* vpre) {
-    PIVP_CHECK_ARG(hidden5 && wt && bias && partials && kerns && B > 0 && K > 0 && num_masks >= 1 && num_masks * 25 <= 256);
+    PIVP_CHECK_ARG(hidden5 && wt && bias && partials && kerns && B > 0 && K > 0 && cdna_kernels_serves(num_masks));
     const int KS = cdna_kernel_partials_slices(K);
     hipLaunchKernelGGL(skinny_linear_partials_kernel<float>, dim3(KS, (B + LIN_BG - 1) / LIN_BG), dim3(256), 0, s, hidden5, wt, partials, B, K);
     hipLaunchKernelGGL(cdna_kernels_finish_kernel, dim3(B), dim3(256), 0, s, partials, bias, kerns, B, KS, num_masks * 25, vpre);
@@ -456,18 +459,26 @@ extern "C" int pivp_debug_cp_stamps(long long* out) {
 namespace pivp {
 #endif
 
-int composite(const float* prev, const float* mask_logits, const float* layer0, const float* aux,
-              float* out, float* masks_out, int B, int H, int W, int num_masks, int mode, int stp_zero_border,
-              hipStream_t s) {
-    PIVP_CHECK_ARG(prev && mask_logits && aux && out && B > 0 && H > 1 && W > 1 && num_masks >= 1 && num_masks <= 11);
-    PIVP_CHECK_ARG(mode >= 0 && mode <= 2 && (mode == 2 || layer0));
-    PIVP_CHECK_ARG(mode != 2 || num_masks == 1);   // TM:389-390
+// bytes of LDS a composite block stages for a W-wide frame with num_masks masks
+static size_t composite_lds_bytes(int W, int num_masks) {
     const int NP = num_masks + 1;
     const int np = CP_TR * W;
     const int win = np + 2 * (NP - 1);
     const int G = np / NP + 2;
-    const size_t lds = sizeof(float) * ((size_t)NP * win + 2 * NP * G + 3 * (CP_TR + 4) * (W + 4) + CP_KL);
-    PIVP_CHECK_ARG(lds <= 160 * 1024 && W + 4 <= 256);
+    return sizeof(float) * ((size_t)NP * win + 2 * NP * G + 3 * (CP_TR + 4) * (W + 4) + CP_KL);
+}
+// the frames and mask counts composite() takes (what pivp_plan_create asks before it accepts a configuration: plan_serves_forward, plan.h)
+bool composite_serves(int H, int W, int num_masks, int mode) {
+    if (H <= 1 || W <= 1 || num_masks < 1 || num_masks > 11 || mode < 0 || mode > 2) return false;
+    if (mode == 2 && num_masks != 1) return false;   // TM:389-390
+    return composite_lds_bytes(W, num_masks) <= 160 * 1024 && W + 4 <= 256;      // (a thread per column of a padded row)
+}
+
+int composite(const float* prev, const float* mask_logits, const float* layer0, const float* aux,
+              float* out, float* masks_out, int B, int H, int W, int num_masks, int mode, int stp_zero_border,
+              hipStream_t s) {
+    PIVP_CHECK_ARG(prev && mask_logits && aux && out && B > 0 && composite_serves(H, W, num_masks, mode) && (mode == 2 || layer0));
+    const size_t lds = composite_lds_bytes(W, num_masks);
     dim3 grid((H + CP_TR - 1) / CP_TR, B);
 #define PIVP_LAUNCH_CP(M)                                                                                   \
     do {                                                                                                    \

@@ -515,9 +515,12 @@ static int launch_wgrad5x5(const WgradDesc& d, hipStream_t s) {
     return PIVP_LAUNCH_STATUS();
 }
 
+// wgrad5x5_kernel<SW> walks chunks of 32 consecutive pixels = 32 / SW whole image rows and takes the sample and the rows' bounds from a chunk's first pixel:
+// a map narrower than a chunk must be whole chunks deep (Hg % (32 / Wg) == 0), or a chunk would run over the end of a sample and pair the next sample's dY
+// rows with this one's X rows (6 x 8, 9 x 8, 9 x 16 maps: the generic kernel takes them).  The model's power-of-two maps all pass.
 static bool takes_fast_path(const WgradDesc& d) {
     return !d.deconv && d.ksize == 5 && d.pad == 2 && d.stride == 1 && d.M % 32 == 0 && d.N % 64 == 0 &&
-           (d.Wg == 8 || d.Wg == 16 || d.Wg % 32 == 0) && d.Hx == d.Hy && d.Wx == d.Wy;
+           (d.Wg == 8 || d.Wg == 16 || d.Wg % 32 == 0) && (d.Wg >= 32 || d.Hg % (32 / d.Wg) == 0) && d.Hx == d.Hy && d.Wx == d.Wy;
 }
 // grid of the generic kernel: a function of the descriptor alone, so a launch, its partial buffer and its reduction agree
 static void generic_grid(const WgradDesc& d, int& wg_n, int& tiles, int& nsplit) {

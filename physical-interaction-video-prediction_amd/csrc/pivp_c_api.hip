@@ -442,8 +442,8 @@ static bool ep_args_ok(const float* ep_src, int ep_ld, int ep_cols, int ep_mode,
     if (!ep_src || !ep_mode) return true;      // the plain conv
     return ep_ld >= (ep_cols < cout ? ep_cols : cout);
 }
-// the L2-direct forms' tiles on an 8-wide map hold two images
-static bool form_serves_map(Operand form, int B, int W) { return !operand_l2_direct(form) || W % 16 == 0 || (W % 8 == 0 && B % 2 == 0); }
+// a packed-operand form runs on the maps its kernels' tiles serve (pivp_kernels.h): asked in front of an entry's first launch, so that a refusal leaves nothing behind
+static bool form_serves_map(Operand form, int B, int H, int W) { return form == Operand::F32 || packed_tiles_serve(H, W, B); }
 extern "C" int pivp_convlstm(const float* x, int cx, int ldx, const float* h_prev, int C, const float* w, const float* bias,
                              const float* c_in, float* c_out, float* h_out, int B, int H, int W, void* stream) {
     if (!x || !w || !bias || !c_in || !c_out || !h_out) return PIVP_ERR_BADARG;
@@ -627,7 +627,7 @@ extern "C" int pivp_convlstm_backward_form(int precision, const float* x, int cx
         B <= 0 || H <= 0 || W <= 0)
         return PIVP_ERR_BADARG;
     const Operand form = (Operand)precision;
-    if ((form != Operand::F32 && (!scratch || (cx + C) % 32)) || !form_serves_map(form, B, W) || !ep_args_ok(ep_src, ep_ld, ep_cols, ep_mode, cx + C))
+    if ((form != Operand::F32 && (!scratch || (cx + C) % 32)) || !form_serves_map(form, B, H, W) || !ep_args_ok(ep_src, ep_ld, ep_cols, ep_mode, cx + C))
         return PIVP_ERR_BADARG;
     const EpSpec ep{ep_src, ep_ld, ep_cols, ep_mode, ep_applied};
     ConvLstmBwdArgs a{};
@@ -717,7 +717,7 @@ extern "C" long long pivp_conv5x5_bf16_weight_elems(int cin, int cout) {
 }
 extern "C" int pivp_conv5x5_bf16(const float* x, int cin, int ldx, const float* w, void* w_bf16, float* out, int cout, int ldo, int accum,
                                  int B, int H, int W, void* stream) {
-    if (!x || !w || !w_bf16 || !out || cin <= 0 || cout <= 0) return PIVP_ERR_BADARG;
+    if (!x || !w || !w_bf16 || !out || cin <= 0 || cout <= 0 || !form_serves_map(Operand::BF16, B, H, W)) return PIVP_ERR_BADARG;
     int rc = pack_lstm_bf16(w, (unsigned short*)w_bf16, cin, cout, (hipStream_t)stream, Operand::BF16, conv5x5_bf16_rows(cout));
     if (rc != PIVP_OK) return rc;
     Conv5x5Bf16Opts o{};
@@ -727,7 +727,7 @@ extern "C" int pivp_conv5x5_bf16(const float* x, int cin, int ldx, const float* 
 // split form (two bf16 pieces per operand): w_bf16 holds 2 * pivp_conv5x5_bf16_weight_elems(cin, cout) elements
 extern "C" int pivp_conv5x5_bf16x3(const float* x, int cin, int ldx, const float* w, void* w_bf16, float* out, int cout, int ldo, int accum,
                                    int B, int H, int W, void* stream) {
-    if (!x || !w || !w_bf16 || !out || cin <= 0 || cout <= 0) return PIVP_ERR_BADARG;
+    if (!x || !w || !w_bf16 || !out || cin <= 0 || cout <= 0 || !form_serves_map(Operand::BF16X3, B, H, W)) return PIVP_ERR_BADARG;
     int rc = pack_lstm_bf16(w, (unsigned short*)w_bf16, cin, cout, (hipStream_t)stream, Operand::BF16X3, conv5x5_bf16_rows(cout));
     if (rc != PIVP_OK) return rc;
     Conv5x5Bf16Opts o{};
@@ -737,7 +737,7 @@ extern "C" int pivp_conv5x5_bf16x3(const float* x, int cin, int ldx, const float
 // three-piece form (six MFMAs per product, fp32-grade): w_bf16 holds 3 * pivp_conv5x5_bf16_weight_elems(cin, cout) elements; W % 16 == 0
 extern "C" int pivp_conv5x5_bf16x6(const float* x, int cin, int ldx, const float* w, void* w_bf16, float* out, int cout, int ldo, int accum,
                                    int B, int H, int W, void* stream) {
-    if (!x || !w || !w_bf16 || !out || cin <= 0 || cout <= 0 || (W % 16 && (W % 8 || B % 2))) return PIVP_ERR_BADARG;
+    if (!x || !w || !w_bf16 || !out || cin <= 0 || cout <= 0 || !form_serves_map(Operand::BF16X6, B, H, W)) return PIVP_ERR_BADARG;
     int rc = pack_lstm_bf16(w, (unsigned short*)w_bf16, cin, cout, (hipStream_t)stream, Operand::BF16X6, conv5x5_bf16_rows(cout), 1);
     if (rc != PIVP_OK) return rc;
     Conv5x5Bf16Opts o{};
@@ -749,7 +749,7 @@ extern "C" int pivp_conv5x5_bf16x6(const float* x, int cin, int ldx, const float
 // + 256 elements, scratch 66 floats (x's partial maxima); x contiguous (ldx == cin), W % 16 == 0 or W % 8 == 0 with an even batch
 extern "C" int pivp_conv5x5_fp16x3(const float* x, int cin, int ldx, const float* w, void* w_bf16, float* out, int cout, int ldo, int accum,
                                    int B, int H, int W, float* scratch, void* stream) {
-    if (!x || !w || !w_bf16 || !out || !scratch || cin <= 0 || cout <= 0 || (W % 16 && (W % 8 || B % 2)) || ldx != cin || B <= 0 || H <= 0) return PIVP_ERR_BADARG;
+    if (!x || !w || !w_bf16 || !out || !scratch || cin <= 0 || cout <= 0 || ldx != cin || B <= 0 || H <= 0 || !form_serves_map(Operand::FP16X3, B, H, W)) return PIVP_ERR_BADARG;
     int rc = pack_lstm_bf16(w, (unsigned short*)w_bf16, cin, cout, (hipStream_t)stream, Operand::FP16X3, conv5x5_bf16_rows(cout), 1);
     if (rc != PIVP_OK) return rc;
     rc = absmax_partials(x, (long)B * H * W * cin, scratch, (hipStream_t)stream);
@@ -766,7 +766,7 @@ extern "C" int pivp_conv5x5_ep(int precision, const float* x, int cin, int ldx, 
     if (applied) *applied = 0;
     if (precision < 1 || precision > 4 || !x || !w || !w_bf16 || !out || cin <= 0 || cout <= 0 || B <= 0 || H <= 0 || W <= 0) return PIVP_ERR_BADARG;
     const Operand form = (Operand)precision;
-    if (!form_serves_map(form, B, W) || (operand_needs_scale(form) && (!scratch || ldx != cin)) || !ep_args_ok(ep_src, ep_ld, ep_cols, ep_mode, cout))
+    if (!form_serves_map(form, B, H, W) || (operand_needs_scale(form) && (!scratch || ldx != cin)) || !ep_args_ok(ep_src, ep_ld, ep_cols, ep_mode, cout))
         return PIVP_ERR_BADARG;
     int rc = pack_lstm_bf16(w, (unsigned short*)w_bf16, cin, cout, (hipStream_t)stream, form, conv5x5_bf16_rows(cout), operand_l2_direct(form) ? 1 : 0);
     if (rc != PIVP_OK) return rc;
@@ -803,6 +803,7 @@ extern "C" int pivp_wgrad5x5_bf16(const float* x, int cx, int ldx, const float* 
 extern "C" int pivp_wgrad5x5_fp16x3_batch(const float* x, int cx, int ldx, const float* h_prev, int C, const float* dG, float* dW, float* db,
                                           int B, int H, int W, int tcount, long long ts_x, long long ts_h, long long ts_dG, float* scratch, void* stream) {
     if (!x || !dG || !dW || !scratch || C <= 0 || cx <= 0 || tcount < 1 || B <= 0 || H <= 0 || W <= 0) return PIVP_ERR_BADARG;
+    if (!form_serves_map(Operand::FP16X3, B, H, W)) return PIVP_ERR_BADARG;      // (in front of the partial maxima's launches)
     for (int j = 0; j < tcount; ++j) {
         const int rc = absmax_partials(reinterpret_cast<const float*>(reinterpret_cast<const char*>(dG) + j * ts_dG), (long)B * H * W * 4 * C,
                                        scratch + (size_t)j * 72, (hipStream_t)stream);

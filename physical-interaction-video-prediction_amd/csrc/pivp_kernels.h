@@ -34,6 +34,10 @@ constexpr int operand_pieces(Operand o) {
 constexpr bool operand_l2_direct(Operand o) { return o == Operand::BF16X6 || o == Operand::FP16X3; }
 // the operand is staged times a power of two taken from its absmax_partials
 constexpr bool operand_needs_scale(Operand o) { return o == Operand::FP16X3; }
+// The maps the packed-operand kernels' tiles serve (convlstm_bf16.hip, conv5x5_bf16.hip, wgrad_bf16.hip): 8 rows deep, and 16 wide or 8 wide with two images
+// to a tile (an even batch).  The one predicate of the kernels' own checks (bf16_geometry_ok, wgrad5x5_bf16_ok), of the forward's per-layer fall-back to fp32,
+// of the sweep's choice of a cell's data- and weight-gradient form (Modes, plan.h) and of the op entries' refusals: they must agree on every map.
+constexpr bool packed_tiles_serve(int H, int W, int B) { return H % 8 == 0 && (W % 16 == 0 || (W % 8 == 0 && B % 2 == 0)); }
 
 struct IgemmDesc {
     const float* x0; const float* x1;   // input sources (channel-concatenated: x0 then x1)
@@ -236,6 +240,8 @@ int stp_params(const float* hidden5, const float* wt1, const float* b1, const fl
 
 // flat-11 softmax + transform + compositing -> next frame (TM:720-728 with TM:341-349 / TM:469-470 / TM:392-415)
 // mode 0 = CDNA (kerns [B][num_masks][25]), 1 = STP (theta [B][6]), 2 = DNA (enc7 planes [B][25][HW])
+bool composite_serves(int H, int W, int num_masks, int mode);   // composite() takes this frame and mask count (LDS staging, a thread per padded column)
+bool cdna_kernels_serves(int num_masks);                        // cdna_kernels() / the finishers take this many masks (25 taps each, 256 threads)
 int composite(const float* prev, const float* mask_logits, const float* layer0, const float* aux,
               float* out, float* masks_out, int B, int H, int W, int num_masks, int mode, int stp_zero_border,
               hipStream_t s);
@@ -347,6 +353,7 @@ int grad_sum_shards(const void* src, int src_bf16, int nsh, long len, void* dst,
 // ---- backward of the heads / trunk ends (csrc/backward_heads.hip) ----
 int scaled_diff(const float* a, const float* b, float* out, long n, float scale, int accum, hipStream_t s);
 int composite_bwd_tiles(int H, int W);
+bool composite_bwd_serves(int mode, int H, int W, int NM, bool det);   // the composite backward of head `mode` takes this frame and mask count (its launcher's limits)
 int composite_bwd_cdna(const float* prev, const float* logits, const float* layer0, const float* kerns, const float* go,
                        float* dmk, float* dz, float* dkpart, float* dprev, int dprev_accum, int B, int H, int W, int NM, hipStream_t s);
 int composite_bwd_stp(const float* prev, const float* logits, const float* layer0, const float* theta, const float* go,

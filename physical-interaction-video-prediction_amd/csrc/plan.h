@@ -54,16 +54,16 @@ inline long long ln_numel(const pivp_config_t& c, int j) {
 // ---- the precision mode: everything the plan derives from it ----
 static_assert((int)Operand::F32 == PIVP_PRECISION_F32 && (int)Operand::BF16 == PIVP_PRECISION_BF16 && (int)Operand::BF16X3 == PIVP_PRECISION_BF16X3 &&
               (int)Operand::BF16X6 == PIVP_PRECISION_BF16X6 && (int)Operand::FP16X3 == PIVP_PRECISION_FP16X3, "Operand is the PIVP_PRECISION_* code");
-// the two-image tile of the L2-direct forms' kernels serves this map (an 8-wide map needs an even batch; otherwise the fp32 kernel takes it)
-inline bool pair_tile_serves(int W, int B) { return W % 16 == 0 || B % 2 == 0; }
 struct Modes {
     Operand precision;      // the mode = the form of the ConvLSTM forward's operands
     // the ConvLSTM forward runs on weight packs (of the form `precision`)
     bool packs() const { return precision != Operand::F32; }
-    // the ConvLSTM data gradient on a W-wide map at batch B: the forward's form where its tiles serve the map
-    Operand dgrad(int W, int B) const { return operand_l2_direct(precision) && !pair_tile_serves(W, B) ? Operand::F32 : precision; }
+    // The ConvLSTM data gradient on an H x W map at batch B: the forward's form where its tiles serve the map -- packed_tiles_serve (pivp_kernels.h), the
+    // predicate by which run_convlstm sends a cell of the L2-direct modes to the fp32 kernel, so the forward and the sweep agree cell by cell (an 8-wide map with
+    // an odd batch, a height that is no multiple of 8: the fp32 kernels take the cell).  The other modes are refused at pivp_plan_set_precision on such a map.
+    Operand dgrad(int H, int W, int B) const { return operand_l2_direct(precision) && !packed_tiles_serve(H, W, B) ? Operand::F32 : precision; }
     // ... and the weight gradient of a batch of timesteps: the split mode has no form of its own and stays fp32
-    Operand wgrad(int W, int B) const { return precision == Operand::BF16X3 ? Operand::F32 : dgrad(W, B); }
+    Operand wgrad(int H, int W, int B) const { return precision == Operand::BF16X3 ? Operand::F32 : dgrad(H, W, B); }
     // ... which those forms batch: BF16 as many timesteps per launch as the rings hold, the L2-direct forms two; fp32 none
     bool wgrad_batches() const { return precision == Operand::BF16 || operand_l2_direct(precision); }
     // a transposed conv.  has_wabs: the layer keeps its weights' absmax partials (enc5 / enc6: pivp_plan::o_wabs), which the fp16-piece form needs -- a layer
@@ -201,6 +201,20 @@ inline float* G(const pivp_plan* p, int idx) { return p->params[idx].grad; }
 
 // the frame sizes every entry point takes: three stride-2 levels under 5x5 ConvLSTMs.  (Each caller adds its own condition on batch and seq_len.)
 inline bool frame_size_ok(const pivp_config_t& c) { return c.height >= 16 && c.width >= 16 && c.height % 8 == 0 && c.width % 8 == 0; }
+// The accepted domain (include/pivp_hip.h, pivp_plan_create), from the kernels' own limits, so that nothing is refused half-way through a rollout or a sweep:
+// ... of the forward: the compositing kernels stage a padded frame row per 256 threads (W + 4 <= 256) within their LDS budget, and the CDNA motion head's
+// finishers give each of the 25 * num_masks kernel taps a thread of one 256-thread block (num_masks <= 10).  Asked by pivp_plan_create.
+inline bool plan_serves_forward(const pivp_config_t& c) {
+    return frame_size_ok(c) && composite_serves(c.height, c.width, c.num_masks, c.model_type) &&
+           (c.model_type != PIVP_MODEL_CDNA || cdna_kernels_serves(c.num_masks));
+}
+// ... of the backward sweep, narrower than the forward's: the composite backward takes 1 .. 10 masks for CDNA and 2 .. 10 for STP (its mask loop has no
+// one-mask form, and eleven masks pass the forward alone), and its tile's staging must fit in LDS -- every mask count up to 128-wide frames, fewer masks on
+// wider ones; det: a deterministic sweep's integer d prev window (STP) is twice as large.  Asked at the entry of pivp_rollout_backward, in front of its
+// first launch.
+inline bool plan_serves_backward(const pivp_config_t& c, bool det) {
+    return plan_serves_forward(c) && composite_bwd_serves(c.model_type, c.height, c.width, c.num_masks, det);
+}
 
 // ---- what crosses the units ----
 void plan_layout(pivp_plan* p);                              // plan_setup.hip: the workspace carve

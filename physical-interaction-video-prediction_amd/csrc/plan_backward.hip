@@ -155,7 +155,7 @@ struct Sweep {
         a.dG = ring + (size_t)ss.wg_slot * dG1; a.wt = ws + g.wt_lstm[i]; a.d_in = DIN(i, true);
         a.B = B; a.H = m.H; a.W = m.W;      // dW = null: the weight gradient is batched below; only the fork's `ready` (behind the gate math) is used
         a.wt_ready = 1;
-        a.operand = md.dgrad(m.W, B);      // (the L2-direct forms' two-image tiles do not fit an 8-wide map with an odd batch: the fp32 kernels take the cell)
+        a.operand = md.dgrad(m.H, m.W, B);      // (a map the L2-direct forms' tiles do not serve: the fp32 kernels take the cell, as in the forward)
         if (a.operand != Operand::F32) a.wt_bf16 = reinterpret_cast<unsigned short*>(ws + g.wtb_lstm[i]);
         if (ss.wg_flush) a.fork = fork_of(SLOT_LSTM + i, f);
         a.ln = &lf[i];
@@ -190,7 +190,7 @@ struct Sweep {
                 RC(lstm_wgrad_reduce(L.cx, L.C, wg_h[i] ? 1 : 0, part, G(&p, p.i_lstm_w[i]), G(&p, p.i_lstm_b[i]), B, m.H, m.W, sw, 0, DET_SLOT_J));
             else lstm_started[i] = true;
         } else {
-            const Operand wform = md.wgrad(m.W, B);
+            const Operand wform = md.wgrad(m.H, m.W, B);
             if (operand_needs_scale(wform)) d.dy_absmax = absmax_ring;      // dG's partial maxima of the batch (run_convlstm_backward left them there)
             d.dy_absmax_stride = 72;
             d.form = (long)B * c.height * c.width > 32L * 64 * 64 ? 2 : 0;      // (frames above 64 x 64 x 32: the eight-wave weight gradient on every layer)
@@ -430,6 +430,8 @@ static int rollout_backward_sweep(pivp_plan_t* plan, const float* images, const 
     for (const ParamInfo& pi : plan->params) if (!pi.ptr || !pi.grad) return PIVP_ERR_STATE;
     const bool params = (plan->sweep_mode & PIVP_SWEEP_PARAMS) != 0, own_loss = (plan->sweep_mode & PIVP_SWEEP_BUILTIN_LOSS) != 0;
     if (!own_loss && !plan->frame_seed && !plan->sg_seed) return PIVP_ERR_STATE;      // nothing to differentiate
+    // a configuration the forward serves and a backward kernel does not (include/pivp_hip.h): refused in front of the first launch, gradients and workspace untouched
+    if (!plan_serves_backward(plan->cfg, plan->det != 0)) return PIVP_ERR_BADARG;
     hipStream_t s = (hipStream_t)stream;
     const pivp_config_t& c = plan->cfg;
     const int B = c.batch, T = c.seq_len, ctx = c.context_frames;

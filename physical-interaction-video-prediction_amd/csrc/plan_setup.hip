@@ -144,6 +144,7 @@ extern "C" int pivp_plan_create(const pivp_config_t* cfg, pivp_plan_t** out) {
     if (cfg->num_masks < 1 || cfg->num_masks > 11) return PIVP_ERR_BADARG;
     if (cfg->model_type == PIVP_MODEL_DNA && cfg->num_masks != 1) return PIVP_ERR_BADARG;  // TM:389-390
     if (cfg->context_frames < 1 || cfg->context_frames >= cfg->seq_len) return PIVP_ERR_BADARG;
+    if (!plan_serves_forward(*cfg)) return PIVP_ERR_BADARG;      // a frame or mask count a kernel of the rollout would refuse: refused here, not at that launch
     pivp_plan* p = new pivp_plan();
     p->cfg = *cfg;
     const int H = cfg->height, W = cfg->width;

@@ -507,10 +507,9 @@ __global__ __launch_bounds__(64 * NW, 1) void wgrad25_bf16_kernel(const WgradDes
 
 bool wgrad5x5_bf16_ok(const WgradDesc& d) {
     if (d.deconv || d.ksize != 5 || d.pad != 2 || d.stride != 1 || d.Hx != d.Hy || d.Wx != d.Wy) return false;
-    if (d.N % 128 || d.cin % 32 || d.c0 % 32 || d.c1 % 32 || d.ld0 % 4 || d.ld1 % 4 || d.ldy % 4 || d.Hx % 8) return false;
+    if (d.N % 128 || d.cin % 32 || d.c0 % 32 || d.c1 % 32 || d.ld0 % 4 || d.ld1 % 4 || d.ldy % 4) return false;
     if (d.tcount > 1 && (d.ts_x0 % 16 || d.ts_x1 % 16 || d.ts_dy % 16)) return false;
-    if (d.Wx % 16 == 0) return true;
-    return d.Wx % 8 == 0 && d.B % 2 == 0;
+    return packed_tiles_serve(d.Hx, d.Wx, d.B);
 }
 
 // the 25-tap kernel: grid = (cin / 32) x (N / 64) output slices x pixel splits over the tiles of ALL timesteps of the batch

@@ -435,7 +435,8 @@ class Model(object):
                                   context_frames=ctx,
                                   keep_activations=1 if keep else 0,
                                   ln_eps=self.ln_eps, stp_zero_border=1 if self.stp_border == 'zeros' else 0)
-            plan = _Plan(lib, cfg)
+            plan = _Plan(lib, cfg)      # the door: a configuration the kernels do not serve is refused here (PIVP_ERR_BADARG), before a parameter is laid out
+            self._ensure_params(H, W)
             for name, value in resolve_plan_options(self.plan_options).items():
                 opt, default, _ = PLAN_OPTIONS[name]
                 if value != default:
@@ -595,7 +596,6 @@ class Model(object):
             T, B, _, H, W = images.shape
             actions = self._as_device(actions, (5,))
             states = self._as_device(states, (5,))
-            self._ensure_params(H, W)
             plan = self._plan_for(B, T, H, W)
             self._active = plan
             ctx = self.num_frame_before_prediction
@@ -779,7 +779,6 @@ class Model(object):
         _, B, _, H, W = images.shape
         T = actions.shape[0] + 1
         P = planes.shape[1] if planes is not None else 0
-        self._ensure_params(H, W)
         plan = self._plan_for(B, T, H, W, keep_activations=False, observed=observed)
         self._active = plan
         gen = torch.empty((T - 1, B, 3, H, W), dtype=torch.float32, device=self.device)

@@ -186,16 +186,20 @@ def test_bf16_precision_refused_for_unsupported_geometry():
 
 
 # ---- plain 5x5 convolution of the same kernel (the ConvLSTM data gradient of the bf16 mode) -----------------------------
-@pytest.mark.parametrize('B,cin,cout,H', [(2, 128, 64, 32), (2, 256, 96, 16), (4, 512, 192, 8), (2, 256, 128, 16), (1, 128, 128, 32),
-                                          (32, 512, 192, 8), (1, 128, 64, 64)])
-def test_conv5x5_bf16_exact_on_bf16_operands(ops, B, cin, cout, H):
+def _conv5x5_bf16_exact(ops, B, cin, cout, H, Wd):
     # shapes of the seven data gradients (cin = 4C gate channels, cout = Cx + C); cout = 96 exercises the padded column block,
     # the 8x8 / B = 4 case the K-split over channel groups with atomic adds, B = 32 the unsplit 8x8 grid
     rs = np.random.RandomState(cin + cout + H)
-    x = _bf16(rs.randn(B, cin, H, H)); W = _bf16(rs.randn(cout, cin, 5, 5) / np.sqrt(25 * cin))
+    x = _bf16(rs.randn(B, cin, H, Wd)); W = _bf16(rs.randn(cout, cin, 5, 5) / np.sqrt(25 * cin))
     ref = R.conv2d(x, W, np.zeros(cout), 1, 2)
     got = ops.conv5x5_bf16(x, W)
     assert np.abs(got - ref).max() < TOL
+
+
+@pytest.mark.parametrize('B,cin,cout,H', [(2, 128, 64, 32), (2, 256, 96, 16), (4, 512, 192, 8), (2, 256, 128, 16), (1, 128, 128, 32),
+                                          (32, 512, 192, 8), (1, 128, 64, 64)])
+def test_conv5x5_bf16_exact_on_bf16_operands(ops, B, cin, cout, H):
+    _conv5x5_bf16_exact(ops, B, cin, cout, H, H)
 
 
 def test_conv5x5_bf16_accumulates(ops):
@@ -240,32 +244,33 @@ def test_wgrad5x5_bf16_first_step_leaves_h_rows_alone(ops):
     assert np.all(got[:, cx:] == 0)
 
 
-@pytest.mark.parametrize('form', [0, 1, 2])      # 1: four-wave blocks (co-resident with the sweep's small kernels; what 0 picks at these sizes), 2: eight-wave blocks
-@pytest.mark.parametrize('B,cx,C,H,T', [(2, 32, 32, 32, 3), (2, 32, 64, 16, 4), (4, 64, 128, 8, 3), (1, 96, 32, 32, 2)])
-def test_wgrad5x5_bf16_batch_of_timesteps(ops, B, cx, C, H, T, form):
+def _wgrad5x5_bf16_batch(ops, B, cx, C, H, Wd, T, form):
     # one launch for T timesteps (operands at signed byte strides) = the sum of the per-timestep gradients
     rs = np.random.RandomState(B + cx + C + H + T)
-    xs = [_bf16(rs.randn(B, cx, H, H)) for _ in range(T)]; hs = [_bf16(rs.randn(B, C, H, H) * 0.5) for _ in range(T)]
-    dGs = [_bf16(rs.randn(B, 4 * C, H, H) * 0.1) for _ in range(T)]
+    xs = [_bf16(rs.randn(B, cx, H, Wd)) for _ in range(T)]; hs = [_bf16(rs.randn(B, C, H, Wd) * 0.5) for _ in range(T)]
+    dGs = [_bf16(rs.randn(B, 4 * C, H, Wd) * 0.1) for _ in range(T)]
     ref = sum(_wgrad_ref(x, h, g) for x, h, g in zip(xs, hs, dGs))
     got, db = ops.wgrad5x5_bf16_batch(xs, hs, dGs, form=form)
     assert np.abs(got - ref).max() < 2e-5 * max(1.0, np.abs(ref).max())
     assert np.abs(db - sum(g.sum(axis=(0, 2, 3)) for g in dGs)).max() < 4e-4
 
 
-@pytest.mark.parametrize('mode', ['fp16x3', 'bf16x6'])
-@pytest.mark.parametrize('gscale', [0.1, 1e-7, 'ragged'])
-@pytest.mark.parametrize('B,cx,C,H,T', [(2, 32, 32, 32, 3), (2, 32, 64, 16, 4), (4, 64, 128, 8, 3), (1, 96, 32, 32, 1)])
-def test_wgrad5x5_fp16x3_batch_of_timesteps(ops, B, cx, C, H, T, gscale, mode):
+@pytest.mark.parametrize('form', [0, 1, 2])      # 1: four-wave blocks (co-resident with the sweep's small kernels; what 0 picks at these sizes), 2: eight-wave blocks
+@pytest.mark.parametrize('B,cx,C,H,T', [(2, 32, 32, 32, 3), (2, 32, 64, 16, 4), (4, 64, 128, 8, 3), (1, 96, 32, 32, 2)])
+def test_wgrad5x5_bf16_batch_of_timesteps(ops, B, cx, C, H, T, form):
+    _wgrad5x5_bf16_batch(ops, B, cx, C, H, H, T, form)
+
+
+def _wgrad5x5_split_batch(ops, B, cx, C, H, Wd, T, gscale, mode):
     # the fp16x3 mode's weight gradient: two fp16 pieces per operand, dG scaled by a power of two from the batch's largest value.  fp32-representable
     # operands against the float64 sums and against the fp32 kernel; dG of gradient size (1e-7) and timesteps / gates whose sizes differ by 1e4
     rs = np.random.RandomState(B + cx + C + H + T + 5)
     f32 = lambda a: np.asarray(a, dtype=np.float32).astype(np.float64)
-    xs = [f32(rs.randn(B, cx, H, H)) for _ in range(T)]; hs = [f32(rs.randn(B, C, H, H) * 0.5) for _ in range(T)]
+    xs = [f32(rs.randn(B, cx, H, Wd)) for _ in range(T)]; hs = [f32(rs.randn(B, C, H, Wd) * 0.5) for _ in range(T)]
     if gscale == 'ragged':
-        dGs = [f32(rs.randn(B, 4 * C, H, H) * 10.0 ** rs.uniform(-7, -3, size=(1, 4 * C, 1, 1)) * 10.0 ** (-t)) for t in range(T)]
+        dGs = [f32(rs.randn(B, 4 * C, H, Wd) * 10.0 ** rs.uniform(-7, -3, size=(1, 4 * C, 1, 1)) * 10.0 ** (-t)) for t in range(T)]
     else:
-        dGs = [f32(rs.randn(B, 4 * C, H, H) * gscale) for _ in range(T)]
+        dGs = [f32(rs.randn(B, 4 * C, H, Wd) * gscale) for _ in range(T)]
     ref = sum(_wgrad_ref(x, h, g) for x, h, g in zip(xs, hs, dGs))
     kw = {'fp16x3': True} if mode == 'fp16x3' else {'bf16x6': True}     # (three bf16 pieces: the bf16x6 mode's form, no scale)
     got, db = ops.wgrad5x5_bf16_batch(xs, hs, dGs, **kw)
@@ -282,6 +287,13 @@ def test_wgrad5x5_fp16x3_batch_of_timesteps(ops, B, cx, C, H, T, gscale, mode):
     if T == 1:       # the sweep's t = 0: no h operand, only the x rows are touched
         got0, _ = ops.wgrad5x5_bf16_batch(xs, hs, dGs, h_is_zero=True, **kw)
         assert np.abs(got0[:, :cx] - ref[:, :cx]).max() < 2e-5 * unit and np.all(got0[:, cx:] == 0)
+
+
+@pytest.mark.parametrize('mode', ['fp16x3', 'bf16x6'])
+@pytest.mark.parametrize('gscale', [0.1, 1e-7, 'ragged'])
+@pytest.mark.parametrize('B,cx,C,H,T', [(2, 32, 32, 32, 3), (2, 32, 64, 16, 4), (4, 64, 128, 8, 3), (1, 96, 32, 32, 1)])
+def test_wgrad5x5_fp16x3_batch_of_timesteps(ops, B, cx, C, H, T, gscale, mode):
+    _wgrad5x5_split_batch(ops, B, cx, C, H, H, T, gscale, mode)
 
 
 def test_bf16_mode_batched_weight_gradients_match_per_step():
@@ -419,12 +431,11 @@ def test_convlstm_bf16x6_first_step_and_narrow_maps(ops):
     assert np.abs(h0 - hr0).max() < 2e-6 and np.abs(c0 - cr0).max() < 2e-6
 
 
-@pytest.mark.parametrize('B,cin,cout,H', [(2, 128, 64, 32), (2, 256, 96, 16), (2, 256, 128, 16), (32, 256, 192, 16), (1, 128, 128, 32), (4, 512, 192, 8), (32, 512, 192, 8)])    # 8-wide maps: tiles of two images (lstm5's data gradient)
-def test_conv5x5_bf16x6(ops, B, cin, cout, H):
+def _conv5x5_bf16x6(ops, B, cin, cout, H, Wd, accumulate=True):
     # the data gradients of the three-piece mode: 64-column blocks on the k-step ring, padded columns (96), K split over the channel groups (B = 32
     # on a 16 x 16 map: 64 tiles x 3 column blocks), against the float64 convolution and the fp32 kernel
     rs = np.random.RandomState(cin + cout + H + 6)
-    x = rs.randn(B, cin, H, H).astype(np.float32).astype(np.float64); W = (rs.randn(cout, cin, 5, 5) / np.sqrt(25 * cin)).astype(np.float32).astype(np.float64)
+    x = rs.randn(B, cin, H, Wd).astype(np.float32).astype(np.float64); W = (rs.randn(cout, cin, 5, 5) / np.sqrt(25 * cin)).astype(np.float32).astype(np.float64)
     ref = R.conv2d(x, W, np.zeros(cout), 1, 2)
     e6 = ops.conv5x5_bf16(x, W, pieces=3) - ref
     ef = ops.conv_s1(x, W, 5) - ref if hasattr(ops, 'conv_s1') else None
@@ -434,20 +445,23 @@ def test_conv5x5_bf16x6(ops, B, cin, cout, H):
     assert np.abs(e6).max() < 2e-5 and np.sqrt((e6 ** 2).mean()) < 7e-7      # (observed up to 6.7e-6 / 5.2e-7; the K-split sums meet by atomic adds in any order)
     if ef is not None:
         assert np.sqrt((e6 ** 2).mean()) < 1.2 * np.sqrt((ef ** 2).mean())
-    acc = rs.randn(B, cout, H, H).astype(np.float32)
-    if B < 32:                                       # accumulate form
+    acc = rs.randn(B, cout, H, Wd).astype(np.float32)
+    if B < 32 and accumulate:                        # accumulate form
         out = ops.conv5x5_bf16(x, W, accum_into=acc.astype(np.float64), pieces=3)
         assert np.abs(out - (ref + acc)).max() < 6e-6       # (+ the rounding of the final add at |values| up to 5)
 
 
-@pytest.mark.parametrize('scale', [1.0, 1e-6, 'ragged'])
-@pytest.mark.parametrize('B,cin,cout,H', [(2, 128, 64, 32), (2, 256, 96, 16), (32, 256, 192, 16), (1, 128, 128, 32), (4, 512, 192, 8), (32, 512, 192, 8)])    # 8-wide maps: the ring kernel's fp16 form (lstm5's data gradient)
-def test_conv5x5_fp16x3(ops, B, cin, cout, H, scale):
+@pytest.mark.parametrize('B,cin,cout,H', [(2, 128, 64, 32), (2, 256, 96, 16), (2, 256, 128, 16), (32, 256, 192, 16), (1, 128, 128, 32), (4, 512, 192, 8), (32, 512, 192, 8)])    # 8-wide maps: tiles of two images (lstm5's data gradient)
+def test_conv5x5_bf16x6(ops, B, cin, cout, H):
+    _conv5x5_bf16x6(ops, B, cin, cout, H, H)
+
+
+def _conv5x5_fp16x3(ops, B, cin, cout, H, Wd, scale, accumulate=True):
     # the data gradients of the fp16x3 mode: two fp16 pieces per operand, x staged times a power of two from its largest |value|.  Unit-scale x, x of
     # gradient size (1e-6: every fp16 piece would be subnormal or zero without the scale), and channels whose sizes differ by 1e6 (the small ones lose
     # second-piece bits: their ABSOLUTE error stays below the rounding of the large ones)
     rs = np.random.RandomState(cin + cout + H + 16)
-    x = rs.randn(B, cin, H, H)
+    x = rs.randn(B, cin, H, Wd)
     if scale == 'ragged':
         x = x * (10.0 ** rs.uniform(-9, -3, size=(1, cin, 1, 1)))
     else:
@@ -461,12 +475,18 @@ def test_conv5x5_fp16x3(ops, B, cin, cout, H, scale):
           % (cin, cout, H, scale, np.abs(e3).max(), np.sqrt((e3 ** 2).mean()), np.abs(ef).max(), np.sqrt((ef ** 2).mean())))
     assert np.abs(e3).max() < 2e-5 and np.sqrt((e3 ** 2).mean()) < 7e-7      # (observed up to 7.8e-6 / 5.3e-7; the K-split sums meet by atomic adds in any order)
     assert np.sqrt((e3 ** 2).mean()) < 1.5 * np.sqrt((ef ** 2).mean())
-    if B < 32 and scale == 1.0:                      # accumulate form
-        acc = rs.randn(B, cout, H, H).astype(np.float32)
+    if B < 32 and scale == 1.0 and accumulate:       # accumulate form
+        acc = rs.randn(B, cout, H, Wd).astype(np.float32)
         out = ops.conv5x5_bf16(x, W, accum_into=acc.astype(np.float64), pieces='fp16x3')
         assert np.abs(out - (ref + acc)).max() < 6e-6
     if scale == 1.0 and B == 2 and cin == 128:       # an all-zero x: scale 1, zeros out
         assert np.abs(ops.conv5x5_bf16(x * 0, W, pieces='fp16x3')).max() == 0
+
+
+@pytest.mark.parametrize('scale', [1.0, 1e-6, 'ragged'])
+@pytest.mark.parametrize('B,cin,cout,H', [(2, 128, 64, 32), (2, 256, 96, 16), (32, 256, 192, 16), (1, 128, 128, 32), (4, 512, 192, 8), (32, 512, 192, 8)])    # 8-wide maps: the ring kernel's fp16 form (lstm5's data gradient)
+def test_conv5x5_fp16x3(ops, B, cin, cout, H, scale):
+    _conv5x5_fp16x3(ops, B, cin, cout, H, H, scale)
 
 
 # ---- two fp16 pieces per operand, three MFMAs per product (weights packed times 2^8): 22-bit operands, forward only ---------------------------
@@ -742,12 +762,16 @@ def test_deconv3x3s2_bf16x3(ops, B, cin, cout, H):
     assert e3 < 3e-5 and e3 < e1 / 50
 
 
-@pytest.mark.parametrize('B,cin,cout,H', [(2, 128, 64, 32), (2, 256, 96, 16), (4, 512, 192, 8), (2, 256, 128, 16), (32, 512, 192, 8)])
-def test_conv5x5_bf16x3(ops, B, cin, cout, H):
+def _conv5x5_bf16x3(ops, B, cin, cout, H, Wd):
     # the data gradients of the split mode: 64-column blocks (four ring slots), 128-column blocks (two slots), padded columns, K split
     rs = np.random.RandomState(cin + cout + H + 5)
-    x = rs.randn(B, cin, H, H); W = rs.randn(cout, cin, 5, 5) / np.sqrt(25 * cin)
+    x = rs.randn(B, cin, H, Wd); W = rs.randn(cout, cin, 5, 5) / np.sqrt(25 * cin)
     ref = R.conv2d(x, W, np.zeros(cout), 1, 2)
     e3 = np.abs(ops.conv5x5_bf16(x, W, split=True) - ref).max(); e1 = np.abs(ops.conv5x5_bf16(x, W) - ref).max()
     print('conv5x5 %d->%d @%d: max |err| split %.2e, plain bf16 %.2e' % (cin, cout, H, e3, e1))
     assert e3 < 5e-5 and e3 < e1 / 50
+
+
+@pytest.mark.parametrize('B,cin,cout,H', [(2, 128, 64, 32), (2, 256, 96, 16), (4, 512, 192, 8), (2, 256, 128, 16), (32, 512, 192, 8)])
+def test_conv5x5_bf16x3(ops, B, cin, cout, H):
+    _conv5x5_bf16x3(ops, B, cin, cout, H, H)

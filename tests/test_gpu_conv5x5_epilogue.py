@@ -169,6 +169,11 @@ CELL_HOOKS = [(96, 96, 96, 1), (128, 128, 128, 1), (32, 64, 32, 2), None]
 BF16X3_ABS, BF16X3_OF_BF16, RATIO = 5e-5, 1.0 / 50, {3: 1.2, 4: 1.5}
 
 
+def _shape(si):
+    """a cell's (B, cx, C, H, W): an index into CELL_SHAPES (square maps), or such a tuple itself (tests/test_gpu_backward_shapes.py: H != W)"""
+    return tuple(si) if isinstance(si, tuple) else CELL_SHAPES[si] + (CELL_SHAPES[si][3],)
+
+
 def _t(a):
     return torch.from_numpy(np.array(a, dtype=np.float32, order='C')).to(DEV)      # (a copy: the cached cases are read-only)
 
@@ -192,11 +197,11 @@ def _rms(a):
 @functools.lru_cache(maxsize=None)
 def _cell_case(si, gscale=1.0):
     """inputs and float64 autograd as tests/test_gpu_backward_ops.py::test_convlstm_backward; gscale multiplies every cotangent"""
-    B, cx, C, H = CELL_SHAPES[si]
+    B, cx, C, H, Wd = _shape(si)
     rs = np.random.RandomState(C + cx)
-    x = rs.randn(B, cx, H, H); h = rs.randn(B, C, H, H) * 0.5; c = rs.randn(B, C, H, H)
+    x = rs.randn(B, cx, H, Wd); h = rs.randn(B, C, H, Wd) * 0.5; c = rs.randn(B, C, H, Wd)
     W = rs.randn(4 * C, cx + C, 5, 5) / np.sqrt(25 * (cx + C)); b = rs.randn(4 * C) * 0.1
-    dh = rs.randn(B, C, H, H) * gscale; dh2 = rs.randn(B, C, H, H) * 0.5 * gscale; dcn = rs.randn(B, C, H, H) * gscale
+    dh = rs.randn(B, C, H, Wd) * gscale; dh2 = rs.randn(B, C, H, Wd) * 0.5 * gscale; dcn = rs.randn(B, C, H, Wd) * gscale
     tx, th, tc = [torch.tensor(v, dtype=torch.float64, requires_grad=True) for v in (x, h, c)]
     tW = torch.tensor(W, dtype=torch.float64, requires_grad=True); tb = torch.tensor(b, dtype=torch.float64, requires_grad=True)
     g = F.conv2d(torch.cat((tx, th), 1), tW, tb, padding=2)
@@ -220,14 +225,14 @@ def _cell_dev(env, si, gscale=1.0):
     if key in _DEV_CACHE:
         return _DEV_CACHE[key]
     pivp, _lib, lib = env
-    B, cx, C, H = CELL_SHAPES[si]
+    B, cx, C, H, Wd = _shape(si)
     inp, _ = _cell_case(si, gscale)
-    M = B * H * H
+    M = B * H * Wd
     d = dict(xd=_nhwc(inp['x']), hd=_nhwc(inp['h']), cd=_nhwc(inp['c']), wd=_t(pivp.to_internal('lstm1/conv/W', inp['W'])), bd=_t(inp['b']))
     d['c_out'] = torch.empty_like(d['cd']); d['h_out'] = torch.empty_like(d['hd'])
     d['gates'] = torch.empty((M, 4 * C), dtype=torch.float32, device=DEV)
     _lib.check(lib.pivp_convlstm_train(d['xd'].data_ptr(), cx, cx, d['hd'].data_ptr(), C, d['wd'].data_ptr(), d['bd'].data_ptr(), d['cd'].data_ptr(),
-                                       d['c_out'].data_ptr(), d['h_out'].data_ptr(), d['gates'].data_ptr(), B, H, H, _st()), 'fwd')
+                                       d['c_out'].data_ptr(), d['h_out'].data_ptr(), d['gates'].data_ptr(), B, H, Wd, _st()), 'fwd')
     # dh_b arrives as the last C channels of a wider buffer (the next step's d_in)
     d['wide'] = torch.zeros((M, cx + C), dtype=torch.float32, device=DEV)
     d['wide'][:, cx:] = _nhwc(inp['dh2']).reshape(M, C)
@@ -240,21 +245,21 @@ def _cell_dev(env, si, gscale=1.0):
 @functools.lru_cache(maxsize=None)
 def _cell_hook_source(si):
     c_src, ld, cols, mode = CELL_HOOKS[si]
-    B, cx, C, H = CELL_SHAPES[si]
+    B, cx, C, H, Wd = _shape(si)
     rs = np.random.RandomState(77 + si)
     if mode == 1:
-        src = _relu_source(rs, (B * H * H, c_src), cols)
+        src = _relu_source(rs, (B * H * Wd, c_src), cols)
     else:
-        src = rs.randn(B * H * H, c_src).astype(np.float32)
+        src = rs.randn(B * H * Wd, c_src).astype(np.float32)
     return _frozen(src)[0]
 
 
 def _run_cell(env, si, prec, det=0, dx_only=0, hook=False, gscale=1.0, legacy=False):
     """one cell backward; d_in prefilled with 1e3.  legacy: through pivp_convlstm_backward."""
     pivp, _lib, lib = env
-    B, cx, C, H = CELL_SHAPES[si]
+    B, cx, C, H, Wd = _shape(si)
     d = _cell_dev(env, si, gscale)
-    M, cin = B * H * H, cx + C
+    M, cin = B * H * Wd, cx + C
     dc = d['dc0'].clone()
     dG = torch.empty((M, 4 * C), dtype=torch.float32, device=DEV)
     wt = torch.empty_like(d['wd'])
@@ -265,7 +270,7 @@ def _run_cell(env, si, prec, det=0, dx_only=0, hook=False, gscale=1.0, legacy=Fa
             d['dha'].data_ptr(), C, d['wide'].data_ptr() + cx * 4, cin, dc.data_ptr(), 1, dG.data_ptr(), wt.data_ptr(), d_in.data_ptr(), dW.data_ptr(),
             db.data_ptr())
     if legacy:
-        _lib.check(lib.pivp_convlstm_backward(*head, B, H, H, _st()), 'pivp_convlstm_backward')
+        _lib.check(lib.pivp_convlstm_backward(*head, B, H, Wd, _st()), 'pivp_convlstm_backward')
     else:
         scratch = torch.zeros(lib.pivp_convlstm_backward_form_scratch_floats(cx, C), dtype=torch.float32, device=DEV)
         ep = (None, 0, 0, 0)
@@ -275,9 +280,9 @@ def _run_cell(env, si, prec, det=0, dx_only=0, hook=False, gscale=1.0, legacy=Fa
             buf[:, ld - c_src:] = _t(_cell_hook_source(si))
             ep = (buf.data_ptr() + (ld - c_src) * 4, ld, cols, mode)
         _lib.check(lib.pivp_convlstm_backward_form(prec, *head, scratch.data_ptr() if prec else None, *ep, ctypes.byref(applied), det, dx_only,
-                                                   B, H, H, _st()), 'pivp_convlstm_backward_form')
+                                                   B, H, Wd, _st()), 'pivp_convlstm_backward_form')
     torch.cuda.synchronize()
-    nchw = lambda t, ch: t.cpu().numpy().reshape(B, H, H, ch).transpose(0, 3, 1, 2)
+    nchw = lambda t, ch: t.cpu().numpy().reshape(B, H, Wd, ch).transpose(0, 3, 1, 2)
     return dict(din=nchw(d_in, cin), din_flat=d_in.cpu().numpy(), dG=nchw(dG, 4 * C), dG_flat=dG.cpu().numpy(), dc=nchw(dc, C), dc_flat=dc.cpu().numpy(),
                 dW=pivp.from_internal('lstm1/conv/W', dW.cpu().numpy(), (4 * C, cin, 5, 5)), db=db.cpu().numpy(), applied=applied.value)
 
@@ -295,7 +300,7 @@ def _form_err(env, si, prec, det, dx_only=0, gscale=1.0):
 
 def _check_cell(env, si, prec, r, det, dx_only=0, gscale=1.0, label=''):
     """the gates of one run: dG and dc from the fp32 gate kernel, no element of d_in left at its 1e3 prefill, d_in by the form's rule"""
-    B, cx, C, H = CELL_SHAPES[si]
+    B, cx, C, H, Wd = _shape(si)
     _, ref = _cell_case(si, gscale)
     cols = slice(0, cx) if dx_only else slice(None)      # dx_only: the h columns are not asserted (left alone, cleared or computed: all within the contract)
     eG, eC = _rel(r['dG'], ref['dG']), _rel(r['dc'], ref['dc'])
