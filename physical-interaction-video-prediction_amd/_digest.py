@@ -2,7 +2,7 @@
 
 build.py embeds it in the library (`pivp_build_digest()`, include/pivp_hip.h) and `_lib.load()` recomputes it from the sources that
 travel with the package: a library older than the code it claims to implement refuses to load, so a GPU test can never pass on a stale
-build.  Sources only (csrc/*.hip, csrc/*.h, the eight public headers): objects, the .so and compile flags are not part of it -- an
+build.  Sources only (csrc/*.hip, csrc/*.h, the nine public headers): objects, the .so and compile flags are not part of it -- an
 instrumented build (PIVP_EXTRA_FLAGS) of the same sources is still the same code."""
 import hashlib
 import os
@@ -17,11 +17,12 @@ INPUT_GRAD_HEADER = os.path.join(HERE, '..', 'include', 'pivp_input_grad.h')    
 STATE_HEADER = os.path.join(HERE, '..', 'include', 'pivp_state.h')      # the recurrent state across rollouts (pivp_plan_set_rollout_state, pivp_state_copy)
 STATE_GRAD_HEADER = os.path.join(HERE, '..', 'include', 'pivp_state_grad.h')      # gradients through that state (pivp_plan_set_state_grad)
 GOAL_COST_HEADER = os.path.join(HERE, '..', 'include', 'pivp_goal_cost.h')      # the planner's goal-image cost (pivp_goal_image_cost)
+MPC_HEADER = os.path.join(HERE, '..', 'include', 'pivp_mpc.h')      # closed-loop planning (pivp_cem_update_ex, pivp_cem_shift)
 
 
 def source_files():
     names = sorted(n for n in os.listdir(CSRC) if n.endswith('.hip') or n.endswith('.h'))
-    return [os.path.join(CSRC, n) for n in names] + [DATA_HEADER, HEADER, OPTIM_HEADER, LOSS_HEADER, INPUT_GRAD_HEADER, STATE_HEADER, STATE_GRAD_HEADER, GOAL_COST_HEADER]
+    return [os.path.join(CSRC, n) for n in names] + [DATA_HEADER, HEADER, OPTIM_HEADER, LOSS_HEADER, INPUT_GRAD_HEADER, STATE_HEADER, STATE_GRAD_HEADER, GOAL_COST_HEADER, MPC_HEADER]
 
 
 def source_digest(paths=None):

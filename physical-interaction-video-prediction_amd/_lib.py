@@ -1,6 +1,6 @@
 """ctypes binding of libpivp_hip.so (the C ABI declared in include/pivp_hip.h, the data feed's entry points of include/pivp_data.h and the
 guarded optimizer step's of include/pivp_optim.h, the image loss's and the seed hook of include/pivp_loss.h, the
-sweep's input gradients and mode of include/pivp_input_grad.h, the recurrent state across rollouts of include/pivp_state.h, the gradients through it of include/pivp_state_grad.h, the planner's goal-image cost of include/pivp_goal_cost.h).
+sweep's input gradients and mode of include/pivp_input_grad.h, the recurrent state across rollouts of include/pivp_state.h, the gradients through it of include/pivp_state_grad.h, the planner's goal-image cost of include/pivp_goal_cost.h, closed-loop planning's of include/pivp_mpc.h).
 
 There is no CPU fallback: if the library is missing or fails to load, `load()` raises."""
 import ctypes
@@ -206,6 +206,11 @@ STATE_GRAD_SIGNATURES = {
 GOAL_COST_SIGNATURES = {
     'pivp_goal_image_cost': (_i, [_vp, _vp, _i, _vp, _f, _vp, _f, _f, _f, _f, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
 }
+# ... and the two include/pivp_mpc.h declares (closed-loop planning: the CEM update with kept elites / the mean / colored noise, the receding-horizon shift)
+MPC_SIGNATURES = {
+    'pivp_cem_update_ex': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _c.c_ulonglong, _i, _i, _i, _i, _f, _vp]),
+    'pivp_cem_shift': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+}
 STATE_SEGMENTS = 14            # PIVP_STATE_SEGMENTS (include/pivp_state.h)
 SWEEP_PARAMS, SWEEP_BUILTIN_LOSS = 1, 2      # PIVP_SWEEP_* (include/pivp_input_grad.h)
 OPTIM_MAX_SEGMENTS = 1024      # PIVP_OPTIM_MAX_SEGMENTS
@@ -226,7 +231,7 @@ def load():
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(DATA_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items())
                               + list(LOSS_SIGNATURES.items()) + list(INPUT_GRAD_SIGNATURES.items()) + list(STATE_SIGNATURES.items())
-                              + list(STATE_GRAD_SIGNATURES.items()) + list(GOAL_COST_SIGNATURES.items())):
+                              + list(STATE_GRAD_SIGNATURES.items()) + list(GOAL_COST_SIGNATURES.items()) + list(MPC_SIGNATURES.items())):
         fn = getattr(lib, name)   # AttributeError if the ABI and the header drift apart
         fn.restype = res
         fn.argtypes = args
@@ -237,7 +242,7 @@ def load():
         shipped = _digest.source_digest()
     except OSError as e:      # a copied / installed package without csrc/ or the repo's include/: say what is missing instead of a bare open() error
         raise RuntimeError('cannot check libpivp_hip.so against its sources: %s is missing (the package needs csrc/*.hip, csrc/*.h and '
-                           '../include/pivp_hip.h, pivp_data.h, pivp_input_grad.h, pivp_loss.h, pivp_state.h, pivp_state_grad.h, pivp_goal_cost.h and pivp_optim.h next to it; there is no CPU fallback)' % e.filename) from e
+                           '../include/pivp_hip.h, pivp_data.h, pivp_input_grad.h, pivp_loss.h, pivp_state.h, pivp_state_grad.h, pivp_goal_cost.h, pivp_mpc.h and pivp_optim.h next to it; there is no CPU fallback)' % e.filename) from e
     built = lib.pivp_build_digest().decode()
     if built != shipped:
         raise RuntimeError(

@@ -21,7 +21,12 @@ candidate in every iteration.
 Planning on a goal image: `GoalImageCost` specifies the task as a frame to reach (weighted squared / absolute error of the predicted frames, with an
 optional region of interest and step weights); `goal_image_cost` is one call of pivp_goal_image_cost (include/pivp_goal_cost.h), value and gradient
 on the device.  `cem_plan(goal_image=)`, `score_actions(goal_image=)` and `refine_actions(goal_image=)` share it, and `cem_refine` composes the two
-optimisers on that one cost: CEM chooses a plan, gradient descent polishes it, the cheapest sequence is returned."""
+optimisers on that one cost: CEM chooses a plan, gradient descent polishes it, the cheapest sequence is returned.
+
+The closed loop: `MPC` plans once per control step from the model's belief, executes the first action and observes; the next plan starts from this
+one moved on by one action (`PlanResult.warm_start`, pivp_cem_shift of include/pivp_mpc.h) and the designated pixels travel as the planes `imagine`
+advected (`cem_plan(designated_planes=)`).  `cem_plan(keep_elites=, add_mean=, noise_beta=)` are the population options of iCEM (Pinneri et al. 2020)
+in pivp_cem_update_ex; all default to off, and then `cem_plan` launches what it always did."""
 import contextlib
 import ctypes
 import inspect
@@ -33,7 +38,8 @@ import torch
 
 from . import _lib
 from .model import Model, using_config
-from .state import is_recurrent_state
+from .state import RecurrentState, is_recurrent_state
+from .state import _config as _state_config
 
 
 def one_hot_planes(coords, H, W, device=None):
@@ -368,6 +374,88 @@ def goal_image_cost(frames, spec, want_grad=False):
     return cost, per_step, grad
 
 
+MAX_COLORED_HORIZON = 64      # PIVP_CEM_MAX_COLORED_STEPS (include/pivp_mpc.h)
+
+
+def _five(v, what, default):
+    """None | scalar | (5,) -> (5,) float64, finite: a per-dimension value of the receding-horizon shift."""
+    a = np.full(5, float(default)) if v is None else _host_array(v, what)
+    if a.shape not in ((), (5,)) or not np.isfinite(a).all():
+        raise ValueError('%s must be a finite scalar or (5,), got shape %s' % (what, a.shape))
+    return np.ascontiguousarray(np.broadcast_to(a, (5,)))
+
+
+class _BeliefToCome(object):
+    """Stands for a batch-1 belief of the frames' size in `_check_cem_args`, where the belief itself does not exist yet."""
+
+
+class PlanWarmStart(object):
+    """What one planning call hands to the next (`cem_plan(warm=)`): the sampling distribution `mean`, `std` (horizon, 5) and the `kept`
+    sequences (horizon, keep_elites, 5) or None, as float32 device tensors.  Made by a plan result's `warm_start()`."""
+
+    def __init__(self, mean, std, kept=None):
+        for name, t in (('mean', mean), ('std', std), ('kept', kept)):
+            if t is None and name == 'kept':
+                continue
+            if not torch.is_tensor(t) or t.dtype != torch.float32:
+                raise ValueError('PlanWarmStart.%s must be a float32 tensor, not %r' % (name, t.dtype if torch.is_tensor(t) else type(t).__name__))
+        if mean.dim() != 2 or mean.shape[1] != 5 or mean.shape[0] < 1 or std.shape != mean.shape:
+            raise ValueError('PlanWarmStart: mean and std must both be (horizon, 5), got %s and %s' % (tuple(mean.shape), tuple(std.shape)))
+        if kept is not None and (kept.dim() != 3 or kept.shape[0] != mean.shape[0] or kept.shape[2] != 5 or kept.shape[1] < 1):
+            raise ValueError('PlanWarmStart: kept must be (%d, keep_elites, 5), got %s' % (mean.shape[0], tuple(kept.shape)))
+        self.mean, self.std, self.kept = mean, std, kept
+
+    def check(self, horizon, keep):
+        """The complaints of `cem_plan(horizon=, keep_elites=, warm=self)`."""
+        if self.mean.shape[0] != horizon:
+            raise ValueError('warm holds a distribution over %d steps, horizon = %d' % (self.mean.shape[0], horizon))
+        if self.kept is not None and self.kept.shape[1] != keep:
+            raise ValueError('warm holds %d kept sequences, keep_elites = %d' % (self.kept.shape[1], keep))
+
+
+class PlanResult(SimpleNamespace):
+    """What `cem_plan` returns: the attributes its docstring lists, and the step to the next control step's plan."""
+
+    def warm_start(self, shift=1, tail_mean=None, tail_std=None, std_floor=None):
+        """The receding-horizon step: -> the `PlanWarmStart` of the next planning call, `shift` executed actions later.  mean, std and the kept
+        sequences move up by `shift` rows (exact copies); the freed rows take tail_mean (default 0) / tail_std (default 1) -- the kept sequences
+        tail_mean clamped to the action box --, and every std is raised to std_floor (default: tail_std, so that a distribution that has collapsed
+        onto the last plan explores again).  Each of the three is a scalar or (5,), or a (5,) float32 device tensor, which is used as it is: with
+        device tensors the call is one pivp_cem_shift on copies of this result's tensors and never synchronises.  This result is left unchanged."""
+        Hh = int(self.mean.shape[0])
+        if isinstance(shift, bool) or not isinstance(shift, (int, np.integer)) or not 1 <= shift < Hh:
+            raise ValueError('shift must be an integer in [1, horizon = %d), not %r' % (Hh, shift))
+        dev = self.mean.device
+        vals = []
+        for name, v, default in (('tail_mean', tail_mean, 0.0), ('tail_std', tail_std, 1.0), ('std_floor', std_floor, None)):
+            if torch.is_tensor(v) and v.is_cuda:
+                if v.dtype != torch.float32 or tuple(v.shape) != (5,):
+                    raise ValueError('%s as a device tensor must be float32 (5,), got %s %s' % (name, v.dtype, tuple(v.shape)))
+                vals.append(v.contiguous())
+            elif v is None and default is None:
+                vals.append(None)
+            else:
+                a = _five(v, name, default)
+                if name != 'tail_mean' and (a < 0).any():
+                    raise ValueError('%s must be non-negative' % name)
+                vals.append(a)
+        if vals[2] is None:
+            vals[2] = vals[1]
+        host = [i for i, v in enumerate(vals) if not torch.is_tensor(v)]
+        if host:      # ONE host-to-device copy for what came from the host
+            up = torch.from_numpy(np.concatenate([vals[i] for i in host]).astype(np.float32)).to(dev)
+            for n, i in enumerate(host):
+                vals[i] = up[5 * n:5 * n + 5]
+        with torch.cuda.device(dev):
+            mean, std = self.mean.clone(), self.std.clone()
+            kept = self.kept.clone() if self.kept is not None else None
+            keep = int(kept.shape[1]) if kept is not None else 0
+            _lib.check(_lib.load().pivp_cem_shift(mean.data_ptr(), std.data_ptr(), kept.data_ptr() if keep else None, None, None, self._low.data_ptr(),
+                                                  self._high.data_ptr(), vals[0].data_ptr(), vals[1].data_ptr(), vals[2].data_ptr(), max(keep, 1), Hh, 0,
+                                                  keep, int(shift), self._model._stream()), 'pivp_cem_shift')
+        return PlanWarmStart(mean, std, kept)
+
+
 def _check_cem_args(model, context_images, state, designated_rc, goal_rc, horizon, past_actions, iterations, samples, elites, init_mean, init_std,
                     min_std, alpha, action_low, action_high, step_weights, plane_weights, miss_cost, chunk, seed, belief=None, goal_image=None):
     """Every complaint of `cem_plan` is a ValueError raised here, before the GPU or the library is needed.  -> the checked host-side values."""
@@ -376,7 +464,11 @@ def _check_cem_args(model, context_images, state, designated_rc, goal_rc, horizo
     if len(si) != 5 or si[1] != 1 or si[2] != 3:
         raise ValueError('context_images must be (ctx, 1, 3, H, W), got shape %s' % (si,))
     if belief is not None:      # one observed frame on top of the belief, whatever the model's context length
-        _check_belief(model, belief, si, past_actions)
+        if isinstance(belief, _BeliefToCome):      # (`MPC.reset` checks its arguments before the frames that make the belief are consumed)
+            if not getattr(model, 'carry_state', False):
+                raise ValueError('belief: the model must be built with carry_state=True')
+        else:
+            _check_belief(model, belief, si, past_actions)
         ctx = 1
     if ctx < 1 or si[0] != ctx:
         raise ValueError('context_images holds %d frames, the model was built with num_frame_before_prediction=%d' % (si[0], ctx))
@@ -458,9 +550,49 @@ def _check_cem_args(model, context_images, state, designated_rc, goal_rc, horizo
                            belief=belief, image=image)
 
 
+def _check_plan_args(model, context_images, state, designated_rc, goal_rc, horizon, past_actions, iterations, samples, elites, init_mean, init_std,
+                     min_std, alpha, action_low, action_high, step_weights, plane_weights, miss_cost, chunk, seed, belief, goal_image, keep_elites,
+                     add_mean, noise_beta, warm, designated_planes):
+    """`_check_cem_args` and the complaints about the closed-loop options (include/pivp_mpc.h): every one a ValueError raised here, before the GPU or
+    the library is needed.  -> `_check_cem_args`' values plus keep, add_mean, beta, warm, planes and ex (whether the loop calls pivp_cem_update_ex)."""
+    if designated_planes is not None:
+        if designated_rc is not None:
+            raise ValueError('designated_planes and designated_rc are two forms of one argument: give one of them')
+        sp, si = Model._host_shape(designated_planes), Model._host_shape(context_images)
+        if len(sp) != 3 or sp[1:] != tuple(si[3:]) or not 1 <= sp[0] <= Model.MAX_TRACK_PLANES:
+            raise ValueError('designated_planes must be (P, H, W) of the frames\' size with 1 <= P <= %d, got shape %s for frames of shape %s'
+                             % (Model.MAX_TRACK_PLANES, sp, si))
+        if torch.is_tensor(designated_planes) and not designated_planes.is_floating_point():
+            raise ValueError('designated_planes must be floating point, not %s' % (designated_planes.dtype,))
+        if not (torch.is_tensor(designated_planes) and designated_planes.is_cuda):      # (a device tensor is taken as it is: looking at it would synchronise)
+            host = _host_array(designated_planes, 'designated_planes')
+            if not np.isfinite(host).all() or (host < 0).any():
+                raise ValueError('designated_planes must be finite and non-negative')
+        designated_rc = np.zeros((sp[0], 2))      # (P pixels as far as the checks of goal_rc and the weights are concerned)
+    a = _check_cem_args(model, context_images, state, designated_rc, goal_rc, horizon, past_actions, iterations, samples, elites, init_mean, init_std,
+                        min_std, alpha, action_low, action_high, step_weights, plane_weights, miss_cost, chunk, seed, belief, goal_image)
+    if isinstance(keep_elites, bool) or not isinstance(keep_elites, (int, np.integer)) or not 0 <= keep_elites <= elites:
+        raise ValueError('keep_elites must be an integer in [0, elites = %d], not %r' % (elites, keep_elites))
+    if not isinstance(add_mean, (bool, np.bool_)):
+        raise ValueError('add_mean must be a bool, not %r' % (add_mean,))
+    if keep_elites + int(add_mean) > samples:
+        raise ValueError('keep_elites = %d and the mean need %d slots, samples = %d' % (keep_elites, keep_elites + 1, samples))
+    noise_beta = _finite_number(noise_beta, 'noise_beta', low=0.0)
+    if noise_beta > 0 and horizon > MAX_COLORED_HORIZON:
+        raise ValueError('noise_beta > 0 is served for a horizon of at most %d steps, not %d' % (MAX_COLORED_HORIZON, horizon))
+    if warm is not None:
+        if not isinstance(warm, PlanWarmStart):
+            raise ValueError('warm must be a PlanWarmStart (a plan result\'s warm_start()), not %r' % (type(warm).__name__,))
+        warm.check(int(horizon), int(keep_elites))
+    a.keep, a.add_mean, a.beta, a.warm, a.planes = int(keep_elites), bool(add_mean), noise_beta, warm, designated_planes
+    a.ex = bool(keep_elites or add_mean or noise_beta > 0 or warm is not None)
+    return a
+
+
 def cem_plan(model, context_images, state, designated_rc, goal_rc, horizon, past_actions=None, iterations=3, samples=32, elites=8, init_mean=None,
              init_std=1.0, min_std=1e-3, alpha=0.0, action_low=None, action_high=None, step_weights=None, plane_weights=None, miss_cost=None,
-             chunk=None, seed=0, trace=False, belief=None, goal_image=None):
+             chunk=None, seed=0, trace=False, keep_elites=0, add_mean=False, noise_beta=0.0, warm=None, designated_planes=None, belief=None,
+             goal_image=None):
     """Cross-entropy-method planning of `horizon` actions that move P designated pixels to their goals, entirely on the model's device.
 
     context_images (ctx, 1, 3, H, W), state (1, 5): what the robot sees now; designated_rc (P, 2) whole (row, col) pixels of the LAST context frame,
@@ -491,11 +623,23 @@ def cem_plan(model, context_images, state, designated_rc, goal_rc, horizon, past
     (horizon, samples), the per-step image costs.  The goal and its weights are uploaded once, in front of the loop.  None: the launches and the bits
     of a call without the argument.
 
+    Closed-loop options (include/pivp_mpc.h; all off by default, and then the loop calls pivp_cem_update and returns the bits it always did):
+    keep_elites: the best `keep_elites` (<= elites) candidates of an iteration stay in the population, slots 0 .. keep_elites-1 in rank order, and are
+    scored again beside the new samples.  add_mean: the slot behind them holds the clamped mean instead of a sample.  noise_beta > 0: each candidate's
+    noise is correlated over the horizon (power-law spectrum f^-beta, unit variance per step; horizon <= 64).  warm: a `PlanWarmStart` -- the
+    previous control step's result moved on by `warm_start()` -- whose mean / std replace init_mean / init_std and whose kept sequences enter slots
+    0 .. keep_elites-1 of the first iteration as they are.  The result's `kept` (horizon, keep_elites, 5) holds the final update's best sequences,
+    and its `warm_start(shift=1, ...)` returns the next call's `PlanWarmStart` through one pivp_cem_shift.
+    designated_planes: (P, H, W) non-negative planes on the last context frame, instead of designated_rc -- the distribution a designated pixel
+    has become after the robot moved (`imagine`'s planes).  Expanded to the chunk size once, in front of the loop; one-hot planes give the bits of
+    designated_rc.  A device tensor is used as it is (its values are not inspected: that would synchronise).
+
     Side effect: the rollouts run on `model` as `imagine` does, so afterwards `model.gen_images` / `gen_states` hold the LAST rollout (the last
     chunk of the last iteration), `pixel_distrib` / `pixel_mass` are None and `backward()` raises until the model is called again.  With
     chunk < samples every rollout copies its slice of the action buffer and allocates its own frames, on the stream, without a host round trip."""
-    a = _check_cem_args(model, context_images, state, designated_rc, goal_rc, horizon, past_actions, iterations, samples, elites, init_mean,
-                        init_std, min_std, alpha, action_low, action_high, step_weights, plane_weights, miss_cost, chunk, seed, belief, goal_image)
+    a = _check_plan_args(model, context_images, state, designated_rc, goal_rc, horizon, past_actions, iterations, samples, elites, init_mean,
+                         init_std, min_std, alpha, action_low, action_high, step_weights, plane_weights, miss_cost, chunk, seed, belief, goal_image,
+                         keep_elites, add_mean, noise_beta, warm, designated_planes)
     with torch.cuda.device(model.device) if torch.cuda.is_available() else contextlib.nullcontext():
         return _cem_iterate(model, a, _cem_upload(model, a, context_images, state), trace)
 
@@ -519,7 +663,9 @@ def _cem_upload(model, a, context_images, state):
         setattr(b, name, packed[at:at + np.size(v)].view(np.shape(v)))
         at += np.size(v)
     b.planes = None
-    if P:
+    if getattr(a, 'planes', None) is not None:      # the designated pixels as distributions: expanded to the chunk size here, once
+        b.planes = model._as_device(a.planes, (H, W)).view(1, P, H, W).expand(C, P, H, W).contiguous()
+    elif P:
         b.planes = torch.zeros((C, P, H * W), dtype=torch.float32, device=dev)
         b.planes.scatter_(2, b.pixel.to(torch.int64).view(1, P, 1).expand(C, P, 1), 1.0)      # one-hot planes, built on the device (H * W < 2^24: exact)
         b.planes = b.planes.view(C, P, H, W)
@@ -531,6 +677,13 @@ def _cem_upload(model, a, context_images, state):
     b.actions = torch.zeros((steps, K, 5), dtype=torch.float32, device=dev)
     if t0:
         b.actions[:t0] = b.past.unsqueeze(1)
+    b.kept_in = 0
+    if getattr(a, 'warm', None) is not None:      # the previous control step's distribution and its kept sequences (copies: the loop writes into them)
+        b.mean = a.warm.mean.to(device=dev, dtype=torch.float32).clone()
+        b.std = a.warm.std.to(device=dev, dtype=torch.float32).clone()
+        if a.keep and a.warm.kept is not None:
+            b.actions[t0:, :a.keep] = a.warm.kept.to(device=dev, dtype=torch.float32)
+            b.kept_in = 1
     b.best_actions = torch.zeros((Hh, 5), dtype=torch.float32, device=dev)
     b.best_cost = torch.full((1,), float('inf'), dtype=torch.float32, device=dev)
     b.per_iter, b.cost, b.mass, b.edist = new(a.iterations), new(K), new(Hh, K, P), new(Hh, K, P)
@@ -554,6 +707,12 @@ def _cem_iterate(model, a, b, trace=False):
     stream = model._stream()
 
     def update(have_cost, it):
+        if getattr(a, 'ex', False):      # kept elites, the mean as a candidate, colored noise or a warm start: include/pivp_mpc.h
+            _lib.check(lib.pivp_cem_update_ex(b.cost.data_ptr() if have_cost else None, b.actions.data_ptr(), b.mean.data_ptr(), b.std.data_ptr(),
+                                              b.best_actions.data_ptr(), b.best_cost.data_ptr(), b.low.data_ptr(), b.high.data_ptr(),
+                                              b.elite_idx.data_ptr(), K, steps, t0, M, a.alpha, a.min_std, ctypes.c_ulonglong(a.seed), it, a.keep,
+                                              0 if have_cost else getattr(b, 'kept_in', 0), int(a.add_mean), a.beta, stream), 'pivp_cem_update_ex')
+            return
         _lib.check(lib.pivp_cem_update(b.cost.data_ptr() if have_cost else None, b.actions.data_ptr(), b.mean.data_ptr(), b.std.data_ptr(),
                                        b.best_actions.data_ptr(), b.best_cost.data_ptr(), b.low.data_ptr(), b.high.data_ptr(),
                                        b.elite_idx.data_ptr(), K, steps, t0, M, a.alpha, a.min_std, ctypes.c_ulonglong(a.seed), it, stream),
@@ -593,8 +752,10 @@ def _cem_iterate(model, a, b, trace=False):
         b.per_iter[a.iterations - 1:].copy_(b.best_cost)
         if trace:
             records[-1]['elites'] = b.elite_idx.clone()
-    return SimpleNamespace(actions=b.best_actions, cost=b.best_cost[0], mean=b.mean, std=b.std, best_cost_per_iteration=b.per_iter,
-                           trace=records if trace else None)
+    keep = getattr(a, 'keep', 0)
+    return PlanResult(actions=b.best_actions, cost=b.best_cost[0], mean=b.mean, std=b.std, best_cost_per_iteration=b.per_iter,
+                      trace=records if trace else None, kept=b.actions[t0:, :keep].contiguous() if keep else None, _model=model, _low=b.low,
+                      _high=b.high)
 
 
 # ---- gradient-based refinement of an action sequence ---------------------------------------------------------------------------------------
@@ -814,6 +975,10 @@ def _check_cem_refine_args(model, context_images, state, horizon, goal_image, pa
             raise ValueError('cem_refine plans and refines on the goal image alone: %s is not served' % name)
     if cem_arguments.get('belief') is not None:
         raise ValueError('cem_refine does not plan from a belief: refinement re-encodes the context frames')
+    for name in ('keep_elites', 'add_mean', 'noise_beta', 'warm', 'designated_planes'):
+        v = cem_arguments.get(name)
+        if v is not None and not (isinstance(v, (bool, int, float, np.bool_, np.integer, np.floating)) and not v):
+            raise ValueError('cem_refine does not serve the closed-loop option %s' % name)
     if goal_image is None:
         raise ValueError('cem_refine needs a goal_image')
     spec = _as_goal_cost(goal_image)
@@ -860,3 +1025,192 @@ def _cem_refine_iterate(model, a, b):
     pick = source.view(1)
     return SimpleNamespace(actions=three.index_select(0, pick)[0], cost=three_costs.index_select(0, pick)[0], source=source, cem=plan,
                            refine_costs=costs)
+
+
+# ---- the closed loop: plan, execute the first action, observe, plan again --------------------------------------------------------------------
+class MPC(object):
+    """Visual model-predictive control (Finn & Levine 2017; Ebert et al. 2018) around `cem_plan`: per control step ONE planning call from the
+    model's belief, warm-started by the previous step's plan moved on by one action.
+
+        ctl = MPC(model, horizon=8, goal_rc=[[40, 24]], samples=32, elites=8)      # model = Model(..., carry_state=True)
+        ctl.reset(context_images, state0, past_actions, designated_rc=[[32, 32]])
+        while True:
+            action = ctl.act()                          # (5,) on the device
+            frame, state = robot.step(action)           # the world
+            ctl.observe(frame, state)                   # the belief, the designated pixels and the plan move on
+
+    model observes: it carries the recurrent state of the frames seen so far (carry_state=True).  planner (default: model) runs the candidates'
+    rollouts from that state and must carry too; a second model with the same weights in another precision serves, the batch-1 observing steps
+    being fp32 only.  The goal is goal_rc (P, 2) for the pixels `reset(designated_rc=)` designates, goal_image (a `GoalImageCost` or a bare frame),
+    or both.  horizon >= 2.  iterations, samples, elites, init_mean, init_std, min_std, alpha, action_low, action_high, step_weights, plane_weights,
+    miss_cost, chunk, keep_elites, add_mean and noise_beta are `cem_plan`'s.  The first `act()` after a `reset()` plans cold with `iterations`;
+    later ones start from the shifted plan and run `warm_iterations` (default 1).  tail_mean / tail_std (scalar or (5,); default: the last row of
+    init_mean / init_std) fill the step that enters the horizon, std_floor (default: tail_std) is the least std a warm start samples with.
+    renormalize: the designated planes are divided by their mass after every observed step (a plane that lost all mass stays zero).  The plan of
+    control step i uses seed + i.
+
+    After `reset()`, `act()` and `observe()` enqueue launches and device-to-device copies only -- given device tensors, they never synchronise
+    with the host (`reset()` does the uploads, once)."""
+
+    def __init__(self, model, horizon, goal_image=None, goal_rc=None, iterations=3, samples=32, elites=8, init_mean=None, init_std=1.0, min_std=1e-3,
+                 alpha=0.0, action_low=None, action_high=None, step_weights=None, plane_weights=None, miss_cost=None, chunk=None, keep_elites=0,
+                 add_mean=False, noise_beta=0.0, warm_iterations=1, tail_mean=None, tail_std=None, std_floor=None, renormalize=True, seed=0,
+                 planner=None):
+        planner = model if planner is None else planner
+        for name, m in (('model', model), ('planner', planner)):
+            if not getattr(m, 'carry_state', False):
+                raise ValueError('MPC: %s must be a Model built with carry_state=True (the belief is its carried recurrent state)' % name)
+        for name, v, lo in (('horizon', horizon, 2), ('warm_iterations', warm_iterations, 1)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo:
+                raise ValueError('%s must be an integer >= %d, not %r' % (name, lo, v))
+        if not isinstance(renormalize, (bool, np.bool_)):
+            raise ValueError('renormalize must be a bool, not %r' % (renormalize,))
+        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= seed < 2 ** 63:
+            raise ValueError('seed must be an integer in [0, 2**63), not %r' % (seed,))
+        if goal_image is None and goal_rc is None:
+            raise ValueError('no goal: give goal_rc (where the designated pixels should go), goal_image (a frame to reach), or both')
+        self.tail_mean = _five(tail_mean, 'tail_mean', 0.0) if tail_mean is not None else _per_step(init_mean, 'init_mean', horizon, 0.0)[-1]
+        self.tail_std = _five(tail_std, 'tail_std', 1.0) if tail_std is not None else _per_step(init_std, 'init_std', horizon, 1.0)[-1]
+        self.std_floor = _five(std_floor, 'std_floor', 0.0) if std_floor is not None else self.tail_std
+        if (self.tail_std < 0).any() or (self.std_floor < 0).any():
+            raise ValueError('tail_std and std_floor must be non-negative')
+        self.model, self.planner, self.horizon, self.goal_image, self.goal_rc = model, planner, int(horizon), goal_image, goal_rc
+        self.warm_iterations, self.renormalize, self.seed = int(warm_iterations), bool(renormalize), int(seed)
+        self._cem = (iterations, samples, elites, init_mean, init_std, min_std, alpha, action_low, action_high, step_weights, plane_weights, miss_cost,
+                     chunk)
+        self._options = (keep_elites, add_mean, noise_beta)
+        self._b = None
+        self.step, self.last_plan = 0, None
+
+    def _check_reset_args(self, context_images, state, past_actions, designated_rc):
+        """Every complaint of `reset` is a ValueError raised here, before the GPU or the library is needed.  -> the checked host-side values."""
+        si = Model._host_shape(context_images)
+        if len(si) != 5 or si[0] < 1 or si[1] != 1 or si[2] != 3:
+            raise ValueError('context_images must be (n, 1, 3, H, W) with n >= 1 observed frames, got shape %s' % (si,))
+        n, _, _, H, W = si
+        if Model._host_shape(state) != (1, 5):
+            raise ValueError('state must be (1, 5): the robot state of the first frame, got shape %s' % (Model._host_shape(state),))
+        past = np.zeros((0, 5)) if past_actions is None else _host_array(past_actions, 'past_actions')
+        if past.size == 0:
+            past = past.reshape(0, 5)
+        if past.shape != (n - 1, 5) or not np.isfinite(past).all():
+            raise ValueError('past_actions must be finite and (%d, 5): the actions taken between the %d observed frames, got shape %s'
+                             % (n - 1, n, past.shape))
+        if (designated_rc is None) != (self.goal_rc is None):
+            raise ValueError('designated_rc goes with goal_rc: the controller was built %s goal_rc' % ('without' if self.goal_rc is None else 'with'))
+        planes = None
+        if designated_rc is not None:
+            planes = one_hot_planes(_pixel_coords(designated_rc, 'designated_rc', H, W, whole=True)[None], H, W)      # (1, P, H, W), on the host
+        frame = np.empty((1, 1, 3, H, W), np.float32)      # (the checks below look at the newest frame's shape alone)
+        a = _check_plan_args(self.planner, frame, state, None, self.goal_rc, self.horizon, None, *self._cem, self.seed, _BeliefToCome(), self.goal_image,
+                             *self._options, None, planes[0] if planes is not None else None)
+        return SimpleNamespace(n=n, H=H, W=W, past=past, planes=planes, cem=a)
+
+    def reset(self, context_images, state, past_actions=None, designated_rc=None):
+        """A new episode.  context_images (n, 1, 3, H, W): the n >= 1 frames observed so far, state (1, 5) the robot state of the FIRST of them,
+        past_actions (n-1, 5) the actions taken between them; designated_rc (P, 2): whole (row, col) pixels of the NEWEST frame, one per goal_rc.
+        The model's state is reset and all frames but the newest are consumed into it (the newest frame's robot state is then the model's own
+        prediction; with n = 1 it is `state`); the designated planes are one-hot; any warm start is forgotten.  Everything the loop needs is
+        uploaded and sized here."""
+        r = self._check_reset_args(context_images, state, past_actions, designated_rc)
+        m, n, H, W = self.model, r.n, r.H, r.W
+        with torch.cuda.device(m.device) if torch.cuda.is_available() else contextlib.nullcontext():
+            m._require_gpu()
+            frames, st = m._as_device(context_images, ()), m._as_device(state, (5,))
+            m.reset_state()
+            if n > 1:
+                m.imagine(frames[:n - 1], m._as_device(r.past, (5,)).view(n - 1, 1, 5), st, observed=n - 1)
+                st = m.gen_states[-1].clone()
+            else:      # nothing seen yet: the belief is the zero state a reset model starts from
+                zero = RecurrentState.empty(1, (H, W), frames.device)
+                zero.data.zero_()
+                m._adopt_state(zero)
+            dev = frames.device
+            self._frame, self._state = frames[n - 1:n].contiguous(), st
+            self._planes = r.planes.to(dev) if r.planes is not None else None
+            a = r.cem
+            a.belief = m.recurrent_state()
+            b = _cem_upload(self.planner, a, self._frame, self._state)
+            self._a_cold = a
+            self._a_warm = SimpleNamespace(**dict(vars(a), iterations=self.warm_iterations, ex=True))
+            b.per_iter_cold, b.per_iter_warm = b.per_iter, torch.empty((self.warm_iterations,), dtype=torch.float32, device=dev)
+            b.init_mean, b.init_std = b.mean.clone(), b.std.clone()
+            b.expand_index = torch.zeros((a.chunk,), dtype=torch.int32, device=dev)
+            b.tails = torch.from_numpy(np.stack([self.tail_mean, self.tail_std, self.std_floor]).astype(np.float32)).to(dev)
+            b.state_config = _state_config(H, W)
+            self._b = b
+        self._warm, self._action = None, None
+        self.step, self.last_plan = 0, None
+
+    def _require_reset(self):
+        if self._b is None:
+            raise RuntimeError('MPC: call reset() first')
+
+    @property
+    def planes(self):
+        """The designated pixels as they are believed to lie on the newest frame: (P, H, W) on the device, or None without goal_rc."""
+        self._require_reset()
+        return self._planes[0] if self._planes is not None else None
+
+    def act(self):
+        """Plan from the belief and the newest frame -- `cem_plan(belief=model.recurrent_state(), warm=..., designated_planes=...)` on the buffers
+        `reset` made -- and return the plan's first action, (5,) on the device.  `last_plan` holds the whole result until the next call."""
+        self._require_reset()
+        m, b = self.model, self._b
+        a = self._a_cold if self._warm is None else self._a_warm
+        a.seed = self.seed + self.step
+        with torch.cuda.device(self._frame.device):
+            b.context.copy_(self._frame.expand_as(b.context))
+            b.state.copy_(self._state.expand_as(b.state))
+            if self._planes is not None:
+                b.planes.copy_(self._planes.expand_as(b.planes))
+            _lib.check(_lib.load().pivp_state_copy(ctypes.byref(b.state_config), m._state.data.data_ptr(), 1, b.belief.data.data_ptr(), a.chunk,
+                                                   b.expand_index.data_ptr(), m._stream()), 'pivp_state_copy')
+            warm = self._warm
+            b.mean.copy_(b.init_mean if warm is None else warm.mean)
+            b.std.copy_(b.init_std if warm is None else warm.std)
+            b.kept_in = 0
+            if warm is not None and warm.kept is not None:
+                b.actions[a.ctx - 1:, :a.keep] = warm.kept
+                b.kept_in = 1
+            b.best_actions.zero_()
+            b.best_cost.fill_(float('inf'))
+            b.per_iter = b.per_iter_cold if warm is None else b.per_iter_warm
+            self.last_plan = _cem_iterate(self.planner, a, b)
+            self._action = b.best_actions[0].clone()
+        return self._action
+
+    def observe(self, frame, state, action=None):
+        """The robot has moved.  frame (3, H, W) or (1, 1, 3, H, W): what it sees now, state (5,) or (1, 5): its state now, action (5,): what it
+        actually executed (default: what the last `act()` returned).  One `imagine` step on the previous newest frame advances the belief and moves
+        the designated planes; the last plan, moved on by one action, becomes the next `act()`'s warm start (an `observe` without an `act()` since
+        the last one leaves none: the next plan is cold)."""
+        self._require_reset()
+        m = self.model
+        H, W = self._frame.shape[3:]
+        if action is None:
+            if self._action is None:
+                raise ValueError('observe() without an action: none was given and act() has not been called since the last observe()')
+            action = self._action
+        if Model._host_shape(frame) not in ((3, H, W), (1, 1, 3, H, W)):
+            raise ValueError('frame must be (3, %d, %d) or (1, 1, 3, %d, %d), got shape %s' % (H, W, H, W, Model._host_shape(frame)))
+        for name, v in (('state', state), ('action', action)):
+            if Model._host_shape(v) not in ((5,), (1, 5)):
+                raise ValueError('%s must be (5,) or (1, 5), got shape %s' % (name, Model._host_shape(v)))
+        with torch.cuda.device(self._frame.device):
+            new_frame = m._as_device(frame, ()).view(1, 1, 3, H, W)
+            new_state = m._as_device(state, ()).view(1, 5)
+            m.imagine(self._frame, m._as_device(action, ()).view(1, 1, 5), self._state, designated=self._planes, observed=1)
+            if self._planes is not None:
+                planes = m.pixel_distrib[0]
+                if self.renormalize:
+                    mass = m.pixel_mass[0]
+                    planes = planes / torch.where(mass > 0, mass, torch.ones_like(mass))[..., None, None]
+                self._planes = planes
+            self._frame, self._state = new_frame, new_state
+            self._warm = None
+            if self.last_plan is not None and self._action is not None:
+                t = self._b.tails
+                self._warm = self.last_plan.warm_start(1, t[0], t[1], t[2])
+        self._action = None
+        self.step += 1
