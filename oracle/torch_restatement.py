@@ -32,7 +32,7 @@ class TorchModel(object):
     def __init__(self, num_masks, is_cdna=True, is_dna=False, is_stp=False, use_state=True,
                  scheduled_sampling_k=-1, num_frame_before_prediction=2, prefix=None,
                  params=None, dtype=torch.float64, ln_eps=1e-6, stp_border='clamp',
-                 requires_grad=False):
+                 requires_grad=False, record=False, relu_masks=None):
         self.model_type = 'CDNA' if is_cdna else 'STP' if is_stp else 'DNA' if is_dna else None
         if self.model_type is None:
             raise ValueError("No network specified")
@@ -46,6 +46,9 @@ class TorchModel(object):
         self.stp_border = stp_border
         self.train = True
         self.rng = np.random
+        self.record = record              # tests only: keep every ReLU's detached pre-activation in self.pre[(site, step)]
+        self.relu_masks = relu_masks      # tests only: {(site, step): bool array}, that site's ReLU becomes x * mask (see _relu)
+        self.pre = {}
         self.p = OrderedDict()
         if params is not None:
             for k, v in params.items():
@@ -59,6 +62,20 @@ class TorchModel(object):
         self.psnr_all = 0.0
         self.c = {n: None for n in LSTM_NAMES}
         self.h = {n: None for n in LSTM_NAMES}
+        self.step = 0                     # timesteps since the last reset_state(): the `step` of a ReLU site's key
+
+    def _relu(self, site, x):
+        """Every ReLU of a timestep goes through here under its site name.  Default: F.relu(x), nothing else.  Tests only: with `record` the detached
+        pre-activation is kept per (site, step); a site listed in `relu_masks` passes x where its mask is set and zero elsewhere, whatever the sign
+        of x -- the branch another implementation took -- so that forward and backward no longer depend on how x near zero was rounded."""
+        key = (site, self.step)
+        if self.record:
+            self.pre[key] = x.detach()
+        mask = self.relu_masks.get(key) if self.relu_masks else None
+        if mask is None:
+            return F.relu(x)
+        mask = torch.as_tensor(np.asarray(mask), dtype=torch.bool).reshape(x.shape)
+        return torch.where(mask, x, torch.zeros_like(x))
 
     def _lstm(self, n, x):                                         # TM:234-276
         C = LSTM_C[n]
@@ -85,23 +102,23 @@ class TorchModel(object):
         from the one the trunk reads, to isolate d out / d prev through the head; the model always passes one tensor."""
         p = self.p
         B, _, H, W = prev.shape
-        enc0 = F.relu(self._ln('norm_enc0', F.conv2d(prev, p['enc0/W'], p['enc0/b'], stride=2, padding=2)))
+        enc0 = self._relu('enc0', self._ln('norm_enc0', F.conv2d(prev, p['enc0/W'], p['enc0/b'], stride=2, padding=2)))
         x = self._ln('hidden1', self._lstm('lstm1', enc0))
         x = self._ln('hidden2', self._lstm('lstm2', x))
-        enc1 = F.relu(F.conv2d(x, p['enc1/W'], p['enc1/b'], stride=2, padding=1))
+        enc1 = self._relu('enc1', F.conv2d(x, p['enc1/W'], p['enc1/b'], stride=2, padding=1))
         x = self._ln('hidden3', self._lstm('lstm3', enc1))
         x = self._ln('hidden4', self._lstm('lstm4', x))
-        enc2 = F.relu(F.conv2d(x, p['enc2/W'], p['enc2/b'], stride=2, padding=1))
+        enc2 = self._relu('enc2', F.conv2d(x, p['enc2/W'], p['enc2/b'], stride=2, padding=1))
         x = enc2
         if self.use_state:                                         # TM:556-567
             x = torch.cat((x, sa[:, :, None, None].expand(-1, -1, x.shape[2], x.shape[3])), 1)
-        enc3 = F.relu(F.conv2d(x, p['enc3/W'], p['enc3/b']))
+        enc3 = self._relu('enc3', F.conv2d(x, p['enc3/W'], p['enc3/b']))
         hidden5 = self._ln('hidden5', self._lstm('lstm5', enc3))
-        enc4 = F.relu(self._deconv('enc4', hidden5))
+        enc4 = self._relu('enc4', self._deconv('enc4', hidden5))
         x = self._ln('hidden6', self._lstm('lstm6', enc4))
-        enc5 = F.relu(self._deconv('enc5', torch.cat((x, enc1), 1)))
+        enc5 = self._relu('enc5', self._deconv('enc5', torch.cat((x, enc1), 1)))
         x = self._ln('hidden7', self._lstm('lstm7', enc5))
-        enc6 = F.relu(self._ln('norm_enc6', self._deconv('enc6', torch.cat((x, enc0), 1))))
+        enc6 = self._relu('enc6', self._ln('norm_enc6', self._deconv('enc6', torch.cat((x, enc0), 1))))
 
         if prev_head is not None:
             prev = prev_head
@@ -111,11 +128,11 @@ class TorchModel(object):
             return F.conv2d(xin, w.permute(1, 0, 2, 3), b)
 
         if self.model_type == 'CDNA':                              # TM:293-351
-            enc7 = F.relu(conv1x1_t(p['model/enc7/W'], p['model/enc7/b'], enc6))
+            enc7 = self._relu('enc7', conv1x1_t(p['model/enc7/W'], p['model/enc7/b'], enc6))
             layers = [torch.sigmoid(enc7)]
             k = F.linear(hidden5.reshape(B, -1), p['model/cdna_kerns/W'], p['model/cdna_kerns/b'])
             k = k.reshape(B, self.num_masks, 25)
-            k = F.relu(k - RELU_SHIFT) + RELU_SHIFT
+            k = self._relu('kern', k - RELU_SHIFT) + RELU_SHIFT
             k = k / k.sum(dim=2, keepdim=True)
             self.last_cdna_kerns = k.reshape(B, self.num_masks, 5, 5)
             # one grouped conv: every (b, colour) plane is a group with num_masks output maps
@@ -127,7 +144,7 @@ class TorchModel(object):
         elif self.model_type == 'STP':                             # TM:434-475
             enc7 = conv1x1_t(p['model/enc7/W'], p['model/enc7/b'], enc6)
             layers = [torch.sigmoid(enc7)]
-            s1 = F.relu(F.linear(hidden5.reshape(B, -1), p['model/stp_input/W'], p['model/stp_input/b']))
+            s1 = self._relu('s1', F.linear(hidden5.reshape(B, -1), p['model/stp_input/W'], p['model/stp_input/b']))
             ident = torch.tensor([1.0, 0, 0, 0, 1.0, 0], dtype=self.dtype)
             theta = (F.linear(s1, p['model/identity_params/W'], p['model/identity_params/b']) + ident).reshape(B, 2, 3)
             grid = F.affine_grid(theta, (B, 3, H, W), align_corners=True)
@@ -137,7 +154,7 @@ class TorchModel(object):
         else:                                                      # DNA TM:368-417
             if self.num_masks != 1:
                 raise ValueError('Only one mask is supported for DNA model.')
-            enc7 = F.relu(conv1x1_t(p['model/enc7/W'], p['model/enc7/b'], enc6))
+            enc7 = self._relu('enc7', conv1x1_t(p['model/enc7/W'], p['model/enc7/b'], enc6))
             padded = F.pad(prev, (2, 2, 2, 2))
             shifted = []
             for xk in range(5):
@@ -146,11 +163,11 @@ class TorchModel(object):
                     tmp = F.pad(tmp, (0, yk, 0, xk))               # TM:402
                     shifted.append(tmp.detach())                   # TM:404 `kernel_inputs.append(tmp.data)`: graph cut, no gradient into prev
             kin = torch.stack(shifted, 1)                          # (B,25,3,H,W)
-            kn = F.relu(enc7 - RELU_SHIFT) + RELU_SHIFT
+            kn = self._relu('kn', enc7 - RELU_SHIFT) + RELU_SHIFT
             kn = kn / kn.sum(dim=1, keepdim=True)
             layers = [(kin * kn[:, :, None]).sum(1)]
 
-        m = F.relu(conv1x1_t(p['masks/W'], p['masks/b'], enc6))    # TM:718-719
+        m = self._relu('masks', conv1x1_t(p['masks/W'], p['masks/b'], enc6))    # TM:718-719
         m = torch.softmax(m.reshape(-1, self.num_masks + 1), dim=1).reshape(B, self.num_masks + 1, H, W)  # TM:720-722
         out = prev * m[:, 0:1]
         for q, layer in enumerate(layers[:self.num_masks]):        # TM:726 zip truncation
@@ -158,6 +175,7 @@ class TorchModel(object):
         new_state = F.linear(sa, p['current_state/W'], p['current_state/b'])    # TM:730
         self.last = dict(enc0=enc0, enc1=enc1, enc2=enc2, enc3=enc3, enc4=enc4, enc5=enc5, enc6=enc6,
                          enc7=enc7, hidden5=hidden5, masks=m)
+        self.step += 1
         return out, new_state
 
     def __call__(self, x, iter_num=-1.0):                          # TM:620-764
