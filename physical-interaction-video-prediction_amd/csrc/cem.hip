@@ -9,6 +9,7 @@
 #include <math.h>
 
 #include "cem_noise.h"
+#include "cem_refit.h"
 #include "pivp_kernels.h"
 
 namespace pivp {
@@ -102,40 +103,9 @@ __global__ __launch_bounds__(CEM_MAXK) void cem_update_kernel(const float* __res
     __shared__ int el[CEM_MAXK];
     const int tid = threadIdx.x, nt = blockDim.x;
     float* __restrict__ cand = actions + (size_t)t0 * K * 5;      // rows t0 .. T-2: [Hh][K][5]
-    if (cost) {
-        const float inf = __builtin_huge_valf();
-        for (int k = tid; k < K; k += nt) { const float c = cost[k]; cs[k] = c == c ? c : inf; }
-        __syncthreads();
-        for (int k = tid; k < K; k += nt) {
-            const float c = cs[k];
-            int rank = 0;
-            for (int j = 0; j < K; ++j) { const float cj = cs[j]; rank += (cj < c || (cj == c && j < k)) ? 1 : 0; }
-            if (rank < M) el[rank] = k;
-        }
-        __syncthreads();
-        if (elite_idx) for (int m = tid; m < M; m += nt) elite_idx[m] = el[m];
-        // the best candidate ever evaluated (read before the resampling below overwrites it)
-        const float c0 = cs[el[0]];
-        const bool better = c0 < best_cost[0];
-        // refit: per (t, d), elites in rank order; the sums and the blend in fp64, rounded to fp32 once
-        for (int i = tid; i < Hh * 5; i += nt) {
-            const int t = i / 5, d = i - t * 5;
-            const float* col = cand + (size_t)t * K * 5 + d;
-            double sum = 0.0;
-            for (int m = 0; m < M; ++m) sum += (double)col[el[m] * 5];
-            const double em = sum / (double)M;
-            double var = 0.0;
-            for (int m = 0; m < M; ++m) { const double dv = (double)col[el[m] * 5] - em; var += dv * dv; }
-            const double es = sqrt(var / (double)M);
-            const double al = (double)alpha;
-            mean[i] = (float)(al * (double)mean[i] + (1.0 - al) * em);
-            stdv[i] = fmaxf((float)(al * (double)stdv[i] + (1.0 - al) * es), min_std);
-            if (better) best_actions[i] = col[el[0] * 5];
-        }
-        __syncthreads();                                          // every read of best_cost[0] and of the candidates lies in front of this barrier
-        if (better && tid == 0) best_cost[0] = c0;
-    }
-    // resample rows t0 .. T-2 (mean / std as this block just wrote them: the barrier above orders the block's own global writes)
+    // rank, refit and record: csrc/cem_refit.h, shared with cem_update_ex_kernel
+    if (cost) cem_rank_refit_record(cost, cand, mean, stdv, best_actions, best_cost, elite_idx, K, Hh, M, alpha, min_std, cs, el);
+    // resample rows t0 .. T-2 (mean / std as this block just wrote them: the phase's last barrier orders the block's own global writes)
     // One thread per (row, candidate): two Philox blocks, three Box-Muller pairs -- d = 4 takes the first normal of the third pair, as the header
     // defines it, and the pair's second normal (z[5]) is dropped.  The row's ten mean / std floats are re-read per candidate: L1 hits in a
     // kernel that the launch, not its loads, bounds.

@@ -1,8 +1,8 @@
 // Closed-loop planning (include/pivp_mpc.h): what one CEM planning call hands to the next.
 //   cem_update_ex   pivp_cem_update with kept elites, the mean as a candidate and temporally correlated noise.  ONE workgroup like cem_update_kernel
-//                (csrc/cem.hip): the rank by counting needs all K costs in LDS, and K <= 1024.  The rank / refit / record phase is that kernel's,
-//                statement for statement (cem.hip's kernel is left as it is, so the phase is restated here rather than shared; the random numbers
-//                ARE shared, csrc/cem_noise.h), so with the options off the two ops give the same bits.  Behind it:
+//                (csrc/cem.hip): the rank by counting needs all K costs in LDS, and K <= 1024.  The rank / refit / record phase is ONE function that both
+//                kernels call (csrc/cem_refit.h), and so are the random numbers (csrc/cem_noise.h): with the options off the two ops give the same
+//                bits.  Behind the phase:
 //                  keep     thread (row, j) reads the rank-j elite's five floats of its row into registers, a barrier, then writes slot j -- a block
 //                           of nt / keep rows per barrier; rows are independent, so nothing else orders the copies.
 //                  beta > 0 Q (n x n, fp64) is built once per launch in LDS: s_j = j^(-beta/2) by the first n/2 + 1 threads, sigma summed by every
@@ -19,6 +19,7 @@
 
 #include "../../include/pivp_mpc.h"
 #include "cem_noise.h"
+#include "cem_refit.h"
 #include "pivp_kernels.h"
 
 namespace pivp {
@@ -60,35 +61,7 @@ __global__ __launch_bounds__(MPC_MAXK) void cem_update_ex_kernel(CemExArgs a) {
     float* stdv = a.stdv;
     float* cand = a.actions + (size_t)a.t0 * K * 5;      // rows t0 .. T-2: [Hh][K][5]; read back after the block's own writes, hence not __restrict__
     if (cost) {
-        const float inf = __builtin_huge_valf();
-        for (int k = tid; k < K; k += nt) { const float c = cost[k]; cs[k] = c == c ? c : inf; }
-        __syncthreads();
-        for (int k = tid; k < K; k += nt) {
-            const float c = cs[k];
-            int rank = 0;
-            for (int j = 0; j < K; ++j) { const float cj = cs[j]; rank += (cj < c || (cj == c && j < k)) ? 1 : 0; }
-            if (rank < M) el[rank] = k;
-        }
-        __syncthreads();
-        if (a.elite_idx) for (int m = tid; m < M; m += nt) a.elite_idx[m] = el[m];
-        const float c0 = cs[el[0]];
-        const bool better = c0 < a.best_cost[0];
-        for (int i = tid; i < Hh * 5; i += nt) {
-            const int t = i / 5, d = i - t * 5;
-            const float* col = cand + (size_t)t * K * 5 + d;
-            double sum = 0.0;
-            for (int m = 0; m < M; ++m) sum += (double)col[el[m] * 5];
-            const double em = sum / (double)M;
-            double var = 0.0;
-            for (int m = 0; m < M; ++m) { const double dv = (double)col[el[m] * 5] - em; var += dv * dv; }
-            const double es = sqrt(var / (double)M);
-            const double al = (double)a.alpha;
-            mean[i] = (float)(al * (double)mean[i] + (1.0 - al) * em);
-            stdv[i] = fmaxf((float)(al * (double)stdv[i] + (1.0 - al) * es), a.min_std);
-            if (better) a.best_actions[i] = col[el[0] * 5];
-        }
-        __syncthreads();                                          // every read of best_cost[0] and the refit's reads of the candidates lie in front of this
-        if (better && tid == 0) a.best_cost[0] = c0;
+        cem_rank_refit_record(cost, cand, mean, stdv, a.best_actions, a.best_cost, a.elite_idx, K, Hh, M, a.alpha, a.min_std, cs, el);
         if (keep > 0) {
             // slot j <- elite el[j], row by row.  keep <= K <= nt: a pass takes nt / keep whole rows, every thread at most one (row, slot).  All of a
             // pass's reads, the barrier, then its writes; another pass touches other rows.  The last barrier also holds back the sampling below

@@ -6,7 +6,8 @@ action sequence.
 body is three stream-ordered calls -- pivp_cem_update (refit + Philox resample, one workgroup), pivp_rollout_predict (the rollout with raw
 tracked planes) and pivp_plan_cost (expected distance to the goals, each plane read once) -- with every input uploaded before the loop, no host
 synchronisation and no host-to-device copy inside it.  It knows about PAST actions: the steps before the last observed frame are fixed, only the
-horizon is optimised (the MPC case).
+horizon is optimised (the MPC case).  `cem_refine` and `MPC` reach the same loop through the same checker, `_check_cem_args`: called by `cem_plan`'s
+keywords, with `cem_plan`'s defaults, and returning one shape of checked values whoever asks.
 
 `refine_actions` is the gradient-based counterpart: Adam on an action sequence, with d cost / d actions from the model's own backward sweep
 (`Model.backward(input_grad=True, params=False, builtin_loss=False)`, include/pivp_input_grad.h) and any torch cost of the predicted frames.
@@ -228,7 +229,6 @@ def _per_step(a, what, horizon, default):
     return np.ascontiguousarray(np.broadcast_to(a, (horizon, 5)))
 
 
-# ---- the goal-image cost (include/pivp_goal_cost.h): one op on the device for CEM, scoring and refinement -----------------------------------
 def _finite_number(v, what, low=None):
     if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v) \
             or abs(float(v)) > float(np.finfo(np.float32).max):      # (the library takes float32 scalars)
@@ -238,6 +238,30 @@ def _finite_number(v, what, low=None):
     return float(v)
 
 
+def _whole_number(v, what, low, high=None):
+    """-> int(v): an integer (a bool is none) with low <= v, and v <= high where there is one."""
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < low or (high is not None and v > high):
+        raise ValueError('%s must be an integer %s, not %r' % (what, '>= %d' % low if high is None else 'in [%d, %d]' % (low, high), v))
+    return int(v)
+
+
+def _five(v, what, default, infinite=False):
+    """None | scalar | (5,) -> (5,) float64, finite (infinite=True: anything but NaN): a per-dimension value of an action."""
+    a = np.full(5, float(default)) if v is None else _host_array(v, what)
+    if a.shape not in ((), (5,)) or np.isnan(a).any() or not (infinite or np.isfinite(a).all()):
+        raise ValueError('%s must be a scalar or (5,), %s, got shape %s' % (what, 'without NaN' if infinite else 'finite', a.shape))
+    return np.ascontiguousarray(np.broadcast_to(a, (5,)))
+
+
+def _action_box(low, high, low_name, high_name):
+    """Each of low, high: None (no bound) | scalar | (5,), no NaN, low <= high -> (low, high), both (5,) float64."""
+    low, high = _five(low, low_name, -np.inf, infinite=True), _five(high, high_name, np.inf, infinite=True)
+    if (low > high).any():
+        raise ValueError('%s exceeds %s' % (low_name, high_name))
+    return low, high
+
+
+# ---- the goal-image cost (include/pivp_goal_cost.h): one op on the device for CEM, scoring and refinement -----------------------------------
 class GoalImageCost(object):
     """The cost of predicted frames against a goal image, the other standard task specification of visual MPC (Finn & Levine 2017; Ebert et al. 2018):
 
@@ -375,18 +399,7 @@ def goal_image_cost(frames, spec, want_grad=False):
 
 
 MAX_COLORED_HORIZON = 64      # PIVP_CEM_MAX_COLORED_STEPS (include/pivp_mpc.h)
-
-
-def _five(v, what, default):
-    """None | scalar | (5,) -> (5,) float64, finite: a per-dimension value of the receding-horizon shift."""
-    a = np.full(5, float(default)) if v is None else _host_array(v, what)
-    if a.shape not in ((), (5,)) or not np.isfinite(a).all():
-        raise ValueError('%s must be a finite scalar or (5,), got shape %s' % (what, a.shape))
-    return np.ascontiguousarray(np.broadcast_to(a, (5,)))
-
-
-class _BeliefToCome(object):
-    """Stands for a batch-1 belief of the frames' size in `_check_cem_args`, where the belief itself does not exist yet."""
+_BELIEF_TO_COME = object()      # stands for a batch-1 belief of the frames' size in `_check_cem_args`, where the belief itself does not exist yet
 
 
 class PlanWarmStart(object):
@@ -423,8 +436,7 @@ class PlanResult(SimpleNamespace):
         onto the last plan explores again).  Each of the three is a scalar or (5,), or a (5,) float32 device tensor, which is used as it is: with
         device tensors the call is one pivp_cem_shift on copies of this result's tensors and never synchronises.  This result is left unchanged."""
         Hh = int(self.mean.shape[0])
-        if isinstance(shift, bool) or not isinstance(shift, (int, np.integer)) or not 1 <= shift < Hh:
-            raise ValueError('shift must be an integer in [1, horizon = %d), not %r' % (Hh, shift))
+        shift = _whole_number(shift, 'shift (it stays below the horizon of %d)' % Hh, 1, Hh - 1)
         dev = self.mean.device
         vals = []
         for name, v, default in (('tail_mean', tail_mean, 0.0), ('tail_std', tail_std, 1.0), ('std_floor', std_floor, None)):
@@ -456,15 +468,20 @@ class PlanResult(SimpleNamespace):
         return PlanWarmStart(mean, std, kept)
 
 
-def _check_cem_args(model, context_images, state, designated_rc, goal_rc, horizon, past_actions, iterations, samples, elites, init_mean, init_std,
-                    min_std, alpha, action_low, action_high, step_weights, plane_weights, miss_cost, chunk, seed, belief=None, goal_image=None):
-    """Every complaint of `cem_plan` is a ValueError raised here, before the GPU or the library is needed.  -> the checked host-side values."""
+def _check_cem_args(model, context_images, state, *, designated_rc, goal_rc, horizon, past_actions, iterations, samples, elites, init_mean, init_std,
+                    min_std, alpha, action_low, action_high, step_weights, plane_weights, miss_cost, chunk, seed, keep_elites, add_mean, noise_beta,
+                    warm, designated_planes, belief, goal_image):
+    """Every complaint of `cem_plan`, those about the closed-loop options (include/pivp_mpc.h) included, is a ValueError raised here, before the GPU
+    or the library is needed.  Everything behind `state` goes by `cem_plan`'s keyword; what is left out takes `cem_plan`'s default (the line below
+    `cem_plan` hands them over: they are written once, in its signature), and a name `cem_plan` does not have is a TypeError.
+    -> the checked host-side values, the same attributes whoever asks -- `cem_plan`, `cem_refine` or `MPC.reset`.  With the options off keep,
+    add_mean, beta, warm, planes, ex, belief and image are 0, False, 0.0, None, None, False, None and None; ex: the loop calls pivp_cem_update_ex."""
     ctx = int(model.num_frame_before_prediction)
     si = Model._host_shape(context_images)
     if len(si) != 5 or si[1] != 1 or si[2] != 3:
         raise ValueError('context_images must be (ctx, 1, 3, H, W), got shape %s' % (si,))
     if belief is not None:      # one observed frame on top of the belief, whatever the model's context length
-        if isinstance(belief, _BeliefToCome):      # (`MPC.reset` checks its arguments before the frames that make the belief are consumed)
+        if belief is _BELIEF_TO_COME:      # (`MPC.reset` checks its arguments before the frames that make the belief are consumed)
             if not getattr(model, 'carry_state', False):
                 raise ValueError('belief: the model must be built with carry_state=True')
         else:
@@ -477,20 +494,32 @@ def _check_cem_args(model, context_images, state, designated_rc, goal_rc, horizo
         raise ValueError('context_images is empty: shape %s' % (si,))
     if Model._host_shape(state) != (1, 5):
         raise ValueError('state must be (1, 5), got shape %s' % (Model._host_shape(state),))
-    for name, v, lo in (('horizon', horizon, 1), ('iterations', iterations, 1), ('samples', samples, 1), ('elites', elites, 1)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo:
-            raise ValueError('%s must be an integer >= %d, not %r' % (name, lo, v))
+    if designated_planes is not None:
+        if designated_rc is not None:
+            raise ValueError('designated_planes and designated_rc are two forms of one argument: give one of them')
+        sp = Model._host_shape(designated_planes)
+        if len(sp) != 3 or sp[1:] != (H, W) or not 1 <= sp[0] <= Model.MAX_TRACK_PLANES:
+            raise ValueError('designated_planes must be (P, H, W) of the frames\' size with 1 <= P <= %d, got shape %s for frames of shape %s'
+                             % (Model.MAX_TRACK_PLANES, sp, si))
+        if torch.is_tensor(designated_planes) and not designated_planes.is_floating_point():
+            raise ValueError('designated_planes must be floating point, not %s' % (designated_planes.dtype,))
+        if not (torch.is_tensor(designated_planes) and designated_planes.is_cuda):      # (a device tensor is taken as it is: looking at it would synchronise)
+            host = _host_array(designated_planes, 'designated_planes')
+            if not np.isfinite(host).all() or (host < 0).any():
+                raise ValueError('designated_planes must be finite and non-negative')
+        designated_rc = np.zeros((sp[0], 2))      # (P pixels as far as the checks of goal_rc and the weights are concerned)
+    horizon, iterations, samples, elites = (_whole_number(v, name, 1) for name, v in (('horizon', horizon), ('iterations', iterations),
+                                                                                      ('samples', samples), ('elites', elites)))
     if samples > MAX_CEM_SAMPLES:
         raise ValueError('samples = %d: the refit runs in one workgroup and serves at most %d' % (samples, MAX_CEM_SAMPLES))
     if elites > samples:
         raise ValueError('elites = %d exceeds samples = %d' % (elites, samples))
-    if chunk is None:
-        chunk = samples
-    if isinstance(chunk, bool) or not isinstance(chunk, (int, np.integer)) or chunk < 1 or chunk > samples or samples % chunk:
+    chunk = samples if chunk is None else _whole_number(chunk, 'chunk', 1, samples)
+    if samples % chunk:
         raise ValueError('chunk must divide samples = %d, not %r' % (samples, chunk))
     image = _as_goal_cost(goal_image)
     if image is not None:
-        image.check_frames(int(horizon), int(samples), H, W)
+        image.check_frames(horizon, samples, H, W)
     pixels = designated_rc is not None or goal_rc is not None
     if not pixels and image is None:
         raise ValueError('no goal: give designated_rc and goal_rc (pixels to move), goal_image (a frame to reach), or both')
@@ -519,74 +548,34 @@ def _check_cem_args(model, context_images, state, designated_rc, goal_rc, horizo
     std = _per_step(init_std, 'init_std', horizon, 1.0)
     if (std < 0).any():
         raise ValueError('init_std must be non-negative')
-    for name, v in (('min_std', min_std), ('alpha', alpha)):
-        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v) or v < 0:
-            raise ValueError('%s must be a finite non-negative number, not %r' % (name, v))
+    min_std, alpha = _finite_number(min_std, 'min_std', 0.0), _finite_number(alpha, 'alpha', 0.0)
     if alpha > 1:
         raise ValueError('alpha must lie in [0, 1], not %r' % (alpha,))
-    bounds = []
-    for name, v, default in (('action_low', action_low, -np.inf), ('action_high', action_high, np.inf)):
-        a = np.full(5, default) if v is None else _host_array(v, name)
-        if a.shape not in ((), (5,)) or np.isnan(a).any():
-            raise ValueError('%s must be a scalar or (5,) without NaN, got shape %s' % (name, a.shape))
-        bounds.append(np.ascontiguousarray(np.broadcast_to(a, (5,))))
-    if (bounds[0] > bounds[1]).any():
-        raise ValueError('action_low exceeds action_high')
+    low, high = _action_box(action_low, action_high, 'action_low', 'action_high')
     weights = []
     for name, v, n in (('step_weights', step_weights, horizon), ('plane_weights', plane_weights, P)):
         a = np.ones(n) if v is None else _host_array(v, name)
         if a.shape != (n,) or not np.isfinite(a).all():
             raise ValueError('%s must be finite and (%d,), got shape %s' % (name, n, a.shape))
         weights.append(a)
-    if miss_cost is None:
-        miss_cost = math.sqrt((H - 1) ** 2 + (W - 1) ** 2)
-    if isinstance(miss_cost, bool) or not isinstance(miss_cost, (int, float, np.integer, np.floating)) or not math.isfinite(miss_cost):
-        raise ValueError('miss_cost must be a finite number, not %r' % (miss_cost,))
-    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= seed < 2 ** 64:
-        raise ValueError('seed must be an integer in [0, 2**64), not %r' % (seed,))
-    return SimpleNamespace(ctx=ctx, H=H, W=W, P=P, K=int(samples), M=int(elites), chunk=int(chunk), horizon=int(horizon), iterations=int(iterations),
-                           designated=designated, goals=goals, past=past, mean=mean, std=std, low=bounds[0], high=bounds[1],
-                           step_w=weights[0], plane_w=weights[1], miss_cost=float(miss_cost), min_std=float(min_std), alpha=float(alpha), seed=int(seed),
-                           belief=belief, image=image)
-
-
-def _check_plan_args(model, context_images, state, designated_rc, goal_rc, horizon, past_actions, iterations, samples, elites, init_mean, init_std,
-                     min_std, alpha, action_low, action_high, step_weights, plane_weights, miss_cost, chunk, seed, belief, goal_image, keep_elites,
-                     add_mean, noise_beta, warm, designated_planes):
-    """`_check_cem_args` and the complaints about the closed-loop options (include/pivp_mpc.h): every one a ValueError raised here, before the GPU or
-    the library is needed.  -> `_check_cem_args`' values plus keep, add_mean, beta, warm, planes and ex (whether the loop calls pivp_cem_update_ex)."""
-    if designated_planes is not None:
-        if designated_rc is not None:
-            raise ValueError('designated_planes and designated_rc are two forms of one argument: give one of them')
-        sp, si = Model._host_shape(designated_planes), Model._host_shape(context_images)
-        if len(sp) != 3 or sp[1:] != tuple(si[3:]) or not 1 <= sp[0] <= Model.MAX_TRACK_PLANES:
-            raise ValueError('designated_planes must be (P, H, W) of the frames\' size with 1 <= P <= %d, got shape %s for frames of shape %s'
-                             % (Model.MAX_TRACK_PLANES, sp, si))
-        if torch.is_tensor(designated_planes) and not designated_planes.is_floating_point():
-            raise ValueError('designated_planes must be floating point, not %s' % (designated_planes.dtype,))
-        if not (torch.is_tensor(designated_planes) and designated_planes.is_cuda):      # (a device tensor is taken as it is: looking at it would synchronise)
-            host = _host_array(designated_planes, 'designated_planes')
-            if not np.isfinite(host).all() or (host < 0).any():
-                raise ValueError('designated_planes must be finite and non-negative')
-        designated_rc = np.zeros((sp[0], 2))      # (P pixels as far as the checks of goal_rc and the weights are concerned)
-    a = _check_cem_args(model, context_images, state, designated_rc, goal_rc, horizon, past_actions, iterations, samples, elites, init_mean, init_std,
-                        min_std, alpha, action_low, action_high, step_weights, plane_weights, miss_cost, chunk, seed, belief, goal_image)
-    if isinstance(keep_elites, bool) or not isinstance(keep_elites, (int, np.integer)) or not 0 <= keep_elites <= elites:
-        raise ValueError('keep_elites must be an integer in [0, elites = %d], not %r' % (elites, keep_elites))
+    miss_cost = _finite_number(math.sqrt((H - 1) ** 2 + (W - 1) ** 2) if miss_cost is None else miss_cost, 'miss_cost')
+    seed = _whole_number(seed, 'seed', 0, 2 ** 64 - 1)
+    keep = _whole_number(keep_elites, 'keep_elites (at most elites)', 0, elites)
     if not isinstance(add_mean, (bool, np.bool_)):
         raise ValueError('add_mean must be a bool, not %r' % (add_mean,))
-    if keep_elites + int(add_mean) > samples:
-        raise ValueError('keep_elites = %d and the mean need %d slots, samples = %d' % (keep_elites, keep_elites + 1, samples))
-    noise_beta = _finite_number(noise_beta, 'noise_beta', low=0.0)
-    if noise_beta > 0 and horizon > MAX_COLORED_HORIZON:
+    if keep + int(add_mean) > samples:
+        raise ValueError('keep_elites = %d and the mean need %d slots, samples = %d' % (keep, keep + 1, samples))
+    beta = _finite_number(noise_beta, 'noise_beta', low=0.0)
+    if beta > 0 and horizon > MAX_COLORED_HORIZON:
         raise ValueError('noise_beta > 0 is served for a horizon of at most %d steps, not %d' % (MAX_COLORED_HORIZON, horizon))
     if warm is not None:
         if not isinstance(warm, PlanWarmStart):
             raise ValueError('warm must be a PlanWarmStart (a plan result\'s warm_start()), not %r' % (type(warm).__name__,))
-        warm.check(int(horizon), int(keep_elites))
-    a.keep, a.add_mean, a.beta, a.warm, a.planes = int(keep_elites), bool(add_mean), noise_beta, warm, designated_planes
-    a.ex = bool(keep_elites or add_mean or noise_beta > 0 or warm is not None)
-    return a
+        warm.check(horizon, keep)
+    return SimpleNamespace(ctx=ctx, H=H, W=W, P=P, K=samples, M=elites, chunk=chunk, horizon=horizon, iterations=iterations, designated=designated,
+                           goals=goals, past=past, mean=mean, std=std, low=low, high=high, step_w=weights[0], plane_w=weights[1], miss_cost=miss_cost,
+                           min_std=min_std, alpha=alpha, seed=seed, keep=keep, add_mean=bool(add_mean), beta=beta, warm=warm, planes=designated_planes,
+                           ex=bool(keep or add_mean or beta > 0 or warm is not None), belief=belief, image=image)
 
 
 def cem_plan(model, context_images, state, designated_rc, goal_rc, horizon, past_actions=None, iterations=3, samples=32, elites=8, init_mean=None,
@@ -637,11 +626,17 @@ def cem_plan(model, context_images, state, designated_rc, goal_rc, horizon, past
     Side effect: the rollouts run on `model` as `imagine` does, so afterwards `model.gen_images` / `gen_states` hold the LAST rollout (the last
     chunk of the last iteration), `pixel_distrib` / `pixel_mass` are None and `backward()` raises until the model is called again.  With
     chunk < samples every rollout copies its slice of the action buffer and allocates its own frames, on the stream, without a host round trip."""
-    a = _check_plan_args(model, context_images, state, designated_rc, goal_rc, horizon, past_actions, iterations, samples, elites, init_mean,
-                         init_std, min_std, alpha, action_low, action_high, step_weights, plane_weights, miss_cost, chunk, seed, belief, goal_image,
-                         keep_elites, add_mean, noise_beta, warm, designated_planes)
+    a = _check_cem_args(model, context_images, state, designated_rc=designated_rc, goal_rc=goal_rc, horizon=horizon, past_actions=past_actions,
+                        iterations=iterations, samples=samples, elites=elites, init_mean=init_mean, init_std=init_std, min_std=min_std, alpha=alpha,
+                        action_low=action_low, action_high=action_high, step_weights=step_weights, plane_weights=plane_weights, miss_cost=miss_cost,
+                        chunk=chunk, seed=seed, keep_elites=keep_elites, add_mean=add_mean, noise_beta=noise_beta, warm=warm,
+                        designated_planes=designated_planes, belief=belief, goal_image=goal_image)
     with torch.cuda.device(model.device) if torch.cuda.is_available() else contextlib.nullcontext():
         return _cem_iterate(model, a, _cem_upload(model, a, context_images, state), trace)
+
+
+# the checker's keywords default to what `cem_plan`'s do (tests/test_goal_cost_host.py compares the two signatures)
+_check_cem_args.__kwdefaults__ = {n: q.default for n, q in inspect.signature(cem_plan).parameters.items() if q.default is not q.empty and n != 'trace'}
 
 
 def _cem_upload(model, a, context_images, state):
@@ -663,66 +658,72 @@ def _cem_upload(model, a, context_images, state):
         setattr(b, name, packed[at:at + np.size(v)].view(np.shape(v)))
         at += np.size(v)
     b.planes = None
-    if getattr(a, 'planes', None) is not None:      # the designated pixels as distributions: expanded to the chunk size here, once
+    if a.planes is not None:      # the designated pixels as distributions: expanded to the chunk size here, once
         b.planes = model._as_device(a.planes, (H, W)).view(1, P, H, W).expand(C, P, H, W).contiguous()
     elif P:
         b.planes = torch.zeros((C, P, H * W), dtype=torch.float32, device=dev)
         b.planes.scatter_(2, b.pixel.to(torch.int64).view(1, P, 1).expand(C, P, 1), 1.0)      # one-hot planes, built on the device (H * W < 2^24: exact)
         b.planes = b.planes.view(C, P, H, W)
     b.image = None
-    if getattr(a, 'image', None) is not None:      # the goal image and its weights: uploaded here, read by every pivp_goal_image_cost of the loop
+    if a.image is not None:      # the goal image and its weights: uploaded here, read by every pivp_goal_image_cost of the loop
         b.image = _goal_upload(a.image, Hh, dev)
         b.image_cost = new(Hh, K)
         b.image_part = new(Hh, C) if C != K else None      # a chunk's per-step costs: [Hh][C] is not a slice of [Hh][K]
     b.actions = torch.zeros((steps, K, 5), dtype=torch.float32, device=dev)
     if t0:
         b.actions[:t0] = b.past.unsqueeze(1)
-    b.kept_in = 0
-    if getattr(a, 'warm', None) is not None:      # the previous control step's distribution and its kept sequences (copies: the loop writes into them)
-        b.mean = a.warm.mean.to(device=dev, dtype=torch.float32).clone()
-        b.std = a.warm.std.to(device=dev, dtype=torch.float32).clone()
-        if a.keep and a.warm.kept is not None:
-            b.actions[t0:, :a.keep] = a.warm.kept.to(device=dev, dtype=torch.float32)
-            b.kept_in = 1
-    b.best_actions = torch.zeros((Hh, 5), dtype=torch.float32, device=dev)
-    b.best_cost = torch.full((1,), float('inf'), dtype=torch.float32, device=dev)
+    b.best_actions, b.best_cost = new(Hh, 5), new(1)
     b.per_iter, b.cost, b.mass, b.edist = new(a.iterations), new(K), new(Hh, K, P), new(Hh, K, P)
     b.part = (new(Hh, C, P), new(Hh, C, P)) if C != K else None      # a chunk's moments: [Hh][C][P] is not a slice of [Hh][K][P]
     b.elite_idx = torch.empty((M,), dtype=torch.int32, device=dev)
     model._ensure_params(H, W)
     b.belief = None
-    if getattr(a, 'belief', None) is not None:      # ONE expansion to the chunk size (pivp_state_copy); every rollout of the loop reads it and leaves it untouched
+    if a.belief is not None:      # ONE expansion to the chunk size (pivp_state_copy); every rollout of the loop reads it and leaves it untouched
         model._checked_state(a.belief)
         b.belief = a.belief.expand(C)
     model._plan_for(C, steps + 1, H, W, keep_activations=False, observed=1 if b.belief is not None else None)      # sized and bound here, not inside the loop
+    _cem_arm(b, a, a.warm)
     return b
 
 
-def _cem_iterate(model, a, b, trace=False):
+def _cem_arm(b, a, start):
+    """The buffers as the first update of a `_cem_iterate` must find them.  start: a `PlanWarmStart` -- its mean / std are copied into b.mean / b.std
+    (the loop writes into them) and its kept sequences, if any, into slots 0 .. keep-1, with `kept_in` saying so -- or None: the initial values
+    `_cem_upload` put there.  No best sequence yet.  Device-to-device copies and fills only: `MPC.act` calls it once per control step."""
+    if start is not None:
+        b.mean.copy_(start.mean)
+        b.std.copy_(start.std)
+    b.kept_in = int(a.keep > 0 and start is not None and start.kept is not None)
+    if b.kept_in:
+        b.actions[a.ctx - 1:, :a.keep].copy_(start.kept)
+    b.best_actions.zero_()
+    b.best_cost.fill_(float('inf'))
+
+
+def _cem_iterate(model, a, b, trace=False, iterations=None, seed=None, ex=None):
     """The loop of `cem_plan` on the buffers of `_cem_upload`: pivp_cem_update, the rollout, pivp_plan_cost and / or pivp_goal_image_cost --
-    stream-ordered launches and device-to-device copies only (tests/test_gpu_planning.py runs it under torch's sync debug mode)."""
+    stream-ordered launches and device-to-device copies only (tests/test_gpu_planning.py runs it under torch's sync debug mode).  iterations, seed,
+    ex: what differs from one `MPC.act` to the next on the same checked values and buffers; None: a.iterations, a.seed, a.ex."""
     lib = _lib.load()
     P, K, M, C, Hh = a.P, a.K, a.M, a.chunk, a.horizon
     t0, steps = a.ctx - 1, a.ctx - 1 + Hh
+    iterations, seed, ex = (own if given is None else given for given, own in ((iterations, a.iterations), (seed, a.seed), (ex, a.ex)))
     stream = model._stream()
 
     def update(have_cost, it):
-        if getattr(a, 'ex', False):      # kept elites, the mean as a candidate, colored noise or a warm start: include/pivp_mpc.h
-            _lib.check(lib.pivp_cem_update_ex(b.cost.data_ptr() if have_cost else None, b.actions.data_ptr(), b.mean.data_ptr(), b.std.data_ptr(),
-                                              b.best_actions.data_ptr(), b.best_cost.data_ptr(), b.low.data_ptr(), b.high.data_ptr(),
-                                              b.elite_idx.data_ptr(), K, steps, t0, M, a.alpha, a.min_std, ctypes.c_ulonglong(a.seed), it, a.keep,
-                                              0 if have_cost else getattr(b, 'kept_in', 0), int(a.add_mean), a.beta, stream), 'pivp_cem_update_ex')
-            return
-        _lib.check(lib.pivp_cem_update(b.cost.data_ptr() if have_cost else None, b.actions.data_ptr(), b.mean.data_ptr(), b.std.data_ptr(),
-                                       b.best_actions.data_ptr(), b.best_cost.data_ptr(), b.low.data_ptr(), b.high.data_ptr(),
-                                       b.elite_idx.data_ptr(), K, steps, t0, M, a.alpha, a.min_std, ctypes.c_ulonglong(a.seed), it, stream),
-                   'pivp_cem_update')
+        shared = (b.cost.data_ptr() if have_cost else None, b.actions.data_ptr(), b.mean.data_ptr(), b.std.data_ptr(), b.best_actions.data_ptr(),
+                  b.best_cost.data_ptr(), b.low.data_ptr(), b.high.data_ptr(), b.elite_idx.data_ptr(), K, steps, t0, M, a.alpha, a.min_std,
+                  ctypes.c_ulonglong(seed), it)
+        if ex:      # kept elites, the mean as a candidate, colored noise or a warm start: include/pivp_mpc.h
+            _lib.check(lib.pivp_cem_update_ex(*shared, a.keep, 0 if have_cost else b.kept_in, int(a.add_mean), a.beta, stream), 'pivp_cem_update_ex')
+        else:
+            _lib.check(lib.pivp_cem_update(*shared, stream), 'pivp_cem_update')
 
-    belief, image = getattr(b, 'belief', None), getattr(b, 'image', None)
+    belief, image = b.belief, b.image
     from_belief = dict(observed=1, advance=False) if belief is not None else {}
     records = []
     with _starting_from(model, belief):      # (the expanded belief, read by every rollout and written by none; None: every rollout from zeros)
-        for it in range(a.iterations):
+        for it in range(iterations):
             update(it > 0, it)
             if it > 0:
                 b.per_iter[it - 1:it].copy_(b.best_cost)
@@ -748,13 +749,12 @@ def _cem_iterate(model, a, b, trace=False):
                 records.append(dict(actions=b.actions.clone(), cost=b.cost.clone(), mass=b.mass.clone(), edist=b.edist.clone()))
                 if image is not None:
                     records[-1]['image_cost'] = b.image_cost.clone()
-        update(True, a.iterations)      # the last candidates count too: best_*, mean and std reflect them (the resampled rows are not used)
-        b.per_iter[a.iterations - 1:].copy_(b.best_cost)
+        update(True, iterations)      # the last candidates count too: best_*, mean and std reflect them (the resampled rows are not used)
+        b.per_iter[iterations - 1:].copy_(b.best_cost)
         if trace:
             records[-1]['elites'] = b.elite_idx.clone()
-    keep = getattr(a, 'keep', 0)
     return PlanResult(actions=b.best_actions, cost=b.best_cost[0], mean=b.mean, std=b.std, best_cost_per_iteration=b.per_iter,
-                      trace=records if trace else None, kept=b.actions[t0:, :keep].contiguous() if keep else None, _model=model, _low=b.low,
+                      trace=records if trace else None, kept=b.actions[t0:, :a.keep].contiguous() if a.keep else None, _model=model, _low=b.low,
                       _high=b.high)
 
 
@@ -804,10 +804,7 @@ def _check_refine_args(model, context_images, state, actions, goal_image, cost_f
         sg = Model._host_shape(goal_image)
         if sg not in ((3, H, W), (B, 3, H, W)):
             raise ValueError('goal_image must be (3, %d, %d) or (%d, 3, %d, %d), got shape %s' % (H, W, B, H, W, sg))
-    if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or steps < 1:
-        raise ValueError('steps must be an integer >= 1, not %r' % (steps,))
-    if isinstance(lr, bool) or not isinstance(lr, (int, float, np.integer, np.floating)) or not math.isfinite(lr) or lr < 0:
-        raise ValueError('lr must be a finite non-negative number, not %r' % (lr,))
+    steps, lr = _whole_number(steps, 'steps', 1), _finite_number(lr, 'lr', 0.0)
     n_past = 0
     if past_actions is not None:
         sp = Model._host_shape(past_actions)
@@ -819,16 +816,8 @@ def _check_refine_args(model, context_images, state, actions, goal_image, cost_f
     if bounds is not None:
         if not isinstance(bounds, (tuple, list)) or len(bounds) != 2:
             raise ValueError('bounds must be a pair (low, high)')
-        pair = []
-        for name, v, default in (('bounds[0]', bounds[0], -np.inf), ('bounds[1]', bounds[1], np.inf)):
-            a = np.full(5, default) if v is None else _host_array(v, name)
-            if a.shape not in ((), (5,)) or np.isnan(a).any():
-                raise ValueError('%s must be a scalar or (5,) without NaN, got shape %s' % (name, a.shape))
-            pair.append(np.ascontiguousarray(np.broadcast_to(a, (5,))))
-        if (pair[0] > pair[1]).any():
-            raise ValueError('bounds: low exceeds high')
-        low, high = pair
-    return SimpleNamespace(ctx=ctx, B=B, H=H, W=W, steps_T=sa[0], n_past=n_past, iters=int(steps), lr=float(lr), low=low, high=high)
+        low, high = _action_box(bounds[0], bounds[1], 'bounds[0]', 'bounds[1]')
+    return SimpleNamespace(ctx=ctx, B=B, H=H, W=W, steps_T=sa[0], n_past=n_past, iters=steps, lr=lr, low=low, high=high)
 
 
 def refine_actions(model, context_images, state, actions, goal_image=None, cost_fn=None, steps=10, lr=0.05, past_actions=None, bounds=None):
@@ -907,7 +896,7 @@ def _refine_iterate(model, a, b, cost_fn=None, adam=_adam_launch):
         finally:
             model.scheduled_sampling_k = k
         gen = model._gen[a.ctx - 1:]
-        spec = getattr(b, 'goal_cost', None)
+        spec = b.goal_cost
         if cost_fn is None and spec is not None:      # a GoalImageCost: value and d sum(cost) / d gen from ONE op call (include/pivp_goal_cost.h)
             c = torch.empty((a.B,), dtype=torch.float32, device=gen.device)
             per_step = torch.empty((nf, a.B), dtype=torch.float32, device=gen.device)
@@ -981,20 +970,12 @@ def _check_cem_refine_args(model, context_images, state, horizon, goal_image, pa
             raise ValueError('cem_refine does not serve the closed-loop option %s' % name)
     if goal_image is None:
         raise ValueError('cem_refine needs a goal_image')
-    spec = _as_goal_cost(goal_image)
-    if spec.batch is not None:
-        raise ValueError('goal_image must be (3, H, W), got shape %s' % (spec.shape,))
-    kw = {n: q.default for n, q in inspect.signature(cem_plan).parameters.items() if q.default is not q.empty}
-    unknown = sorted(set(cem_arguments) - set(kw))
-    if unknown:
-        raise TypeError('cem_refine got unexpected keyword arguments %s' % (unknown,))
-    kw.update(cem_arguments)
-    trace = kw.pop('trace')
-    cem = _check_cem_args(model, context_images, state, None, None, horizon, past_actions, kw['iterations'], kw['samples'], kw['elites'], kw['init_mean'],
-                          kw['init_std'], kw['min_std'], kw['alpha'], kw['action_low'], kw['action_high'], None, None, None, kw['chunk'], kw['seed'],
-                          None, spec)
+    spec = _as_goal_cost(goal_image)      # (one goal per sample is `_check_cem_args`' complaint)
+    kw = dict(cem_arguments, designated_rc=None, goal_rc=None, horizon=horizon, past_actions=past_actions, goal_image=spec)
+    trace = kw.pop('trace', False)
+    cem = _check_cem_args(model, context_images, state, **kw)      # (what was refused above is None or off, as the checker's defaults are)
     shaped = lambda *shape: np.broadcast_to(np.float32(0), shape)      # the refinement's arguments exist on the device only: their shapes are checked
-    low, high = kw['action_low'], kw['action_high']
+    low, high = kw.get('action_low'), kw.get('action_high')
     refine = _check_refine_args(model, shaped(cem.ctx, 2, 3, cem.H, cem.W), shaped(2, 5), shaped(cem.ctx - 1 + cem.horizon, 2, 5), spec, None, refine_steps,
                                 lr, cem.past if cem.ctx > 1 else None, None if low is None and high is None else (low, high))
     return SimpleNamespace(cem=cem, refine=refine, spec=spec, trace=bool(trace))
@@ -1043,7 +1024,7 @@ class MPC(object):
     rollouts from that state and must carry too; a second model with the same weights in another precision serves, the batch-1 observing steps
     being fp32 only.  The goal is goal_rc (P, 2) for the pixels `reset(designated_rc=)` designates, goal_image (a `GoalImageCost` or a bare frame),
     or both.  horizon >= 2.  iterations, samples, elites, init_mean, init_std, min_std, alpha, action_low, action_high, step_weights, plane_weights,
-    miss_cost, chunk, keep_elites, add_mean and noise_beta are `cem_plan`'s.  The first `act()` after a `reset()` plans cold with `iterations`;
+    miss_cost, chunk, keep_elites, add_mean and noise_beta are `cem_plan`'s keywords, with its defaults.  The first `act()` after a `reset()` plans cold with `iterations`;
     later ones start from the shifted plan and run `warm_iterations` (default 1).  tail_mean / tail_std (scalar or (5,); default: the last row of
     init_mean / init_std) fill the step that enters the horizon, std_floor (default: tail_std) is the least std a warm start samples with.
     renormalize: the designated planes are divided by their mass after every observed step (a plane that lost all mass stays zero).  The plan of
@@ -1052,33 +1033,35 @@ class MPC(object):
     After `reset()`, `act()` and `observe()` enqueue launches and device-to-device copies only -- given device tensors, they never synchronise
     with the host (`reset()` does the uploads, once)."""
 
-    def __init__(self, model, horizon, goal_image=None, goal_rc=None, iterations=3, samples=32, elites=8, init_mean=None, init_std=1.0, min_std=1e-3,
-                 alpha=0.0, action_low=None, action_high=None, step_weights=None, plane_weights=None, miss_cost=None, chunk=None, keep_elites=0,
-                 add_mean=False, noise_beta=0.0, warm_iterations=1, tail_mean=None, tail_std=None, std_floor=None, renormalize=True, seed=0,
-                 planner=None):
+    CEM_ARGUMENTS = ('iterations', 'samples', 'elites', 'init_mean', 'init_std', 'min_std', 'alpha', 'action_low', 'action_high', 'step_weights',
+                     'plane_weights', 'miss_cost', 'chunk', 'keep_elites', 'add_mean', 'noise_beta')      # `cem_plan`'s, with its defaults
+
+    def __init__(self, model, horizon, goal_image=None, goal_rc=None, warm_iterations=1, tail_mean=None, tail_std=None, std_floor=None,
+                 renormalize=True, seed=0, planner=None, **cem_arguments):
         planner = model if planner is None else planner
         for name, m in (('model', model), ('planner', planner)):
             if not getattr(m, 'carry_state', False):
                 raise ValueError('MPC: %s must be a Model built with carry_state=True (the belief is its carried recurrent state)' % name)
-        for name, v, lo in (('horizon', horizon, 2), ('warm_iterations', warm_iterations, 1)):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo:
-                raise ValueError('%s must be an integer >= %d, not %r' % (name, lo, v))
+        unknown = sorted(set(cem_arguments) - set(self.CEM_ARGUMENTS))
+        if unknown:
+            raise TypeError('MPC got unexpected keyword arguments %s' % (unknown,))
+        horizon, warm_iterations = _whole_number(horizon, 'horizon', 2), _whole_number(warm_iterations, 'warm_iterations', 1)
         if not isinstance(renormalize, (bool, np.bool_)):
             raise ValueError('renormalize must be a bool, not %r' % (renormalize,))
-        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= seed < 2 ** 63:
-            raise ValueError('seed must be an integer in [0, 2**63), not %r' % (seed,))
+        seed = _whole_number(seed, 'seed', 0, 2 ** 63 - 1)
         if goal_image is None and goal_rc is None:
             raise ValueError('no goal: give goal_rc (where the designated pixels should go), goal_image (a frame to reach), or both')
+        init_mean, init_std = cem_arguments.get('init_mean'), cem_arguments.get('init_std')      # (None: `cem_plan`'s 0 and 1, as `_per_step` fills them)
         self.tail_mean = _five(tail_mean, 'tail_mean', 0.0) if tail_mean is not None else _per_step(init_mean, 'init_mean', horizon, 0.0)[-1]
         self.tail_std = _five(tail_std, 'tail_std', 1.0) if tail_std is not None else _per_step(init_std, 'init_std', horizon, 1.0)[-1]
         self.std_floor = _five(std_floor, 'std_floor', 0.0) if std_floor is not None else self.tail_std
         if (self.tail_std < 0).any() or (self.std_floor < 0).any():
             raise ValueError('tail_std and std_floor must be non-negative')
-        self.model, self.planner, self.horizon, self.goal_image, self.goal_rc = model, planner, int(horizon), goal_image, goal_rc
-        self.warm_iterations, self.renormalize, self.seed = int(warm_iterations), bool(renormalize), int(seed)
-        self._cem = (iterations, samples, elites, init_mean, init_std, min_std, alpha, action_low, action_high, step_weights, plane_weights, miss_cost,
-                     chunk)
-        self._options = (keep_elites, add_mean, noise_beta)
+        self.model, self.planner, self.horizon, self.goal_image, self.goal_rc = model, planner, horizon, goal_image, goal_rc
+        self.warm_iterations, self.renormalize, self.seed = warm_iterations, bool(renormalize), seed
+        # what every plan of this controller is checked with, by `cem_plan`'s keywords; `reset` adds the planes, the belief stands for the one to come
+        self._plan_arguments = dict(cem_arguments, designated_rc=None, goal_rc=goal_rc, horizon=horizon, goal_image=goal_image, seed=seed,
+                                    belief=_BELIEF_TO_COME)
         self._b = None
         self.step, self.last_plan = 0, None
 
@@ -1102,9 +1085,9 @@ class MPC(object):
         if designated_rc is not None:
             planes = one_hot_planes(_pixel_coords(designated_rc, 'designated_rc', H, W, whole=True)[None], H, W)      # (1, P, H, W), on the host
         frame = np.empty((1, 1, 3, H, W), np.float32)      # (the checks below look at the newest frame's shape alone)
-        a = _check_plan_args(self.planner, frame, state, None, self.goal_rc, self.horizon, None, *self._cem, self.seed, _BeliefToCome(), self.goal_image,
-                             *self._options, None, planes[0] if planes is not None else None)
+        a = _check_cem_args(self.planner, frame, state, designated_planes=planes[0] if planes is not None else None, **self._plan_arguments)
         return SimpleNamespace(n=n, H=H, W=W, past=past, planes=planes, cem=a)
+
 
     def reset(self, context_images, state, past_actions=None, designated_rc=None):
         """A new episode.  context_images (n, 1, 3, H, W): the n >= 1 frames observed so far, state (1, 5) the robot state of the FIRST of them,
@@ -1131,10 +1114,9 @@ class MPC(object):
             a = r.cem
             a.belief = m.recurrent_state()
             b = _cem_upload(self.planner, a, self._frame, self._state)
-            self._a_cold = a
-            self._a_warm = SimpleNamespace(**dict(vars(a), iterations=self.warm_iterations, ex=True))
+            self._a = a
             b.per_iter_cold, b.per_iter_warm = b.per_iter, torch.empty((self.warm_iterations,), dtype=torch.float32, device=dev)
-            b.init_mean, b.init_std = b.mean.clone(), b.std.clone()
+            b.init = PlanWarmStart(b.mean.clone(), b.std.clone())      # (what a cold `act()` starts from: the loop writes into b.mean / b.std)
             b.expand_index = torch.zeros((a.chunk,), dtype=torch.int32, device=dev)
             b.tails = torch.from_numpy(np.stack([self.tail_mean, self.tail_std, self.std_floor]).astype(np.float32)).to(dev)
             b.state_config = _state_config(H, W)
@@ -1156,9 +1138,7 @@ class MPC(object):
         """Plan from the belief and the newest frame -- `cem_plan(belief=model.recurrent_state(), warm=..., designated_planes=...)` on the buffers
         `reset` made -- and return the plan's first action, (5,) on the device.  `last_plan` holds the whole result until the next call."""
         self._require_reset()
-        m, b = self.model, self._b
-        a = self._a_cold if self._warm is None else self._a_warm
-        a.seed = self.seed + self.step
+        m, b, a, warm = self.model, self._b, self._a, self._warm
         with torch.cuda.device(self._frame.device):
             b.context.copy_(self._frame.expand_as(b.context))
             b.state.copy_(self._state.expand_as(b.state))
@@ -1166,19 +1146,15 @@ class MPC(object):
                 b.planes.copy_(self._planes.expand_as(b.planes))
             _lib.check(_lib.load().pivp_state_copy(ctypes.byref(b.state_config), m._state.data.data_ptr(), 1, b.belief.data.data_ptr(), a.chunk,
                                                    b.expand_index.data_ptr(), m._stream()), 'pivp_state_copy')
-            warm = self._warm
-            b.mean.copy_(b.init_mean if warm is None else warm.mean)
-            b.std.copy_(b.init_std if warm is None else warm.std)
-            b.kept_in = 0
-            if warm is not None and warm.kept is not None:
-                b.actions[a.ctx - 1:, :a.keep] = warm.kept
-                b.kept_in = 1
-            b.best_actions.zero_()
-            b.best_cost.fill_(float('inf'))
+            # cold: the initial distribution, `iterations` rounds of the update `cem_plan` would call; warm: the shifted plan and its kept sequences,
+            # `warm_iterations` rounds, always of pivp_cem_update_ex
+            _cem_arm(b, a, b.init if warm is None else warm)
             b.per_iter = b.per_iter_cold if warm is None else b.per_iter_warm
-            self.last_plan = _cem_iterate(self.planner, a, b)
+            how = {} if warm is None else dict(iterations=self.warm_iterations, ex=True)
+            self.last_plan = _cem_iterate(self.planner, a, b, seed=self.seed + self.step, **how)
             self._action = b.best_actions[0].clone()
         return self._action
+
 
     def observe(self, frame, state, action=None):
         """The robot has moved.  frame (3, H, W) or (1, 1, 3, H, W): what it sees now, state (5,) or (1, 5): its state now, action (5,): what it

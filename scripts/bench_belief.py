@@ -70,10 +70,10 @@ def main():
                 seer.imagine(imgs[:1], acts[:1], stas[0], observed=1)
                 belief, state1 = seer.recurrent_state(), seer.gen_states[-1].clone()
                 del seer
-                common = (planning._check_cem_args, [designated], [goal], HORIZON)
-                tail = (ITERS, K, ELITES, None, 1.0, 1e-3, 0.0, -2.0, 2.0, None, None, None, None, 1)
-                a_frames = common[0](m, imgs[:CTX], stas[0], *common[1:], acts[:CTX - 1, 0], *tail)
-                a_belief = common[0](m, imgs[1:2], state1, *common[1:], None, *tail, belief)
+                kw = dict(designated_rc=[designated], goal_rc=[goal], horizon=HORIZON, iterations=ITERS, samples=K, elites=ELITES, action_low=-2.0,
+                          action_high=2.0, seed=1)
+                a_frames = planning._check_cem_args(m, imgs[:CTX], stas[0], past_actions=acts[:CTX - 1, 0], **kw)
+                a_belief = planning._check_cem_args(m, imgs[1:2], state1, belief=belief, **kw)
                 b_frames = planning._cem_upload(m, a_frames, imgs[:CTX], stas[0])
                 b_belief = planning._cem_upload(m, a_belief, imgs[1:2], state1)
                 planning._cem_iterate(m, a_frames, b_frames)

@@ -111,8 +111,8 @@ def main():
     state_k = torch.from_numpy(state_np).to(dev).expand(K, -1).contiguous()
     fixed = torch.randn((steps_n, K, 5), device=dev) * 0.3
     m.imagine(ctx_k, fixed, state_k)
-    a = planning._check_cem_args(m, ctx_np, state_np, None, None, HORIZON, past_np, ITERS, K, ELITES, None, 1.0, 1e-3, 0.0, -2.0, 2.0, None, None, None,
-                                 None, 1, None, spec)
+    a = planning._check_cem_args(m, ctx_np, state_np, designated_rc=None, goal_rc=None, horizon=HORIZON, past_actions=past_np, iterations=ITERS,
+                                 samples=K, elites=ELITES, action_low=-2.0, action_high=2.0, seed=1, goal_image=spec)
     bufs = planning._cem_upload(m, a, ctx_np, state_np)
 
     def rollouts_only():

@@ -108,8 +108,7 @@ def main():
             def cem_hip():
                 return planning.cem_plan(m, ctx_k[:, :1], state_k[:1], **kw)
 
-            a = planning._check_cem_args(m, ctx_np, state_np, kw['designated_rc'], kw['goal_rc'], HORIZON, past_np, ITERS, K, ELITES, None, 1.0, 1e-3,
-                                         0.0, -2.0, 2.0, None, None, None, None, 1)
+            a = planning._check_cem_args(m, ctx_np, state_np, **kw)
             bufs = planning._cem_upload(m, a, ctx_np, state_np)
 
             def cem_hip_loop():

@@ -128,7 +128,12 @@ def test_cem_plan_goal_image_argument_errors():
     m = pivp_amd.Model(10, num_frame_before_prediction=2)
     sig = inspect.signature(planning.cem_plan).parameters
     assert list(sig)[-2:] == ['belief', 'goal_image'] and sig['goal_image'].default is None
-    assert list(inspect.signature(planning._check_cem_args).parameters)[-2:] == ['belief', 'goal_image']
+    # the checker: three positional arguments, then `cem_plan`'s own keywords (all but trace, which is no checked value) with `cem_plan`'s defaults
+    own = {n: q for n, q in sig.items() if n not in ('model', 'context_images', 'state', 'trace')}
+    checker = inspect.signature(planning._check_cem_args).parameters
+    assert list(checker)[:3] == ['model', 'context_images', 'state'] and list(checker)[3:] == list(own)
+    assert all(checker[n].kind is inspect.Parameter.KEYWORD_ONLY and checker[n].default == own[n].default for n in own)
+    assert [n for n in own if own[n].default is inspect.Parameter.empty] == ['designated_rc', 'goal_rc', 'horizon']
     assert inspect.signature(planning.score_actions).parameters['goal_image'].default is None
     G = planning.GoalImageCost
     g64 = np.zeros((3, 64, 64), np.float32)
@@ -145,15 +150,18 @@ def test_cem_plan_goal_image_argument_errors():
         planning.cem_plan(m, **_good(goal_image=None))
     with pytest.raises(ValueError, match='plane_weights'):
         planning.cem_plan(m, **_good(plane_weights=[1.0]))
-    args = [_good()[k] for k in ('context_images', 'state', 'designated_rc', 'goal_rc', 'horizon', 'past_actions')]
-    tail = (3, 32, 8, None, 1.0, 1e-3, 0.0, None, None, None, None, None, None, 0, None)
-    a = planning._check_cem_args(m, *args, *tail, g64)
+    kw = _good()
+    ctx, st = kw.pop('context_images'), kw.pop('state')
+    a = planning._check_cem_args(m, ctx, st, **kw)                                      # (goal_image=g64; the rest: the defaults)
     assert a.P == 0 and a.designated.shape == (0, 2) and isinstance(a.image, G) and a.image.weight == 1.0 and a.plane_w.shape == (0,)
     spec = G(g64, l1=0.5, step_weights=np.arange(4.0), weight=2.0)
-    args[2:4] = [[3, 4]], [[5.5, 6]]
-    a = planning._check_cem_args(m, *args, *tail, spec)
+    kw.update(designated_rc=[[3, 4]], goal_rc=[[5.5, 6]])
+    a = planning._check_cem_args(m, ctx, st, **dict(kw, goal_image=spec))
     assert a.P == 1 and a.image is spec
-    assert planning._check_cem_args(m, *args, *tail).image is None                      # a trailing default: positional callers are unaffected
+    assert planning._check_cem_args(m, ctx, st, **dict(kw, goal_image=None)).image is None
+    for args, over in (((kw['designated_rc'],), {}), ((), dict(trace=False)), ((), dict(no_such_argument=1))):      # a fourth positional; unknown names
+        with pytest.raises(TypeError):
+            planning._check_cem_args(m, ctx, st, *args, **dict(kw, **over))
     if not torch.cuda.is_available():
         for over in (dict(), dict(goal_image=spec), dict(goal_image=spec, designated_rc=[[3, 4]], goal_rc=[[5, 6]])):
             with pytest.raises(RuntimeError, match='no CPU fallback'):

@@ -8,7 +8,7 @@ import pytest
 import torch
 
 from pivp_amd import dataset as ds
-from pivp_amd.data import concat_examples
+from pivp_amd import concat_examples
 import gather_ops as GO
 
 pytestmark = pytest.mark.gpu

@@ -258,8 +258,7 @@ def test_cem_plan_on_a_goal_image_alone():
     _check_image_trace(torch, pivp_amd, ch, spec, ctx_imgs, state, past, chunk=4)
     # the loop under sync debug mode, its uploads in front
     kw = dict(SETUP, chunk=4)
-    a = planning._check_cem_args(m, ctx_imgs, state, None, None, kw['horizon'], past, kw['iterations'], kw['samples'], kw['elites'], None, kw['init_std'],
-                                 1e-3, 0.0, None, None, None, None, None, kw['chunk'], kw['seed'], None, spec)
+    a = planning._check_cem_args(m, ctx_imgs, state, designated_rc=None, goal_rc=None, past_actions=past, goal_image=spec, **kw)
     b = planning._cem_upload(m, a, ctx_imgs, state)
     quiet = _no_sync(torch, lambda: planning._cem_iterate(m, a, b, trace=False))
     assert torch.equal(quiet.actions, ch.actions) and torch.equal(quiet.best_cost_per_iteration, ch.best_cost_per_iteration)

@@ -332,8 +332,7 @@ def test_the_loop_never_synchronises_with_the_host():
         except RuntimeError:
             detects = True
         if detects:
-            a = planning._check_cem_args(m, ctx_imgs, state, kw['designated_rc'], kw['goal_rc'], kw['horizon'], past, kw['iterations'], kw['samples'],
-                                         kw['elites'], None, kw['init_std'], 1e-3, 0.0, None, None, None, None, None, kw['chunk'], kw['seed'])
+            a = planning._check_cem_args(m, ctx_imgs, state, past_actions=past, **kw)
             torch.cuda.set_sync_debug_mode('default')
             b = planning._cem_upload(m, a, ctx_imgs, state)                              # the uploads, once, in front of the loop
             torch.cuda.set_sync_debug_mode('error')

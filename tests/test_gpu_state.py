@@ -372,8 +372,7 @@ def test_the_belief_loop_never_synchronises_with_the_host():
         except RuntimeError:
             detects = True
         if detects:
-            a = planning._check_cem_args(m, imgs[1:2], state1, kw['designated_rc'], kw['goal_rc'], kw['horizon'], None, kw['iterations'], kw['samples'],
-                                         kw['elites'], None, kw['init_std'], 1e-3, 0.0, None, None, None, None, None, kw['chunk'], kw['seed'], belief)
+            a = planning._check_cem_args(m, imgs[1:2], state1, belief=belief, **kw)
             torch.cuda.set_sync_debug_mode('default')
             b = planning._cem_upload(m, a, imgs[1:2], state1)                 # the uploads and the ONE expansion of the belief, in front of the loop
             assert b.belief.batch == 16

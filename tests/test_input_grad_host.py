@@ -175,7 +175,7 @@ def test_refine_actions_adam_schedule_against_numpy():
         p -= np.float32(lr_t) * m / (v.sqrt() + np.float32(1e-8))
 
     a = SimpleNamespace(ctx=ctx, B=B, H=2, W=2, steps_T=T1, n_past=1, iters=iters, lr=lr, low=None, high=None)
-    b = SimpleNamespace(actions=torch.zeros((T1 + 1, B, 5)), images=None, states=None, goal=goal, low=None, high=None)
+    b = SimpleNamespace(actions=torch.zeros((T1 + 1, B, 5)), images=None, states=None, goal=goal, goal_cost=None, low=None, high=None)
     b.actions[:T1] = torch.from_numpy(start)
     with pivp_amd.using_config('train', False):
         refined, costs = planning._refine_iterate(stub, a, b, adam=adam)

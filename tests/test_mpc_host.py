@@ -144,24 +144,34 @@ def test_cem_plan_option_errors_come_before_the_library():
                    dict(std_floor=-0.5), dict(std_floor=np.full(5, np.inf))):
             with pytest.raises(ValueError):
                 res.warm_start(**kw)
-        # the options through _check_plan_args: what the loop reads
-        args = [_good()[k] for k in ('context_images', 'state', 'designated_rc', 'goal_rc', 'horizon', 'past_actions')]
-        tail = (2, 8, 3, None, 1.0, 1e-3, 0.0, None, None, None, None, None, None, 0, None, None)
-        a = planning._check_plan_args(m, *args, *tail, 0, False, 0.0, None, None)
-        assert (a.keep, a.add_mean, a.beta, a.warm, a.planes, a.ex) == (0, False, 0.0, None, None, False)
-        a = planning._check_plan_args(m, *args, *tail, 2, True, 1.5, None, None)
+        # the options through _check_cem_args: what the loop reads
+        kw = _good(iterations=2)
+        ctx, st = kw.pop('context_images'), kw.pop('state')
+        check = lambda **over: planning._check_cem_args(m, ctx, st, **dict(kw, **over))
+        off = check()
+        assert (off.keep, off.add_mean, off.beta, off.warm, off.planes, off.ex, off.belief, off.image) == (0, False, 0.0, None, None, False, None, None)
+        a = check(keep_elites=2, add_mean=True, noise_beta=1.5)
         assert (a.keep, a.add_mean, a.beta, a.ex) == (2, True, 1.5, True)
         w = _warm()
-        assert planning._check_plan_args(m, *args, *tail, 2, False, 0.0, w, None).warm is w
-        assert planning._check_plan_args(m, *args, *tail, 0, False, 0.0, _warm(keep=0), None).ex is True      # a warm start alone
-        args[2] = None
-        a = planning._check_plan_args(m, *args, *tail, 0, False, 0.0, None, one_hot)
+        assert check(keep_elites=2, warm=w).warm is w
+        assert check(warm=_warm(keep=0)).ex is True      # a warm start alone
+        a = check(designated_rc=None, designated_planes=one_hot)
         assert a.P == 1 and a.planes is one_hot and a.ex is False and a.goals.tolist() == [[40.0, 24.0]]
-        # cem_refine refuses what it does not serve instead of dropping it
+        # one shape of checked values, whoever asks and whatever is switched on
         train = pivp_amd.Model(10, num_frame_before_prediction=2, keep_activations=True)
-        for kw in (dict(keep_elites=1), dict(add_mean=True), dict(noise_beta=1.0), dict(warm=w), dict(designated_planes=one_hot)):
+        g64 = np.zeros((3, 64, 64), np.float32)
+        on = check(keep_elites=2, add_mean=True, noise_beta=1.5, warm=w, goal_image=g64, designated_rc=None, designated_planes=one_hot)
+        refine = planning._check_cem_refine_args(train, ctx, st, 3, g64, kw['past_actions'], 2, 0.05, dict(samples=8, elites=3)).cem
+        ctl = planning.MPC(pivp_amd.Model(10, carry_state=True), 3, goal_rc=[[40, 24]], samples=8, elites=3, keep_elites=2)
+        reset = ctl._check_reset_args(ctx, st, kw['past_actions'], [[32, 32]]).cem
+        assert set(vars(off)) == set(vars(on)) == set(vars(refine)) == set(vars(reset))
+        assert (refine.keep, refine.add_mean, refine.beta, refine.warm, refine.planes, refine.ex, refine.belief, refine.P) == (0, False, 0.0, None, None, False, None, 0)
+        assert (reset.keep, reset.ex, reset.warm, reset.P, reset.goals.tolist()) == (2, True, None, 1, [[40.0, 24.0]]) and reset.planes.shape == (1, 64, 64)
+        assert reset.belief is planning._BELIEF_TO_COME and not hasattr(ctl, '_cem') and not hasattr(ctl, '_options') and not hasattr(planning, '_check_plan_args')
+        # cem_refine refuses what it does not serve instead of dropping it
+        for over in (dict(keep_elites=1), dict(add_mean=True), dict(noise_beta=1.0), dict(warm=w), dict(designated_planes=one_hot)):
             with pytest.raises(ValueError, match='closed-loop'):
-                planning.cem_refine(train, args[0], args[1], 3, np.zeros((3, 64, 64), np.float32), past_actions=args[5], **kw)
+                planning.cem_refine(train, ctx, st, 3, g64, past_actions=kw['past_actions'], **over)
     finally:
         _lib.load = real
     assert not calls

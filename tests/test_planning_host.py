@@ -11,7 +11,8 @@ import torch
 
 import pivp_amd
 from pivp_amd import _lib, planning
-from pivp_amd.planning import cem_plan
+
+cem_plan = planning.cem_plan      # (an attribute: `from pivp_amd.planning import` would load a second copy of the module under the alias's name)
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import plan_reference as PR  # noqa: E402
@@ -174,8 +175,8 @@ def test_cem_plan_argument_errors_need_no_gpu():
         with pytest.raises(RuntimeError, match='no CPU fallback'):
             cem_plan(m1, **_good(context_images=np.zeros((1, 1, 3, 64, 64), np.float32), past_actions=None))
     # the checked values
-    a = planning._check_cem_args(m, *[_good()[k] for k in ('context_images', 'state', 'designated_rc', 'goal_rc', 'horizon', 'past_actions')],
-                                 3, 32, 8, None, 1.0, 1e-3, 0.0, None, None, None, None, None, None, 0)
+    good = _good()
+    a = planning._check_cem_args(m, good.pop('context_images'), good.pop('state'), **good)      # (everything else: `cem_plan`'s defaults)
     assert abs(a.miss_cost - np.sqrt(2 * 63.0 ** 2)) < 1e-12 and a.chunk == 32 and a.mean.shape == (4, 5) and (a.std == 1).all()
     assert a.low.tolist() == [-np.inf] * 5 and a.step_w.tolist() == [1.0] * 4
 
@@ -184,3 +185,10 @@ def test_score_actions_and_the_helpers_are_still_there():
     assert 'optimiser' in planning.__doc__ and "is the caller's" not in planning.__doc__
     with pytest.raises(ValueError):
         planning.score_actions(None, np.zeros((2, 2, 3, 8, 8)), np.zeros((1, 5)), np.zeros((4, 3, 5)), (1, 1), (2, 2))
+
+
+def test_this_module_loaded_no_second_copy_of_the_package_s_modules():
+    # `from pivp_amd.planning import` would execute planning.py and model.py again under the alias's name, with a `config` that `pivp_amd.using_config`
+    # does not set.  (predict / train, which the package does not import itself, bring such a model.py when another test module has loaded them.)
+    assert 'pivp_amd.planning' not in sys.modules and pivp_amd.planning is planning and planning.using_config is pivp_amd.using_config
+    assert 'pivp_amd.model' not in sys.modules or {'pivp_amd.predict', 'pivp_amd.train'} & set(sys.modules)
