@@ -1,10 +1,11 @@
-"""ctypes binding of libpivp_hip.so (the C ABI declared in include/pivp_hip.h, the data feed's entry points of include/pivp_data.h and the
-guarded optimizer step's of include/pivp_optim.h, the image loss's and the seed hook of include/pivp_loss.h, the
-sweep's input gradients and mode of include/pivp_input_grad.h, the recurrent state across rollouts of include/pivp_state.h, the gradients through it of include/pivp_state_grad.h, the planner's goal-image cost of include/pivp_goal_cost.h, closed-loop planning's of include/pivp_mpc.h).
+"""ctypes binding of libpivp_hip.so: the C ABI declared in the public headers under include/, one `*_SIGNATURES` table per header
+(`HEADER_SIGNATURES` below maps each header to its table, in `_digest.PUBLIC_HEADERS`' order).
 
 There is no CPU fallback: if the library is missing or fails to load, `load()` raises."""
 import ctypes
 import os
+
+from . import _digest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, 'libpivp_hip.so')
@@ -211,6 +212,12 @@ MPC_SIGNATURES = {
     'pivp_cem_update_ex': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _c.c_ulonglong, _i, _i, _i, _i, _f, _vp]),
     'pivp_cem_shift': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
 }
+# header -> the table of what it declares: what load() binds
+HEADER_SIGNATURES = {'pivp_data.h': DATA_SIGNATURES, 'pivp_hip.h': SIGNATURES, 'pivp_optim.h': OPTIM_SIGNATURES, 'pivp_loss.h': LOSS_SIGNATURES,
+                     'pivp_input_grad.h': INPUT_GRAD_SIGNATURES, 'pivp_state.h': STATE_SIGNATURES, 'pivp_state_grad.h': STATE_GRAD_SIGNATURES,
+                     'pivp_goal_cost.h': GOAL_COST_SIGNATURES, 'pivp_mpc.h': MPC_SIGNATURES}
+if tuple(HEADER_SIGNATURES) != _digest.PUBLIC_HEADERS:
+    raise ImportError('HEADER_SIGNATURES and _digest.PUBLIC_HEADERS disagree: a public header without a table of its symbols, or a table without its header')
 STATE_SEGMENTS = 14            # PIVP_STATE_SEGMENTS (include/pivp_state.h)
 SWEEP_PARAMS, SWEEP_BUILTIN_LOSS = 1, 2      # PIVP_SWEEP_* (include/pivp_input_grad.h)
 OPTIM_MAX_SEGMENTS = 1024      # PIVP_OPTIM_MAX_SEGMENTS
@@ -229,20 +236,18 @@ def load():
             "libpivp_hip.so is missing (%s). Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "or `python physical-interaction-video-prediction_amd/build.py`. There is no CPU fallback." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in (list(SIGNATURES.items()) + list(DATA_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items())
-                              + list(LOSS_SIGNATURES.items()) + list(INPUT_GRAD_SIGNATURES.items()) + list(STATE_SIGNATURES.items())
-                              + list(STATE_GRAD_SIGNATURES.items()) + list(GOAL_COST_SIGNATURES.items()) + list(MPC_SIGNATURES.items())):
-        fn = getattr(lib, name)   # AttributeError if the ABI and the header drift apart
-        fn.restype = res
-        fn.argtypes = args
+    for table in HEADER_SIGNATURES.values():
+        for name, (res, args) in table.items():
+            fn = getattr(lib, name)   # AttributeError if the ABI and the header drift apart
+            fn.restype = res
+            fn.argtypes = args
     # a library older (or newer) than the sources next to it must never stand in for them: a GPU test would then pass or fail on code
     # other than the code it claims to test
-    from . import _digest
     try:
         shipped = _digest.source_digest()
     except OSError as e:      # a copied / installed package without csrc/ or the repo's include/: say what is missing instead of a bare open() error
         raise RuntimeError('cannot check libpivp_hip.so against its sources: %s is missing (the package needs csrc/*.hip, csrc/*.h and '
-                           '../include/pivp_hip.h, pivp_data.h, pivp_input_grad.h, pivp_loss.h, pivp_state.h, pivp_state_grad.h, pivp_goal_cost.h, pivp_mpc.h and pivp_optim.h next to it; there is no CPU fallback)' % e.filename) from e
+                           '../include/%s next to it; there is no CPU fallback)' % (e.filename, ', '.join(HEADER_SIGNATURES))) from e
     built = lib.pivp_build_digest().decode()
     if built != shipped:
         raise RuntimeError(

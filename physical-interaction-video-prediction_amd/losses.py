@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from . import metrics as _metrics      # (the package's own module object: `from .metrics import ...` would load a second copy under the alias package name)
+from . import metrics as _metrics
 
 TERMS = ('mse', 'l1', 'gdl', 'dssim')
 MAX_FRAME = 11      # the largest window

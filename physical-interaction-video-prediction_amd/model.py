@@ -24,7 +24,7 @@ import torch
 
 from . import _lib
 from . import checkpoint as ckpt
-from .state import RecurrentState, is_recurrent_state
+from .state import RecurrentState
 
 
 class _Config(object):
@@ -532,7 +532,7 @@ class Model(object):
         self._state = s.clone()
 
     def _checked_state(self, s):
-        if not is_recurrent_state(s):
+        if not isinstance(s, RecurrentState):
             raise ValueError('a RecurrentState (or None) is expected, not %r' % (type(s).__name__,))
         if self._hw is not None and s.hw != self._hw:
             raise ValueError('the model was sized for %dx%d frames, the state is of %dx%d' % (self._hw + s.hw))
@@ -827,7 +827,7 @@ class Model(object):
         if initial_state_grad and not self._carried_start:
             raise ValueError('initial_state_grad=True: the last call started from zeros (after reset_state()), not from a carried state')
         if final_state_grad is not None:
-            if not is_recurrent_state(final_state_grad):
+            if not isinstance(final_state_grad, RecurrentState):
                 raise ValueError('final_state_grad must be a RecurrentState (or None), not %r' % (type(final_state_grad).__name__,))
             self._checked_state(final_state_grad)
             swept = self._swept_shape()

@@ -39,7 +39,7 @@ import torch
 
 from . import _lib
 from .model import Model, using_config
-from .state import RecurrentState, is_recurrent_state
+from .state import RecurrentState
 from .state import _config as _state_config
 
 
@@ -97,7 +97,7 @@ def expected_distance(distrib, goal_rc):
 
 def _check_belief(model, belief, ctx_shape, past_actions=None):
     """The complaints about `belief` (a batch-1 RecurrentState of the frames' size on a carry_state model, with ONE context frame and no past actions)."""
-    if not is_recurrent_state(belief):
+    if not isinstance(belief, RecurrentState):
         raise ValueError('belief must be a RecurrentState (Model.recurrent_state()), not %r' % (type(belief).__name__,))
     if not getattr(model, 'carry_state', False):
         raise ValueError('belief: the model must be built with carry_state=True')

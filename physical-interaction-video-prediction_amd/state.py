@@ -32,12 +32,6 @@ def state_layout(H, W):
     return [int(n) for n in seg], int(total.value)
 
 
-def is_recurrent_state(s):
-    """Is `s` a RecurrentState -- by its surface, not by its class object: the package is importable under two names (its directory's and the
-    `pivp_amd` alias), and a submodule imported through both is loaded twice, each time with a class object of its own."""
-    return type(s).__name__ == 'RecurrentState' and all(hasattr(s, k) for k in ('data', 'batch', 'hw', 'expand', 'select', 'clone'))
-
-
 class RecurrentState(object):
     """`data`: flat float32 tensor of batch * floats_per_sample elements; `batch`; `hw` = (H, W) of the frames."""
 

@@ -8,7 +8,7 @@ Two ways to train on a long sequence in pieces:
     every window but the last forward twice."""
 import numpy as np
 
-from .state import is_recurrent_state
+from .state import RecurrentState
 
 
 def split_windows(x, n):
@@ -84,6 +84,6 @@ def chunked_backward(model, windows, iter_num=-1.0):
             seed = model.initial_state_grad if carried else None      # (only the first window can have started from zeros)
     finally:
         _rng_restore(rng, after)
-        if is_recurrent_state(final):
+        if isinstance(final, RecurrentState):
             model._adopt_state(final)
     return total

@@ -53,7 +53,7 @@ def test_product_build_records_no_extra_flags_and_a_missing_source_tree_is_named
     from pivp_amd import _digest
     assert _lib.build_flags() == ''
     monkeypatch.setattr(_lib, '_lib', None)
-    monkeypatch.setattr(_digest, 'HEADER', os.path.join(ROOT, 'include', 'no_such_header.h'))
+    monkeypatch.setattr(_digest, 'PUBLIC_HEADERS', _digest.PUBLIC_HEADERS + ('no_such_header.h',))
     with pytest.raises(RuntimeError, match='no_such_header.h is missing'):
         _lib.load()
     monkeypatch.undo()

@@ -4,6 +4,7 @@ build and digest lists, the argument errors of `GradientClipping` / `Adam.add_ho
 import math
 import os
 import re
+import shutil
 import subprocess
 import sys
 
@@ -63,15 +64,16 @@ def test_host_side_argument_checks_of_the_entry_points_need_no_gpu():
 def test_stale_library_is_refused_after_an_edit_to_the_optim_header(monkeypatch, tmp_path):
     from pivp_amd import _digest
     before = _digest.source_digest()
-    edited = tmp_path / 'pivp_optim.h'
-    edited.write_bytes(open(_digest.OPTIM_HEADER, 'rb').read() + b'\n/* edited */\n')
-    monkeypatch.setattr(_digest, 'OPTIM_HEADER', str(edited))
+    include = shutil.copytree(_digest.INCLUDE, str(tmp_path / 'include'))      # the public headers, one of them edited ...
+    with open(os.path.join(include, 'pivp_optim.h'), 'ab') as f:
+        f.write(b'\n/* edited */\n')
+    monkeypatch.setattr(_digest, 'INCLUDE', include)
     assert _digest.source_digest() != before
     monkeypatch.setattr(_lib, '_lib', None)
     with pytest.raises(RuntimeError, match='stale'):
         _lib.load()
-    monkeypatch.setattr(_digest, 'OPTIM_HEADER', str(tmp_path / 'gone' / 'pivp_optim.h'))
-    with pytest.raises(RuntimeError, match=r'pivp_optim\.h is missing .*pivp_optim\.h next to it'):
+    os.remove(os.path.join(include, 'pivp_optim.h'))                           # ... then absent
+    with pytest.raises(RuntimeError, match=r'pivp_optim\.h is missing .*include/.*pivp_optim\.h.* next to it'):
         _lib.load()
     monkeypatch.undo()
     assert _lib.load().pivp_abi_version() == 17

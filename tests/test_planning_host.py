@@ -11,8 +11,7 @@ import torch
 
 import pivp_amd
 from pivp_amd import _lib, planning
-
-cem_plan = planning.cem_plan      # (an attribute: `from pivp_amd.planning import` would load a second copy of the module under the alias's name)
+from pivp_amd.planning import cem_plan
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import plan_reference as PR  # noqa: E402
@@ -188,7 +187,8 @@ def test_score_actions_and_the_helpers_are_still_there():
 
 
 def test_this_module_loaded_no_second_copy_of_the_package_s_modules():
-    # `from pivp_amd.planning import` would execute planning.py and model.py again under the alias's name, with a `config` that `pivp_amd.using_config`
-    # does not set.  (predict / train, which the package does not import itself, bring such a model.py when another test module has loaded them.)
-    assert 'pivp_amd.planning' not in sys.modules and pivp_amd.planning is planning and planning.using_config is pivp_amd.using_config
-    assert 'pivp_amd.model' not in sys.modules or {'pivp_amd.predict', 'pivp_amd.train'} & set(sys.modules)
+    # `from pivp_amd.planning import` hands out the package's own planning.py, whose `config` is the one `pivp_amd.using_config` sets -- and so does
+    # every other import through the alias, whichever test module made it
+    assert sys.modules['pivp_amd.planning'] is planning is pivp_amd.planning and planning.using_config is pivp_amd.using_config
+    own = pivp_amd.__name__
+    assert own != 'pivp_amd' and all(mod is sys.modules[own + name[len('pivp_amd'):]] for name, mod in list(sys.modules.items()) if name.startswith('pivp_amd.'))

@@ -16,13 +16,11 @@ import pytest
 import torch
 
 import pivp_amd
-from pivp_amd import _lib
+from pivp_amd import RecurrentState, _lib
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import state_grad_reference as SR  # noqa: E402
 
-MODEL_MODULE = sys.modules[pivp_amd.Model.__module__]
-RecurrentState = MODEL_MODULE.RecurrentState
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = {'pivp_plan_set_state_grad', 'pivp_plan_get_state_grad', 'pivp_state_grad_gather', 'pivp_state_grad_scatter'}
 STATE_NAMES = {'pivp_state_layout', 'pivp_plan_set_rollout_state', 'pivp_plan_get_rollout_state', 'pivp_state_copy'}
@@ -44,8 +42,8 @@ def test_state_grad_header_library_and_ctypes_table_agree():
     declared = _declared('pivp_state_grad.h')
     exported = set(re.findall(r' T (pivp_[a-z0-9_]+)', subprocess.check_output(['nm', '-D', _lib.LIB_PATH]).decode()))
     assert declared == set(_lib.STATE_GRAD_SIGNATURES) == NAMES and declared <= exported
-    for other in (_lib.SIGNATURES, _lib.DATA_SIGNATURES, _lib.OPTIM_SIGNATURES, _lib.LOSS_SIGNATURES, _lib.INPUT_GRAD_SIGNATURES, _lib.STATE_SIGNATURES):
-        assert not declared & set(other)
+    for header, other in _lib.HEADER_SIGNATURES.items():
+        assert header == 'pivp_state_grad.h' or not declared & set(other)
     # the model's ABI, its version and the state header stay what they were
     assert len(_declared('pivp_hip.h') - {'pivp_config', 'pivp_plan'}) == 118 == len(_lib.SIGNATURES)
     assert _declared('pivp_state.h') == set(_lib.STATE_SIGNATURES) == STATE_NAMES
@@ -132,15 +130,10 @@ class _Tensor(object):
         return self._ptr
 
 
-class _State(object):
-    def __init__(self, ptr, batch=2, hw=(64, 64)):
+class _State(RecurrentState):
+    def __init__(self, ptr, batch=2, hw=(64, 64)):      # (not the parent's: no buffer is sized or checked)
         self.data, self.batch, self.hw = _Tensor(ptr), batch, hw
         self.data.device = torch.device('cpu')
-
-    expand = select = clone = None
-
-
-_State.__name__ = 'RecurrentState'      # (states are recognised by surface: state.is_recurrent_state)
 
 
 def _after_a_call(m, rec, carried):
