@@ -131,6 +131,30 @@ struct LastRollout {
     bool state_lost;            // ... which that rollout overwrote with its own final state (state_in == state_out)
 };
 
+// The forms a timestep's launches take as far as cfg, the precision mode and the options decide them: computed once (step_form, below) where any of the
+// three is assigned, read by Rollout::step (plan_forward.hip) and pivp_get_tap.  The other half of each choice is made per launch: a norm is applied
+// inside its consumer only if the producer's launcher reported LayerNorm partials (LnPartOut::nparts > 0), and frame_head runs only if enc6's did.
+enum class MotionHead { None, Rider, InHead, Separate };   // DNA has none; the finisher rides behind enc5's tiles; inside frame_head; cdna_kernels / stp_params
+enum class Output { FrameHead, Separate };                 // one launch (frame_head.hip) / heads_1x1 + the motion head + composite
+struct StepForm {
+    bool keep;               // a launch that applies a norm also writes the tensor and its (mean, rstd): training plans
+    bool norm_inside[9];     // norm j (hidden1..hidden7; 8 = norm_enc6) is applied by its consumer -- 1, 3: lstm2 / lstm4; 2, 4: enc1 / enc2; 6, 7: enc5 / enc6;
+                             // 8: heads_1x1, where Output::Separate runs.  (norm_enc0 and hidden5 keep their launches.)
+    bool enc3_in_enc2;       // enc3 + the state predictor in enc2's epilogue
+    bool enc4_partials;      // enc4 shares its grid with the partial sums of the motion head's Linear
+    MotionHead motion;
+    Output output;
+};
+
+// pivp_plan_set_profiling: an event pair around every ConvLSTM launch of a rollout, which reaches it through Rollout::prof.  tag: cell + 8 for a
+// first-step launch without the h half of K
+struct StepProfile {
+    bool on = false; std::vector<hipEvent_t> ev; std::vector<int> layer; size_t used = 0;
+    bool room() const { return used + 2 <= ev.size(); }
+    void begin(hipStream_t s) { if (room()) (void)hipEventRecord(ev[used], s); }
+    void end(int tag, hipStream_t s) { if (room()) { (void)hipEventRecord(ev[used + 1], s); layer[used / 2] = tag; used += 2; } }
+};
+
 }  // namespace pivp
 #pragma GCC visibility pop
 
@@ -151,7 +175,8 @@ struct pivp_plan {
     // hidden2 / hidden4 applied (and written) by enc1 / enc2's launches (0: ln_apply launches); WGRAD_BATCH: timesteps per ConvLSTM weight-gradient launch
     // (tests, measurements), whatever the precision mode; 0 = the mode's own choice
     int opt[PIVP_OPT_COUNT] = {1, 1, 1, 1, 0};
-    int wg_cap = 1;                   // dG ring slots per ring = min(T - 2, WG_BATCH_MAX), fixed when the workspace is laid out
+    pivp::StepForm form = {};         // step_form(*this): recomputed wherever mode or opt is assigned
+    int wg_cap = 1;                  // dG ring slots per ring = min(T - 2, WG_BATCH_MAX), fixed when the workspace is laid out
     int eg_cap = 1;                   // slots per enc dY ring (Grads::cat6): min(T - 2, WG_BATCH_MAX), cut to ENC_RING_BYTES_MAX
     float* ws; long long ws_floats;
     int nslabs;
@@ -176,19 +201,16 @@ struct pivp_plan {
     // pivp_plan_set_state_grad (include/pivp_state_grad.h): the sweep serves a rollout that started from a state (sg_enable), is seeded with d / d (its final
     // state) (sg_seed) and leaves d loss / d (its initial state) (sg_dstate_in); null / 0: none of it
     int sg_enable = 0; const float* sg_seed = nullptr; float* sg_dstate_in = nullptr;
-    // ---- written by the rollouts ----
+    // ---- written by the rollouts: packs_valid and last by their shared prologue / epilogue, prof through Rollout::prof.  (What a rollout passes to its
+    // own steps is the Rollout's, plan_forward.hip) ----
     pivp::LastRollout last = {};
-    bool masks_every_step = false;    // pivp_rollout_predict with tracked planes: the head writes its softmaxed masks at every step
-    bool prof_on = false;             // pivp_plan_set_profiling; run_step records into prof_ev
-    std::vector<hipEvent_t> prof_ev;
-    std::vector<int> prof_layer;
-    size_t prof_used = 0;
+    pivp::StepProfile prof;
     // ---- the weight gradients' stream and its events (side_lane.h): a sweep reads it, only create / the destructor change it.  (What a sweep mutates
     // is its own: Sweep, plan_backward.hip) ----
     pivp::SideLane lane;
     ~pivp_plan() {
         lane.sync();
-        for (hipEvent_t e : prof_ev) (void)hipEventDestroy(e);
+        for (hipEvent_t e : prof.ev) (void)hipEventDestroy(e);
         lane.destroy();
     }
 };
@@ -216,11 +238,44 @@ inline bool plan_serves_backward(const pivp_config_t& c, bool det) {
     return plan_serves_forward(c) && composite_bwd_serves(c.model_type, c.height, c.width, c.num_masks, det);
 }
 
+// The static half of a timestep's choices (StepForm), each predicate with the arguments and thresholds its launch site had.
+inline StepForm step_form(const pivp_plan& p) {
+    const pivp_config_t& c = p.cfg;
+    const int B = c.batch, H = c.height, W = c.width;
+    const bool train = c.keep_activations != 0, fold_opt = p.opt[PIVP_OPT_LN_FOLD_TRAIN] || !train;
+    const Modes& md = p.mode;
+    StepForm f = {};
+    f.keep = train;
+    // lstm2 / lstm4: inference rollouts in the L2-direct modes, with enough tiles
+    f.norm_inside[1] = !train && convlstm_ln_in_ok(md.precision, 32, 32, 32, B, p.H2, p.W2) && (long)B * (p.H2 / 8) * (p.W2 / 16) >= 128;
+    f.norm_inside[3] = !train && convlstm_ln_in_ok(md.precision, 64, 64, 64, B, p.H4, p.W4) && (long)B * (p.H4 / 8) * (p.W4 / 16) >= 64;
+    f.norm_inside[2] = fold_opt && conv3x3s2_ln_ok(32, 32, B, p.H2, p.W2);      // enc1 / enc2: training plans by PIVP_OPT_LN_FOLD_TRAIN
+    f.norm_inside[4] = fold_opt && conv3x3s2_ln_ok(64, 64, B, p.H4, p.W4);
+    f.enc3_in_enc2 = !train && f.norm_inside[4] && p.opt[PIVP_OPT_FUSE_ENC3] && (p.H8 * p.W8) % 32 == 0;
+    // enc5 / enc6: only while the norm is a launch-bound 5-us kernel (<= 6 MB of hidden tensor: 64 x 64 frames at B = 32): the consumer's column blocks
+    // each stage the patch and its gamma / beta again, which at config 5's 128 x 128 costs more than one bandwidth-bound ln_apply pass
+    // (B = 32, T = 20: rollout 65.5 -> 65.9 ms with the fold, so it is not taken there).
+    auto fold_small = [](long long floats) { return floats * 4 <= 6LL << 20; };
+    f.norm_inside[6] = fold_small((long long)B * 64 * p.H4 * p.W4) && deconv3x3s2_ln_ok(64, 32, 96, B, p.H4, p.W4);
+    f.norm_inside[7] = fold_small((long long)B * 32 * p.H2 * p.W2) && deconv3x3s2_ln_ok(32, 32, 64, B, p.H2, p.W2);
+    f.norm_inside[8] = (H * W) % 64 == 0;
+    // the output side: frame_head where it beats the separate kernels, finishing the Linear's partial sums itself where it can -- which an fp32 enc4 then forms
+    const bool fh = frame_head_pays(c.model_type, B, H, W, c.num_masks);
+    const bool fh_fin = fh && c.model_type != PIVP_MODEL_DNA && frame_head_finishes(p.K5);
+    f.output = fh ? Output::FrameHead : Output::Separate;
+    f.enc4_partials = fh_fin && md.deconv(false) == Operand::F32;
+    f.motion = c.model_type == PIVP_MODEL_DNA ? MotionHead::None
+             : !fh_fin ? MotionHead::Separate
+             : f.norm_inside[6] && p.opt[PIVP_OPT_FINISH_RIDER] ? MotionHead::Rider : MotionHead::InHead;
+    return f;
+}
+
 // ---- what crosses the units ----
 void plan_layout(pivp_plan* p);                              // plan_setup.hip: the workspace carve
 size_t state_bytes(const pivp_config_t& c);                  // ... bytes of the recurrent state at batch c.batch
 bool ranges_overlap(const void* a, const void* b, size_t bytes);
-const float* step_input(const pivp_plan* plan, int t, const float* images, const unsigned char* gt_select, const float* gen_images, size_t fr);   // plan_forward.hip
+// plan_forward.hip: the frame fed to step t; ctx: the leading steps fed from `images` (0: cfg.context_frames)
+const float* step_input(const pivp_plan* plan, int t, const float* images, const unsigned char* gt_select, const float* gen_images, size_t fr, int ctx = 0);
 int state_grad_gather(const pivp_config_t& c, const float* const dc[7], const float* const din[7], float* d_state_in, hipStream_t s);             // plan_backward.hip
 int state_grad_scatter(const pivp_config_t& c, const float* d_state_out, float* const dc[7], hipStream_t s);
 

@@ -3,279 +3,290 @@
 
 using namespace pivp;
 
-// ------------------------------------------------------------------------------------------------------------
-// forward, one timestep (TM:659-731)
-// ------------------------------------------------------------------------------------------------------------
-static int run_step(pivp_plan* p, int t, const float* prev, const float* action, const float* state_prev,
-                    float* gen_out, float* state_out, hipStream_t s) {
-    const pivp_config_t& c = p->cfg;
+namespace {
+
+// what varies from one timestep of a rollout to the next
+struct StepIn { int t; const float* prev; const float* action; const float* state_prev; float* gen_out; float* state_out; };
+
+// One pivp_rollout_forward / pivp_rollout_predict call: what the rollout passes to its own steps and what a step mutates on the host live here -- the plan
+// is read only.  Which forms the launches take is the plan's StepForm (plan.h); a step adds the run-time half, np.
+struct Rollout {
+    // ---- constants of the call.  ctx: the leading steps fed from the caller's frames; state_in: the registered (c, h) step 0 reads (null: zeros);
+    // prof: the plan's profile record (null: profiling is off) ----
+    const pivp_plan& p; hipStream_t s; int ctx; const float* state_in; StepProfile* prof;
+    bool masks_every_step = false;    // pivp_rollout_predict with tracked planes: the head writes its softmaxed masks at every step
+    const pivp_config_t& c = p.cfg; const StepForm& f = p.form; const Modes& md = p.mode;
+    float* const ws = p.ws; float* const lnpA = ws + p.o_lnpart; float* const lnpB = ws + p.o_lnpart2;
     const int B = c.batch, H = c.height, W = c.width;
-    float* ws = p->ws;
-    const Slab& S = p->slabs[t % p->nslabs];
-    const Slab* Sp = t > 0 ? &p->slabs[(t - 1) % p->nslabs] : nullptr;
-    float* lnp = ws + p->o_lnpart;
     const float eps = c.ln_eps;
-    const bool train = c.keep_activations != 0;
+    const int ln_cap = ln_partial_cap(H * W);   // partial slots per sample in lnp (see the workspace carve)
+    const int n2 = 32 * p.H2 * p.W2, n4 = 64 * p.H4 * p.W4, n8 = 128 * p.H8 * p.W8;
+    // ---- the step in flight: set at the top of step() ----
+    int t = 0; const Slab* S = nullptr; const Slab* Sp = nullptr;      // the step's slab and the one below it (t = 0: none)
+    float* lnp = nullptr; int np = 0;       // the LayerNorm partials of the tensor last produced: their buffer, and how many per sample its launcher reported (0: none)
+    bool enc3_done = false;                 // enc2's epilogue ran enc3 + the state predictor
+    bool partials_done = false;             // the partial sums of the motion head's Linear are in o_linpart
+    MotionHead motion = MotionHead::None;   // the form the motion head takes in this step: f.motion, or InHead where the rider's launch did not run
+
     // t = 0: h == 0, skipped, and c from the zero buffer -- unless the rollout starts from a registered state (pivp_plan_set_rollout_state): then the
     // ordinary two-operand launch on the caller's (c, h)
-    const float* const sin = t == 0 ? p->state_in : nullptr;
-    auto hp = [&](int i) -> const float* { return Sp ? ws + Sp->h[i] : sin ? sin + state_seg_offset(c, 2 * i + 1) : nullptr; };
-    auto cp = [&](int i) -> const float* { return Sp ? ws + Sp->c[i] : sin ? sin + state_seg_offset(c, 2 * i) : ws + p->o_zero; };
-    const int ln_cap = ln_partial_cap(H * W);   // partial slots per sample in lnp (see the workspace carve)
-    int np = 0;
-    const Modes& md = p->mode;
+    const float* hp(int i) const { return Sp ? ws + Sp->h[i] : state_in ? state_in + state_seg_offset(c, 2 * i + 1) : nullptr; }
+    const float* cp(int i) const { return Sp ? ws + Sp->c[i] : state_in ? state_in + state_seg_offset(c, 2 * i) : ws + p.o_zero; }
+    float* other(float* q) const { return q == lnpA ? lnpB : lnpA; }
     // cell i on x; ln_in: x is the raw output of the cell in front, normalised while staged -- the partials of this cell's own output then go to part_out
-    auto lstm = [&](int i, const float* x, int ldx, const LnIn* ln_in = nullptr, float* part_out = nullptr) {
-        const bool prof = p->prof_on && p->prof_used + 2 <= p->prof_ev.size();
-        if (prof) (void)hipEventRecord(p->prof_ev[p->prof_used], s);
+    int lstm(int i, const float* x, int ldx, const LnIn* ln_in = nullptr, float* part_out = nullptr) {
+        if (prof) prof->begin(s);
         const MapSize m = lstm_map(c, i);
         ConvLstmOpts o{};
-        if (train) o.gates_out = ws + S.gates[i];
+        if (f.keep) o.gates_out = ws + S->gates[i];
         // the LayerNorm behind every ConvLSTM gets its statistics from the ConvLSTM epilogue (np partials per sample)
         o.ln_out.part = part_out ? part_out : lnp; o.ln_out.cap = ln_cap; o.ln_out.nparts = &np;
-        if (md.packs()) { o.w_bf16 = reinterpret_cast<const unsigned short*>(ws + p->o_wbf16[i]); o.operand = md.precision; }
+        if (md.packs()) { o.w_bf16 = reinterpret_cast<const unsigned short*>(ws + p.o_wbf16[i]); o.operand = md.precision; }
         o.ln_in = ln_in;
-        int rc = run_convlstm(x, kLstm[i].cx, ldx, hp(i), kLstm[i].C, P(p, p->i_lstm_w[i]), P(p, p->i_lstm_b[i]),
-                              cp(i), ws + S.c[i], ws + S.h[i], B, m.H, m.W, s, o);
-        if (prof) {
-            (void)hipEventRecord(p->prof_ev[p->prof_used + 1], s);
-            p->prof_layer[p->prof_used / 2] = i + (hp(i) ? 0 : 8);   // +8: first-step launch without the h half of K
-            p->prof_used += 2;
-        }
+        int rc = run_convlstm(x, kLstm[i].cx, ldx, hp(i), kLstm[i].C, P(&p, p.i_lstm_w[i]), P(&p, p.i_lstm_b[i]),
+                              cp(i), ws + S->c[i], ws + S->h[i], B, m.H, m.W, s, o);
+        if (prof) prof->end(i + (hp(i) ? 0 : 8), s);   // +8: first-step launch without the h half of K
         return rc;
-    };
-    auto ln = [&](int j, const float* x, float* out, int n, int C, int ldo, int relu, int fused_nparts) {
+    }
+    float* stat(int j) const { return ws + S->lnstat + (size_t)j * B * 2; }      // norm j's (mean, rstd) per sample
+    int ln(int j, const float* x, float* out, int n, int C, int ldo, int relu) {      // norm j by a launch of its own, from the current partials (none: ln_stats first)
         LayerNormOpts o{};
-        o.stat_out = ws + S.lnstat + (size_t)j * B * 2; o.fused_nparts = fused_nparts;
-        return run_layernorm(x, P(p, p->i_ln_g[j]), P(p, p->i_ln_b[j]), out, lnp, B, n, C, ldo, eps, relu, s, o);
-    };
-    auto norm_in = [&](int j) { return LnIn{P(p, p->i_ln_g[j]), P(p, p->i_ln_b[j]), lnp, np, eps}; };      // norm j applied by its consumer, from the current partials
-    auto keep = [&](int j, float* out, int ld) { return NormKeep{out, ld, ws + S.lnstat + (size_t)j * B * 2}; };      // ... which a training plan has it write
-    const int n2 = 32 * p->H2 * p->W2, n4 = 64 * p->H4 * p->W4, n8 = 128 * p->H8 * p->W8;
-
-    // group 0 (TM:595): enc0 -> norm_enc0 -> relu   => cat7[:, 32:64]
-    RC(conv_enc0(prev, P(p, p->i_enc_w[0]), P(p, p->i_enc_b[0]), ws + S.e0raw, B, H, W, s, lnp, ln_cap, &np));
-    RC(ln(0, ws + S.e0raw, ws + S.cat7 + 32, n2, 32, 64, 1, np));
-    // group 1 (TM:596): lstm1 -> hidden1 -> lstm2 -> hidden2 -> enc1 -> relu  => cat6[:, 64:96]
-    RC(lstm(0, ws + S.cat7 + 32, 64));
-    // Inference rollouts in the L2-direct modes: hidden1 / hidden3 feed only lstm2 / lstm4, whose eight-wave kernels apply the norm while
-    // they stage their patch (the partials of their own output go to the second buffer: their blocks finish while others still read the input's).
-    float* const lnpA = ws + p->o_lnpart, * const lnpB = ws + p->o_lnpart2;
-    auto other = [&](float* q) { return q == lnpA ? lnpB : lnpA; };
-    const bool fold_l2 = !train && np > 0 && convlstm_ln_in_ok(md.precision, 32, 32, 32, B, p->H2, p->W2) &&
-                         (long)B * (p->H2 / 8) * (p->W2 / 16) >= 128;
-    if (fold_l2) {
-        const LnIn li = norm_in(1);
-        float* q = other(lnp);
-        RC(lstm(1, ws + S.h[0], 32, &li, q));
-        lnp = q;
-    } else {
-        RC(ln(1, ws + S.h[0], ws + S.n1, n2, 32, 32, 0, np));
-        RC(lstm(1, ws + S.n1, 32));
+        o.stat_out = stat(j); o.fused_nparts = np;
+        return run_layernorm(x, P(&p, p.i_ln_g[j]), P(&p, p.i_ln_b[j]), out, lnp, B, n, C, ldo, eps, relu, s, o);
     }
-    // Inference rollouts: hidden2 / hidden4 feed only enc1 / enc2, so their norms are applied while those convs stage their input
-    // (run_conv3x3s2_ln) instead of by a launch of their own; training keeps the materialised tensors (the backward sweep reads them).
-    // Training plans take the same launch (round 6) and have it WRITE the normalised hidden2 / hidden4 (every input pixel of a stride-2 3x3 conv is the
-    // tap (1..2, 1..2) of exactly one anchor) and the samples' (mean, rstd) for the backward sweep: two ln_apply launches per timestep less.
-    if (np > 0 && (p->opt[PIVP_OPT_LN_FOLD_TRAIN] || !train) && conv3x3s2_ln_ok(32, 32, B, p->H2, p->W2)) {
-        Conv3x3LnOpts o{};
-        if (train) o.keep = keep(2, ws + S.n2, 32);
-        RC(run_conv3x3s2_ln(ws + S.h[1], 32, P(p, p->i_enc_w[1]), P(p, p->i_enc_b[1]), ws + S.cat6 + 64, 32, 96, 1, B, p->H2, p->W2, s, norm_in(2), o));
-    } else {
-        RC(ln(2, ws + S.h[1], ws + S.n2, n2, 32, 32, 0, np));
-        RC(run_conv3x3s2(ws + S.n2, 32, 32, P(p, p->i_enc_w[1]), P(p, p->i_enc_b[1]), ws + S.cat6 + 64, 32, 96, 1, B, p->H2, p->W2, s, 0));
-    }
-    // group 2 (TM:597)
-    RC(lstm(2, ws + S.cat6 + 64, 96));
-    const bool fold_l4 = !train && np > 0 && convlstm_ln_in_ok(md.precision, 64, 64, 64, B, p->H4, p->W4) &&
-                         (long)B * (p->H4 / 8) * (p->W4 / 16) >= 64;
-    if (fold_l4) {
-        const LnIn li = norm_in(3);
-        float* q = other(lnp);
-        RC(lstm(3, ws + S.h[2], 64, &li, q));
-        lnp = q;
-    } else {
-        RC(ln(3, ws + S.h[2], ws + S.n3, n4, 64, 64, 0, np));
-        RC(lstm(3, ws + S.n3, 64));
-    }
-    bool enc3_done = false;
-    if (train && np > 0 && p->opt[PIVP_OPT_LN_FOLD_TRAIN] && conv3x3s2_ln_ok(64, 64, B, p->H4, p->W4)) {
-        Conv3x3LnOpts o{};
-        o.keep = keep(4, ws + S.n4, 64);
-        RC(run_conv3x3s2_ln(ws + S.h[3], 64, P(p, p->i_enc_w[2]), P(p, p->i_enc_b[2]), ws + S.e2, 64, 64, 1, B, p->H4, p->W4, s, norm_in(4), o));
-    } else
-    if (!train && np > 0 && conv3x3s2_ln_ok(64, 64, B, p->H4, p->W4)) {
-        // Inference: group 3 (TM:598) and the state predictor (TM:730) in enc2's epilogue (round 6): enc3_state_kernel's launch
-        // disappears; bit-identical to it (the same fmaf chain on the matrix cores).  PIVP_OPT_FUSE_ENC3 = 0: two launches, as before.
-        Enc3Fuse f3;
-        memset(&f3, 0, sizeof(f3));
-        if (p->opt[PIVP_OPT_FUSE_ENC3] && (p->H8 * p->W8) % 32 == 0) {
-            f3.w3 = P(p, p->i_enc_w[3]); f3.b3 = P(p, p->i_enc_b[3]); f3.action = action; f3.state = state_prev; f3.wcs = P(p, p->i_cs_w); f3.bcs = P(p, p->i_cs_b);
-            f3.e3 = ws + S.e3; f3.state_out = state_out; f3.use_state = c.use_state;
-            enc3_done = true;
+    LnIn norm_in(int j) const { return LnIn{P(&p, p.i_ln_g[j]), P(&p, p.i_ln_b[j]), lnp, np, eps}; }      // norm j applied by its consumer, from the current partials
+    NormKeep keep(int j, float* out, int ld) const { return NormKeep{out, ld, stat(j)}; }                 // ... which a training plan has it write
+    // cell i (lstm2 / lstm4) behind norm i of the raw h in front of it: applied while the cell stages its patch (the partials of its own output go to the
+    // second buffer: its blocks finish while others still read the input's), or written to `normed` by a launch of its own
+    int lstm_behind_norm(int i, size_t normed, int n) {
+        const int C = kLstm[i].cx;
+        const float* raw = ws + S->h[i - 1];
+        if (f.norm_inside[i] && np > 0) {
+            const LnIn li = norm_in(i);
+            float* q = other(lnp);
+            RC(lstm(i, raw, C, &li, q));
+            lnp = q;
+            return PIVP_OK;
         }
-        Conv3x3LnOpts o{};
-        o.fuse3 = &f3;
-        RC(run_conv3x3s2_ln(ws + S.h[3], 64, P(p, p->i_enc_w[2]), P(p, p->i_enc_b[2]), ws + S.e2, 64, 64, 1, B, p->H4, p->W4, s, norm_in(4), o));
-    } else {
-        RC(ln(4, ws + S.h[3], ws + S.n4, n4, 64, 64, 0, np));
-        RC(run_conv3x3s2(ws + S.n4, 64, 64, P(p, p->i_enc_w[2]), P(p, p->i_enc_b[2]), ws + S.e2, 64, 64, 1, B, p->H4, p->W4, s, 0));
+        RC(ln(i, raw, ws + normed, n, C, C, 0));
+        return lstm(i, ws + normed, C);
     }
+    // enc1 / enc2 (layer e, C channels in and out) behind norm j of the raw h in front of it.  Inference rollouts: hidden2 / hidden4 feed only these convs,
+    // so the norm is applied while they stage their input (run_conv3x3s2_ln) instead of by a launch of its own.  Training plans take the same launch
+    // (round 6) and have it WRITE the normalised tensor (every input pixel of a stride-2 3x3 conv is the tap (1..2, 1..2) of exactly one anchor) and the
+    // samples' (mean, rstd) for the backward sweep: two ln_apply launches per timestep less.  f3 (inference): what enc2's epilogue adds, if anything.
+    int enc_behind_norm(int e, int j, size_t normed, int n, int C, float* out, int ldo, int Hin, int Win, const Enc3Fuse* f3) {
+        const float* raw = ws + S->h[j - 1];
+        if (f.norm_inside[j] && np > 0) {
+            Conv3x3LnOpts o{};
+            if (f.keep) o.keep = keep(j, ws + normed, C);
+            else o.fuse3 = f3;
+            return run_conv3x3s2_ln(raw, C, P(&p, p.i_enc_w[e]), P(&p, p.i_enc_b[e]), out, C, ldo, 1, B, Hin, Win, s, norm_in(j), o);
+        }
+        RC(ln(j, raw, ws + normed, n, C, C, 0));
+        return run_conv3x3s2(ws + normed, C, C, P(&p, p.i_enc_w[e]), P(&p, p.i_enc_b[e]), out, C, ldo, 1, B, Hin, Win, s, 0);
+    }
+    // the motion head's output, and the launch that forms it from hidden5 alone
+    float* motion_out() const { return ws + (c.model_type == PIVP_MODEL_STP ? S->theta : S->kerns); }
+    int motion_dbl() const { return c.model_type == PIVP_MODEL_STP ? 1 : 0; }
+    int motion_separate() {
+        if (c.model_type == PIVP_MODEL_CDNA)
+            return cdna_kernels(ws + S->n5, P(&p, p.i_head_w), P(&p, p.i_head_b), ws + p.o_linpart, ws + S->kerns, B, p.K5, c.num_masks, s, ws + S->vpre);
+        return stp_params(ws + S->n5, P(&p, p.i_head_w), P(&p, p.i_head_b), P(&p, p.i_head2_w), P(&p, p.i_head2_b), ws + p.o_linpart,
+                          ws + S->theta, B, p.K5, s, ws + S->vpre);
+    }
+    int linear_partials() {      // ... its Linear's K-slice partial sums alone, for a finisher elsewhere (once per step)
+        if (partials_done) return PIVP_OK;
+        partials_done = true;
+        return motion_partials(ws + S->n5, P(&p, p.i_head_w), ws + p.o_linpart, B, p.K5, motion_dbl(), s);
+    }
+
+    int encoder(const StepIn& in);
+    int bottleneck(const StepIn& in);
+    int decoder();
+    int head(const StepIn& in);
+    // forward, one timestep (TM:659-731)
+    int step(const StepIn& in) {
+        t = in.t;
+        S = &p.slabs[t % p.nslabs]; Sp = t > 0 ? &p.slabs[(t - 1) % p.nslabs] : nullptr;
+        lnp = lnpA; np = 0;
+        enc3_done = partials_done = false;
+        motion = f.motion;
+        RC(encoder(in));
+        RC(bottleneck(in));
+        RC(decoder());
+        return head(in);
+    }
+};
+
+int Rollout::encoder(const StepIn& in) {
+    // group 0 (TM:595): enc0 -> norm_enc0 -> relu   => cat7[:, 32:64]
+    RC(conv_enc0(in.prev, P(&p, p.i_enc_w[0]), P(&p, p.i_enc_b[0]), ws + S->e0raw, B, H, W, s, lnp, ln_cap, &np));
+    RC(ln(0, ws + S->e0raw, ws + S->cat7 + 32, n2, 32, 64, 1));
+    // group 1 (TM:596): lstm1 -> hidden1 -> lstm2 -> hidden2 -> enc1 -> relu  => cat6[:, 64:96]
+    RC(lstm(0, ws + S->cat7 + 32, 64));
+    RC(lstm_behind_norm(1, S->n1, n2));
+    RC(enc_behind_norm(1, 2, S->n2, n2, 32, ws + S->cat6 + 64, 96, p.H2, p.W2, nullptr));
+    // group 2 (TM:597)
+    RC(lstm(2, ws + S->cat6 + 64, 96));
+    RC(lstm_behind_norm(3, S->n3, n4));
+    // Inference: group 3 (TM:598) and the state predictor (TM:730) in enc2's epilogue (round 6): enc3_state_kernel's launch
+    // disappears; bit-identical to it (the same fmaf chain on the matrix cores).  PIVP_OPT_FUSE_ENC3 = 0: two launches, as before.
+    Enc3Fuse f3;
+    memset(&f3, 0, sizeof(f3));
+    if (f.enc3_in_enc2 && np > 0) {
+        f3.w3 = P(&p, p.i_enc_w[3]); f3.b3 = P(&p, p.i_enc_b[3]); f3.action = in.action; f3.state = in.state_prev; f3.wcs = P(&p, p.i_cs_w); f3.bcs = P(&p, p.i_cs_b);
+        f3.e3 = ws + S->e3; f3.state_out = in.state_out; f3.use_state = c.use_state;
+        enc3_done = true;
+    }
+    return enc_behind_norm(2, 4, S->n4, n4, 64, ws + S->e2, 64, p.H4, p.W4, &f3);
+}
+
+int Rollout::bottleneck(const StepIn& in) {
     // group 3 (TM:598) + state predictor (TM:730)
     if (!enc3_done)
-    RC(enc3_state(ws + S.e2, action, state_prev, P(p, p->i_enc_w[3]), P(p, p->i_enc_b[3]), P(p, p->i_cs_w), P(p, p->i_cs_b),
-                  ws + S.e3, state_out, B, p->H8 * p->W8, c.use_state, s));
+        RC(enc3_state(ws + S->e2, in.action, in.state_prev, P(&p, p.i_enc_w[3]), P(&p, p.i_enc_b[3]), P(&p, p.i_cs_w), P(&p, p.i_cs_b),
+                      ws + S->e3, in.state_out, B, p.H8 * p.W8, c.use_state, s));
     // group 4 (TM:599)
-    RC(lstm(4, ws + S.e3, 64));
+    RC(lstm(4, ws + S->e3, 64));
     // (hidden5's norm was folded the same way into enc4's four-phase form and the motion head's Linear, which then has to run here, in front
     // of lstm6: the two consumers lost more than the launch saves, rollout 8.52 -> 8.60 ms.  It keeps its own launch.)
-    RC(ln(5, ws + S.h[4], ws + S.n5, n8, 128, 128, 0, np));
+    RC(ln(5, ws + S->h[4], ws + S->n5, n8, 128, 128, 0));
     // enc4 and the motion head's Linear both read hidden5 and nothing else: when the output side runs as frame_head (which finishes the
     // Linear's partial sums itself), the two share ONE grid here -- 1,024 + 256 blocks that each filled a fraction of the chip
-    const bool fh = frame_head_pays(c.model_type, B, H, W, c.num_masks);
-    const bool fh_fin = fh && c.model_type != PIVP_MODEL_DNA && frame_head_finishes(p->K5);
-    bool partials_done = false;
-    if (fh_fin && md.deconv(false) == Operand::F32) {
-        RC(run_deconv3x3s2_and_partials(ws + S.n5, 128, P(p, p->i_enc_w[4]), P(p, p->i_enc_b[4]), ws + S.e4, 128, 128, 1, B, p->H8, p->W8, s,
-                                        P(p, p->i_head_w), ws + p->o_linpart, c.model_type == PIVP_MODEL_STP ? 1 : 0));
+    if (f.enc4_partials) {
+        RC(run_deconv3x3s2_and_partials(ws + S->n5, 128, P(&p, p.i_enc_w[4]), P(&p, p.i_enc_b[4]), ws + S->e4, 128, 128, 1, B, p.H8, p.W8, s,
+                                        P(&p, p.i_head_w), ws + p.o_linpart, motion_dbl()));
         partials_done = true;
-    } else {
-        DeconvOpts o{};
-        o.operand = md.deconv(false);
-        RC(run_deconv3x3s2(ws + S.n5, 128, 128, P(p, p->i_enc_w[4]), P(p, p->i_enc_b[4]), ws + S.e4, 128, 128, 1, B, p->H8, p->W8, s, o));
+        return PIVP_OK;
     }
+    DeconvOpts o{};
+    o.operand = md.deconv(false);
+    return run_deconv3x3s2(ws + S->n5, 128, 128, P(&p, p.i_enc_w[4]), P(&p, p.i_enc_b[4]), ws + S->e4, 128, 128, 1, B, p.H8, p.W8, s, o);
+}
+
+int Rollout::decoder() {
     // group 5 (TM:600): lstm6 -> hidden6 -> concat(., enc1) -> enc5 -> relu
-    RC(lstm(5, ws + S.e4, 128));
+    RC(lstm(5, ws + S->e4, 128));
     const Operand dform = md.deconv(true);      // enc5 / enc6
     // The norms of hidden6 / hidden7 feed only enc5 / enc6, whose tile kernel applies them while it stages its patch ([hidden6 | enc1],
-    // [hidden7 | enc0] as two sources).
+    // [hidden7 | enc0] as two sources) -- where StepForm::norm_inside says it pays.
     // Training plans take the same launch and have it WRITE the normalised hidden6 / hidden7 (each pixel by the block that owns it) and the
     // samples' (mean, rstd) for the backward sweep: no ln_apply launch there either.
-    // Only while the norm is a launch-bound 5-us kernel (<= 6 MB of hidden tensor: 64 x 64 frames at B = 32): the consumer's column blocks
-    // each stage the patch and its gamma / beta again, which at config 5's 128 x 128 costs more than one bandwidth-bound ln_apply pass
-    // (B = 32, T = 20: rollout 65.5 -> 65.9 ms with the fold, so it is not taken there).
-    auto fold_small = [&](long long floats) { return floats * 4 <= 6LL << 20; };
-    // The motion head's finisher (sum of the Linear's K-slice partials, bias, activation, normalisation: per-SAMPLE work) rides behind enc5's tiles as
-    // B extra blocks (192 tiles on 256 CUs at B = 32) instead of being repeated by each of frame_head's 16 bands per sample (round 6).
-    bool finished = false;
-    if (np > 0 && fold_small((long long)B * n4) && deconv3x3s2_ln_ok(64, 32, 96, B, p->H4, p->W4)) {
+    if (f.norm_inside[6] && np > 0) {
+        // MotionHead::Rider: the motion head's finisher (sum of the Linear's K-slice partials, bias, activation, normalisation: per-SAMPLE work) rides behind
+        // enc5's tiles as B extra blocks (192 tiles on 256 CUs at B = 32) instead of being repeated by each of frame_head's 16 bands per sample (round 6).
         MotionRider rd;
         memset(&rd, 0, sizeof(rd));
-        if (fh_fin && p->opt[PIVP_OPT_FINISH_RIDER]) {
-            if (!partials_done) { RC(motion_partials(ws + S.n5, P(p, p->i_head_w), ws + p->o_linpart, B, p->K5, c.model_type == PIVP_MODEL_STP ? 1 : 0, s)); partials_done = true; }
-            rd.mode = c.model_type == PIVP_MODEL_STP ? 2 : 1; rd.KS = cdna_kernel_partials_slices(p->K5); rd.nout = 25 * c.num_masks;
-            rd.partials = ws + p->o_linpart; rd.bias = P(p, p->i_head_b); rd.vpre = ws + S.vpre;
-            if (rd.mode == 2) { rd.w2 = P(p, p->i_head2_w); rd.b2 = P(p, p->i_head2_b); rd.out = ws + S.theta; }
-            else rd.out = ws + S.kerns;
-            finished = true;
+        if (motion == MotionHead::Rider) {
+            RC(linear_partials());
+            rd.mode = c.model_type == PIVP_MODEL_STP ? 2 : 1; rd.KS = cdna_kernel_partials_slices(p.K5); rd.nout = 25 * c.num_masks;
+            rd.partials = ws + p.o_linpart; rd.bias = P(&p, p.i_head_b); rd.vpre = ws + S->vpre;
+            if (rd.mode == 2) { rd.w2 = P(&p, p.i_head2_w); rd.b2 = P(&p, p.i_head2_b); }
+            rd.out = motion_out();
         }
         DeconvLnOpts o{};
-        o.x1 = ws + S.cat6 + 64; o.c1 = 32; o.ld1 = 96;
-        o.operand = dform; o.wscale_part = ws + p->o_wabs[0];
-        if (train) o.keep = keep(6, ws + S.cat6, 96);
+        o.x1 = ws + S->cat6 + 64; o.c1 = 32; o.ld1 = 96;
+        o.operand = dform; o.wscale_part = ws + p.o_wabs[0];
+        if (f.keep) o.keep = keep(6, ws + S->cat6, 96);
         o.rider = &rd;
-        RC(run_deconv3x3s2_ln(ws + S.h[5], 64, P(p, p->i_enc_w[5]), P(p, p->i_enc_b[5]), ws + S.e5, 96, 96, 1, B, p->H4, p->W4, s, norm_in(6), o));
+        RC(run_deconv3x3s2_ln(ws + S->h[5], 64, P(&p, p.i_enc_w[5]), P(&p, p.i_enc_b[5]), ws + S->e5, 96, 96, 1, B, p.H4, p.W4, s, norm_in(6), o));
     } else {
-        RC(ln(6, ws + S.h[5], ws + S.cat6, n4, 64, 96, 0, np));
+        if (motion == MotionHead::Rider) motion = MotionHead::InHead;      // no launch to ride on: frame_head finishes, as it does without the option
+        RC(ln(6, ws + S->h[5], ws + S->cat6, n4, 64, 96, 0));
         DeconvOpts o{};
-        o.operand = dform; o.wscale_part = ws + p->o_wabs[0];
-        RC(run_deconv3x3s2(ws + S.cat6, 96, 96, P(p, p->i_enc_w[5]), P(p, p->i_enc_b[5]), ws + S.e5, 96, 96, 1, B, p->H4, p->W4, s, o));
+        o.operand = dform; o.wscale_part = ws + p.o_wabs[0];
+        RC(run_deconv3x3s2(ws + S->cat6, 96, 96, P(&p, p.i_enc_w[5]), P(&p, p.i_enc_b[5]), ws + S->e5, 96, 96, 1, B, p.H4, p.W4, s, o));
     }
     // group 6 (TM:601): lstm7 -> hidden7 -> concat(., enc0) -> enc6 -> norm_enc6 -> relu
-    RC(lstm(6, ws + S.e5, 96));
-    if (np > 0 && fold_small((long long)B * n2) && deconv3x3s2_ln_ok(32, 32, 64, B, p->H2, p->W2)) {
+    RC(lstm(6, ws + S->e5, 96));
+    if (f.norm_inside[7] && np > 0) {
         // enc6's blocks write the partials of norm_enc6 while others still read hidden7's: the second partial buffer
         float* lnp2 = other(lnp);
         const LnIn li = norm_in(7);      // (np as hidden7's producer left it: the launch overwrites it)
         DeconvLnOpts o{};
-        o.x1 = ws + S.cat7 + 32; o.c1 = 32; o.ld1 = 64;
+        o.x1 = ws + S->cat7 + 32; o.c1 = 32; o.ld1 = 64;
         o.ln_out.part = lnp2; o.ln_out.cap = ln_cap; o.ln_out.nparts = &np;
-        o.operand = dform; o.wscale_part = ws + p->o_wabs[1];
-        if (train) o.keep = keep(7, ws + S.cat7, 64);
-        RC(run_deconv3x3s2_ln(ws + S.h[6], 32, P(p, p->i_enc_w[6]), P(p, p->i_enc_b[6]), ws + S.e6raw, 64, 64, 0, B, p->H2, p->W2, s, li, o));
+        o.operand = dform; o.wscale_part = ws + p.o_wabs[1];
+        if (f.keep) o.keep = keep(7, ws + S->cat7, 64);
+        RC(run_deconv3x3s2_ln(ws + S->h[6], 32, P(&p, p.i_enc_w[6]), P(&p, p.i_enc_b[6]), ws + S->e6raw, 64, 64, 0, B, p.H2, p.W2, s, li, o));
         lnp = lnp2;
     } else {
-        RC(ln(7, ws + S.h[6], ws + S.cat7, n2, 32, 64, 0, np));
+        RC(ln(7, ws + S->h[6], ws + S->cat7, n2, 32, 64, 0));
         DeconvOpts o{};
         o.ln_out.part = lnp; o.ln_out.cap = ln_cap; o.ln_out.nparts = &np;
-        o.operand = dform; o.wscale_part = ws + p->o_wabs[1];
-        RC(run_deconv3x3s2(ws + S.cat7, 64, 64, P(p, p->i_enc_w[6]), P(p, p->i_enc_b[6]), ws + S.e6raw, 64, 64, 0, B, p->H2, p->W2, s, o));
+        o.operand = dform; o.wscale_part = ws + p.o_wabs[1];
+        RC(run_deconv3x3s2(ws + S->cat7, 64, 64, P(&p, p.i_enc_w[6]), P(&p, p.i_enc_b[6]), ws + S->e6raw, 64, 64, 0, B, p.H2, p.W2, s, o));
     }
-    // heads (TM:711-728).  One launch (csrc/frame_head.hip) for norm_enc6 + relu + the 1x1 heads + the motion head's finisher + flat softmax +
+    return PIVP_OK;
+}
+
+// heads (TM:711-728)
+int Rollout::head(const StepIn& in) {
+    // Output::FrameHead: one launch (csrc/frame_head.hip) for norm_enc6 + relu + the 1x1 heads + the motion head's finisher + flat softmax +
     // transform + compositing, behind the Linear's partial sums: bit-identical to the four launches below it, which remain for geometries
-    // it does not take or where it is slower (frames wider than 64: frame_head_pays).  The softmaxed masks are kept for the rollout's last step only (pivp_get_tap).
-    if (fh && np > 0) {
-        const bool fin = !finished && (c.model_type == PIVP_MODEL_DNA || frame_head_finishes(p->K5));
+    // it does not take or where it is slower.  The softmaxed masks are kept for the rollout's last step only (pivp_get_tap), or where a rollout asks.
+    if (f.output == Output::FrameHead && np > 0) {
         FrameHeadArgs a;
         memset(&a, 0, sizeof(a));
-        if (finished) {
-            a.aux = c.model_type == PIVP_MODEL_STP ? ws + S.theta : ws + S.kerns;
-        } else if (c.model_type == PIVP_MODEL_CDNA) {
-            if (fin) { if (!partials_done) RC(motion_partials(ws + S.n5, P(p, p->i_head_w), ws + p->o_linpart, B, p->K5, 0, s)); }
-            else RC(cdna_kernels(ws + S.n5, P(p, p->i_head_w), P(p, p->i_head_b), ws + p->o_linpart, ws + S.kerns, B, p->K5, c.num_masks, s, ws + S.vpre));
-            a.aux = ws + S.kerns; a.kerns_out = ws + S.kerns;
-        } else if (c.model_type == PIVP_MODEL_STP) {
-            if (fin) { if (!partials_done) RC(motion_partials(ws + S.n5, P(p, p->i_head_w), ws + p->o_linpart, B, p->K5, 1, s)); }
-            else RC(stp_params(ws + S.n5, P(p, p->i_head_w), P(p, p->i_head_b), P(p, p->i_head2_w), P(p, p->i_head2_b), ws + p->o_linpart,
-                               ws + S.theta, B, p->K5, s, ws + S.vpre));
-            a.aux = ws + S.theta; a.kerns_out = ws + S.theta; a.w2 = P(p, p->i_head2_w); a.b2 = P(p, p->i_head2_b);
+        switch (motion) {
+        case MotionHead::None: break;
+        case MotionHead::Rider: a.aux = motion_out(); break;      // finished behind enc5's tiles
+        case MotionHead::InHead:      // frame_head finishes the partial sums, and leaves the result and the Linear's pre-activation
+            RC(linear_partials());
+            a.partials = ws + p.o_linpart; a.KS = cdna_kernel_partials_slices(p.K5); a.hbias = P(&p, p.i_head_b);
+            a.kerns_out = motion_out(); a.vpre_out = ws + S->vpre;
+            break;
+        case MotionHead::Separate:
+            RC(motion_separate());
+            a.aux = motion_out();
+            break;
         }
-        if (fin && c.model_type != PIVP_MODEL_DNA) {
-            a.partials = ws + p->o_linpart; a.KS = cdna_kernel_partials_slices(p->K5); a.hbias = P(p, p->i_head_b); a.aux = nullptr;
-            a.vpre_out = ws + S.vpre;
-        } else {
-            a.kerns_out = nullptr;      // already written by the separate finisher
-        }
-        a.e6raw = ws + S.e6raw; a.ln_part = lnp; a.ln_nparts = np; a.gamma = P(p, p->i_ln_g[8]); a.beta = P(p, p->i_ln_b[8]); a.eps = eps;
-        a.wm = P(p, p->i_masks_w); a.bm = P(p, p->i_masks_b); a.we = P(p, p->i_enc7_w); a.be = P(p, p->i_enc7_b);
-        a.prev = prev; a.out = gen_out; a.enc7 = ws + S.enc7;
-        a.masks_out = (t == c.seq_len - 2 || p->masks_every_step) ? ws + p->o_masks : nullptr;
-        a.stat_out = ws + S.lnstat + (size_t)8 * B * 2;
-        if (train) { a.logits_out = ws + S.logits; a.layer0_out = ws + S.layer0; a.y_out = ws + S.e6; }
+        if (c.model_type == PIVP_MODEL_STP && motion != MotionHead::Rider) { a.w2 = P(&p, p.i_head2_w); a.b2 = P(&p, p.i_head2_b); }
+        a.e6raw = ws + S->e6raw; a.ln_part = lnp; a.ln_nparts = np; a.gamma = P(&p, p.i_ln_g[8]); a.beta = P(&p, p.i_ln_b[8]); a.eps = eps;
+        a.wm = P(&p, p.i_masks_w); a.bm = P(&p, p.i_masks_b); a.we = P(&p, p.i_enc7_w); a.be = P(&p, p.i_enc7_b);
+        a.prev = in.prev; a.out = in.gen_out; a.enc7 = ws + S->enc7;
+        a.masks_out = (t == c.seq_len - 2 || masks_every_step) ? ws + p.o_masks : nullptr;
+        a.stat_out = stat(8);
+        if (f.keep) { a.logits_out = ws + S->logits; a.layer0_out = ws + S->layer0; a.y_out = ws + S->e6; }
         a.B = B; a.H = H; a.W = W; a.NM = c.num_masks; a.stp_zero = c.stp_zero_border;
         return frame_head(a, c.model_type, s);
     }
-    if (np > 0 && (H * W) % 64 == 0) {
-        RC(heads_1x1(ws + S.e6raw, P(p, p->i_masks_w), P(p, p->i_masks_b), P(p, p->i_enc7_w), P(p, p->i_enc7_b),
-                     ws + S.logits, ws + S.enc7, ws + S.layer0, B, H * W, p->NP, p->NE, c.model_type, s,
-                     lnp, np, P(p, p->i_ln_g[8]), P(p, p->i_ln_b[8]), eps, train ? ws + S.e6 : nullptr,
-                     ws + S.lnstat + (size_t)8 * B * 2));
+    // Output::Separate, or enc6's launcher left no partials: heads_1x1 (with norm_enc6 inside it, or behind a launch of its own), the motion head by its own
+    // launch whatever the step has formed of it so far, composite
+    if (f.norm_inside[8] && np > 0) {
+        RC(heads_1x1(ws + S->e6raw, P(&p, p.i_masks_w), P(&p, p.i_masks_b), P(&p, p.i_enc7_w), P(&p, p.i_enc7_b),
+                     ws + S->logits, ws + S->enc7, ws + S->layer0, B, H * W, p.NP, p.NE, c.model_type, s,
+                     lnp, np, P(&p, p.i_ln_g[8]), P(&p, p.i_ln_b[8]), eps, f.keep ? ws + S->e6 : nullptr, stat(8)));
     } else {
-        RC(ln(8, ws + S.e6raw, ws + S.e6, 64 * H * W, 64, 64, 1, np));
-        RC(heads_1x1(ws + S.e6, P(p, p->i_masks_w), P(p, p->i_masks_b), P(p, p->i_enc7_w), P(p, p->i_enc7_b),
-                     ws + S.logits, ws + S.enc7, ws + S.layer0, B, H * W, p->NP, p->NE, c.model_type, s));
+        RC(ln(8, ws + S->e6raw, ws + S->e6, 64 * H * W, 64, 64, 1));
+        RC(heads_1x1(ws + S->e6, P(&p, p.i_masks_w), P(&p, p.i_masks_b), P(&p, p.i_enc7_w), P(&p, p.i_enc7_b),
+                     ws + S->logits, ws + S->enc7, ws + S->layer0, B, H * W, p.NP, p.NE, c.model_type, s));
     }
     // (The motion head's generator needs hidden5 only and could run on the side stream under lstm6 .. heads: measured, the rollout got
     // SLOWER, 8.68 -> 8.79 ms: the co-running kernels cost the ConvLSTMs more than the 16 us they hide; again with the ConvLSTM waves at
     // priority 3 and the generator at 0: 8.57 -> 8.67 / 8.73 ms; and forked only behind norm(hidden7), i.e. beside enc6 and the heads kernel,
     // no ConvLSTM: 8.60 -> 8.68 / 8.69 ms -- a cross-stream event pair per timestep costs more than the 16 us.  It stays in line.)
-    const float* aux = nullptr;
-    if (c.model_type == PIVP_MODEL_CDNA) {
-        RC(cdna_kernels(ws + S.n5, P(p, p->i_head_w), P(p, p->i_head_b), ws + p->o_linpart, ws + S.kerns, B, p->K5, c.num_masks, s,
-                        ws + S.vpre));
-        aux = ws + S.kerns;
-    } else if (c.model_type == PIVP_MODEL_STP) {
-        RC(stp_params(ws + S.n5, P(p, p->i_head_w), P(p, p->i_head_b), P(p, p->i_head2_w), P(p, p->i_head2_b),
-                      ws + p->o_linpart, ws + S.theta, B, p->K5, s, ws + S.vpre));
-        aux = ws + S.theta;
-    } else {
-        aux = ws + S.enc7;
+    const float* aux = ws + S->enc7;
+    if (c.model_type != PIVP_MODEL_DNA) {
+        RC(motion_separate());
+        aux = motion_out();
     }
-    RC(composite(prev, ws + S.logits, ws + S.layer0, aux, gen_out, ws + p->o_masks, B, H, W, c.num_masks,
-                 c.model_type, c.stp_zero_border, s));
-    return PIVP_OK;
+    return composite(in.prev, ws + S->logits, ws + S->layer0, aux, in.gen_out, ws + p.o_masks, B, H, W, c.num_masks, c.model_type, c.stp_zero_border, s);
 }
 
-// the frame fed to step t (TM:663-673)
-const float* pivp::step_input(const pivp_plan* plan, int t, const float* images, const unsigned char* gt_select, const float* gen_images, size_t fr) {
-    const int ctx = plan->cfg.context_frames;
-    if (t < ctx) return images + t * fr;
-    if (!gt_select) return gen_images + (t - 1) * fr;
-    return plan->ws + plan->slabs[t % plan->nslabs].prevsel;
+// the caller's tensors of a rollout, time-major
+struct RolloutIo { const float* images; const float* actions; const float* states; const unsigned char* gt_select; float* gen_images; float* gen_states; };
+
+// what step t reads and writes: the frame fed to it (step_input), its action, the state in front of it (TM:646, TM:730) and where its outputs go
+StepIn step_in(const pivp_plan& p, const RolloutIo& io, int t, int ctx) {
+    const size_t fr = (size_t)p.cfg.batch * 3 * p.cfg.height * p.cfg.width, st = (size_t)p.cfg.batch * 5;
+    return StepIn{t, step_input(&p, t, io.images, io.gt_select, io.gen_images, fr, ctx), io.actions + t * st,
+                  t == 0 ? io.states : io.gen_states + (t - 1) * st, io.gen_images + t * fr, io.gen_states + t * st};
 }
 
-// in front of a rollout's first timestep (pivp_rollout_forward and pivp_rollout_predict)
-static int rollout_prepare_packs(pivp_plan* plan, hipStream_t s) {
+// in front of a rollout's first timestep
+int rollout_prepare_packs(pivp_plan* plan, hipStream_t s) {
     // The precision modes' weight packs: rebuilt at the start of every rollout (the parameters may have changed since the last call: optimizer step,
     // checkpoint load) unless the caller keeps them -- pivp_plan_set_pack_cache(plan, 1) -- and reports every change with pivp_plan_params_changed.
     const bool repack = !(plan->pack_cache && plan->packs_valid);
@@ -298,7 +309,7 @@ static int rollout_prepare_packs(pivp_plan* plan, hipStream_t s) {
 }
 
 // behind a rollout's last timestep: the last slab's (c, h) of the seven cells -> the registered state_out, ONE launch (csrc/state.hip)
-static int rollout_pack_state(pivp_plan* plan, hipStream_t s) {
+int rollout_pack_state(const pivp_plan* plan, hipStream_t s) {
     if (!plan->state_out) return PIVP_OK;
     const pivp_config_t& c = plan->cfg;
     const Slab& S = plan->slabs[(c.seq_len - 2) % plan->nslabs];
@@ -308,45 +319,68 @@ static int rollout_pack_state(pivp_plan* plan, hipStream_t s) {
     return state_copy(seg, nullptr, c.batch, s);
 }
 
+// The prologue of either rollout, behind its own argument checks: a bound workspace and every parameter, no record of an earlier rollout (an error from
+// here on leaves nothing to tap or back-propagate), the weight packs.
+int rollout_begin(pivp_plan* plan, hipStream_t s) {
+    if (!plan->ws) return PIVP_ERR_STATE;
+    for (const ParamInfo& pi : plan->params) if (!pi.ptr) return PIVP_ERR_STATE;
+    plan->last = {};
+    return rollout_prepare_packs(plan, s);
+}
+// ... and its epilogue, behind the last timestep: the state pack, what the entry still has to launch (tail), and the record of the call, assigned whole
+template <class Tail>
+int rollout_end(pivp_plan* plan, hipStream_t s, const LastRollout& rec, Tail tail) {
+    RC(rollout_pack_state(plan, s));
+    RC(tail());
+    plan->last = rec;
+    return PIVP_OK;
+}
+
+}  // namespace
+
+// the frame fed to step t (TM:663-673)
+const float* pivp::step_input(const pivp_plan* plan, int t, const float* images, const unsigned char* gt_select, const float* gen_images, size_t fr, int ctx) {
+    if (t < (ctx > 0 ? ctx : plan->cfg.context_frames)) return images + t * fr;
+    if (!gt_select) return gen_images + (t - 1) * fr;
+    return plan->ws + plan->slabs[t % plan->nslabs].prevsel;
+}
+
 extern "C" int pivp_rollout_forward(pivp_plan_t* plan, const float* images, const float* actions, const float* states,
                                     const unsigned char* gt_select, float* gen_images, float* gen_states, float* results,
                                     void* stream) {
     if (!plan || !images || !actions || !states || !gen_images || !gen_states || !results) return PIVP_ERR_BADARG;
-    if (!plan->ws) return PIVP_ERR_STATE;
-    for (const ParamInfo& pi : plan->params) if (!pi.ptr) return PIVP_ERR_STATE;
     hipStream_t s = (hipStream_t)stream;
+    RC(rollout_begin(plan, s));
     const pivp_config_t& c = plan->cfg;
     const int B = c.batch, T = c.seq_len, ctx = c.context_frames;
     const size_t fr = (size_t)B * 3 * c.height * c.width;
-    plan->last = {};                         // an error below leaves nothing to tap or back-propagate
-    RC(rollout_prepare_packs(plan, s));
+    Rollout r{*plan, s, ctx, plan->state_in, plan->prof.on ? &plan->prof : nullptr};
+    const RolloutIo io{images, actions, states, gt_select, gen_images, gen_states};
     for (int t = 0; t < T - 1; ++t) {
         if (t >= ctx && gt_select)                                     // TM:667-670
             RC(run_select_frames(images + t * fr, gen_images + (t - 1) * fr, gt_select + (size_t)t * B,
                                  plan->ws + plan->slabs[t % plan->nslabs].prevsel, B, (int)(fr / B), s));
-        const float* prev = step_input(plan, t, images, gt_select, gen_images, fr);
-        const float* st_prev = t == 0 ? states : gen_states + (size_t)(t - 1) * B * 5;   // TM:646, TM:730
-        RC(run_step(plan, t, prev, actions + (size_t)t * B * 5, st_prev, gen_images + t * fr, gen_states + (size_t)t * B * 5, s));
+        RC(r.step(step_in(*plan, io, t, ctx)));
     }
-    RC(rollout_pack_state(plan, s));
-    // loss (TM:737-759): frames ctx..T-1 vs gen[ctx-1..T-2]
-    const int nf = T - ctx;
-    float* lp = plan->ws + plan->o_losspart;
-    // target frames and predictions are contiguous over time: when a frame is a whole number of partial chunks, ONE launch over
-    // all nf frames leaves the partials in the same per-frame layout as nf launches would
-    const bool whole_chunks = loss_partials_count((int)fr + 1) == loss_partials_count((int)fr) + 1;   // fr divisible by the chunk
-    if (nf > 0 && (whole_chunks || nf == 1) && fr * nf < (1u << 30)) {
-        RC(frame_sqerr_partials(images + (size_t)ctx * fr, gen_images + (size_t)(ctx - 1) * fr, lp, (int)(fr * nf), s));
-    } else {
-        for (int i = 0; i < nf; ++i)
-            RC(frame_sqerr_partials(images + (size_t)(ctx + i) * fr, gen_images + (size_t)(ctx - 1 + i) * fr,
-                                    lp + (size_t)i * plan->loss_nparts, (int)fr, s));
-    }
-    RC(loss_finalize(lp, plan->loss_nparts, nf, (int)fr, states + (size_t)ctx * B * 5, gen_states + (size_t)(ctx - 1) * B * 5,
-                     B * 5, (float)(T - ctx), results, s));
     // state_in: what the sweep's t = 0 will read again when it is enabled (pivp_plan_set_state_grad) -- gone if this rollout wrote its final state over it
-    plan->last = LastRollout{T - 1, gt_select != nullptr, false, plan->state_in != nullptr, plan->state_in, plan->state_in && plan->state_in == plan->state_out};
-    return PIVP_OK;
+    const LastRollout rec{T - 1, gt_select != nullptr, false, plan->state_in != nullptr, plan->state_in, plan->state_in && plan->state_in == plan->state_out};
+    return rollout_end(plan, s, rec, [&] {
+        // loss (TM:737-759): frames ctx..T-1 vs gen[ctx-1..T-2]
+        const int nf = T - ctx;
+        float* lp = plan->ws + plan->o_losspart;
+        // target frames and predictions are contiguous over time: when a frame is a whole number of partial chunks, ONE launch over
+        // all nf frames leaves the partials in the same per-frame layout as nf launches would
+        const bool whole_chunks = loss_partials_count((int)fr + 1) == loss_partials_count((int)fr) + 1;   // fr divisible by the chunk
+        if (nf > 0 && (whole_chunks || nf == 1) && fr * nf < (1u << 30)) {
+            RC(frame_sqerr_partials(images + (size_t)ctx * fr, gen_images + (size_t)(ctx - 1) * fr, lp, (int)(fr * nf), s));
+        } else {
+            for (int i = 0; i < nf; ++i)
+                RC(frame_sqerr_partials(images + (size_t)(ctx + i) * fr, gen_images + (size_t)(ctx - 1 + i) * fr,
+                                        lp + (size_t)i * plan->loss_nparts, (int)fr, s));
+        }
+        return loss_finalize(lp, plan->loss_nparts, nf, (int)fr, states + (size_t)ctx * B * 5, gen_states + (size_t)(ctx - 1) * B * 5,
+                             B * 5, (float)(T - ctx), results, s);
+    });
 }
 
 // Open-loop rollout (include/pivp_hip.h): the timesteps of pivp_rollout_forward in feed-self mode, no loss; optionally P tracked planes advected
@@ -360,29 +394,20 @@ extern "C" int pivp_rollout_predict(pivp_plan_t* plan, const float* context_imag
     const int B = c.batch, T = c.seq_len, ctx = plan->observed > 0 ? plan->observed : c.context_frames, P = track_planes, f = track_frame;
     if (ctx < 1 || T - 1 < ctx) return PIVP_ERR_BADARG;
     if (track_in ? (P < 1 || P > 8 || !track_out || f < 0 || f > ctx - 1) : P != 0) return PIVP_ERR_BADARG;
-    if (!plan->ws) return PIVP_ERR_STATE;
-    for (const ParamInfo& pi : plan->params) if (!pi.ptr) return PIVP_ERR_STATE;
     hipStream_t s = (hipStream_t)stream;
-    const size_t fr = (size_t)B * 3 * c.height * c.width;
+    RC(rollout_begin(plan, s));
     const size_t pl = (size_t)B * P * c.height * c.width;
-    plan->last = {};                         // an error below leaves nothing to tap or back-propagate
-    RC(rollout_prepare_packs(plan, s));
-    int rc = PIVP_OK;
-    for (int t = 0; t < T - 1 && rc == PIVP_OK; ++t) {
-        plan->masks_every_step = P > 0 && t >= f;
-        const float* prev = t < ctx ? context_images + t * fr : gen_images + (t - 1) * fr;      // TM:663-666
-        const float* st_prev = t == 0 ? state0 : gen_states + (size_t)(t - 1) * B * 5;
-        rc = run_step(plan, t, prev, actions + (size_t)t * B * 5, st_prev, gen_images + t * fr, gen_states + (size_t)t * B * 5, s);
-        if (rc == PIVP_OK && P > 0 && t >= f) {
+    Rollout r{*plan, s, ctx, plan->state_in, plan->prof.on ? &plan->prof : nullptr};
+    const RolloutIo io{context_images, actions, state0, nullptr, gen_images, gen_states};
+    for (int t = 0; t < T - 1; ++t) {
+        r.masks_every_step = P > 0 && t >= f;
+        RC(r.step(step_in(*plan, io, t, ctx)));
+        if (r.masks_every_step) {
             const Slab& S = plan->slabs[t % plan->nslabs];
             const float* aux = plan->ws + (c.model_type == PIVP_MODEL_CDNA ? S.kerns : c.model_type == PIVP_MODEL_STP ? S.theta : S.enc7);
-            rc = pixel_track(t == f ? track_in : track_out + (size_t)(t - f - 1) * pl, plan->ws + plan->o_masks, aux,
-                             track_out + (size_t)(t - f) * pl, B, P, c.height, c.width, c.num_masks, c.model_type, c.stp_zero_border, s);
+            RC(pixel_track(t == f ? track_in : track_out + (size_t)(t - f - 1) * pl, plan->ws + plan->o_masks, aux,
+                           track_out + (size_t)(t - f) * pl, B, P, c.height, c.width, c.num_masks, c.model_type, c.stp_zero_border, s));
         }
     }
-    plan->masks_every_step = false;
-    if (rc != PIVP_OK) return rc;
-    RC(rollout_pack_state(plan, s));
-    plan->last = LastRollout{T - 1, false, true, plan->state_in != nullptr, nullptr, false};
-    return PIVP_OK;
+    return rollout_end(plan, s, LastRollout{T - 1, false, true, plan->state_in != nullptr, nullptr, false}, [] { return PIVP_OK; });
 }

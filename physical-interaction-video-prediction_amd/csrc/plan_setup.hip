@@ -135,6 +135,7 @@ void pivp::plan_layout(pivp_plan* p) {
         }
     }
     p->ws_floats = (long long)off;
+    p->form = step_form(*p);
 }
 
 extern "C" int pivp_plan_create(const pivp_config_t* cfg, pivp_plan_t** out) {
@@ -249,6 +250,7 @@ extern "C" int pivp_plan_set_precision(pivp_plan_t* plan, int precision_code) {
     plan->mode = cand;
     plan->packs_valid = 0;
     if (!plan->ws) plan_layout(plan);
+    else plan->form = step_form(*plan);
     return PIVP_OK;
 }
 // Deterministic training (include/pivp_hip.h): every sum of the forward and the backward sweep in an order fixed by the problem shape.  Served:
@@ -288,7 +290,7 @@ extern "C" int pivp_plan_set_option(pivp_plan_t* plan, int option, int value) {
     if (value < 0 || value > (option == PIVP_OPT_WGRAD_BATCH ? WG_BATCH_MAX : 1)) return PIVP_ERR_BADARG;
     if (plan->ws) return PIVP_ERR_STATE;
     plan->opt[option] = value;
-    if (option == PIVP_OPT_WGRAD_BATCH) plan_layout(plan);
+    plan_layout(plan);      // the batch sets the dG rings' depth, the switches the step's form
     return PIVP_OK;
 }
 extern "C" int pivp_plan_get_option(const pivp_plan_t* plan, int option) {
@@ -407,15 +409,16 @@ extern "C" int pivp_reset_state(pivp_plan_t* plan, void* stream) {
 // ------------------------------------------------------------------------------------------------------------
 extern "C" int pivp_plan_set_profiling(pivp_plan_t* plan, int enable) {
     if (!plan) return PIVP_ERR_BADARG;
-    if (enable && plan->prof_ev.empty()) {
+    StepProfile& pr = plan->prof;
+    if (enable && pr.ev.empty()) {
         const size_t n = (size_t)2 * 7 * (plan->cfg.seq_len - 1);
-        plan->prof_ev.resize(n);
-        plan->prof_layer.assign(n / 2, 0);
+        pr.ev.resize(n);
+        pr.layer.assign(n / 2, 0);
         for (size_t i = 0; i < n; ++i)
-            if (hipEventCreate(&plan->prof_ev[i]) != hipSuccess) { plan->prof_ev.resize(i); return PIVP_ERR_LAUNCH; }
+            if (hipEventCreate(&pr.ev[i]) != hipSuccess) { pr.ev.resize(i); return PIVP_ERR_LAUNCH; }
     }
-    plan->prof_on = enable != 0;
-    plan->prof_used = 0;
+    pr.on = enable != 0;
+    pr.used = 0;
     return PIVP_OK;
 }
 
@@ -430,15 +433,16 @@ extern "C" int pivp_plan_profile_read(pivp_plan_t* plan, double* ms_per_layer, i
         fl_full[i] = 2.0 * M * 4.0 * kLstm[i].C * 25.0 * (kLstm[i].cx + kLstm[i].C);
         fl_first[i] = 2.0 * M * 4.0 * kLstm[i].C * 25.0 * kLstm[i].cx;     // executed flops when h == 0 is skipped
     }
-    for (size_t k = 0; k + 1 < plan->prof_used; k += 2) {
+    StepProfile& pr = plan->prof;
+    for (size_t k = 0; k + 1 < pr.used; k += 2) {
         float ms = 0.f;
-        if (hipEventElapsedTime(&ms, plan->prof_ev[k], plan->prof_ev[k + 1]) != hipSuccess) return PIVP_ERR_STATE;
-        const int tag = plan->prof_layer[k / 2];
+        if (hipEventElapsedTime(&ms, pr.ev[k], pr.ev[k + 1]) != hipSuccess) return PIVP_ERR_STATE;
+        const int tag = pr.layer[k / 2];
         const int L = tag & 7;
         ms_per_layer[L] += ms; launches_per_layer[L] += 1;
         flops_per_layer[L] += (tag & 8) ? fl_first[L] : fl_full[L];   // SUM of executed flops over the launches
     }
-    plan->prof_used = 0;
+    pr.used = 0;
     return PIVP_OK;
 }
 
@@ -452,13 +456,13 @@ extern "C" long long pivp_get_tap(pivp_plan_t* plan, const char* name, int step,
     const Slab& S = plan->slabs[step % plan->nslabs];
     float* ws = plan->ws;
     const int HW = c.height * c.width, HW2 = plan->H2 * plan->W2, HW4 = plan->H4 * plan->W4, HW8 = plan->H8 * plan->W8;
-    struct T { const char* n; size_t off; int C, hw, ld; };
+    struct T { const char* n; size_t off; int C, hw, ld; int norm = 0; };      // norm j: the tensor is hidden<j>, norm j of cell j - 1's h
     const T taps[] = {
         {"enc0", S.cat7 + 32, 32, HW2, 64}, {"enc1", S.cat6 + 64, 32, HW4, 96}, {"enc2", S.e2, 64, HW8, 64},
         {"enc3", S.e3, 64, HW8, 64}, {"enc4", S.e4, 128, HW4, 128}, {"enc5", S.e5, 96, HW2, 96}, {"enc6", S.e6, 64, HW, 64},
-        {"hidden1", S.n1, 32, HW2, 32}, {"hidden2", S.n2, 32, HW2, 32}, {"hidden3", S.n3, 64, HW4, 64},
-        {"hidden4", S.n4, 64, HW4, 64}, {"hidden5", S.n5, 128, HW8, 128}, {"hidden6", S.cat6, 64, HW4, 96},
-        {"hidden7", S.cat7, 32, HW2, 64},
+        {"hidden1", S.n1, 32, HW2, 32, 1}, {"hidden2", S.n2, 32, HW2, 32, 2}, {"hidden3", S.n3, 64, HW4, 64, 3},
+        {"hidden4", S.n4, 64, HW4, 64, 4}, {"hidden5", S.n5, 128, HW8, 128, 5}, {"hidden6", S.cat6, 64, HW4, 96, 6},
+        {"hidden7", S.cat7, 32, HW2, 64, 7},
         {"lstm1_h", S.h[0], 32, HW2, 32}, {"lstm2_h", S.h[1], 32, HW2, 32}, {"lstm3_h", S.h[2], 64, HW4, 64},
         {"lstm4_h", S.h[3], 64, HW4, 64}, {"lstm5_h", S.h[4], 128, HW8, 128}, {"lstm6_h", S.h[5], 64, HW4, 64},
         {"lstm7_h", S.h[6], 32, HW2, 32},
@@ -472,24 +476,16 @@ extern "C" long long pivp_get_tap(pivp_plan_t* plan, const char* name, int step,
                           ws + S.e6, B, 64 * HW, 64, 64, c.ln_eps, 1, s, nullptr, -1);
         if (rc != PIVP_OK) return rc;
     }
-    if (!c.keep_activations) {
-        // inference applies the norms of hidden2 / hidden4 / hidden6 / hidden7 inside their consumers (run_step): rebuild the tensor on request from
-        // the raw ConvLSTM output (statistics recomputed by ln_stats: equal to the fused ones up to fp32 summation order)
-        struct F { const char* n; int layer, norm; size_t dst; int C, hw, ld; int split_only = 0; };
-        const F folded[] = {{"hidden2", 1, 2, S.n2, 32, HW2, 32}, {"hidden4", 3, 4, S.n4, 64, HW4, 64}, {"hidden6", 5, 6, S.cat6, 64, HW4, 96},
-                            {"hidden7", 6, 7, S.cat7, 32, HW2, 64},
-                            {"hidden1", 0, 1, S.n1, 32, HW2, 32, 1}, {"hidden3", 2, 3, S.n3, 64, HW4, 64, 1}};      // (the split modes: inside lstm2 / lstm4)
-        const bool split = operand_l2_direct(plan->mode.precision);
-        for (const F& f : folded)
-            if (strcmp(f.n, name) == 0 && (!f.split_only || split)) {
-                int rc = run_layernorm(ws + S.h[f.layer], P(plan, plan->i_ln_g[f.norm]), P(plan, plan->i_ln_b[f.norm]), ws + f.dst,
-                                       ws + plan->o_lnpart, B, f.C * f.hw, f.C, f.ld, c.ln_eps, 0, s);
-                if (rc != PIVP_OK) return rc;
-            }
-    }
     for (const T& t : taps) {
         if (strcmp(t.n, name) == 0) {
-            int rc = nhwc_to_nchw(ws + t.off, out, B, t.C, t.hw, t.ld, s);
+            int rc = PIVP_OK;
+            // Where the step's form (StepForm) applies a norm inside its consumer, an inference plan never wrote the tensor: rebuild it on request from the
+            // raw ConvLSTM output (statistics recomputed by ln_stats: equal to the fused ones up to fp32 summation order).  Everywhere else the step wrote it.
+            if (t.norm && plan->form.norm_inside[t.norm] && !plan->form.keep)
+                rc = run_layernorm(ws + S.h[t.norm - 1], P(plan, plan->i_ln_g[t.norm]), P(plan, plan->i_ln_b[t.norm]), ws + t.off,
+                                   ws + plan->o_lnpart, B, t.C * t.hw, t.C, t.ld, c.ln_eps, 0, s);
+            if (rc != PIVP_OK) return rc;
+            rc = nhwc_to_nchw(ws + t.off, out, B, t.C, t.hw, t.ld, s);
             return rc == PIVP_OK ? (long long)B * t.C * t.hw : rc;
         }
     }

@@ -575,6 +575,26 @@ class Model(object):
             raise ValueError('unexpected trailing shape %s' % (tuple(a.shape),))
         return a
 
+    def _sync_packs(self, plan):
+        """The precision modes' weight packs are kept across calls while the parameters are untouched: torch counts in-place writes to the flat
+        buffer and its views (_version), the optimizer's own kernel reports itself (_params_epoch)."""
+        pkey = (self._flat_params.data_ptr(), self._flat_params._version, getattr(self, '_params_epoch', 0))
+        if getattr(plan, 'packed_key', None) != pkey:
+            _lib.check(plan.lib.pivp_plan_params_changed(plan.h), 'pivp_plan_params_changed')
+            plan.packed_key = pkey
+
+    def _left_by_rollout(self, inputs, gen, gen_states, results):
+        """What either rollout leaves on the model.  results: pivp_rollout_forward's, or None behind pivp_rollout_predict (taps exist, a loss does not)."""
+        self._inputs = inputs   # keep alive until the stream has consumed them
+        self._gen = gen
+        self._gen_states = gen_states
+        self._results = results
+        self._imagined = results is None
+        self.gen_images = [gen[t] for t in range(gen.shape[0])]
+        self.gen_states = [gen_states[t] for t in range(gen_states.shape[0])]
+        self.loss_terms = None
+        self._loss_grad = None
+
     def __call__(self, x, iter_num=-1.0):
         """TM:620-764.  x = [images (T,B,3,H,W), actions (T,B,5), states (T,B,5)], time-major."""
         if len(x) > 1:
@@ -610,29 +630,16 @@ class Model(object):
             gen_states = torch.empty((T - 1, B, 5), dtype=torch.float32, device=self.device)
             nf = T - ctx
             results = torch.empty(2 + 3 * nf, dtype=torch.float32, device=self.device)
-            # the precision modes' weight packs are kept across calls while the parameters are untouched: torch counts in-place writes to the flat
-            # buffer and its views (_version), the optimizer's own kernel reports itself (_params_epoch)
-            pkey = (self._flat_params.data_ptr(), self._flat_params._version, getattr(self, '_params_epoch', 0))
-            if getattr(plan, 'packed_key', None) != pkey:
-                _lib.check(plan.lib.pivp_plan_params_changed(plan.h), 'pivp_plan_params_changed')
-                plan.packed_key = pkey
+            self._sync_packs(plan)
             with self._carried(plan, B, H, W) as carried:
                 _lib.check(plan.lib.pivp_rollout_forward(plan.h, images.data_ptr(), actions.data_ptr(), states.data_ptr(),
                                                          gt_ptr, gen.data_ptr(), gen_states.data_ptr(), results.data_ptr(),
                                                          self._stream()), 'pivp_rollout_forward')
             self._carried_start = carried
-            self._inputs = (images, actions, states)   # keep alive until the stream has consumed them
-            self._gen = gen
-            self._gen_states = gen_states
-            self._results = results
-            self._imagined = False
+            self._left_by_rollout((images, actions, states), gen, gen_states, results)
             self._nf = nf
-            self.gen_images = [gen[t] for t in range(T - 1)]
-            self.gen_states = [gen_states[t] for t in range(T - 1)]
             self.loss = results[0]
             self.psnr_all = results[1]
-            self.loss_terms = None
-            self._loss_grad = None
             if self._extra_loss:
                 self._add_image_loss(gen, images, ctx, config.train and self.keep_activations)
         return self.loss
@@ -784,24 +791,13 @@ class Model(object):
         gen = torch.empty((T - 1, B, 3, H, W), dtype=torch.float32, device=self.device)
         gen_states = torch.empty((T - 1, B, 5), dtype=torch.float32, device=self.device)
         track = torch.empty((T - 1 - f, B, P, H, W), dtype=torch.float32, device=self.device) if P else None
-        pkey = (self._flat_params.data_ptr(), self._flat_params._version, getattr(self, '_params_epoch', 0))
-        if getattr(plan, 'packed_key', None) != pkey:
-            _lib.check(plan.lib.pivp_plan_params_changed(plan.h), 'pivp_plan_params_changed')
-            plan.packed_key = pkey
+        self._sync_packs(plan)
         with self._carried(plan, B, H, W, advance=advance, observed=observed or 0):
             _lib.check(plan.lib.pivp_rollout_predict(plan.h, images.data_ptr(), actions.data_ptr(), state.data_ptr(),
                                                      planes.data_ptr() if P else None, P, f, gen.data_ptr(), gen_states.data_ptr(),
                                                      track.data_ptr() if P else None, self._stream()), 'pivp_rollout_predict')
-        self._inputs = (images, actions, state, planes)   # keep alive until the stream has consumed them
+        self._left_by_rollout((images, actions, state, planes), gen, gen_states, None)
         self._gt_mask = None
-        self._gen = gen
-        self._gen_states = gen_states
-        self._results = None
-        self._imagined = True
-        self.loss_terms = None
-        self._loss_grad = None
-        self.gen_images = [gen[t] for t in range(T - 1)]
-        self.gen_states = [gen_states[t] for t in range(T - 1)]
         self.pixel_mass = None
         self.pixel_distrib = None
         return gen, track

@@ -184,6 +184,57 @@ def test_inference_taps_of_norms_applied_inside_their_consumers(pivp):
         assert np.abs(got - ref.taps[2][tap]).max() < 5e-4, tap
 
 
+@pytest.mark.parametrize('H,W', [(16, 16), (24, 40)])
+def test_inference_taps_where_the_norms_are_not_folded(pivp, H, W):
+    """Frame sizes on which an inference plan applies none of the norms of hidden2 / hidden4 inside enc1 / enc2 (StepForm rules the fold out from the
+    geometry): tap() then returns the tensor the step wrote and the model used, not a rebuild.  Every tap is held to the float64 oracle at the gate of the
+    test above; hidden2 / hidden4 are bit-equal to those of a training plan without 'ln_fold_train', whose ln_apply launches are the same ones."""
+    B, T = 3, 4
+    P = R.init_params(seed=3, dtype=np.float32, scale=1.0, height=H, width=W)
+    imgs, acts, stas = R.synthetic_batch(B, T, height=H, width=W)
+    ref = R.Model(10, params=P, dtype=np.float64, prefix='x'); ref.train = False
+    ref([imgs, acts, stas], 0, tap_steps=(T - 2,))
+    m, loss, gen = _run(pivp, 'CDNA', 10, imgs, acts, stas, P)              # keep_activations = False
+    assert R.per_pixel_l2(gen, np.stack(ref.gen_images)).max() < GATE
+    got = {}
+    for tap in ['hidden%d' % j for j in range(1, 8)] + ['enc1', 'enc2', 'enc5', 'enc6']:
+        got[tap] = m.tap(tap).cpu().numpy()
+        err = np.abs(got[tap] - ref.taps[T - 2][tap]).max()
+        print('%dx%d %s: max abs difference from the float64 oracle %.3e' % (H, W, tap, err))
+        assert err < 5e-4, tap
+    mt, _, _ = _run(pivp, 'CDNA', 10, imgs, acts, stas, P, keep_activations=True, plan_options={'ln_fold_train': 0})
+    for tap in ('hidden2', 'hidden4'):
+        assert np.array_equal(mt.tap(tap, T - 2).cpu().numpy(), got[tap]), tap
+
+
+def test_profile_record_of_a_rollout(pivp):
+    """pivp_plan_set_profiling: a rollout of T - 1 = 3 steps leaves three timed launches per ConvLSTM cell -- one without the h half of K, two full ones, in
+    executed flops -- and reading the record empties it."""
+    import ctypes
+    B, T, H, W = 2, 4, 16, 16
+    P = R.init_params(seed=3, dtype=np.float32, scale=1.0, height=H, width=W)
+    imgs, acts, stas = R.synthetic_batch(B, T, height=H, width=W)
+    m, _, _ = _run(pivp, 'CDNA', 10, imgs, acts, stas, P)
+    plan = m._active
+    ms, n, fl = (ctypes.c_double * 7)(), (ctypes.c_int * 7)(), (ctypes.c_double * 7)()
+    assert plan.lib.pivp_plan_set_profiling(plan.h, 1) == 0
+    try:
+        with pivp.using_config('train', False):
+            m([imgs, acts, stas], 0)
+        import torch
+        torch.cuda.synchronize()
+        assert plan.lib.pivp_plan_profile_read(plan.h, ms, n, fl) == 0
+        cells = [(32, 32, 2), (32, 32, 2), (32, 64, 4), (64, 64, 4), (64, 128, 8), (128, 64, 4), (96, 32, 2)]      # (cx, C, pyramid level) of lstm1..lstm7
+        for i, (cx, C, lv) in enumerate(cells):
+            M = B * (H // lv) * (W // lv)
+            first, full = 2.0 * M * 4 * C * 25 * cx, 2.0 * M * 4 * C * 25 * (cx + C)
+            assert n[i] == 3 and ms[i] > 0.0 and fl[i] == first + 2 * full, (i, n[i], ms[i], fl[i])
+        assert plan.lib.pivp_plan_profile_read(plan.h, ms, n, fl) == 0
+        assert list(n) == [0] * 7 and list(ms) == [0.0] * 7 and list(fl) == [0.0] * 7
+    finally:
+        assert plan.lib.pivp_plan_set_profiling(plan.h, 0) == 0
+
+
 def test_batch32_properties(pivp):
     """Full-size batch (config 2: B=32, T=10): size-independent properties instead of the slow oracle.
     (a) samples are independent: rows of a B=32 run equal the same sequences run as B=2;

@@ -188,6 +188,22 @@ def test_product_path_does_not_import_the_oracle():
             assert 'oracle' not in src.replace('no oracle', ''), fn
 
 
+def test_a_rollout_passes_itself_no_argument_through_the_plan():
+    """What one rollout call hands to its own timesteps lives in the call (Rollout, csrc/plan_forward.hip), and a step reads the plan const: struct
+    pivp_plan has no member a rollout sets for its steps, and pivp_get_tap reads the step's form instead of a table of its own."""
+    csrc = os.path.join(ROOT, 'physical-interaction-video-prediction_amd', 'csrc')
+    header = open(os.path.join(csrc, 'plan.h')).read()
+    body = re.search(r'^struct pivp_plan \{\n(.*?)^\};', header, re.S | re.M).group(1)
+    assert 'cfg;' in body and 'last' in body                                 # (the struct was found whole)
+    assert 'masks_every_step' not in body
+    assert not re.search(r'\bprof_(on|ev|layer|used)\b', body)               # the profile record is one member with begin / end
+    forward = open(os.path.join(csrc, 'plan_forward.hip')).read()
+    rollout = re.search(r'^struct Rollout \{\n(.*?)^\};', forward, re.S | re.M).group(1)
+    assert re.search(r'\bconst pivp_plan& p;', rollout) and 'masks_every_step' in rollout
+    assert not re.search(r'\bpivp_plan\s*\*\s*\w+\s*[,)]', rollout)          # no member function takes a plan it could write
+    assert 'split_only' not in open(os.path.join(csrc, 'plan_setup.hip')).read()
+
+
 def test_graft_entry_build_in_a_fresh_interpreter():
     # the driver calls build() from its own process: no module this suite happens to import may be relied on
     import subprocess
