@@ -545,7 +545,8 @@ int pivp_grad_unpack_bf16(const void* src_bf16, float* dst, long long n, void* s
  * rounded once to bf16 (dst_bf16) or kept fp32.  An all-reduce of a bf16 buffer rounds its running sum at every hop instead. */
 int pivp_grad_sum_shards(const void* src, int src_bf16, int nshards, long long shard_len, void* dst, int dst_bf16, void* stream);
 
-/* L.Convolution2D(cout,(3,3),stride=2,pad=1) (TM:501-502) + optional ReLU; w [9][cin/32][cout][32]. */
+/* L.Convolution2D(cout,(3,3),stride=2,pad=1) (TM:501-502) + optional ReLU; w [9][cin/32][cout][32].  Which kernel this and the transposed conv
+ * below launch depends on the batch, the map size and the alignment of out / bias: pivp_conv_form of pivp_conv_forms.h tells which. */
 int pivp_conv3x3s2(const float* x, int cin, int ldx, const float* w, const float* bias, float* out, int cout,
                    int ldo, int relu, int B, int Hin, int Win, void* stream);
 

@@ -12,7 +12,7 @@ CSRC = os.path.join(HERE, 'csrc')
 INCLUDE = os.path.join(HERE, '..', 'include')
 # the public headers, in the order the digest takes them (_lib.HEADER_SIGNATURES: what each declares)
 PUBLIC_HEADERS = ('pivp_data.h', 'pivp_hip.h', 'pivp_optim.h', 'pivp_loss.h', 'pivp_input_grad.h', 'pivp_state.h', 'pivp_state_grad.h',
-                  'pivp_goal_cost.h', 'pivp_mpc.h')
+                  'pivp_goal_cost.h', 'pivp_mpc.h', 'pivp_conv_forms.h')
 
 
 def source_files():

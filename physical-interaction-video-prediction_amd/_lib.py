@@ -212,10 +212,31 @@ MPC_SIGNATURES = {
     'pivp_cem_update_ex': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _c.c_ulonglong, _i, _i, _i, _i, _f, _vp]),
     'pivp_cem_shift': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
 }
+
+
+class PivpEnc3Epilogue(ctypes.Structure):      # pivp_enc3_epilogue_t
+    _fields_ = [('w3', _vp), ('b3', _vp), ('action', _vp), ('state', _vp), ('wcs', _vp), ('bcs', _vp), ('e3_out', _vp), ('state_out', _vp), ('use_state', _i)]
+
+
+# ... and those include/pivp_conv_forms.h declares (which launch form a plain convolution takes; the LayerNorm-on-load conv and the producers' LayerNorm
+# partials as ops)
+CONV_FORMS_SIGNATURES = {
+    'pivp_conv_form': (_i, [_i, _i, _i, _i, _i, _i, _i]),
+    'pivp_conv_enc0_form': (_i, [_i, _i, _i]),
+    'pivp_conv3x3s2_ln_fits': (_i, [_i, _i, _i, _i, _i]),
+    'pivp_conv3x3s2_ln': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _c.POINTER(PivpEnc3Epilogue), _i, _i, _i, _vp]),
+    'pivp_conv_layernorm_scratch_floats': (_ll, [_i, _i, _i, _i, _i]),
+    'pivp_conv_layernorm': (_i, [_i, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _f, _i, _i, _i, _i, _c.POINTER(_i), _vp]),
+}
+# the PIVP_CONV_FORM_* / PIVP_ENC0_FORM_* / PIVP_CONV_KIND_* codes of that header
+CONV_FORM = {'deconv_tile': 1, 'long_k_dgrad': 2, 'small1': 11, 'small2': 12, 'small3': 13, 'f32_128x32': 21, 'f32_128x64': 22, 'f32_128x96': 23,
+             'f32_128x128': 24, 'f32_64x64': 25, 'f32_64x128': 26, 'f32_32x128': 27}
+ENC0_FORM = {'rows': 1, 'generic': 2}
+CONV_KIND = {'enc0': 0, 'conv3x3s2': 1, 'deconv3x3s2': 2}
 # header -> the table of what it declares: what load() binds
 HEADER_SIGNATURES = {'pivp_data.h': DATA_SIGNATURES, 'pivp_hip.h': SIGNATURES, 'pivp_optim.h': OPTIM_SIGNATURES, 'pivp_loss.h': LOSS_SIGNATURES,
                      'pivp_input_grad.h': INPUT_GRAD_SIGNATURES, 'pivp_state.h': STATE_SIGNATURES, 'pivp_state_grad.h': STATE_GRAD_SIGNATURES,
-                     'pivp_goal_cost.h': GOAL_COST_SIGNATURES, 'pivp_mpc.h': MPC_SIGNATURES}
+                     'pivp_goal_cost.h': GOAL_COST_SIGNATURES, 'pivp_mpc.h': MPC_SIGNATURES, 'pivp_conv_forms.h': CONV_FORMS_SIGNATURES}
 if tuple(HEADER_SIGNATURES) != _digest.PUBLIC_HEADERS:
     raise ImportError('HEADER_SIGNATURES and _digest.PUBLIC_HEADERS disagree: a public header without a table of its symbols, or a table without its header')
 STATE_SEGMENTS = 14            # PIVP_STATE_SEGMENTS (include/pivp_state.h)

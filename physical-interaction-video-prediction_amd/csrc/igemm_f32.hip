@@ -772,54 +772,35 @@ int igemm_conv_ksplit(const IgemmDesc& d) {
 int igemm_conv(const IgemmDesc& d, hipStream_t stream, int* ln_nparts) {
     int rc = igemm_validate(d, false);
     if (rc != PIVP_OK) return rc;
-    const int nt = d.N / 32;
-    // transposed conv on maps that tile into 8 x 16 input patches: all four parities per block (deconv_tile.hip), unless the grid would be tiny
-    if (deconv_tile_ok(d) && (long)d.B * (d.Hin / 8) * (d.Win / 16) * nt >= 16)
-        return deconv_tile(d, stream, ln_nparts);
-    const long full = (long)((d.M + 127) / 128) * d.nphase;   // blocks with BM = 128 and the whole N in one block
+    // the form is decided by conv_form (conv_form.h) from the descriptor's integers; dgrad_choice adds the long-K data gradient's tile and K split
     int bt = -1, bks = 1;
-    if (dgrad_choice(d, bt, bks)) {
-        switch (bt) {
-            case 0: return launch_igemm<2, 2, 2, false>(d, stream, bks, ln_nparts);
-            case 1: return launch_igemm<4, 1, 1, false>(d, stream, bks, ln_nparts);
-            case 2: return launch_igemm<4, 1, 2, false>(d, stream, bks, ln_nparts);
-            case 3: return launch_igemm<4, 1, 3, false>(d, stream, bks, ln_nparts);
-            case 4: return launch_igemm<4, 1, 4, false>(d, stream, bks, ln_nparts);
-            case 5: return launch_igemm<2, 2, 4, false>(d, stream, bks, ln_nparts);
-            case 6: return launch_igemm<1, 4, 4, false>(d, stream, bks, ln_nparts);
-        }
-        return PIVP_ERR_BADARG;
+    const bool dgrad = dgrad_choice(d, bt, bks);
+    const bool aligned = d.ldo % 4 == 0 && ((uintptr_t)d.out & 15) == 0 && (!d.bias || ((uintptr_t)d.bias & 15) == 0);
+    const bool tile_ok = deconv_tile_ok(d);
+    // (a transposed conv the tile kernel's own check refuses -- none is built: deconv3x3s2_desc's maps pass it whenever the map tiles -- is asked as an untiled map)
+    switch (conv_form(d.deconv, d.c0 + d.c1, d.N, d.B, tile_ok ? d.Hin : 1, d.Win, aligned, dgrad, d.ksize, d.M)) {
+        case ConvForm::DeconvTile: return deconv_tile(d, stream, ln_nparts);
+        case ConvForm::LongKDgrad:
+            switch (bt) {
+                case 0: return launch_igemm<2, 2, 2, false>(d, stream, bks, ln_nparts);
+                case 1: return launch_igemm<4, 1, 1, false>(d, stream, bks, ln_nparts);
+                case 2: return launch_igemm<4, 1, 2, false>(d, stream, bks, ln_nparts);
+                case 3: return launch_igemm<4, 1, 3, false>(d, stream, bks, ln_nparts);
+                case 4: return launch_igemm<4, 1, 4, false>(d, stream, bks, ln_nparts);
+                case 5: return launch_igemm<2, 2, 4, false>(d, stream, bks, ln_nparts);
+                case 6: return launch_igemm<1, 4, 4, false>(d, stream, bks, ln_nparts);
+            }
+            return PIVP_ERR_BADARG;
+        case ConvForm::Small1: case ConvForm::Small2: case ConvForm::Small3: return igemm_small(d, stream, ln_nparts);
+        case ConvForm::F32_128x32: return launch_igemm<4, 1, 1, false>(d, stream, 1, ln_nparts);
+        case ConvForm::F32_128x64: return launch_igemm<4, 1, 2, false>(d, stream, 1, ln_nparts);
+        case ConvForm::F32_128x96: return launch_igemm<4, 1, 3, false>(d, stream, 1, ln_nparts);
+        case ConvForm::F32_128x128: return launch_igemm<4, 1, 4, false>(d, stream, 1, ln_nparts);
+        case ConvForm::F32_64x64: return launch_igemm<2, 2, 2, false>(d, stream, 1, ln_nparts);
+        case ConvForm::F32_64x128: return launch_igemm<2, 2, 4, false>(d, stream, 1, ln_nparts);
+        case ConvForm::F32_32x128: return launch_igemm<1, 4, 4, false>(d, stream, 1, ln_nparts);
     }
-    // Short K (the 3x3 stride-2 convs and the transposed convs: 2..18 chunks) or too few big tiles to fill the chip:
-    // 32-row tiles with K split over the waves (igemm_small.hip).  Measured at B = 32 (scripts/bench_tail_ops.py):
-    // enc1 15.0 -> 6.6 us, enc2 21.4 -> 9.7, enc4 19.3 -> 14.2, enc5 33.7 -> 23.8, enc6 47.6 -> 39.5.
-    {
-        const bool can = d.ldo % 4 == 0 && ((uintptr_t)d.out & 15) == 0 && (!d.bias || ((uintptr_t)d.bias & 15) == 0);
-        const long big = full * ((nt + 3) / 4);
-        const int chunks = (d.deconv ? 4 : d.ksize * d.ksize) * ((d.c0 + d.c1) / 32);
-        if (can && (big < 128 || chunks <= 40)) {
-            return igemm_small(d, stream, ln_nparts);
-        }
-    }
-    if (nt > 4) {                                             // wide outputs: several column blocks
-        if (nt % 4 == 0) return full * (nt / 4) >= 256 ? launch_igemm<4, 1, 4, false>(d, stream, 1, ln_nparts) : launch_igemm<2, 2, 4, false>(d, stream, 1, ln_nparts);
-        if (nt % 3 == 0) return launch_igemm<4, 1, 3, false>(d, stream, 1, ln_nparts);
-        if (nt % 2 == 0) return full * (nt / 2) >= 256 ? launch_igemm<4, 1, 2, false>(d, stream, 1, ln_nparts) : launch_igemm<2, 2, 2, false>(d, stream, 1, ln_nparts);
-        return launch_igemm<4, 1, 1, false>(d, stream, 1, ln_nparts);
-    }
-    if (full >= 256) {
-        switch (nt) {
-            case 1: return launch_igemm<4, 1, 1, false>(d, stream, 1, ln_nparts);
-            case 2: return launch_igemm<4, 1, 2, false>(d, stream, 1, ln_nparts);
-            case 3: return launch_igemm<4, 1, 3, false>(d, stream, 1, ln_nparts);
-            case 4: return launch_igemm<4, 1, 4, false>(d, stream, 1, ln_nparts);
-        }
-        return PIVP_ERR_BADARG;
-    }
-    if (nt == 4 && full * 2 < 256) return launch_igemm<1, 4, 4, false>(d, stream, 1, ln_nparts);   // BM 32
-    if (nt == 4) return launch_igemm<2, 2, 4, false>(d, stream, 1, ln_nparts);                      // BM 64
-    if (nt == 2 && full * 2 >= 128) return launch_igemm<2, 2, 2, false>(d, stream, 1, ln_nparts);  // BM 64
-    return launch_igemm<4, 1, 1, false>(d, stream, 1, ln_nparts);                                    // BN 32: N/32 column blocks
+    return PIVP_ERR_BADARG;
 }
 
 }  // namespace pivp

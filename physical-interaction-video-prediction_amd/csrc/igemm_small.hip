@@ -307,11 +307,7 @@ __global__ __launch_bounds__(256) void igemm_small_kernel(const IgemmDesc d) {
 int igemm_small(const IgemmDesc& d, hipStream_t stream, int* ln_nparts) {
     PIVP_CHECK_ARG(d.ldo % 4 == 0 && ((uintptr_t)d.out & 15) == 0 && (!d.bias || ((uintptr_t)d.bias & 15) == 0));
     const int mblk = (d.M + 31) / 32, nt = d.N / 32;
-    // widest column block that still leaves >= 4 blocks per CU (enc4: 1 tile 14.2 us vs 2 tiles 15.3; enc5: 3 tiles 23.8 vs 1 tile
-    // 25.7; enc6: 2 tiles 39.5 vs 1 tile 44.9)
-    int ntb = 1;
-    if (nt % 3 == 0 && (long)mblk * (nt / 3) * d.nphase >= 1024) ntb = 3;
-    else if (nt % 2 == 0 && (long)mblk * (nt / 2) * d.nphase >= 1024) ntb = 2;
+    int ntb = small_ntb(d.M, nt, d.nphase);      // (conv_form.h)
     if (d.f3_out) {      // the fused 1x1 behind this conv: 64 columns in one block, tiles inside one sample, LayerNorm-on-load form only
         PIVP_CHECK_ARG(d.in_g && nt == 2 && d.nphase == 1 && (d.Hg * d.Wg) % 32 == 0 && !d.accum && !d.ln_part);
         PIVP_CHECK_ARG(d.f3_w && d.f3_b && d.f3_action && d.f3_state && (!d.f3_state_out || (d.f3_wcs && d.f3_bcs)));

@@ -7,6 +7,7 @@
 
 #include "../../include/pivp_hip.h"
 #include "../../include/pivp_data.h"
+#include "../../include/pivp_conv_forms.h"
 #include "pivp_host.h"
 
 using namespace pivp;
@@ -52,10 +53,9 @@ int run_convlstm(const float* x, int cx, int ldx, const float* h_prev, int C, co
 bool convlstm_ln_in_ok(Operand form, int cx, int ldx, int C, int B, int H, int W) {
     return operand_l2_direct(form) && cx <= 64 && ldx == cx && cx % 8 == 0 && C % 16 == 0 && H % 8 == 0 && W % 16 == 0;
 }
-int run_conv3x3s2(const float* x, int cin, int ldx, const float* w, const float* bias, float* out, int cout,
-                  int ldo, int relu, int B, int Hin, int Win, hipStream_t s, int accum) {
+static int conv3x3s2_desc(IgemmDesc& d, const float* x, int cin, int ldx, const float* w, const float* bias, float* out, int cout,
+                          int ldo, int relu, int B, int Hin, int Win, int accum) {
     if (Hin % 2 || Win % 2) return PIVP_ERR_BADARG;
-    IgemmDesc d;
     memset(&d, 0, sizeof(d));
     d.x0 = x; d.c0 = cin; d.ld0 = ldx; d.wcin = cin; d.w = w; d.bias = bias;
     d.B = B; d.Hin = Hin; d.Win = Win; d.Hg = Hin / 2; d.Wg = Win / 2; d.in_step = 2;
@@ -65,6 +65,13 @@ int run_conv3x3s2(const float* x, int cin, int ldx, const float* w, const float*
     if (!fits31(b0) || !fits31(bw)) return PIVP_ERR_BADARG;
     d.bytes0 = (int)b0; d.bytesw = (int)bw;
     d.out_step = 1; d.Hout = d.Hg; d.Wout = d.Wg; d.out = out; d.ldo = ldo; d.relu = relu; d.accum = accum;
+    return PIVP_OK;
+}
+int run_conv3x3s2(const float* x, int cin, int ldx, const float* w, const float* bias, float* out, int cout,
+                  int ldo, int relu, int B, int Hin, int Win, hipStream_t s, int accum) {
+    IgemmDesc d;
+    int rc = conv3x3s2_desc(d, x, cin, ldx, w, bias, out, cout, ldo, relu, B, Hin, Win, accum);
+    if (rc != PIVP_OK) return rc;
     return igemm_conv(d, s);
 }
 
@@ -1044,6 +1051,103 @@ extern "C" int pivp_deconv3x3s2_fp16x3(const float* x, int cin, int ldx, const f
 }
 extern "C" int pivp_conv_enc0(const float* img, const float* w, const float* bias, float* out, int B, int H, int W, void* stream) {
     return conv_enc0(img, w, bias, out, B, H, W, (hipStream_t)stream);
+}
+// ---- include/pivp_conv_forms.h: the launch forms of the plain convolutions as host-only queries, and op entries for what a rollout reaches mid-step ----
+static_assert((int)ConvForm::DeconvTile == PIVP_CONV_FORM_DECONV_TILE && (int)ConvForm::LongKDgrad == PIVP_CONV_FORM_LONG_K_DGRAD &&
+              (int)ConvForm::Small1 == PIVP_CONV_FORM_SMALL_1 && (int)ConvForm::Small2 == PIVP_CONV_FORM_SMALL_2 && (int)ConvForm::Small3 == PIVP_CONV_FORM_SMALL_3 &&
+              (int)ConvForm::F32_128x32 == PIVP_CONV_FORM_F32_128X32 && (int)ConvForm::F32_128x64 == PIVP_CONV_FORM_F32_128X64 &&
+              (int)ConvForm::F32_128x96 == PIVP_CONV_FORM_F32_128X96 && (int)ConvForm::F32_128x128 == PIVP_CONV_FORM_F32_128X128 &&
+              (int)ConvForm::F32_64x64 == PIVP_CONV_FORM_F32_64X64 && (int)ConvForm::F32_64x128 == PIVP_CONV_FORM_F32_64X128 &&
+              (int)ConvForm::F32_32x128 == PIVP_CONV_FORM_F32_32X128 && (int)Enc0Form::Rows == PIVP_ENC0_FORM_ROWS && (int)Enc0Form::Generic == PIVP_ENC0_FORM_GENERIC,
+              "conv_form.h and include/pivp_conv_forms.h disagree on a form's code");
+extern "C" int pivp_conv_form(int deconv, int cin, int cout, int B, int Hin, int Win, int aligned) {
+    if (deconv < 0 || deconv > 1 || cin <= 0 || cin % 32 || cout <= 0 || cout % 32 || B <= 0 || Hin <= 0 || Win <= 0) return PIVP_ERR_BADARG;
+    if (!deconv && (Hin % 2 || Win % 2)) return PIVP_ERR_BADARG;
+    if (!fits31(view_bytes(B, Hin, Win, cin)) || !fits31(9LL * cin * cout * 4)) return PIVP_ERR_BADARG;
+    // (the ops' descriptors never qualify as long-K data gradients: run_conv3x3s2 / run_deconv3x3s2 allow no K split)
+    return (int)conv_form(deconv, cin, cout, B, Hin, Win, aligned ? 1 : 0, 0);
+}
+extern "C" int pivp_conv_enc0_form(int B, int H, int W) {
+    if (B <= 0 || H <= 0 || W <= 0 || H % 2 || W % 2) return PIVP_ERR_BADARG;
+    return (int)enc0_form(B, H, W, 1);
+}
+extern "C" int pivp_conv3x3s2_ln_fits(int cin, int cout, int B, int Hin, int Win) {
+    if (cin <= 0 || cout <= 0 || B <= 0 || Hin <= 0 || Win <= 0) return 0;
+    return conv3x3s2_ln_ok(cin, cout, B, Hin, Win) ? 1 : 0;
+}
+extern "C" int pivp_conv3x3s2_ln(const float* x_raw, int cin, const float* w, const float* bias, const float* gamma, const float* beta, float eps,
+                                 float* partials, float* out, int cout, int ldo, int relu, float* keep_out, int keep_ld, float* stat_out,
+                                 const pivp_enc3_epilogue_t* ep, int B, int Hin, int Win, void* stream) {
+    if (!x_raw || !w || !gamma || !beta || !partials || !out || !pivp_conv3x3s2_ln_fits(cin, cout, B, Hin, Win)) return PIVP_ERR_BADARG;
+    // everything run_conv3x3s2_ln and igemm_small refuse is refused here, in front of the statistics pass
+    if (ldo < cout || ldo % 4 || ((uintptr_t)out & 15) || (bias && ((uintptr_t)bias & 15))) return PIVP_ERR_BADARG;
+    if (keep_out && (keep_ld < cin || keep_ld % 4 || ((uintptr_t)keep_out & 15) || !fits31((long long)B * Hin * Win * keep_ld))) return PIVP_ERR_BADARG;
+    Enc3Fuse f3;
+    memset(&f3, 0, sizeof(f3));
+    if (ep) {
+        if (!ep->w3 || !ep->b3 || !ep->action || !ep->state || !ep->e3_out || (ep->state_out && (!ep->wcs || !ep->bcs))) return PIVP_ERR_BADARG;
+        if (cout != 64 || ldo != 64 || !relu || !bias || keep_out) return PIVP_ERR_BADARG;
+        f3.w3 = ep->w3; f3.b3 = ep->b3; f3.action = ep->action; f3.state = ep->state; f3.wcs = ep->wcs; f3.bcs = ep->bcs;
+        f3.e3 = ep->e3_out; f3.state_out = ep->state_out; f3.use_state = ep->use_state;
+    }
+    const int n = Hin * Win * cin;
+    int rc = ln_stats(x_raw, partials, B, n, (hipStream_t)stream);
+    if (rc != PIVP_OK) return rc;
+    const LnIn ln{gamma, beta, partials, ln_stats_slices(n), eps};
+    Conv3x3LnOpts o{};
+    if (ep) o.fuse3 = &f3;
+    o.keep = NormKeep{keep_out, keep_ld, stat_out};
+    return run_conv3x3s2_ln(x_raw, cin, w, bias, out, cout, ldo, relu, B, Hin, Win, (hipStream_t)stream, ln, o);
+}
+// the partial slots per sample pivp_conv_layernorm offers the producer: what any of its forms may write, and the separate pass's slices
+static int conv_ln_cap(int kind, int cout, int Hin, int Win) {
+    const bool up = kind == PIVP_CONV_KIND_DECONV3X3S2;
+    const int Hout = up ? 2 * Hin : Hin / 2, Wout = up ? 2 * Win : Win / 2;
+    const int tiles = kind == PIVP_CONV_KIND_ENC0 ? (Hout * Wout + 63) / 64 : ((up ? Hin * Win : Hout * Wout) + 31) / 32 * (cout / 32) * (up ? 4 : 1);
+    const int slices = ln_stats_slices(Hout * Wout * cout);
+    return tiles > slices ? tiles : slices;
+}
+static bool conv_ln_args_ok(int kind, int cout, int B, int Hin, int Win) {
+    if (kind < PIVP_CONV_KIND_ENC0 || kind > PIVP_CONV_KIND_DECONV3X3S2 || cout <= 0 || cout % 32 || B <= 0 || Hin <= 0 || Win <= 0) return false;
+    if (kind != PIVP_CONV_KIND_DECONV3X3S2 && (Hin % 2 || Win % 2)) return false;
+    const bool up = kind == PIVP_CONV_KIND_DECONV3X3S2;
+    const long long n = (long long)(up ? 2 * Hin : Hin / 2) * (up ? 2 * Win : Win / 2) * cout;      // the output, per sample
+    return (kind != PIVP_CONV_KIND_ENC0 || cout == 32) && fits31(n * B * 4);
+}
+extern "C" long long pivp_conv_layernorm_scratch_floats(int kind, int cout, int B, int Hin, int Win) {
+    if (!conv_ln_args_ok(kind, cout, B, Hin, Win)) return PIVP_ERR_BADARG;
+    return (long long)B * conv_ln_cap(kind, cout, Hin, Win) * 4;
+}
+extern "C" int pivp_conv_layernorm(int kind, const float* x, int cin, int ldx, const float* w, const float* bias, float* raw_out, int cout, int relu,
+                                   const float* gamma, const float* beta, float* ln_out, int ldo, float* partials, float eps, int relu_ln,
+                                   int B, int Hin, int Win, int* fused, void* stream) {
+    if (fused) *fused = 0;
+    if (!x || !w || !raw_out || !gamma || !beta || !ln_out || !partials || !conv_ln_args_ok(kind, cout, B, Hin, Win)) return PIVP_ERR_BADARG;
+    if (ldo < cout || ldo % 4) return PIVP_ERR_BADARG;
+    if (kind == PIVP_CONV_KIND_ENC0 && (cin != 3 || relu || !bias)) return PIVP_ERR_BADARG;
+    hipStream_t s = (hipStream_t)stream;
+    const bool up = kind == PIVP_CONV_KIND_DECONV3X3S2;
+    const int Hout = up ? 2 * Hin : Hin / 2, Wout = up ? 2 * Win : Win / 2;
+    const int cap = conv_ln_cap(kind, cout, Hin, Win);
+    int np = 0, rc = PIVP_ERR_BADARG;
+    if (kind == PIVP_CONV_KIND_ENC0) {
+        rc = conv_enc0(x, w, bias, raw_out, B, Hin, Win, s, partials, cap, &np);
+    } else if (kind == PIVP_CONV_KIND_CONV3X3S2) {
+        IgemmDesc d;
+        rc = conv3x3s2_desc(d, x, cin, ldx, w, bias, raw_out, cout, cout, relu, B, Hin, Win, 0);
+        if (rc != PIVP_OK) return rc;
+        d.ln_part = partials; d.ln_cap = cap;
+        rc = igemm_conv(d, s, &np);
+    } else {
+        DeconvOpts o{};
+        o.ln_out.part = partials; o.ln_out.cap = cap; o.ln_out.nparts = &np;
+        rc = run_deconv3x3s2(x, cin, ldx, w, bias, raw_out, cout, cout, relu, B, Hin, Win, s, o);
+    }
+    if (rc != PIVP_OK) return rc;
+    if (fused) *fused = np;
+    LayerNormOpts lo{};
+    lo.fused_nparts = np;      // (as Rollout::ln: 0 = the statistics pass first)
+    return run_layernorm(raw_out, gamma, beta, ln_out, partials, B, Hout * Wout * cout, cout, ldo, eps, relu_ln, s, lo);
 }
 extern "C" long long pivp_layernorm_scratch_floats(int B, int n) {
     if (B <= 0 || n <= 0) return PIVP_ERR_BADARG;

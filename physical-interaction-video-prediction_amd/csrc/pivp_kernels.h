@@ -10,6 +10,7 @@
 //     LN gamma/beta NHWC-flat.
 #pragma once
 #include "pivp_common.h"
+#include "conv_form.h"
 
 namespace pivp {
 

@@ -54,7 +54,7 @@ __global__ __launch_bounds__(256) void conv_enc0_kernel(const float* __restrict_
 // ((2*rows+3) x (W+3) x 3, zero padded) and the weights are staged in LDS with every load of a thread in flight at
 // once.  The element-per-thread kernel above issued 75 image loads behind bounds branches and re-read the weights with
 // one load in flight: ~11 us for 6 MB of traffic.
-constexpr int E0_PR = 4;   // patch rows per thread and channel
+// (E0_PR, conv_form.h: patch rows per thread and channel)
 __global__ __launch_bounds__(256) void conv_enc0_rows_kernel(const float* __restrict__ img, const float* __restrict__ w,
                                                              const float* __restrict__ bias, float* __restrict__ out,
                                                              int B, int H, int W, float* __restrict__ ln_part) {
@@ -140,9 +140,9 @@ int conv_enc0(const float* img, const float* w, const float* bias, float* out, i
     PIVP_CHECK_ARG(img && w && bias && out && B > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0);
     const int H2 = H / 2, W2 = W / 2;
     const int total = B * H2 * W2;
-    if ((W2 == 8 || W2 == 16 || W2 == 32 || W2 == 64) && H2 % (64 / W2) == 0 && ((uintptr_t)w & 15) == 0) {
-        const int rows = 64 / W2, R = 2 * rows + 3, npatch = 3 * R * (W + 3);
-        if (W + 3 <= 256 && R <= E0_PR * (256 / (W + 3))) {
+    switch (enc0_form(B, H, W, ((uintptr_t)w & 15) == 0)) {      // (conv_form.h)
+        case Enc0Form::Rows: {
+            const int rows = 64 / W2, R = 2 * rows + 3, npatch = 3 * R * (W + 3);
             const size_t lds = sizeof(float) * (75 * 32 + npatch);
             const int np = H2 / rows;   // row tiles = LayerNorm partials per sample
             float* lp = (ln_part && np <= ln_cap) ? ln_part : nullptr;
@@ -150,9 +150,11 @@ int conv_enc0(const float* img, const float* w, const float* bias, float* out, i
             hipLaunchKernelGGL(conv_enc0_rows_kernel, dim3(B * np), dim3(256), lds, s, img, w, bias, out, B, H, W, lp);
             return PIVP_LAUNCH_STATUS();
         }
+        case Enc0Form::Generic:
+            hipLaunchKernelGGL(conv_enc0_kernel, dim3((total + 63) / 64), dim3(256), 0, s, img, w, bias, out, B, H, W);
+            return PIVP_LAUNCH_STATUS();
     }
-    hipLaunchKernelGGL(conv_enc0_kernel, dim3((total + 63) / 64), dim3(256), 0, s, img, w, bias, out, B, H, W);
-    return PIVP_LAUNCH_STATUS();
+    return PIVP_ERR_BADARG;
 }
 
 // ------------------------------------------------------------------------------------------
