@@ -67,14 +67,22 @@ typedef struct pivp_config {
     int keep_activations;  /* 1: keep every timestep's activations (training/BPTT); 0: rolling   */
     float ln_eps;          /* chainer.links.LayerNormalization eps (1e-6 in 2.0.x)               */
     int stp_zero_border;   /* 0: clamp sampling coords (Chainer 2.0.x), 1: zero outside          */
+    int action_dim;        /* A, numbers per action, 1 .. 16; 0 = the reference data's 5         */
+    int state_dim;         /* S, numbers per robot state, 1 .. 16; 0 = 5 (TM:529 L.Linear(5))    */
 } pivp_config_t;
+/* action_dim / state_dim: the struct grew by these two trailing ints within ABI 17, without a version change and without a new symbol: a caller that
+ * zero-fills the tail means what it meant before (5 / 5).  Library and binding travel together (the binding refuses a library of another source digest),
+ * so no caller of an older, shorter struct meets this library.  With them enc3/W is [64 + (use_state ? A + S : 0)][64], current_state/W [S][A + S] and
+ * current_state/b [S]; actions are [T][B][A], states and gen_states [..][B][S].  The per-op entries below (pivp_enc3_state, pivp_enc3_state_backward,
+ * pivp_action_grad, pivp_gather_batch, the pivp_cem_* family) have no width argument and keep meaning 5 / 5. */
 
 /* The accepted domain.  pivp_plan_create returns PIVP_ERR_BADARG for everything outside it, before it allocates anything; what it accepts rolls out
  * (pivp_rollout_forward / _predict) without a refusal half-way:
  *   batch >= 1, seq_len >= 2, 1 <= context_frames < seq_len;
  *   height, width >= 16 and multiples of 8, width <= 248 (the compositing kernels give a frame row padded by 4 the 256 threads of a block);
  *   num_masks: CDNA 1 .. 10 (the motion head's finishers give each of its 25 * num_masks kernel taps a thread of one 256-thread block),
- *              STP 1 .. 11, DNA 1 (TM:389-390).
+ *              STP 1 .. 11, DNA 1 (TM:389-390);
+ *   action_dim, state_dim: 0 (= 5) or 1 .. 16 (the enc3 / state-predictor kernels hold the smeared [action, state] vector in 32 floats of LDS).
  * Training is narrower: pivp_rollout_backward serves CDNA with 1 .. 10 masks, STP with 2 .. 10 (the STP composite backward has no one-mask form; eleven
  * masks pass the forward alone) and DNA, on frames whose composite-backward tile fits in LDS -- every mask count on frames up to 128 wide, which is as far as
  * the sweep is validated; fewer masks on wider frames (csrc/backward_heads.hip, composite_bwd_serves).  A plan outside that is refused with PIVP_ERR_BADARG

@@ -20,7 +20,8 @@ _vp, _i, _f, _ll = _c.c_void_p, _c.c_int, _c.c_float, _c.c_longlong
 class PivpConfig(ctypes.Structure):
     _fields_ = [('batch', _i), ('seq_len', _i), ('height', _i), ('width', _i), ('num_masks', _i),
                 ('model_type', _i), ('use_state', _i), ('context_frames', _i), ('keep_activations', _i),
-                ('ln_eps', _f), ('stp_zero_border', _i)]
+                ('ln_eps', _f), ('stp_zero_border', _i),
+                ('action_dim', _i), ('state_dim', _i)]      # 1 .. 16 each; 0 (a caller that does not name them) = the reference data's 5
 
 
 class PivpFrameHeadArgs(ctypes.Structure):

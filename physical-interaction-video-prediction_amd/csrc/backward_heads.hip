@@ -1057,24 +1057,27 @@ int stp_params_bwd(const float* hidden5, const float* wt1, const float* s1, cons
 // enc3 (smear + 1x1 + ReLU) and state predictor backward (forward enc3_state_kernel; TM:556-567, 503, 730).
 //   dpre = d e3 [e3 > 0];  d e2 = dpre W3x^T;  dW3x += e2^T dpre;  db3 += colsum(dpre);
 //   dW3s[j] += sa[j] colsum;  d sa[j] = W3s[j] . colsum + sum_o Wcs[o][j] d snew[o];  dWcs, dbcs from d snew.
-//   d state_prev = d sa[5:10]  (the predicted state is fed back, TM:676)
-// One block per (64-pixel tile, sample); small sums through atomics.
+//   d state_prev = d sa[A : A + S]  (the predicted state is fed back, TM:676)
+// One block per (64-pixel tile, sample); small sums through atomics.  <AT, ST>: the widths of an action / a state as constants (<5, 5>), or
+// <0, 0>: a_rt / s_rt, 1 .. SMEAR_MAX_DIM each, as enc3_state_kernel's.
 // ------------------------------------------------------------------------------------------
+template <int AT, int ST>
 __global__ __launch_bounds__(256) void enc3_state_bwd_kernel(const float* __restrict__ e2, const float* __restrict__ e3, const float* __restrict__ de3, int ldd3,
                                                              const float* __restrict__ action, const float* __restrict__ state,
                                                              const float* __restrict__ w3, const float* __restrict__ wcs,
                                                              const float* __restrict__ dsnew, float* __restrict__ de2,
                                                              float* __restrict__ dw3, float* __restrict__ db3, float* __restrict__ dwcs,
                                                              float* __restrict__ dbcs, float* __restrict__ dstate_prev,
-                                                             int HW8, int use_state, int mask_e2, float* __restrict__ part) {
+                                                             int HW8, int use_state, int mask_e2, float* __restrict__ part, int a_rt, int s_rt) {
     PIVP_SET_MAIN_PRIO();
     __shared__ float xt[64 * 65];
     __shared__ float dt[64 * 65];
     __shared__ __attribute__((aligned(16))) float wl[64 * 64];
-    __shared__ float colsum[64], sa[10], dsa[10];
+    __shared__ float colsum[64], sa[AT ? AT + ST : 2 * SMEAR_MAX_DIM], dsa[AT ? AT + ST : 2 * SMEAR_MAX_DIM];
+    const int A = AT ? AT : a_rt, S = ST ? ST : s_rt, AS = A + S;
     const int b = blockIdx.y, tile = blockIdx.x, tid = threadIdx.x;
-    if (tid < 5) sa[tid] = action[b * 5 + tid]; else if (tid < 10) sa[tid] = state[b * 5 + tid - 5];
-    if (tid < 10) dsa[tid] = 0.f;
+    if (tid < A) sa[tid] = action[b * A + tid]; else if (tid < AS) sa[tid] = state[b * S + tid - A];
+    if (tid < AS) dsa[tid] = 0.f;
     const int npx = min(64, HW8 - tile * 64);
     const size_t base = ((size_t)b * HW8 + tile * 64) * 64;
     {   // sixteen independent 16-B loads per thread, then the LDS stores (the element loops made ~48 serial round trips)
@@ -1104,11 +1107,11 @@ __global__ __launch_bounds__(256) void enc3_state_bwd_kernel(const float* __rest
     // blockIdx.z = quarter q: 16 of the tile's 64 pixels for d e2 and 16 of the 64 input channels for dW (every quarter stages the whole
     // tile: 48 KB from L2).  One block per (tile, sample) ran 2 x 64 iterations of 16 FMAs on 32 of 256 CUs: 41 us for 17 MFLOP.
     const int q = blockIdx.z;
-    // deterministic sweeps (part != null): the (tile, sample) pair's row [dw3 | db3 | dwcs | dbcs] and its five d state_prev values, stored instead of
+    // deterministic sweeps (part != null): the (tile, sample) pair's row [dw3 | db3 | dwcs | dbcs] and its S d state_prev values, stored instead of
     // added (enc3_state_bwd_det_floats); every element of the row is written by one of the pair's four quarters
-    const int cin3 = use_state ? 74 : 64, rowlen = cin3 * 64 + 64 + 55;
+    const int cin3 = use_state ? 64 + AS : 64, rowlen = cin3 * 64 + 64 + S * AS + S;
     float* const row = part ? part + ((size_t)b * gridDim.x + tile) * rowlen : nullptr;
-    float* const dsrow = part ? part + (size_t)gridDim.y * gridDim.x * rowlen + ((size_t)b * gridDim.x + tile) * 5 : nullptr;
+    float* const dsrow = part ? part + (size_t)gridDim.y * gridDim.x * rowlen + ((size_t)b * gridDim.x + tile) * S : nullptr;
     if (tid < 64) {
         float c = 0.f;
         for (int p = 0; p < 64; ++p) c += dt[p * 65 + tid];
@@ -1149,47 +1152,57 @@ __global__ __launch_bounds__(256) void enc3_state_bwd_kernel(const float* __rest
     __syncthreads();
     if (use_state && tid < 64) {
 #pragma unroll
-        for (int j = 0; j < 10; ++j) { if (row) row[(64 + j) * 64 + tid] = sa[j] * colsum[tid]; else atomicAdd(dw3 + (64 + j) * 64 + tid, sa[j] * colsum[tid]); }
+        for (int j = 0; j < AS; ++j) { if (row) row[(64 + j) * 64 + tid] = sa[j] * colsum[tid]; else atomicAdd(dw3 + (64 + j) * 64 + tid, sa[j] * colsum[tid]); }
     }
-    if (tid < 10) {
+    if (tid < AS) {
         float v = 0.f;
         if (use_state) for (int co = 0; co < 64; ++co) v = fmaf(w3[(64 + tid) * 64 + co], colsum[co], v);
-        if (tile == 0) for (int o = 0; o < 5; ++o) v = fmaf(wcs[o * 10 + tid], dsnew[b * 5 + o], v);
-        if (tid >= 5) { if (dsrow) dsrow[tid - 5] = v; else atomicAdd(dstate_prev + b * 5 + tid - 5, v); }
+        if (tile == 0) for (int o = 0; o < S; ++o) v = fmaf(wcs[o * AS + tid], dsnew[b * S + o], v);
+        if (tid >= A) { if (dsrow) dsrow[tid - A] = v; else atomicAdd(dstate_prev + b * S + tid - A, v); }
     }
-    if (row && tid >= 64 && tid < 64 + 50) {      // (the state predictor's rows: sample b's value in tile 0's row, zeros in the others)
-        const int o = (tid - 64) / 10, j = (tid - 64) % 10;
-        row[cin3 * 64 + 64 + o * 10 + j] = tile == 0 ? dsnew[b * 5 + o] * sa[j] : 0.f;
-        if (j == 0) row[cin3 * 64 + 64 + 50 + o] = tile == 0 ? dsnew[b * 5 + o] : 0.f;
+    // the state predictor's S * (A + S) weights over threads 64 .. 255 (one pass at 5 / 5; up to three at 16 / 16)
+    if (row && tid >= 64) {      // (sample b's value in tile 0's row, zeros in the others)
+        for (int i = tid - 64; i < S * AS; i += 192) {
+            const int o = i / AS, j = i - o * AS;
+            row[cin3 * 64 + 64 + i] = tile == 0 ? dsnew[b * S + o] * sa[j] : 0.f;
+            if (j == 0) row[cin3 * 64 + 64 + S * AS + o] = tile == 0 ? dsnew[b * S + o] : 0.f;
+        }
     }
-    if (!row && tile == 0 && tid >= 64 && tid < 64 + 50) {
-        const int o = (tid - 64) / 10, j = (tid - 64) % 10;
-        atomicAdd(dwcs + o * 10 + j, dsnew[b * 5 + o] * sa[j]);
-        if (j == 0) atomicAdd(dbcs + o, dsnew[b * 5 + o]);
+    if (!row && tile == 0 && tid >= 64) {
+        for (int i = tid - 64; i < S * AS; i += 192) {
+            const int o = i / AS, j = i - o * AS;
+            atomicAdd(dwcs + i, dsnew[b * S + o] * sa[j]);
+            if (j == 0) atomicAdd(dbcs + o, dsnew[b * S + o]);
+        }
     }
 }
 int enc3_state_bwd(const float* e2, const float* e3, const float* de3, int ldd3, const float* action, const float* state, const float* w3,
                    const float* wcs, const float* dsnew, float* de2, float* dw3, float* db3, float* dwcs, float* dbcs,
-                   float* dstate_prev, int B, int HW8, int use_state, hipStream_t s, int mask_e2, float* det_part) {
+                   float* dstate_prev, int B, int HW8, int use_state, hipStream_t s, int mask_e2, float* det_part, int A, int S) {
     PIVP_CHECK_ARG(e2 && e3 && de3 && action && state && w3 && wcs && dsnew && de2 && dw3 && db3 && dwcs && dbcs && dstate_prev && B > 0 && HW8 > 0);
+    PIVP_CHECK_ARG(smear_dims_ok(A, S));
     const int tiles = (HW8 + 63) / 64;
-    hipLaunchKernelGGL(enc3_state_bwd_kernel, dim3(tiles, B, 4), dim3(256), 0, s, e2, e3, de3, ldd3, action, state, w3, wcs, dsnew, de2,
-                       dw3, db3, dwcs, dbcs, dstate_prev, HW8, use_state, mask_e2, det_part);
+    if (A == 5 && S == 5)
+        hipLaunchKernelGGL((enc3_state_bwd_kernel<5, 5>), dim3(tiles, B, 4), dim3(256), 0, s, e2, e3, de3, ldd3, action, state, w3, wcs, dsnew, de2,
+                           dw3, db3, dwcs, dbcs, dstate_prev, HW8, use_state, mask_e2, det_part, A, S);
+    else
+        hipLaunchKernelGGL((enc3_state_bwd_kernel<0, 0>), dim3(tiles, B, 4), dim3(256), 0, s, e2, e3, de3, ldd3, action, state, w3, wcs, dsnew, de2,
+                           dw3, db3, dwcs, dbcs, dstate_prev, HW8, use_state, mask_e2, det_part, A, S);
     if (det_part) {      // the weights over all (sample, tile) rows; d state_prev per sample over its tiles (inside the timestep: the next step reads it)
         int rc = PIVP_LAUNCH_STATUS();
         if (rc != PIVP_OK) return rc;
-        const int cin3 = use_state ? 74 : 64, rowlen = cin3 * 64 + 64 + 55;
-        DetSegs w{{dw3, db3, dwcs, dbcs, nullptr}, {cin3 * 64, 64, 50, 5, 0}, 4};
+        const int cin3 = use_state ? 64 + A + S : 64, rowlen = cin3 * 64 + 64 + S * (A + S) + S;
+        DetSegs w{{dw3, db3, dwcs, dbcs, nullptr}, {cin3 * 64, 64, S * (A + S), S, 0}, 4};
         rc = det_rows_reduce(det_part, B * tiles, 1, w, s);
         if (rc != PIVP_OK) return rc;
-        DetSegs ds{{dstate_prev, nullptr, nullptr, nullptr, nullptr}, {5, 0, 0, 0, 0}, 1};
+        DetSegs ds{{dstate_prev, nullptr, nullptr, nullptr, nullptr}, {S, 0, 0, 0, 0}, 1};
         return det_rows_reduce(det_part + (size_t)B * tiles * rowlen, tiles, B, ds, s);
     }
     return PIVP_LAUNCH_STATUS();
 }
-long long enc3_state_bwd_det_floats(int B, int HW8, int use_state) {
+long long enc3_state_bwd_det_floats(int B, int HW8, int use_state, int A, int S) {
     const long long rows = (long long)B * ((HW8 + 63) / 64);
-    return rows * ((use_state ? 74 : 64) * 64 + 64 + 55) + rows * 5;
+    return rows * ((use_state ? 64 + A + S : 64) * 64 + 64 + S * (A + S) + S) + rows * S;
 }
 
 // ------------------------------------------------------------------------------------------

@@ -3,7 +3,7 @@
 // state half (j = 5..9) as d state_prev; action_grad_kernel forms the action half (j = 0..4) from the same tensors, which that kernel leaves unmodified
 // (it writes d e2 and parameter gradients only), so the two launches may run in either order behind the step's d e3 and d snew.
 //   colsum[o]  = sum_p (e3[b,p,o] > 0 ? de3[b,p,o] : 0)                                                      (enc3's ReLU mask; 64 channels)
-//   dact[b][j] = (use_state ? sum_o w3[64+j][o] colsum[o] : 0) + sum_o wcs[o*10+j] dsnew[b][o],  j = 0..4
+//   dact[b][j] = (use_state ? sum_o w3[64+j][o] colsum[o] : 0) + sum_o wcs[o*(A+S)+j] dsnew[b][o],  j = 0..A-1      (A = S = 5 on the reference's data)
 // One 256-thread block per sample: thread (row group r = tid / 16, channel quad q = tid % 16) adds rows r, r + 16, ... of its four channels, a 16-byte
 // load of de3 and one of e3 per row, four rows in flight; fp64 from the first add.  The sixteen row groups meet in a fixed tree in LDS, five threads
 // finish the two dot products in fp64 in ascending o and round once.  No atomics, no workspace: the value of sample b depends on that sample's bytes, on
@@ -17,7 +17,7 @@ namespace pivp {
 
 __global__ __launch_bounds__(256) void action_grad_kernel(const float* __restrict__ e3, const float* __restrict__ de3, int ldd3,
                                                           const float* __restrict__ w3, const float* __restrict__ wcs,
-                                                          const float* __restrict__ dsnew, float* __restrict__ dact, int HW8, int use_state) {
+                                                          const float* __restrict__ dsnew, float* __restrict__ dact, int HW8, int use_state, int A, int S) {
     __shared__ double red[16 * 64];
     __shared__ double colsum[64];
     const int b = blockIdx.x, tid = threadIdx.x, rg = tid >> 4, cq = (tid & 15) * 4;
@@ -53,22 +53,22 @@ __global__ __launch_bounds__(256) void action_grad_kernel(const float* __restric
         colsum[tid] = v[0];
     }
     __syncthreads();
-    if (tid < 5) {
+    if (tid < A) {
         double v = 0.0;
         if (use_state) for (int o = 0; o < 64; ++o) v += (double)w3[(64 + tid) * 64 + o] * colsum[o];
         double u = 0.0;
-        for (int o = 0; o < 5; ++o) u += (double)wcs[o * 10 + tid] * (double)dsnew[b * 5 + o];
-        dact[b * 5 + tid] = (float)(v + u);
+        for (int o = 0; o < S; ++o) u += (double)wcs[o * (A + S) + tid] * (double)dsnew[b * S + o];
+        dact[b * A + tid] = (float)(v + u);
     }
 }
 
 int action_grad(const float* e3, const float* de3, int ldd3, const float* w3, const float* wcs, const float* dsnew, float* dact, int B, int HW8,
-                int use_state, hipStream_t s) {
-    PIVP_CHECK_ARG(e3 && de3 && wcs && dsnew && dact && (w3 || !use_state) && B > 0 && HW8 > 0 && ldd3 >= 64 && ldd3 % 4 == 0);
+                int use_state, hipStream_t s, int A, int S) {
+    PIVP_CHECK_ARG(e3 && de3 && wcs && dsnew && dact && (w3 || !use_state) && B > 0 && HW8 > 0 && ldd3 >= 64 && ldd3 % 4 == 0 && smear_dims_ok(A, S));
     PIVP_CHECK_ARG(!((reinterpret_cast<uintptr_t>(e3) | reinterpret_cast<uintptr_t>(de3)) & 15));
     PIVP_CHECK_ARG(!((reinterpret_cast<uintptr_t>(w3) | reinterpret_cast<uintptr_t>(wcs) | reinterpret_cast<uintptr_t>(dsnew) |
                       reinterpret_cast<uintptr_t>(dact)) & 3));
-    hipLaunchKernelGGL(action_grad_kernel, dim3(B), dim3(256), 0, s, e3, de3, ldd3, w3, wcs, dsnew, dact, HW8, use_state);
+    hipLaunchKernelGGL(action_grad_kernel, dim3(B), dim3(256), 0, s, e3, de3, ldd3, w3, wcs, dsnew, dact, HW8, use_state, A, S);
     return PIVP_LAUNCH_STATUS();
 }
 

@@ -215,10 +215,13 @@ int ln_apply(const float* x, const float* partials, const float* gamma, const fl
              int B, int n, int C, int ldo, float eps, int relu, hipStream_t s, float* stat_out = nullptr,
              int nparts = 0);   // nparts > 0: `partials` holds that many producer-written partials per sample
 
-// enc3: smear(action,state) + 1x1 conv + ReLU (TM:556-567, TM:503) and the state predictor (TM:730)
+// enc3: smear(action,state) + 1x1 conv + ReLU (TM:556-567, TM:503) and the state predictor (TM:730).  A, S (1 .. SMEAR_MAX_DIM each): the widths of
+// an action and of a state -- action [B][A], state / state_out [B][S], w3 [64 (+ A + S)][64], wcs [S][A + S]; 5 / 5 runs the instance with constant widths
+constexpr int SMEAR_MAX_DIM = 16;
+inline bool smear_dims_ok(int A, int S) { return A >= 1 && A <= SMEAR_MAX_DIM && S >= 1 && S <= SMEAR_MAX_DIM; }
 int enc3_state(const float* e2, const float* action, const float* state, const float* w3, const float* b3,
                const float* wcs, const float* bcs, float* e3, float* state_out,
-               int B, int HW8, int use_state, hipStream_t s);
+               int B, int HW8, int use_state, hipStream_t s, int A = 5, int S = 5);
 
 // 1x1 heads on enc6: mask logits (relu) and enc7 (TM:288/315-317, TM:429/454-455, TM:364/387-388, TM:718-719)
 // enc7_mode: 0 = CDNA (relu; layer0 = sigmoid), 1 = STP (no relu; layer0 = sigmoid), 2 = DNA (relu; no layer0)
@@ -377,8 +380,9 @@ int enc3_state_bwd(const float* e2, const float* e3, const float* de3, int ldd3,
                    const float* wcs, const float* dsnew, float* de2, float* dw3, float* db3, float* dwcs, float* dbcs,
                    float* dstate_prev, int B, int HW8, int use_state, hipStream_t s,
                    int mask_e2 = 0,    // 1: de2 is masked by (e2 > 0), i.e. it is the gradient in front of enc2's ReLU
-                   float* det_part = nullptr);      // det_part (enc3_state_bwd_det_floats): per-block rows + det_rows_reduce instead of atomics
-long long enc3_state_bwd_det_floats(int B, int HW8, int use_state);
+                   float* det_part = nullptr,      // det_part (enc3_state_bwd_det_floats): per-block rows + det_rows_reduce instead of atomics
+                   int A = 5, int S = 5);          // the widths, as enc3_state's: dwcs [S][A + S], dbcs [S], dsnew / dstate_prev [B][S]
+long long enc3_state_bwd_det_floats(int B, int HW8, int use_state, int A = 5, int S = 5);
 int enc0_bwd(const float* img, const float* w, const float* d, float* dw, float* db, float* dimg, int dimg_accum, int B, int H, int W,
              hipStream_t s, const SideFork* fork = nullptr,   // fork: where the weight / bias gradient kernel runs
              float* det_part = nullptr);      // det_part (enc0_bwd_det_floats): per-block rows + det_rows_reduce instead of atomics
@@ -387,7 +391,7 @@ long long enc0_bwd_det_floats(int B, int H, int W);
 int enc0_bwd_data(const float* w, const float* d, float* dimg, int dimg_accum, int B, int H, int W, hipStream_t s);
 // csrc/input_grad.hip: the action half of enc3's smeared-input gradient (include/pivp_input_grad.h, pivp_action_grad), one block per sample
 int action_grad(const float* e3, const float* de3, int ldd3, const float* w3, const float* wcs, const float* dsnew, float* dact, int B, int HW8,
-                int use_state, hipStream_t s);
+                int use_state, hipStream_t s, int A = 5, int S = 5);      // dact [B][A], dsnew [B][S], wcs [S][A + S]
 int add_strided(float* dst, int ldd, const float* src, int lds_, int C, long npix, hipStream_t s);
 
 // planar NCHW <-> NHWC helpers for taps (conv_res) and tests

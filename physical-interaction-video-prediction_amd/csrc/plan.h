@@ -40,8 +40,10 @@ struct EncSpec { int mode, layer, c, ldx, ldo, ldy, level; };
 inline const EncSpec kEnc[5] = {{1, 6, 64, 64, 64, 64, 2}, {1, 5, 96, 96, 96, 128, 4}, {1, 4, 128, 128, 128, 192, 8}, {0, 2, 64, 64, 64, 64, 4}, {0, 1, 32, 32, 96, 96, 2}};
 // parameter sizes: enc0 5x5 on 3 channels, enc3 1x1 on e2 (+ the smeared action / state), the others 3x3 with as many channels in as out
 inline const int kEncB[7] = {32, 32, 64, 64, 128, 96, 64};
+// (c: a plan's cfg, whose action_dim / state_dim pivp_plan_create has resolved to 1 .. 16)
+inline int smear_width(const pivp_config_t& c) { return c.action_dim + c.state_dim; }      // the [action, state] vector of TM:556-567
 inline long long enc_w_numel(const pivp_config_t& c, int i) {
-    return i == 0 ? 75 * 32 : i == 3 ? (64 + (c.use_state ? 10 : 0)) * 64LL : 9LL * kEncB[i] * kEncB[i];
+    return i == 0 ? 75 * 32 : i == 3 ? (64 + (c.use_state ? smear_width(c) : 0)) * 64LL : 9LL * kEncB[i] * kEncB[i];
 }
 // elements per sample of the nine LayerNorms: norm_enc0, hidden1..hidden7 (behind cell j - 1), norm_enc6
 inline long long ln_numel(const pivp_config_t& c, int j) {
@@ -140,7 +142,7 @@ struct StepForm {
     bool keep;               // a launch that applies a norm also writes the tensor and its (mean, rstd): training plans
     bool norm_inside[9];     // norm j (hidden1..hidden7; 8 = norm_enc6) is applied by its consumer -- 1, 3: lstm2 / lstm4; 2, 4: enc1 / enc2; 6, 7: enc5 / enc6;
                              // 8: heads_1x1, where Output::Separate runs.  (norm_enc0 and hidden5 keep their launches.)
-    bool enc3_in_enc2;       // enc3 + the state predictor in enc2's epilogue
+    bool enc3_in_enc2;       // enc3 + the state predictor in enc2's epilogue (its fmaf chains are written for 5 / 5: other widths take the separate launch)
     bool enc4_partials;      // enc4 shares its grid with the partial sums of the motion head's Linear
     MotionHead motion;
     Output output;
@@ -193,7 +195,7 @@ struct pivp_plan {
     pivp_grad_group_cb grad_cb = nullptr; void* grad_cb_user = nullptr;   // gradient-group-final notifications (t = 0 sweep)
     bool group_join = true;           // pivp_plan_set_group_join
     const float* frame_seed = nullptr;   // pivp_plan_set_frame_grad: an additional d loss / d gen_images[ctx-1 .. T-2] for the sweep (null: the plan's own seed alone)
-    float* in_dact = nullptr; float* in_dstate0 = nullptr;   // pivp_plan_set_input_grad: d loss / d actions [T-1][B][5] and d loss / d states[0] [B][5] (null: not wanted)
+    float* in_dact = nullptr; float* in_dstate0 = nullptr;   // pivp_plan_set_input_grad: d loss / d actions [T-1][B][A] and d loss / d states[0] [B][S] (null: not wanted)
     int sweep_mode = 3;               // pivp_plan_set_sweep_mode: PIVP_SWEEP_PARAMS | PIVP_SWEEP_BUILTIN_LOSS (include/pivp_input_grad.h)
     // pivp_plan_set_rollout_state (include/pivp_state.h): where the next rollouts read their initial (c, h) of the seven cells and leave their final ones
     // (null: zeros / nowhere), and how many leading steps pivp_rollout_predict feeds from context_images (0: cfg.context_frames)
@@ -251,7 +253,8 @@ inline StepForm step_form(const pivp_plan& p) {
     f.norm_inside[3] = !train && convlstm_ln_in_ok(md.precision, 64, 64, 64, B, p.H4, p.W4) && (long)B * (p.H4 / 8) * (p.W4 / 16) >= 64;
     f.norm_inside[2] = fold_opt && conv3x3s2_ln_ok(32, 32, B, p.H2, p.W2);      // enc1 / enc2: training plans by PIVP_OPT_LN_FOLD_TRAIN
     f.norm_inside[4] = fold_opt && conv3x3s2_ln_ok(64, 64, B, p.H4, p.W4);
-    f.enc3_in_enc2 = !train && f.norm_inside[4] && p.opt[PIVP_OPT_FUSE_ENC3] && (p.H8 * p.W8) % 32 == 0;
+    f.enc3_in_enc2 = !train && f.norm_inside[4] && p.opt[PIVP_OPT_FUSE_ENC3] && (p.H8 * p.W8) % 32 == 0 &&
+                     c.action_dim == 5 && c.state_dim == 5;
     // enc5 / enc6: only while the norm is a launch-bound 5-us kernel (<= 6 MB of hidden tensor: 64 x 64 frames at B = 32): the consumer's column blocks
     // each stage the patch and its gamma / beta again, which at config 5's 128 x 128 costs more than one bandwidth-bound ln_apply pass
     // (B = 32, T = 20: rollout 65.5 -> 65.9 ms with the fold, so it is not taken there).

@@ -352,16 +352,16 @@ int Sweep::step(const StepIn& in) {
     // group 3 (TM:598) + state predictor (TM:730): d e3 = x-part of lstm5's d_in (ld 192)
     RC(join(SLOT_ENC + 3));          // d e2
     RC(enc3_state_bwd(ws + S->e2, ws + S->e3, DIN(4, true), 192, action, state_prev, P(&p, p.i_enc_w[3]), P(&p, p.i_cs_w),
-                      ws + g.dstate + (size_t)t * B * 5, d_e2, G(&p, p.i_enc_w[3]), G(&p, p.i_enc_b[3]), G(&p, p.i_cs_w),
-                      G(&p, p.i_cs_b), t > 0 ? ws + g.dstate + (size_t)(t - 1) * B * 5 : ws + g.dstate + (size_t)(c.seq_len - 1) * B * 5,
-                      B, p.H8 * p.W8, c.use_state, s, 1, p.det ? ws + g.det_enc3 : nullptr));      // d e2 comes out masked by enc2's ReLU
+                      ws + g.dstate + (size_t)t * B * c.state_dim, d_e2, G(&p, p.i_enc_w[3]), G(&p, p.i_enc_b[3]), G(&p, p.i_cs_w),
+                      G(&p, p.i_cs_b), t > 0 ? ws + g.dstate + (size_t)(t - 1) * B * c.state_dim : ws + g.dstate + (size_t)(c.seq_len - 1) * B * c.state_dim,
+                      B, p.H8 * p.W8, c.use_state, s, 1, p.det ? ws + g.det_enc3 : nullptr, c.action_dim, c.state_dim));      // d e2 comes out masked by enc2's ReLU
     // d action[t]: the other half of the smeared-input gradient, from the tensors enc3_state_bwd has just read (it wrote d e2 and gradients only)
     if (p.in_dact)
-        RC(action_grad(ws + S->e3, DIN(4, true), 192, P(&p, p.i_enc_w[3]), P(&p, p.i_cs_w), ws + g.dstate + (size_t)t * B * 5,
-                       p.in_dact + (size_t)t * B * 5, B, p.H8 * p.W8, c.use_state, s));
+        RC(action_grad(ws + S->e3, DIN(4, true), 192, P(&p, p.i_enc_w[3]), P(&p, p.i_cs_w), ws + g.dstate + (size_t)t * B * c.state_dim,
+                       p.in_dact + (size_t)t * B * c.action_dim, B, p.H8 * p.W8, c.use_state, s, c.action_dim, c.state_dim));
     // d states[0]: the state chain ends in slot T-1 of g.dstate (this launch's d state_prev at t = 0; behind its det_rows_reduce in deterministic plans)
     if (t == 0 && p.in_dstate0 &&
-        hipMemcpyAsync(p.in_dstate0, ws + g.dstate + (size_t)(c.seq_len - 1) * B * 5, (size_t)B * 5 * 4, hipMemcpyDeviceToDevice, s) != hipSuccess)
+        hipMemcpyAsync(p.in_dstate0, ws + g.dstate + (size_t)(c.seq_len - 1) * B * c.state_dim, (size_t)B * c.state_dim * 4, hipMemcpyDeviceToDevice, s) != hipSuccess)
         return PIVP_ERR_LAUNCH;
     // group 2 (TM:597): enc2 conv (ReLU) <- hidden4 <- lstm4 <- hidden3 <- lstm3 <- enc1
     RC(encb(3, ws + S->n4, d_e2, nullptr, ws + g.n4, 0));
@@ -439,7 +439,7 @@ static int rollout_backward_sweep(pivp_plan_t* plan, const float* images, const 
     float* ws = plan->ws;
     const Grads& g = plan->g;
     const float fscale = 2.0f / ((float)fr * (float)(T - ctx));              // d/d gen of mean-squared error / (T - ctx)
-    const float sscale = 2.0f * 1e-4f / ((float)(B * 5) * (float)(T - ctx));
+    const float sscale = 2.0f * 1e-4f / ((float)(B * c.state_dim) * (float)(T - ctx));
     const Modes& md = plan->mode;
     // the lane this sweep forks its weight gradients to, decided once: none when the sweep forms no parameter gradients, the option is off or creation failed
     if (params && plan->opt[PIVP_OPT_SIDE_STREAM]) plan->lane.create();
@@ -464,11 +464,12 @@ static int rollout_backward_sweep(pivp_plan_t* plan, const float* images, const 
     if (plan->det && g.det_stp_acc &&      // STP's integer d prev accumulator starts at zero (each launch's finish clears what it used)
         hipMemsetAsync(ws + g.det_stp_acc, 0, (size_t)B * 3 * c.height * c.width * 8, s) != hipSuccess) return PIVP_ERR_LAUNCH;
     // d loss / d gen_states[t] for every t (zero before ctx-1), later accumulated with the state recurrence
-    if (hipMemsetAsync(ws + g.dstate, 0, (size_t)T * B * 5 * 4, s) != hipSuccess) return PIVP_ERR_LAUNCH;
+    if (hipMemsetAsync(ws + g.dstate, 0, (size_t)T * B * c.state_dim * 4, s) != hipSuccess) return PIVP_ERR_LAUNCH;
     // (gen_states[t] against states[t + 1], t = ctx-1 .. T-2: contiguous in t, one launch; likewise the frames' loss terms below -- 16 launches per sweep before)
     // (without the plan's own loss, pivp_plan_set_sweep_mode: the memset above is the state seed, a zero fill the frames')
     if (own_loss)
-        RC(scaled_diff(gen_states + (size_t)(ctx - 1) * B * 5, states + (size_t)ctx * B * 5, ws + g.dstate + (size_t)(ctx - 1) * B * 5, (long)(T - ctx) * B * 5, sscale, 0, s));
+        RC(scaled_diff(gen_states + (size_t)(ctx - 1) * B * c.state_dim, states + (size_t)ctx * B * c.state_dim, ws + g.dstate + (size_t)(ctx - 1) * B * c.state_dim,
+                       (long)(T - ctx) * B * c.state_dim, sscale, 0, s));
     // d loss / d gen[t], t = ctx-1 .. T-2 (gen[t] is compared with images[t + 1]); the sweep adds the feed-back terms of step t + 1 into frame t in place
     if (own_loss)
         RC(scaled_diff(gen_images + (size_t)(ctx - 1) * fr, images + (size_t)ctx * fr, ws + g.go + (size_t)(ctx - 1) * fr, (long)(T - ctx) * (long)fr, fscale, 0, s));
@@ -514,13 +515,13 @@ static int rollout_backward_sweep(pivp_plan_t* plan, const float* images, const 
         // d gen[t-1] holds its loss term (if it has one: t - 1 >= ctx - 1, which prev_has_grad implies); this step's composite / enc0 backward add the feed-back term
         const bool next_loss = (t - 1) >= ctx - 1 && t >= 1;
         const float* prev = step_input(plan, t, images, gt_select, gen_images, fr);
-        const float* st_prev = t == 0 ? states : gen_states + (size_t)(t - 1) * B * 5;
+        const float* st_prev = t == 0 ? states : gen_states + (size_t)(t - 1) * B * c.state_dim;
         // the ConvLSTM weight gradients: batches of wg_batch timesteps (sweep_schedule.h)
         const BatchSlot wg = batch_slot(T, t, sweep.wg_batch);
         // (1 / 2 / 4 timesteps per launch instead of the rings' 8, r05_c23: config 3 11.63 / 11.24 / 11.22 ms against 11.10, fp32 train 28.08 / 27.90 / 27.67 against 27.41)
         const BatchSlot eg = batch_slot(T, t, plan->eg_cap);      // the stride-2 3x3 layers' weight gradients: as many timesteps per launch as their rings hold, every mode
         const StepSlots ss{wg.batch & 1, wg.slot, wg.flush, eg.batch & 1, eg.slot, eg.flush, eq_next};
-        RC(sweep.step(StepIn{t, prev, prev_has_grad && has_go, actions + (size_t)t * B * 5, st_prev, has_go, go, go_prev, last_step, ss}));
+        RC(sweep.step(StepIn{t, prev, prev_has_grad && has_go, actions + (size_t)t * B * c.action_dim, st_prev, has_go, go, go_prev, last_step, ss}));
         eq_next = ss.eg_ring * plan->eg_cap + ss.eg_slot;
         has_go = next_loss || (prev_has_grad && has_go);
     }

@@ -146,7 +146,7 @@ int Rollout::bottleneck(const StepIn& in) {
     // group 3 (TM:598) + state predictor (TM:730)
     if (!enc3_done)
         RC(enc3_state(ws + S->e2, in.action, in.state_prev, P(&p, p.i_enc_w[3]), P(&p, p.i_enc_b[3]), P(&p, p.i_cs_w), P(&p, p.i_cs_b),
-                      ws + S->e3, in.state_out, B, p.H8 * p.W8, c.use_state, s));
+                      ws + S->e3, in.state_out, B, p.H8 * p.W8, c.use_state, s, c.action_dim, c.state_dim));
     // group 4 (TM:599)
     RC(lstm(4, ws + S->e3, 64));
     // (hidden5's norm was folded the same way into enc4's four-phase form and the motion head's Linear, which then has to run here, in front
@@ -280,8 +280,9 @@ struct RolloutIo { const float* images; const float* actions; const float* state
 
 // what step t reads and writes: the frame fed to it (step_input), its action, the state in front of it (TM:646, TM:730) and where its outputs go
 StepIn step_in(const pivp_plan& p, const RolloutIo& io, int t, int ctx) {
-    const size_t fr = (size_t)p.cfg.batch * 3 * p.cfg.height * p.cfg.width, st = (size_t)p.cfg.batch * 5;
-    return StepIn{t, step_input(&p, t, io.images, io.gt_select, io.gen_images, fr, ctx), io.actions + t * st,
+    const size_t fr = (size_t)p.cfg.batch * 3 * p.cfg.height * p.cfg.width;
+    const size_t ac = (size_t)p.cfg.batch * p.cfg.action_dim, st = (size_t)p.cfg.batch * p.cfg.state_dim;
+    return StepIn{t, step_input(&p, t, io.images, io.gt_select, io.gen_images, fr, ctx), io.actions + t * ac,
                   t == 0 ? io.states : io.gen_states + (t - 1) * st, io.gen_images + t * fr, io.gen_states + t * st};
 }
 
@@ -378,8 +379,8 @@ extern "C" int pivp_rollout_forward(pivp_plan_t* plan, const float* images, cons
                 RC(frame_sqerr_partials(images + (size_t)(ctx + i) * fr, gen_images + (size_t)(ctx - 1 + i) * fr,
                                         lp + (size_t)i * plan->loss_nparts, (int)fr, s));
         }
-        return loss_finalize(lp, plan->loss_nparts, nf, (int)fr, states + (size_t)ctx * B * 5, gen_states + (size_t)(ctx - 1) * B * 5,
-                             B * 5, (float)(T - ctx), results, s);
+        return loss_finalize(lp, plan->loss_nparts, nf, (int)fr, states + (size_t)ctx * B * c.state_dim, gen_states + (size_t)(ctx - 1) * B * c.state_dim,
+                             B * c.state_dim, (float)(T - ctx), results, s);
     });
 }
 

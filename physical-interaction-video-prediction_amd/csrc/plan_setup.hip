@@ -111,14 +111,14 @@ void pivp::plan_layout(pivp_plan* p) {
             }
             g.det_heads = carve((size_t)heads_bwd_det_floats(B, (int)HW, p->NP, p->NE));
             g.det_dv = carve((size_t)B * 256);
-            g.det_enc3 = carve((size_t)enc3_state_bwd_det_floats(B, (int)HW8, cfg->use_state));
+            g.det_enc3 = carve((size_t)enc3_state_bwd_det_floats(B, (int)HW8, cfg->use_state, cfg->action_dim, cfg->state_dim));
             g.det_enc0 = carve((size_t)enc0_bwd_det_floats(B, H, W));
             if (cfg->model_type == PIVP_MODEL_STP) { g.det_stp = carve((size_t)B * 706); g.det_stp_acc = carve((size_t)B * 3 * HW * 2); }   // (64-bit integers)
         }
         g.go = carve((size_t)(T - 1) * B * 3 * HW);
         g.dmk = carve((size_t)B * p->NP * HW); g.dz = carve((size_t)B * p->NE * HW);
         g.dkpart = carve((size_t)B * composite_bwd_tiles(H, W) * 256);
-        g.dstate = carve((size_t)T * B * 5);
+        g.dstate = carve((size_t)T * B * cfg->state_dim);
         g.lnpart = carve((size_t)B * ln_bwd_slices((int)(64 * HW)) * 2);
         g.ln_ppart_floats = 0;
         for (int j = 0; j < 9; ++j) {
@@ -146,8 +146,13 @@ extern "C" int pivp_plan_create(const pivp_config_t* cfg, pivp_plan_t** out) {
     if (cfg->model_type == PIVP_MODEL_DNA && cfg->num_masks != 1) return PIVP_ERR_BADARG;  // TM:389-390
     if (cfg->context_frames < 1 || cfg->context_frames >= cfg->seq_len) return PIVP_ERR_BADARG;
     if (!plan_serves_forward(*cfg)) return PIVP_ERR_BADARG;      // a frame or mask count a kernel of the rollout would refuse: refused here, not at that launch
+    // the widths of an action and of a robot state: 0 = the reference data's 5; the enc3 / state-predictor kernels hold both in 32 floats of LDS
+    if (cfg->action_dim < 0 || cfg->action_dim > 16 || cfg->state_dim < 0 || cfg->state_dim > 16) return PIVP_ERR_BADARG;
     pivp_plan* p = new pivp_plan();
     p->cfg = *cfg;
+    if (!p->cfg.action_dim) p->cfg.action_dim = 5;
+    if (!p->cfg.state_dim) p->cfg.state_dim = 5;
+    cfg = &p->cfg;      // (from here on the resolved widths)
     const int H = cfg->height, W = cfg->width;
     p->H2 = H / 2; p->W2 = W / 2; p->H4 = H / 4; p->W4 = W / 4; p->H8 = H / 8; p->W8 = W / 8;
     p->NP = cfg->num_masks + 1;
@@ -172,8 +177,8 @@ extern "C" int pivp_plan_create(const pivp_config_t* cfg, pivp_plan_t** out) {
     }
     p->i_masks_w = add("masks/W", 64LL * p->NP);
     p->i_masks_b = add("masks/b", p->NP);
-    p->i_cs_w = add("current_state/W", 50);
-    p->i_cs_b = add("current_state/b", 5);
+    p->i_cs_w = add("current_state/W", (long long)cfg->state_dim * smear_width(*cfg));
+    p->i_cs_b = add("current_state/b", cfg->state_dim);
     p->i_enc7_w = add("model/enc7/W", 64LL * p->NE);
     p->i_enc7_b = add("model/enc7/b", p->NE);
     p->i_head_w = p->i_head_b = p->i_head2_w = p->i_head2_b = -1;

@@ -272,20 +272,24 @@ int ln_apply(const float* x, const float* partials, const float* gamma, const fl
 // Group 3 of the op program (TM:598): smear(state_action) -> concat -> 1x1 conv (74 -> 64) -> ReLU.
 // Algebraically the tiled 10-vector only adds a per-sample bias W[:,64:74].sa, so nothing is
 // tiled or concatenated.  The same launch evaluates current_state = Linear(state_action) (TM:730).
-// e2/e3 NHWC [B][HW8][64]; w3 [64 (+10)][64] K-major; wcs reference layout (5,10).
+// e2/e3 NHWC [B][HW8][64]; w3 [64 (+ A + S)][64] K-major; wcs reference layout (S, A + S): (5, 10) on the reference's data.
+// <AT, ST>: the widths as constants (the reference's <5, 5>: its loops unroll as they always did), or <0, 0>: a_rt / s_rt, 1 .. SMEAR_MAX_DIM each.
+// Either way the fmaf order is: bias, the smear terms with the action's first and j ascending, then k ascending.
 // ------------------------------------------------------------------------------------------
+template <int AT, int ST>
 __global__ __launch_bounds__(256) void enc3_state_kernel(const float* __restrict__ e2, const float* __restrict__ action,
                                                          const float* __restrict__ state, const float* __restrict__ w3,
                                                          const float* __restrict__ b3, const float* __restrict__ wcs,
                                                          const float* __restrict__ bcs, float* __restrict__ e3,
-                                                         float* __restrict__ state_out, int HW8, int use_state) {
+                                                         float* __restrict__ state_out, int HW8, int use_state, int a_rt, int s_rt) {
     __shared__ float xt[64 * 65];
     __shared__ __attribute__((aligned(16))) float wl[64 * 64];
     __shared__ float sb[64];
-    __shared__ float sa[10];
+    __shared__ float sa[AT ? AT + ST : 2 * SMEAR_MAX_DIM];
+    const int A = AT ? AT : a_rt, S = ST ? ST : s_rt, AS = A + S;
     const int b = blockIdx.y, tile = blockIdx.x, tid = threadIdx.x;
-    if (tid < 5) sa[tid] = action[b * 5 + tid];
-    else if (tid < 10) sa[tid] = state[b * 5 + tid - 5];
+    if (tid < A) sa[tid] = action[b * A + tid];
+    else if (tid < AS) sa[tid] = state[b * S + tid - A];
     const int npx = min(64, HW8 - tile * 64);
     const float* src = e2 + ((size_t)b * HW8 + tile * 64) * 64;
     {   // all eight 16-B loads of a thread are issued before the first LDS store (one round trip, not thirty-two)
@@ -308,16 +312,16 @@ __global__ __launch_bounds__(256) void enc3_state_kernel(const float* __restrict
         float v = b3[tid];
         if (use_state) {
 #pragma unroll
-            for (int j = 0; j < 10; ++j) v = fmaf(sa[j], w3[(64 + j) * 64 + tid], v);
+            for (int j = 0; j < AS; ++j) v = fmaf(sa[j], w3[(64 + j) * 64 + tid], v);
         }
         sb[tid] = v;
     }
-    if (tile == 0 && tid >= 64 && tid < 69) {
+    if (tile == 0 && tid >= 64 && tid < 64 + S) {
         const int o = tid - 64;
         float v = bcs[o];
 #pragma unroll
-        for (int j = 0; j < 10; ++j) v = fmaf(wcs[o * 10 + j], sa[j], v);
-        state_out[b * 5 + o] = v;
+        for (int j = 0; j < AS; ++j) v = fmaf(wcs[o * AS + j], sa[j], v);
+        state_out[b * S + o] = v;
     }
     __syncthreads();
     const int p = tid >> 2, cg = tid & 3;
@@ -345,10 +349,14 @@ __global__ __launch_bounds__(256) void enc3_state_kernel(const float* __restrict
 
 int enc3_state(const float* e2, const float* action, const float* state, const float* w3, const float* b3,
                const float* wcs, const float* bcs, float* e3, float* state_out,
-               int B, int HW8, int use_state, hipStream_t s) {
-    PIVP_CHECK_ARG(e2 && action && state && w3 && b3 && wcs && bcs && e3 && state_out && B > 0 && HW8 > 0);
-    hipLaunchKernelGGL(enc3_state_kernel, dim3((HW8 + 63) / 64, B), dim3(256), 0, s,
-                       e2, action, state, w3, b3, wcs, bcs, e3, state_out, HW8, use_state);
+               int B, int HW8, int use_state, hipStream_t s, int A, int S) {
+    PIVP_CHECK_ARG(e2 && action && state && w3 && b3 && wcs && bcs && e3 && state_out && B > 0 && HW8 > 0 && smear_dims_ok(A, S));
+    if (A == 5 && S == 5)
+        hipLaunchKernelGGL((enc3_state_kernel<5, 5>), dim3((HW8 + 63) / 64, B), dim3(256), 0, s,
+                           e2, action, state, w3, b3, wcs, bcs, e3, state_out, HW8, use_state, A, S);
+    else
+        hipLaunchKernelGGL((enc3_state_kernel<0, 0>), dim3((HW8 + 63) / 64, B), dim3(256), 0, s,
+                           e2, action, state, w3, b3, wcs, bcs, e3, state_out, HW8, use_state, A, S);
     return PIVP_LAUNCH_STATUS();
 }
 

@@ -36,7 +36,8 @@ def write_map(data_dir, rows):
 
 
 def load_dataset(data_dir):
-    """train_model.py:826-834: every sequence into RAM as float32: images (N,T,H,W,3), actions (N,T,5), states (N,T,5)."""
+    """train_model.py:826-834: every sequence into RAM as float32: images (N,T,H,W,3), actions (N,T,A), states (N,T,S) -- whatever widths
+    the files hold (5 / 5 in the push data set)."""
     rows = read_map(data_dir)
     images = np.asarray([np.float32(np.load(os.path.join(data_dir, r[2]))) for r in rows], dtype=np.float32)
     actions = np.asarray([np.float32(np.load(os.path.join(data_dir, r[3]))) for r in rows], dtype=np.float32)
@@ -291,6 +292,17 @@ def check_indices(indices, N):
     return np.ascontiguousarray(idx, dtype=np.int32)
 
 
+DEVICE_WIDTH = 5      # pivp_gather_batch copies five columns of an action and of a state (include/pivp_data.h)
+
+
+def check_device_widths(action_dim, state_dim):
+    """The device-resident feed serves the reference data's widths alone; every other width goes through the host feed (`load_dataset`,
+    `concat_examples`, `DeviceFeeder`), which serves any."""
+    if (action_dim, state_dim) != (DEVICE_WIDTH, DEVICE_WIDTH):
+        raise ValueError('a DeviceDataset holds actions and states of width 5 (the on-device gather copies five columns), got action_dim=%s, '
+                         'state_dim=%s: use the host feed for other widths' % (action_dim, state_dim))
+
+
 def check_set_shapes(images_shape, actions_shape, states_shape):
     """-> (N, T, H, W) of a data set with images (N,T,H,W,3), actions (N,T,5), states (N,T,5); ValueError otherwise."""
     if len(images_shape) != 5 or images_shape[4] != 3 or min(images_shape) < 1:
@@ -326,7 +338,10 @@ class DeviceDataset(object):
     with the device after the upload; there is no CPU path."""
 
     def __init__(self, images, actions, states, device='cuda:0', storage='auto', chunk=256):
-        shape = check_set_shapes(np.shape(images), np.shape(actions), np.shape(states))
+        sa, ss = np.shape(actions), np.shape(states)
+        if len(sa) == 3 and len(ss) == 3:      # (anything else: check_set_shapes' complaint)
+            check_device_widths(sa[2], ss[2])
+        shape = check_set_shapes(np.shape(images), sa, ss)
         self._begin(shape, device, storage)
         for lo in range(0, self.N, chunk):
             self._put(lo, images[lo:lo + chunk], actions[lo:lo + chunk], states[lo:lo + chunk])
@@ -348,6 +363,8 @@ class DeviceDataset(object):
         for lo in range(0, self.N, chunk):
             part = rows[lo:lo + chunk]
             arrays = [np.stack([load(r, col) for r in part]) for col in cols]
+            if arrays[1].ndim == 3 and arrays[2].ndim == 3:
+                check_device_widths(arrays[1].shape[2], arrays[2].shape[2])
             check_set_shapes((self.N,) + arrays[0].shape[1:], (self.N,) + arrays[1].shape[1:], (self.N,) + arrays[2].shape[1:])
             if arrays[0].shape[1:] != (self.T, self.H, self.W, 3):
                 raise ValueError('sequences %d.. have frames %s, the first one %s' % (lo, arrays[0].shape[1:], (self.T, self.H, self.W, 3)))

@@ -33,6 +33,9 @@ def build_parser():
     p.add_argument('--context_frames', type=int, default=2)
     p.add_argument('--use_state', type=int, default=1)
     p.add_argument('--num_masks', type=int, default=10)
+    # the widths of an action and of a robot state in the data (the push data set's 5 / 5; BAIR pushing 4 / 3, RoboNet 4 / 5): Model(action_dim=, state_dim=)
+    p.add_argument('--action_dim', type=int, default=5)
+    p.add_argument('--state_dim', type=int, default=5)
     p.add_argument('--image_height', type=int, default=64)
     p.add_argument('--image_width', type=int, default=64)
     p.add_argument('--gpu', type=int, default=0)
@@ -87,11 +90,12 @@ def evaluate(args):
     device = 'cuda:%d' % args.gpu
     model = Model(num_masks=args.num_masks, is_cdna=model_type == 'CDNA', is_dna=model_type == 'DNA', is_stp=model_type == 'STP',
                   use_state=args.use_state, scheduled_sampling_k=args.schedsamp_k, num_frame_before_prediction=args.context_frames,
-                  prefix='evaluate', device=device)
+                  prefix='evaluate', device=device, action_dim=args.action_dim, state_dim=args.state_dim)
     load_npz(os.path.join(path, args.model_name), model)
     curves = StepCurves()
     size = (args.image_height, args.image_width)
     if args.device_dataset:
+        ds.check_device_widths(args.action_dim, args.state_dim)
         from . import _lib
         lib = _lib.load()
         dset = ds.DeviceDataset.from_dir(args.data_dir, device, storage=args.device_storage, raw=True)

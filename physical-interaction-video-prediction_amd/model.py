@@ -50,14 +50,26 @@ LSTM_SIZES = OrderedDict(lstm1=(32, 32), lstm2=(32, 32), lstm3=(32, 64), lstm4=(
                          lstm5=(64, 128), lstm6=(128, 64), lstm7=(96, 32))   # name -> (x channels, C); TM:509-515
 
 
-def reference_param_shapes(num_masks, model_type, use_state, height, width):
-    """Key -> shape in the reference's Chainer npz layout (TM:499-542)."""
+MAX_INPUT_DIM = 16      # include/pivp_hip.h, the accepted domain: action_dim, state_dim 1 .. 16
+
+
+def check_input_dim(name, value):
+    """The width of an action or of a robot state: an integer 1 .. 16 (a bool, a float or a string is not one)."""
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not 1 <= value <= MAX_INPUT_DIM:
+        raise ValueError('%s must be an integer 1 .. %d, not %r' % (name, MAX_INPUT_DIM, value))
+    return int(value)
+
+
+def reference_param_shapes(num_masks, model_type, use_state, height, width, action_dim=5, state_dim=5):
+    """Key -> shape in the reference's Chainer npz layout (TM:499-542).  action_dim / state_dim: the widths of an action and of a
+    robot state (5 / 5 in the reference's data): enc3's input is sized by the data (TM:503), the state predictor is L.Linear(state_dim) (TM:529)."""
+    smear = action_dim + state_dim
     h2, w2, h4, w4, h8, w8 = height // 2, width // 2, height // 4, width // 4, height // 8, width // 8
     s = OrderedDict()
     s['enc0/W'] = (32, 3, 5, 5); s['enc0/b'] = (32,)
     s['enc1/W'] = (32, 32, 3, 3); s['enc1/b'] = (32,)
     s['enc2/W'] = (64, 64, 3, 3); s['enc2/b'] = (64,)
-    s['enc3/W'] = (64, 64 + (10 if use_state else 0), 1, 1); s['enc3/b'] = (64,)
+    s['enc3/W'] = (64, 64 + (smear if use_state else 0), 1, 1); s['enc3/b'] = (64,)
     s['enc4/W'] = (128, 128, 3, 3); s['enc4/b'] = (128,)
     s['enc5/W'] = (96, 96, 3, 3); s['enc5/b'] = (96,)
     s['enc6/W'] = (64, 64, 3, 3); s['enc6/b'] = (64,)
@@ -71,7 +83,7 @@ def reference_param_shapes(num_masks, model_type, use_state, height, width):
         s[name + '/norm/gamma'] = (n,)
         s[name + '/norm/beta'] = (n,)
     s['masks/W'] = (64, num_masks + 1, 1, 1); s['masks/b'] = (num_masks + 1,)
-    s['current_state/W'] = (5, 10); s['current_state/b'] = (5,)
+    s['current_state/W'] = (state_dim, smear); s['current_state/b'] = (state_dim,)
     if model_type == 'CDNA':
         s['model/enc7/W'] = (64, 3, 1, 1); s['model/enc7/b'] = (3,)
         s['model/cdna_kerns/W'] = (25 * num_masks, 128 * h8 * w8); s['model/cdna_kerns/b'] = (25 * num_masks,)
@@ -198,14 +210,23 @@ class Model(object):
     state as a constant -- truncated back-propagation through time across calls (include/pivp_state_grad.h).  `backward(initial_state_grad=True)`
     also leaves d loss / d (that state) in `model.initial_state_grad`, and `backward(final_state_grad=rs)` seeds the sweep with d (a later loss) /
     d (the state the call left): chained over consecutive windows that is the exact gradient in the memory of one window
-    (`pivp_amd.chunked_backward`).  The model then alternates two state buffers instead of advancing one in place -- same frames, same states."""
+    (`pivp_amd.chunked_backward`).  The model then alternates two state buffers instead of advancing one in place -- same frames, same states.
+
+    action_dim, state_dim (integers 1 .. 16, default 5 / 5, the reference's push data): the widths of an action and of a robot state.  The reference
+    reads them off its data (enc3's input is sized lazily, TM:503; only L.Linear(5), TM:529, pins the state); here they are explicit: actions are
+    (T, B, action_dim), states (T, B, state_dim), enc3/W (64, 64 + action_dim + state_dim, 1, 1), current_state/W (state_dim, action_dim + state_dim),
+    and a call with other widths raises ValueError.  `planning.cem_plan` / `cem_refine` / `MPC` and `DeviceDataset` serve 5 / 5 alone."""
 
     DETERMINISTIC_PRECISIONS = ('fp32', 'bf16', 'bf16x3')
 
     def __init__(self, num_masks, is_cdna=True, is_dna=False, is_stp=False, use_state=True,
                  scheduled_sampling_k=-1, num_frame_before_prediction=2, prefix=None,
                  device='cuda:0', ln_eps=1e-6, stp_border='clamp', keep_activations=False, precision='fp32', main_priority=None,
-                 deterministic=False, image_loss=None, plan_options=None, state_backward=False, carry_state=False):
+                 deterministic=False, image_loss=None, plan_options=None, state_backward=False, action_dim=5, state_dim=5,
+                 carry_state=False):
+        # the widths of an action and of a robot state (the reference's data: 5 / 5); explicit, not sized by the first batch (TM:503 sizes enc3 lazily)
+        self.action_dim = check_input_dim('action_dim', action_dim)
+        self.state_dim = check_input_dim('state_dim', state_dim)
         if is_cdna:                      # TM:531-542, precedence cdna > stp > dna
             self.model_type = 'CDNA'
         elif is_stp:
@@ -258,8 +279,8 @@ class Model(object):
         self.loss_terms = None         # with an image loss: device scalars mse / l1 / gdl / dssim (means over the scored frames) and extra (their weighted sum
                                        # beyond the reference's loss) of the last call
         self._loss_grad = None         # ... and d extra / d gen_images[ctx-1:], when the call kept what backward() needs
-        self.action_grad = None        # backward(input_grad=True): d loss / d actions[:T-1] (T-1, B, 5) and ...
-        self.state_grad = None         # ... d loss / d states[0] (B, 5), device tensors
+        self.action_grad = None        # backward(input_grad=True): d loss / d actions[:T-1] (T-1, B, action_dim) and ...
+        self.state_grad = None         # ... d loss / d states[0] (B, state_dim), device tensors
         if not isinstance(carry_state, bool):
             raise ValueError('carry_state must be a bool, not %r' % (carry_state,))
         self.carry_state = carry_state
@@ -302,7 +323,7 @@ class Model(object):
     # ---- parameters ---------------------------------------------------------------------
     def _shapes(self):
         H, W = self._hw
-        return reference_param_shapes(self.num_masks, self.model_type, self.use_state, H, W)
+        return reference_param_shapes(self.num_masks, self.model_type, self.use_state, H, W, self.action_dim, self.state_dim)
 
     def _require_gpu(self):
         if not torch.cuda.is_available():
@@ -434,7 +455,8 @@ class Model(object):
                                   use_state=1 if self.use_state else 0,
                                   context_frames=ctx,
                                   keep_activations=1 if keep else 0,
-                                  ln_eps=self.ln_eps, stp_zero_border=1 if self.stp_border == 'zeros' else 0)
+                                  ln_eps=self.ln_eps, stp_zero_border=1 if self.stp_border == 'zeros' else 0,
+                                  action_dim=self.action_dim, state_dim=self.state_dim)
             plan = _Plan(lib, cfg)      # the door: a configuration the kernels do not serve is refused here (PIVP_ERR_BADARG), before a parameter is laid out
             self._ensure_params(H, W)
             for name, value in resolve_plan_options(self.plan_options).items():
@@ -565,14 +587,14 @@ class Model(object):
             self.device = torch.device('cuda:%d' % device if isinstance(device, int) else device)
         return self
 
-    def _as_device(self, a, shape_tail):
+    def _as_device(self, a, shape_tail, what=None):
         if isinstance(a, (list, tuple)):
             a = torch.stack([x if torch.is_tensor(x) else torch.from_numpy(np.asarray(x, dtype=np.float32)) for x in a])
         elif not torch.is_tensor(a):
             a = torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float32)))
         a = a.to(device=self.device, dtype=torch.float32).contiguous()
         if tuple(a.shape[-len(shape_tail):]) != tuple(shape_tail) and shape_tail:
-            raise ValueError('unexpected trailing shape %s' % (tuple(a.shape),))
+            raise ValueError('unexpected trailing shape %s%s' % (tuple(a.shape), ': %s' % what if what else ''))
         return a
 
     def _sync_packs(self, plan):
@@ -596,7 +618,7 @@ class Model(object):
         self._loss_grad = None
 
     def __call__(self, x, iter_num=-1.0):
-        """TM:620-764.  x = [images (T,B,3,H,W), actions (T,B,5), states (T,B,5)], time-major."""
+        """TM:620-764.  x = [images (T,B,3,H,W), actions (T,B,action_dim), states (T,B,state_dim)], time-major (5 / 5 unless the model was built otherwise)."""
         if len(x) > 1:
             images, actions, states = x
         else:
@@ -614,8 +636,8 @@ class Model(object):
             if images.dim() != 5 or images.shape[2] != 3:
                 raise ValueError('images must be time-major (T, B, 3, H, W)')
             T, B, _, H, W = images.shape
-            actions = self._as_device(actions, (5,))
-            states = self._as_device(states, (5,))
+            actions = self._as_device(actions, (self.action_dim,), 'actions must be (T, B, %d), the model\'s action_dim' % self.action_dim)
+            states = self._as_device(states, (self.state_dim,), 'states must be (T, B, %d), the model\'s state_dim' % self.state_dim)
             plan = self._plan_for(B, T, H, W)
             self._active = plan
             ctx = self.num_frame_before_prediction
@@ -627,7 +649,7 @@ class Model(object):
                 self._gt_mask = torch.from_numpy(mask).to(self.device)
                 gt_ptr = self._gt_mask.data_ptr()
             gen = torch.empty((T - 1, B, 3, H, W), dtype=torch.float32, device=self.device)
-            gen_states = torch.empty((T - 1, B, 5), dtype=torch.float32, device=self.device)
+            gen_states = torch.empty((T - 1, B, self.state_dim), dtype=torch.float32, device=self.device)
             nf = T - ctx
             results = torch.empty(2 + 3 * nf, dtype=torch.float32, device=self.device)
             self._sync_packs(plan)
@@ -715,12 +737,13 @@ class Model(object):
         if B < 1 or H < 1 or W < 1:
             raise ValueError('context_images is empty: shape %s' % (si,))
         self._check_carried_shape(B, H, W)
-        if len(sa) != 3 or sa[1] != B or sa[2] != 5:
-            raise ValueError('actions must be (T-1, %d, 5), got shape %s' % (B, sa))
+        A, S = self.action_dim, self.state_dim
+        if len(sa) != 3 or sa[1] != B or sa[2] != A:
+            raise ValueError('actions must be (T-1, %d, %d) for a model with action_dim=%d, got shape %s' % (B, A, A, sa))
         if sa[0] < ctx:
             raise ValueError('actions cover %d steps; at least the %d context steps are needed (T - 1 >= ctx)' % (sa[0], ctx))
-        if ss != (B, 5):
-            raise ValueError('state must be (%d, 5): the robot state of frame 0, got shape %s' % (B, ss))
+        if ss != (B, S):
+            raise ValueError('state must be (%d, %d) for a model with state_dim=%d: the robot state of frame 0, got shape %s' % (B, S, S, ss))
         T = sa[0] + 1
         P, f = 0, ctx - 1
         if designated is None:
@@ -743,7 +766,7 @@ class Model(object):
 
     def imagine(self, context_images, actions, state, designated=None, designated_frame=None, normalize=False, observed=None, advance=True):
         """Open-loop prediction for planning: roll the model forward from `context_images` (ctx, B, 3, H, W) -- the observed frames --, the robot
-        `state` (B, 5) of frame 0 and candidate `actions` (T-1, B, 5), feeding its own predictions back after the context.  No ground truth beyond
+        `state` (B, state_dim) of frame 0 and candidate `actions` (T-1, B, action_dim), feeding its own predictions back after the context.  No ground truth beyond
         the context, no loss: `loss` / `psnr_all` are left alone, `summaries` is [] and `backward()` raises until the model is called again.  Always
         feed-self (ignores config.train and scheduled sampling) and always on an inference plan.  Sets `gen_images` / `gen_states` as `__call__`
         does and returns the frames as one tensor (T-1, B, 3, H, W): bit-identical to a feed-self `__call__` on the same context.
@@ -769,8 +792,8 @@ class Model(object):
         with torch.cuda.device(self.device) if torch.cuda.is_available() else contextlib.nullcontext():
             self._require_gpu()
             images = self._as_device(context_images, ())
-            actions = self._as_device(actions, (5,))
-            state = self._as_device(state, (5,))
+            actions = self._as_device(actions, (self.action_dim,))
+            state = self._as_device(state, (self.state_dim,))
             planes = self._as_device(designated, ()) if P else None
             gen, track = self._rollout_predict(images, actions, state, planes, f, observed=observed, advance=advance)
             if P:
@@ -789,7 +812,7 @@ class Model(object):
         plan = self._plan_for(B, T, H, W, keep_activations=False, observed=observed)
         self._active = plan
         gen = torch.empty((T - 1, B, 3, H, W), dtype=torch.float32, device=self.device)
-        gen_states = torch.empty((T - 1, B, 5), dtype=torch.float32, device=self.device)
+        gen_states = torch.empty((T - 1, B, self.state_dim), dtype=torch.float32, device=self.device)
         track = torch.empty((T - 1 - f, B, P, H, W), dtype=torch.float32, device=self.device) if P else None
         self._sync_packs(plan)
         with self._carried(plan, B, H, W, advance=advance, observed=observed or 0):
@@ -864,8 +887,8 @@ class Model(object):
         gradient group i (slice grad_group_ranges()[i]) has been enqueued on the model's stream -- the hook the
         data-parallel all-reduce uses to overlap communication with the rest of the sweep.
 
-        input_grad=True: the sweep also leaves d loss / d actions[:T-1] in `model.action_grad` (T-1, B, 5) and d loss / d states[0] in
-        `model.state_grad` (B, 5), float32 tensors on the model's device (pivp_plan_set_input_grad, include/pivp_input_grad.h).  They are overwritten, not
+        input_grad=True: the sweep also leaves d loss / d actions[:T-1] in `model.action_grad` (T-1, B, action_dim) and d loss / d states[0] in
+        `model.state_grad` (B, state_dim), float32 tensors on the model's device (pivp_plan_set_input_grad, include/pivp_input_grad.h).  They are overwritten, not
         accumulated; the buffers are reused by the next such call of the same shape, and nothing synchronises.
         params=False: the sweep skips every launch that only forms parameter gradients (pivp_plan_set_sweep_mode) -- for callers who want the input
         gradients alone.  `_flat_grads` then holds unspecified values: `cleargrads()` before the next full sweep.  `on_group` must be None.
@@ -917,10 +940,10 @@ class Model(object):
             _lib.check(plan.lib.pivp_plan_set_grad_callback(plan.h, ctypes.cast(cb, ctypes.c_void_p), None), 'pivp_plan_set_grad_callback')
         mode = (_lib.SWEEP_PARAMS if params else 0) | (_lib.SWEEP_BUILTIN_LOSS if builtin_loss else 0)
         if input_grad:
-            shape = (images.shape[0] - 1, images.shape[1], 5)
+            shape = (images.shape[0] - 1, images.shape[1], self.action_dim)
             if self.action_grad is None or tuple(self.action_grad.shape) != shape or self.action_grad.device != images.device:
                 self.action_grad = torch.empty(shape, dtype=torch.float32, device=images.device)
-                self.state_grad = torch.empty(shape[1:], dtype=torch.float32, device=images.device)
+                self.state_grad = torch.empty((shape[1], self.state_dim), dtype=torch.float32, device=images.device)
         state_dst = self._state_grad_buffer(final_state_grad) if initial_state_grad else None
         try:
             # the model's device must be the CURRENT one for the launches (and for the plan's own side stream, created on first use)

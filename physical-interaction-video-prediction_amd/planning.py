@@ -138,11 +138,11 @@ def score_actions(model, context_images, state, candidates, designated_rc, goal_
     """Cost of K candidate action sequences for moving one designated pixel to a goal.
 
     belief: a batch-1 `RecurrentState` (carry_state=True models).  context_images is then (1, 1, 3, H, W), the newest frame only; `state` its robot
-    state; candidates (K, horizon, 5).  The belief is expanded to K and every candidate runs `horizon` steps from it (`imagine(observed=1,
+    state; candidates (K, horizon, action_dim).  The belief is expanded to K and every candidate runs `horizon` steps from it (`imagine(observed=1,
     advance=False)`); the model's own carried state is what it was afterwards.  None: the path below, with the bits it always had.
 
-    context_images (ctx, 1, 3, H, W), state (1, 5): what the robot sees now; candidates (K, T-1, 5); designated_rc, goal_rc: (row, col) on the
-    last context frame.  The context is replicated K times and ONE `imagine` runs at batch K with normalised distributions; the cost of
+    context_images (ctx, 1, 3, H, W), state (1, state_dim): what the robot sees now; candidates (K, T-1, action_dim) -- the model's widths, 5 / 5
+    unless it was built otherwise; designated_rc, goal_rc: (row, col) on the last context frame.  The context is replicated K times and ONE `imagine` runs at batch K with normalised distributions; the cost of
     candidate k is the sum over the predicted frames of `expected_distance` to the goal.  -> (K,) tensor on the model's device.
 
     goal_image: a `GoalImageCost` or a bare (3, H, W) array (its defaults): `goal_image_cost` of the predicted frames -- the cost `cem_plan(goal_image=)`
@@ -154,10 +154,11 @@ def score_actions(model, context_images, state, candidates, designated_rc, goal_
     if belief is not None:
         _check_belief(model, belief, ctx_shape)
     cand_shape = Model._host_shape(candidates)
-    if len(cand_shape) != 3 or cand_shape[2] != 5 or cand_shape[0] < 1:
-        raise ValueError('candidates must be (K, T-1, 5), got shape %s' % (cand_shape,))
-    if Model._host_shape(state) != (1, 5):
-        raise ValueError('state must be (1, 5), got shape %s' % (Model._host_shape(state),))
+    A, S = _widths(model)
+    if len(cand_shape) != 3 or cand_shape[2] != A or cand_shape[0] < 1:
+        raise ValueError('candidates must be (K, T-1, %d), got shape %s' % (A, cand_shape))
+    if Model._host_shape(state) != (1, S):
+        raise ValueError('state must be (1, %d), got shape %s' % (S, Model._host_shape(state)))
     K = cand_shape[0]
     H, W = ctx_shape[3:]
     image = _as_goal_cost(goal_image)
@@ -190,6 +191,20 @@ def score_actions(model, context_images, state, candidates, designated_rc, goal_
 
 
 MAX_CEM_SAMPLES = 1024
+
+
+def _widths(model):
+    """(action_dim, state_dim) of a model; 5 / 5 for an object that does not say (the reference's data)."""
+    return int(getattr(model, 'action_dim', 5)), int(getattr(model, 'state_dim', 5))
+
+
+def _check_cem_widths(model):
+    """The CEM kernels (pivp_cem_update / _ex / _shift, include/pivp_hip.h, include/pivp_mpc.h) carry [..][K][5] action rows and the five-column Philox
+    pairing in their contract, and the planner's state buffers are laid out for five numbers: `cem_plan`, `cem_refine` and `MPC` serve 5 / 5 models."""
+    A, S = _widths(model)
+    if (A, S) != (5, 5):
+        raise ValueError('the on-device CEM samples and refits five-column actions: a model with action_dim=%d, state_dim=%d is not served '
+                         '(score_actions and refine_actions are, at any width)' % (A, S))
 
 
 def _host_array(a, what):
@@ -245,17 +260,17 @@ def _whole_number(v, what, low, high=None):
     return int(v)
 
 
-def _five(v, what, default, infinite=False):
-    """None | scalar | (5,) -> (5,) float64, finite (infinite=True: anything but NaN): a per-dimension value of an action."""
-    a = np.full(5, float(default)) if v is None else _host_array(v, what)
-    if a.shape not in ((), (5,)) or np.isnan(a).any() or not (infinite or np.isfinite(a).all()):
-        raise ValueError('%s must be a scalar or (5,), %s, got shape %s' % (what, 'without NaN' if infinite else 'finite', a.shape))
-    return np.ascontiguousarray(np.broadcast_to(a, (5,)))
+def _five(v, what, default, infinite=False, dim=5):
+    """None | scalar | (5,) -> (5,) float64, finite (infinite=True: anything but NaN): a per-dimension value of an action (dim: of another width)."""
+    a = np.full(dim, float(default)) if v is None else _host_array(v, what)
+    if a.shape not in ((), (dim,)) or np.isnan(a).any() or not (infinite or np.isfinite(a).all()):
+        raise ValueError('%s must be a scalar or (%d,), %s, got shape %s' % (what, dim, 'without NaN' if infinite else 'finite', a.shape))
+    return np.ascontiguousarray(np.broadcast_to(a, (dim,)))
 
 
-def _action_box(low, high, low_name, high_name):
-    """Each of low, high: None (no bound) | scalar | (5,), no NaN, low <= high -> (low, high), both (5,) float64."""
-    low, high = _five(low, low_name, -np.inf, infinite=True), _five(high, high_name, np.inf, infinite=True)
+def _action_box(low, high, low_name, high_name, dim=5):
+    """Each of low, high: None (no bound) | scalar | (5,), no NaN, low <= high -> (low, high), both (5,) float64 (dim: of another action width)."""
+    low, high = _five(low, low_name, -np.inf, infinite=True, dim=dim), _five(high, high_name, np.inf, infinite=True, dim=dim)
     if (low > high).any():
         raise ValueError('%s exceeds %s' % (low_name, high_name))
     return low, high
@@ -476,6 +491,7 @@ def _check_cem_args(model, context_images, state, *, designated_rc, goal_rc, hor
     `cem_plan` hands them over: they are written once, in its signature), and a name `cem_plan` does not have is a TypeError.
     -> the checked host-side values, the same attributes whoever asks -- `cem_plan`, `cem_refine` or `MPC.reset`.  With the options off keep,
     add_mean, beta, warm, planes, ex, belief and image are 0, False, 0.0, None, None, False, None and None; ex: the loop calls pivp_cem_update_ex."""
+    _check_cem_widths(model)
     ctx = int(model.num_frame_before_prediction)
     si = Model._host_shape(context_images)
     if len(si) != 5 or si[1] != 1 or si[2] != 3:
@@ -784,12 +800,13 @@ def _check_refine_args(model, context_images, state, actions, goal_image, cost_f
     B, H, W = si[1], si[3], si[4]
     if H < 2 or W < 2:
         raise ValueError('context_images is empty: shape %s' % (si,))
-    if Model._host_shape(state) != (B, 5):
-        raise ValueError('state must be (%d, 5), got shape %s' % (B, Model._host_shape(state)))
+    A, S = _widths(model)
+    if Model._host_shape(state) != (B, S):
+        raise ValueError('state must be (%d, %d), got shape %s' % (B, S, Model._host_shape(state)))
     sa = Model._host_shape(actions)
-    if len(sa) != 3 or sa[1] != B or sa[2] != 5 or sa[0] < ctx:
-        raise ValueError('actions must be (T-1, %d, 5) with T-1 >= %d (one action per rollout step, the steps between the context frames included), '
-                         'got shape %s' % (B, ctx, sa))
+    if len(sa) != 3 or sa[1] != B or sa[2] != A or sa[0] < ctx:
+        raise ValueError('actions must be (T-1, %d, %d) with T-1 >= %d (one action per rollout step, the steps between the context frames included), '
+                         'got shape %s' % (B, A, ctx, sa))
     if not getattr(model, 'keep_activations', False):
         raise ValueError('refine_actions back-propagates through the rollout: the model needs keep_activations=True')
     if getattr(model, '_extra_loss', False):
@@ -808,15 +825,15 @@ def _check_refine_args(model, context_images, state, actions, goal_image, cost_f
     n_past = 0
     if past_actions is not None:
         sp = Model._host_shape(past_actions)
-        if ctx < 2 or sp not in ((ctx - 1, 5), (ctx - 1, B, 5)):
-            raise ValueError('past_actions must be (%d, 5) or (%d, %d, 5): the actions taken between the %d observed frames, got shape %s'
-                             % (ctx - 1, ctx - 1, B, ctx, sp))
+        if ctx < 2 or sp not in ((ctx - 1, A), (ctx - 1, B, A)):
+            raise ValueError('past_actions must be (%d, %d) or (%d, %d, %d): the actions taken between the %d observed frames, got shape %s'
+                             % (ctx - 1, A, ctx - 1, B, A, ctx, sp))
         n_past = ctx - 1
     low = high = None
     if bounds is not None:
         if not isinstance(bounds, (tuple, list)) or len(bounds) != 2:
             raise ValueError('bounds must be a pair (low, high)')
-        low, high = _action_box(bounds[0], bounds[1], 'bounds[0]', 'bounds[1]')
+        low, high = _action_box(bounds[0], bounds[1], 'bounds[0]', 'bounds[1]', dim=A)
     return SimpleNamespace(ctx=ctx, B=B, H=H, W=W, steps_T=sa[0], n_past=n_past, iters=steps, lr=lr, low=low, high=high)
 
 
@@ -824,7 +841,8 @@ def refine_actions(model, context_images, state, actions, goal_image=None, cost_
     """Gradient descent (Adam) on an action sequence, with the gradient from the model's own backward sweep.
 
     context_images (ctx, B, 3, H, W), state (B, 5): what each of B robots sees now; actions (T-1, B, 5): the sequence to start from, one action per
-    rollout step (rows t < ctx-1 are the steps between the context frames).  past_actions (ctx-1, 5) or (ctx-1, B, 5): when given, those first rows
+    rollout step (rows t < ctx-1 are the steps between the context frames) -- every 5 here is the model's action_dim, or state_dim for `state`.
+    past_actions (ctx-1, 5) or (ctx-1, B, 5): when given, those first rows
     are set to it and held fixed (the MPC case: they have been executed); None: every row is free (explaining an observed video).
 
     Per iteration: ONE feed-self training-mode rollout (`model(...)` under config.train with scheduled sampling off, whatever the model's
@@ -861,12 +879,13 @@ def _refine_upload(model, a, context_images, state, actions, goal_image, past_ac
     b = SimpleNamespace()
     b.images = torch.zeros((T, a.B, 3, a.H, a.W), dtype=torch.float32, device=dev)
     b.images[:a.ctx] = model._as_device(context_images, ())
-    b.states = torch.zeros((T, a.B, 5), dtype=torch.float32, device=dev)
-    b.states[0] = model._as_device(state, (5,))
-    b.actions = torch.zeros((T, a.B, 5), dtype=torch.float32, device=dev)      # (the rollout's action tensor is (T, B, 5); row T-1 is never read)
-    b.actions[:T - 1] = model._as_device(actions, (5,))
+    A, S = _widths(model)
+    b.states = torch.zeros((T, a.B, S), dtype=torch.float32, device=dev)
+    b.states[0] = model._as_device(state, (S,))
+    b.actions = torch.zeros((T, a.B, A), dtype=torch.float32, device=dev)      # (the rollout's action tensor is (T, B, A); row T-1 is never read)
+    b.actions[:T - 1] = model._as_device(actions, (A,))
     if a.n_past:
-        past = model._as_device(past_actions, (5,))
+        past = model._as_device(past_actions, (A,))
         b.actions[:a.n_past] = past if past.dim() == 3 else past.unsqueeze(1)
     b.goal, b.goal_cost = None, None
     if isinstance(goal_image, GoalImageCost):      # the spec's goal and weights: uploaded here, read by the loop's one pivp_goal_image_cost per iteration

@@ -41,6 +41,9 @@ def build_parser():
     p.add_argument('--use_state', type=int, default=1)
     p.add_argument('--model_type', default='CDNA')
     p.add_argument('--num_masks', type=int, default=10)
+    # the widths of an action and of a robot state in the data (the push data set's 5 / 5; BAIR pushing 4 / 3, RoboNet 4 / 5): Model(action_dim=, state_dim=)
+    p.add_argument('--action_dim', type=int, default=5)
+    p.add_argument('--state_dim', type=int, default=5)
     p.add_argument('--schedsamp_k', type=float, default=900.0)
     p.add_argument('--train_val_split', type=float, default=0.95)
     p.add_argument('--batch_size', type=int, default=32)
@@ -139,6 +142,10 @@ def main(argv=None):
     device = 'cuda:%d' % local_rank
 
     if args.device_dataset:
+        try:
+            ds.check_device_widths(args.action_dim, args.state_dim)
+        except ValueError as e:
+            raise SystemExit('--device_dataset 1: %s' % e)
         dset = ds.DeviceDataset.from_dir(args.data_dir, device, storage=args.device_storage)
         train_set, valid_set = ds.split_index_ranges(dset.N, args.train_val_split)      # sequence numbers: the iterators draw those
         n_all = dset.N
@@ -152,7 +159,8 @@ def main(argv=None):
     model = Model(num_masks=args.num_masks, is_cdna=args.model_type == 'CDNA', is_dna=args.model_type == 'DNA',
                   is_stp=args.model_type == 'STP', use_state=args.use_state, scheduled_sampling_k=args.schedsamp_k,
                   num_frame_before_prediction=args.context_frames, prefix='train', device=device, keep_activations=True,
-                  deterministic=bool(args.deterministic), image_loss=image_loss_from_args(args), **model_state_flags(args))
+                  deterministic=bool(args.deterministic), image_loss=image_loss_from_args(args), action_dim=args.action_dim, state_dim=args.state_dim,
+                  **model_state_flags(args))
     extra_loss = model.image_loss is not None
     if args.grad_clip < 0 or args.grad_clip != args.grad_clip:
         raise SystemExit('--grad_clip must be >= 0 (0: off)')

@@ -20,7 +20,8 @@ _i, _f, _vp, _ll = ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_longl
 
 class Config(ctypes.Structure):      # pivp_config_t
     _fields_ = [('batch', _i), ('seq_len', _i), ('height', _i), ('width', _i), ('num_masks', _i), ('model_type', _i), ('use_state', _i),
-                ('context_frames', _i), ('keep_activations', _i), ('ln_eps', _f), ('stp_zero_border', _i)]
+                ('context_frames', _i), ('keep_activations', _i), ('ln_eps', _f), ('stp_zero_border', _i),
+                ('action_dim', _i), ('state_dim', _i)]      # 0 / 0 (config() below leaves them out) = the reference data's 5 / 5
 
 
 MODELS = (('CDNA', 0, 10), ('STP', 1, 10), ('DNA', 2, 1))
