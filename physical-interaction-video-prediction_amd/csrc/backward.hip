@@ -4,11 +4,9 @@
 // igemm_f32.hip / igemm_wgrad.hip.  All gradient buffers ACCUMULATE (Chainer: cleargrads() then backward()).
 #include <string.h>
 
-#include "pivp_kernels.h"
+#include "lstm_gate_epilogue.h"
 
 namespace pivp {
-
-__device__ __forceinline__ float fast_tanh_b(float x) { return 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(-2.0f * x)) - 1.0f; }
 
 // ------------------------------------------------------------------------------------------
 // ConvLSTM gate math backward (TM:269-272):  c' = c*f + i*j,  h = tanh(c')*o  with the stored activations
@@ -70,7 +68,7 @@ __global__ __launch_bounds__(256) void lstm_gates_bwd_kernel(const float* __rest
     f32x4 oj, oi, of, oo, dcn;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        const float tc = fast_tanh_b(cn[k]);
+        const float tc = b_tanh(cn[k]);
         const float dct = dh[k] * ao[k] * (1.f - tc * tc) + dcv[k];
         oj[k] = dct * ai[k] * (1.f - aj[k] * aj[k]);
         oi[k] = dct * aj[k] * ai[k] * (1.f - ai[k]);

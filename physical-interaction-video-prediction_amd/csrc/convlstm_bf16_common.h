@@ -6,7 +6,7 @@
 #include <type_traits>
 #include <utility>
 
-#include "pivp_kernels.h"
+#include "lstm_gate_epilogue.h"
 
 namespace pivp {
 
@@ -57,12 +57,38 @@ constexpr int ring_depth() {
 }
 template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
 
-__device__ __forceinline__ float b_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-__device__ __forceinline__ float b_tanh(float x) { return 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(-2.0f * x)) - 1.0f; }
-
 __device__ __forceinline__ unsigned pack2(float a, float b) {   // two fp32 -> packed bf16, round to nearest even
     f32x2 v = {a, b};
     return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
+}
+// A staging thread's 8-channel piece (first channel ch of concat(x, h), in the 64-channel group that starts at gch) of pixel a_pix (-1: outside the
+// image).  The source of the piece (x or h) differs between the lanes of a wave only in the ONE 64-channel group that straddles c0.
+// Written as a per-lane choice of descriptor (rounds 2-5) every load became a waterfall loop -- readfirstlane x 4, two 64-bit compares, exec
+// juggling: 14 instructions per load, 42-107 such loops per kernel.  Now the choice is block-uniform: a group inside one source loads from
+// it; the straddling group loads from both with the other source's lanes out of range (the hardware's zeros) and ORs the two.
+__device__ __forceinline__ void concat_piece_load(const __amdgpu_buffer_rsrc_t& rs0, const __amdgpu_buffer_rsrc_t& rs1, int a_pix, int gch, int ch,
+                                                  int c0, int cin, int ld0, int ld1, f32x4& lo, f32x4& hi) {
+    constexpr unsigned OOB = 0xC0000000u;
+    const bool s0 = ch < c0, s1 = !s0 && ch < cin;
+    const bool use0 = gch < c0, use1 = gch + 64 > c0 && gch < cin;      // block-uniform
+    const unsigned off0 = (a_pix >= 0 && s0) ? (unsigned)((a_pix * ld0 + ch) * 4) : OOB;
+    const unsigned off1 = (a_pix >= 0 && s1) ? (unsigned)((a_pix * ld1 + ch - c0) * 4) : OOB;
+    auto ld2 = [&](const __amdgpu_buffer_rsrc_t& rs, unsigned off, f32x4& l, f32x4& h) {
+        l = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0));
+        h = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 16, 0));
+    };
+    if (use0 && use1) {
+        f32x4 blo, bhi;
+        ld2(rs0, off0, lo, hi);
+        ld2(rs1, off1, blo, bhi);
+        typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+        lo = __builtin_bit_cast(f32x4, __builtin_bit_cast(u32x4, lo) | __builtin_bit_cast(u32x4, blo));      // (one of the two is the hardware's zeros)
+        hi = __builtin_bit_cast(f32x4, __builtin_bit_cast(u32x4, hi) | __builtin_bit_cast(u32x4, bhi));
+    } else if (use0) {
+        ld2(rs0, off0, lo, hi);
+    } else {
+        ld2(rs1, off1, lo, hi);           // (a group past cin: every lane out of range)
+    }
 }
 // LDS reads and their waits as inline asm (see the kernel: the compiler must not see them as LDS accesses)
 template <int OFF>
@@ -97,6 +123,19 @@ inline bool bf16_geometry_ok(const IgemmDesc& d) {
     if (d.ksize != 5 || d.pad != 2 || d.in_step != 1) return false;
     if (d.c0 % 8 || d.c1 % 8 || d.ld0 % 4 || d.ld1 % 4) return false;
     return packed_tiles_serve(d.Hin, d.Win, d.B);
+}
+
+// host side of both kernels' launchers: the divisors of a block's tile decode (tiles, tiles per image, tiles per row) as multiplier / shift pairs
+static inline void packed_decode_divisors(IgemmDesc& dd, int n_tiles, int tpi, int tpr) {
+    pivp_fastdiv((unsigned)n_tiles, &dd.fd_mb_mul, &dd.fd_mb_sh);
+    pivp_fastdiv((unsigned)tpi, &dd.fd_hw_mul, &dd.fd_hw_sh);
+    pivp_fastdiv((unsigned)tpr, &dd.fd_w_mul, &dd.fd_w_sh);
+}
+// ... and whether the cell writes LayerNorm partials: np per image (one per tile and column block), if asked for and the caller's buffer holds them
+static inline void packed_ln_slots(IgemmDesc& dd, int np, int* ln_nparts) {
+    dd.ln_nparts = (dd.ln_part && np <= dd.ln_cap) ? np : 0;
+    if (!dd.ln_nparts) dd.ln_part = nullptr;
+    if (ln_nparts) *ln_nparts = dd.ln_nparts;
 }
 
 #ifdef PIVP_BF16_STAMPS   // in-kernel phase stamps of every block's wave 0, constant-rate 100 MHz counter (scripts/bf16_stamps.py)

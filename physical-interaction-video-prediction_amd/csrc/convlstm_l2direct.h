@@ -102,37 +102,20 @@ __global__ __launch_bounds__(64 * NWM * NWN, 1) void convlstm_x6g_kernel(const I
     const __amdgpu_buffer_rsrc_t rsg = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(IN_LN ? d.in_g : d.x0), 0, IN_LN ? H * W * c0 * 4 : 0, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsb = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(IN_LN ? d.in_b : d.x0), 0, IN_LN ? H * W * c0 * 4 : 0, 0x00020000);
     auto patch_load = [&](int cg, int rnd) {
-        const int gch = cg * 64;                          // block-uniform: the source choice below is a uniform branch (see convlstm_ring.h: as a
-        const int ch = gch + cpiece * 8;                  // per-lane choice of descriptor every load was a 14-instruction waterfall loop)
-        const bool s0 = ch < c0, s1 = !s0 && ch < cin;
-        const bool use0 = gch < c0, use1 = gch + 64 > c0 && gch < cin;
-        const int co = s0 ? ch : ch - c0;
+        const int gch = cg * 64;                          // block-uniform, and with it the choice between x and h (concat_piece_load)
+        const int ch = gch + cpiece * 8;
 #pragma unroll
         for (int j = 0; j < NPJX; ++j) {
             int a_pix, a_lds;
             pix_of(rnd * NPJX + j, a_pix, a_lds);
-            const unsigned off0 = (a_pix >= 0 && s0) ? (unsigned)((a_pix * ld0 + ch) * 4) : OOB;
-            const unsigned off1 = (a_pix >= 0 && s1) ? (unsigned)((a_pix * ld1 + ch - c0) * 4) : OOB;
             if constexpr (IN_LN) {          // (pieces of h channels and pixels outside the image: the zeros of an out-of-range load)
-                const unsigned go = (a_pix >= 0 && s0) ? (unsigned)(((a_pix - b0 * H * W) * c0 + co) * 4) : OOB;
+                const unsigned go = (a_pix >= 0 && ch < c0) ? (unsigned)(((a_pix - b0 * H * W) * c0 + ch) * 4) : OOB;
                 glo[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsg, go, 0, 0));
                 ghi[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsg, go, 16, 0));
                 blo[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsb, go, 0, 0));
                 bhi[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsb, go, 16, 0));
             }
-            if (use0 && use1) {
-                typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-                const u32x4 alo = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs0, off0, 0, 0)), ahi = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs0, off0, 16, 0));
-                const u32x4 blo2 = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs1, off1, 0, 0)), bhi2 = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs1, off1, 16, 0));
-                plo[j] = __builtin_bit_cast(f32x4, alo | blo2);      // (one of the two is the hardware's zeros)
-                phi[j] = __builtin_bit_cast(f32x4, ahi | bhi2);
-            } else if (use0) {
-                plo[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs0, off0, 0, 0));
-                phi[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs0, off0, 16, 0));
-            } else {
-                plo[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs1, off1, 0, 0));
-                phi[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs1, off1, 16, 0));
-            }
+            concat_piece_load(rs0, rs1, a_pix, gch, ch, c0, cin, ld0, ld1, plo[j], phi[j]);
         }
     };
     auto patch_store = [&](int rnd, int cg = 0) {      // cg: which 64-channel group was loaded (IN_LN: its x pieces are normalised)
@@ -355,142 +338,52 @@ __global__ __launch_bounds__(64 * NWM * NWN, 1) void convlstm_x6g_kernel(const I
     BF_STAMP(3);
 
     if constexpr (!LSTM) {
-        // ---- plain epilogue: accumulator row = anchor, column = output channel; 32 lanes write 128 contiguous bytes -------------------
-        // (the epilogue hook's second tensor is requested for all of the lane's outputs first: see convlstm_bf16_kernel)
+        // ---- plain epilogue (plain_hook_load / plain_store: the hook's second tensor is requested for all of the lane's outputs first) ----
+        const int col = (nblk * NWN + wn) * 32 + l31;
+        auto pixel = [&](int mt, int r) -> size_t {
+            int ti, ay, ax;
+            anchor(32 * MT * wm + 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * half, ti, ay, ax);
+            return (size_t)(((b0 + ti) * H + y0 + ay) * W + x0 + ax);
+        };
         float ev[MT][16];
         if (d.ep_mode) {                                // block-uniform
-            const int col = (nblk * NWN + wn) * 32 + l31;
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    int ti, ay, ax;
-                    anchor(32 * MT * wm + 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * half, ti, ay, ax);
-                    const size_t m = (size_t)(((b0 + ti) * H + y0 + ay) * W + x0 + ax);
-                    ev[mt][r] = (col < ncols && col < d.ep_cols) ? d.ep_src[m * d.ep_ld + col] : (d.ep_mode == 1 ? 1.f : 0.f);
-                }
+                for (int r = 0; r < 16; ++r) ev[mt][r] = plain_hook_load(d, pixel(mt, r), col, ncols);
         }
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                int ti, ay, ax;
-                anchor(32 * MT * wm + 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * half, ti, ay, ax);
-                const size_t m = (size_t)(((b0 + ti) * H + y0 + ay) * W + x0 + ax);
-                const int col = (nblk * NWN + wn) * 32 + l31;
-                if (col < ncols) {                      // the pack's rows past the real column count are zero padding
-                    float* o = d.out + m * d.ldo + col;
-                    float v = acc[mt][r];
-                    if (d.ep_mode == 1) v = ev[mt][r] > 0.f ? v : 0.f;         // (unsplit grids only: the launcher clears ep_mode otherwise)
-                    else if (d.ep_mode == 2) v += ev[mt][r];
-                    if (gridDim.y > 1) atomicAdd(o, v);
-                    else if (d.accum) *o += v;
-                    else *o = v;
-                }
-            }
+            for (int r = 0; r < 16; ++r) plain_store(d, acc[mt][r], ev[mt][r], pixel(mt, r), col, ncols);
         return;
     }
     // ---- epilogue: the gate math of convlstm_bf16_kernel's 16-channel blocks (a wave's 32 columns = 4 gates x 8 channels) -------------
-    auto pick = [&](const float (&v)[4], int idx) -> float {
-        const float lo = (idx & 1) ? v[1] : v[0], hi = (idx & 1) ? v[3] : v[2];
-        return (idx & 2) ? hi : lo;
-    };
-    float sv[MT][4];
+    float sv[MT * 4];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            float rows[4], val[4], g4[4];
+            float rows[4], g4[4];
 #pragma unroll
             for (int g = 0; g < 4; ++g) rows[g] = acc[mt][k * 4 + g];
-            val[0] = pick(rows, grp);
-#pragma unroll
-            for (int x = 1; x < 4; ++x) val[x] = __shfl_xor(pick(rows, grp ^ x), x * 8, 64);
-#pragma unroll
-            for (int g = 0; g < 4; ++g) g4[g] = pick(val, g ^ grp);
+            gate_exchange<4, 8>(rows, grp, g4);
             const int r = k * 4 + grp;
             int ti, ay, ax;
             anchor(32 * MT * wm + 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * half, ti, ay, ax);
             const int m = ((b0 + ti) * H + y0 + ay) * W + x0 + ax;
-            const size_t o = (size_t)m * C + ch;
-            const float aj = b_tanh(g4[0] + bj), ai = b_sigmoid(g4[1] + bi);
-            const float af = b_sigmoid(g4[2] + bf), ao = b_sigmoid(g4[3] + bo);
-            const float cn = cpre[mt][k] * af + ai * aj;
-            d.cstate_out[o] = cn;
-            const float hn = b_tanh(cn) * ao;
-            d.hout[o] = hn;
-            sv[mt][k] = hn;
-            if (d.gates_out) {
-                float* gp = d.gates_out + (size_t)m * 4 * C + ch;
-                gp[0] = aj; gp[C] = ai; gp[2 * C] = af; gp[3 * C] = ao;
-            }
+            const LstmCell cell = lstm_cell<GateActPacked>(g4, bj, bi, bf, bo, cpre[mt][k]);
+            lstm_cell_store(d, cell, m, ch);
+            sv[mt * 4 + k] = cell.h;
         }
     BF_STAMP(4);
 #ifdef PIVP_BF16_STAMPS
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     BF_STAMP(5);
 #endif
-    if (d.ln_part) {                                   // (count, mean, M2) of the block's h tile, two passes, fixed order over the eight waves
-        float* red = reinterpret_cast<float*>(lds);
-        float s1 = 0.f;
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) s1 += sv[mt][k];
-        s1 = wave_sum(s1);
-        __syncthreads();
-        if (lane == 0) red[wave8] = s1;
-        __syncthreads();
-        if constexpr (!W8) {
-            const float cnt = (float)NW * 64.f * 4.f * MT;
-            const float ssum = ((red[0] + red[1]) + (red[2] + red[3])) + ((red[4] + red[5]) + (red[6] + red[7]));
-            const float mean = ssum / cnt;
-            float q = 0.f;
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                for (int k = 0; k < 4; ++k) { const float dd = sv[mt][k] - mean; q = fmaf(dd, dd, q); }
-            q = wave_sum(q);
-            if (lane == 0) red[8 + wave8] = q;
-            __syncthreads();
-            if (tid == 0) {
-                float* p = d.ln_part + ((size_t)b0 * d.ln_nparts + (size_t)trem * n_nblk + nblk) * 4;
-                const float qs = ((red[8] + red[9]) + (red[10] + red[11])) + ((red[12] + red[13]) + (red[14] + red[15]));
-                p[0] = cnt; p[1] = mean; p[2] = qs; p[3] = 0.f;
-            }
-        } else {
-            // two images per tile: the waves wm < NWM / 2 (of every wave column) own image 0, the others image 1 -- a wave's 32 MT anchors lie inside one image
-            const int img = (wm * MT) >> 1;
-            const float cnt = (float)(NW / 2) * 64.f * 4.f * MT;
-            float ssum = 0.f;
-#pragma unroll
-            for (int w = 0; w < NW; ++w) ssum += ((((w % NWM) * MT) >> 1) == img) ? red[w] : 0.f;      // fixed order
-            const float mean = ssum / cnt;
-            float q = 0.f;
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                for (int k = 0; k < 4; ++k) { const float dd = sv[mt][k] - mean; q = fmaf(dd, dd, q); }
-            q = wave_sum(q);
-            if (lane == 0) red[8 + wave8] = q;
-            __syncthreads();
-            if (lane == 0 && wn == 0 && wm == img * (NWM / 2)) {      // one writer per image
-                float* p = d.ln_part + ((size_t)(b0 + img) * d.ln_nparts + (size_t)trem * n_nblk + nblk) * 4;
-                float qs = 0.f;
-#pragma unroll
-                for (int w = 0; w < NW; ++w) qs += ((((w % NWM) * MT) >> 1) == img) ? red[8 + w] : 0.f;
-                p[0] = cnt; p[1] = mean; p[2] = qs; p[3] = 0.f;
-            }
-        }
-    }
+    if (d.ln_part) ln_tile_partial<NWM, NWN>(d, sv, reinterpret_cast<float*>(lds), W8, wm, wn, lane, b0, (size_t)trem * n_nblk + nblk);
 }
 
-// the divisors of a block's tile decode (tiles, tiles per image, tiles per row) as multiplier / shift pairs
-static inline void x6g_decode_divisors(IgemmDesc& dd, int n_tiles, int tpi, int tpr) {
-    pivp_fastdiv((unsigned)n_tiles, &dd.fd_mb_mul, &dd.fd_mb_sh);
-    pivp_fastdiv((unsigned)tpi, &dd.fd_hw_mul, &dd.fd_hw_sh);
-    pivp_fastdiv((unsigned)tpr, &dd.fd_w_mul, &dd.fd_w_sh);
-}
 template <int NWM, int NWN, int PCS, bool IN_LN, bool W8 = false>
 static int launch_x6g_impl(const IgemmDesc& d, const unsigned short* wb, hipStream_t stream, int* ln_nparts) {
     constexpr int THX = TH, lds_bytes = PCS * (W8 ? PATCH_BYTES : PH * RP16);
@@ -500,13 +393,10 @@ static int launch_x6g_impl(const IgemmDesc& d, const unsigned short* wb, hipStre
     PIVP_CHECK_ARG(d.Hin % THX == 0 && d.Win % (W8 ? 8 : 16) == 0 && (!W8 || d.B % 2 == 0));
     IgemmDesc dd = d;
     const int tpi = (d.Hin / THX) * (d.Win / (W8 ? 8 : 16)), nb = d.C / (8 * NWN);
-    const int np = tpi * nb;
-    dd.ln_nparts = (d.ln_part && np <= d.ln_cap) ? np : 0;
-    if (!dd.ln_nparts) dd.ln_part = nullptr;
-    if (ln_nparts) *ln_nparts = dd.ln_nparts;
+    packed_ln_slots(dd, tpi * nb, ln_nparts);
     const long long wbytes = (long long)lstm_bf16_weight_elems(d.c0 + (d.c1 ? d.c1 : d.C), 4 * d.C) * PCS * 2;
     if (wbytes >= (1LL << 31)) return PIVP_ERR_BADARG;
-    x6g_decode_divisors(dd, (d.B / (W8 ? 2 : 1)) * tpi, tpi, d.Win / (W8 ? 8 : 16));
+    packed_decode_divisors(dd, (d.B / (W8 ? 2 : 1)) * tpi, tpi, d.Win / (W8 ? 8 : 16));
     hipLaunchKernelGGL((convlstm_x6g_kernel<NWM, NWN, true, PCS, IN_LN, W8>), dim3((d.B / (W8 ? 2 : 1)) * tpi * nb), dim3(64 * NWM * NWN), lds_bytes, stream, dd, wb, (int)wbytes, 0);
     return PIVP_LAUNCH_STATUS();
 }
@@ -536,7 +426,7 @@ static int launch_x6g_plain(const IgemmDesc& dsc, const unsigned short* wb, hipS
     const int tpi = (dd.Hin / TH) * (dd.Win / (W8 ? 8 : 16));
     const long long wbytes = (long long)lstm_bf16_weight_elems(dd.c0 + dd.c1, dd.N) * PCS * 2;
     if (wbytes >= (1LL << 31)) return PIVP_ERR_BADARG;
-    x6g_decode_divisors(dd, (dd.B / (W8 ? 2 : 1)) * tpi, tpi, dd.Win / (W8 ? 8 : 16));
+    packed_decode_divisors(dd, (dd.B / (W8 ? 2 : 1)) * tpi, tpi, dd.Win / (W8 ? 8 : 16));
     hipLaunchKernelGGL((convlstm_x6g_kernel<4, 2, false, PCS, false, W8>), dim3((dd.B / (W8 ? 2 : 1)) * tpi * nb, ks), dim3(512), lds_bytes, stream, dd, wb, (int)wbytes, ncols);
     return PIVP_LAUNCH_STATUS();
 }

@@ -87,7 +87,6 @@ __global__ __launch_bounds__(512, 1) void convlstm_bf16_kernel(const IgemmDesc d
 
     const __amdgpu_buffer_rsrc_t rs0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(d.x0), 0, d.bytes0, 0x00020000);
     const __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(d.c1 ? d.x1 : d.x0), 0, d.c1 ? d.bytes1 : d.bytes0, 0x00020000);
-    constexpr unsigned OOB = 0xC0000000u;
 
     // ---- patch staging (all 8 waves): thread = (pixel (tid >> 3) + 64 j, 8-channel piece tid & 7), j < 5 -------------------
     const int cpiece = tid & 7;
@@ -104,36 +103,10 @@ __global__ __launch_bounds__(512, 1) void convlstm_bf16_kernel(const IgemmDesc d
         a_lds[j] = p < npix ? (ti * PH + py) * RP + px * PP : PW * PP;
     }
     f32x4 plo[NPJ], phi[NPJ];                          // a patch in flight (live only between the two halves of a staging)
-    // The source of a thread's 8-channel piece (x or h) differs between the lanes of a wave only in the ONE 64-channel group that straddles c0.
-    // Written as a per-lane choice of descriptor (rounds 2-5) every load became a waterfall loop -- readfirstlane x 4, two 64-bit compares, exec
-    // juggling: 14 instructions per load, 42-107 such loops per kernel.  Now the choice is block-uniform: a group inside one source loads from
-    // it; the straddling group loads from both with the other source's lanes out of range (the hardware's zeros) and ORs the two.
-    auto patch_load = [&](int cg) {
+    auto patch_load = [&](int cg) {                    // (the block-uniform choice between x and h: concat_piece_load)
         const int gch = (cgbase + cg) * 64;               // the group's first channel: block-uniform
-        const int ch = gch + cpiece * 8;                  // first of this thread's 8 channels of concat(x, h)
-        const bool s0 = ch < c0, s1 = !s0 && ch < cin;
-        const bool use0 = gch < c0, use1 = gch + 64 > c0 && gch < cin;
-        auto ld2 = [&](const __amdgpu_buffer_rsrc_t& rs, unsigned off, f32x4& lo, f32x4& hi) {
-            lo = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0));
-            hi = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 16, 0));
-        };
 #pragma unroll
-        for (int j = 0; j < NPJ; ++j) {
-            const unsigned off0 = (a_pix[j] >= 0 && s0) ? (unsigned)((a_pix[j] * ld0 + ch) * 4) : OOB;
-            const unsigned off1 = (a_pix[j] >= 0 && s1) ? (unsigned)((a_pix[j] * ld1 + ch - c0) * 4) : OOB;
-            if (use0 && use1) {
-                f32x4 blo, bhi;
-                ld2(rs0, off0, plo[j], phi[j]);
-                ld2(rs1, off1, blo, bhi);
-                typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-                plo[j] = __builtin_bit_cast(f32x4, __builtin_bit_cast(u32x4, plo[j]) | __builtin_bit_cast(u32x4, blo));
-                phi[j] = __builtin_bit_cast(f32x4, __builtin_bit_cast(u32x4, phi[j]) | __builtin_bit_cast(u32x4, bhi));
-            } else if (use0) {
-                ld2(rs0, off0, plo[j], phi[j]);
-            } else {
-                ld2(rs1, off1, plo[j], phi[j]);           // (a group past cin: every lane out of range)
-            }
-        }
+        for (int j = 0; j < NPJ; ++j) concat_piece_load(rs0, rs1, a_pix[j], gch, gch + cpiece * 8, c0, cin, ld0, ld1, plo[j], phi[j]);
     };
     auto patch_store = [&]() {
 #pragma unroll
@@ -412,9 +385,7 @@ __global__ __launch_bounds__(512, 1) void convlstm_bf16_kernel(const IgemmDesc d
     }   // !LATE
     if constexpr (!LSTM) {
         // ---- plain epilogue: accumulator row = anchor, column = output channel; 32 lanes write 128 contiguous bytes ----------
-        // The epilogue hook's second tensor (d.ep_src) is requested for ALL of the lane's outputs first and met below: read next to each store
-        // it cost one exposed round trip per accumulator row (the data gradients ran 9-11 us longer per launch with it, more than the pass it
-        // replaces).  Neutral elements where the hook does not apply: 1 for the mask, 0 for the sum.
+        // (in both forms below the epilogue hook's second tensor is requested for ALL of the lane's outputs first: why, at plain_hook_load)
         const long long out_bytes = (long long)d.B * H * W * d.ldo * 4, ep_bytes = d.ep_mode ? (long long)d.B * H * W * d.ep_ld * 4 : 0;
         if (out_bytes < (1LL << 31) && ep_bytes < (1LL << 31)) {
             // Round 6: as the fp32 data gradient's epilogue (igemm_f32.hip): the lane-dependent part of an element's address is ONE 32-bit offset of a
@@ -465,61 +436,34 @@ __global__ __launch_bounds__(512, 1) void convlstm_bf16_kernel(const IgemmDesc d
                 }
             return;
         }
+        // (outputs or hook tensors of 2 GB and more: plain pointers, the tail convlstm_x6g_kernel has too)
+        auto pixel = [&](int mt, int r) -> size_t {
+            const int i = 64 * wm + 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * half;
+            const int ti = tw == 16 ? 0 : i >> 6, ay = tw == 16 ? i >> 4 : (i >> 3) & 7, ax = tw == 16 ? i & 15 : i & 7;
+            return (size_t)(((b0 + ti) * H + y0 + ay) * W + x0 + ax);
+        };
         float ev[2][TPW][16];
         if (d.ep_mode) {                                // block-uniform
 #pragma unroll
             for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int i = 64 * wm + 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * half;
-                    const int ti = tw == 16 ? 0 : i >> 6, ay = tw == 16 ? i >> 4 : (i >> 3) & 7, ax = tw == 16 ? i & 15 : i & 7;
-                    const size_t m = (size_t)(((b0 + ti) * H + y0 + ay) * W + x0 + ax);
+                for (int r = 0; r < 16; ++r)
 #pragma unroll
-                    for (int t = 0; t < TPW; ++t) {
-                        const int col = nblk * BN + (wn * TPW + t) * 32 + l31;
-                        ev[mt][t][r] = (col < ncols && col < d.ep_cols) ? d.ep_src[m * d.ep_ld + col] : (d.ep_mode == 1 ? 1.f : 0.f);
-                    }
-                }
+                    for (int t = 0; t < TPW; ++t) ev[mt][t][r] = plain_hook_load(d, pixel(mt, r), nblk * BN + (wn * TPW + t) * 32 + l31, ncols);
         }
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int i = 64 * wm + 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * half;
-                const int ti = tw == 16 ? 0 : i >> 6, ay = tw == 16 ? i >> 4 : (i >> 3) & 7, ax = tw == 16 ? i & 15 : i & 7;
-                const size_t m = (size_t)(((b0 + ti) * H + y0 + ay) * W + x0 + ax);
+            for (int r = 0; r < 16; ++r)
 #pragma unroll
-                for (int t = 0; t < TPW; ++t) {
-                    const int col = nblk * BN + (wn * TPW + t) * 32 + l31;
-                    if (col < ncols) {                  // the pack's rows past the real column count are zero padding
-                        float* o = d.out + m * d.ldo + col;
-                        float v = acc[mt][t][r];
-                        if (d.ep_mode == 1) v = ev[mt][t][r] > 0.f ? v : 0.f;      // (unsplit grids only: the launcher clears ep_mode otherwise)
-                        else if (d.ep_mode == 2) v += ev[mt][t][r];
-                        if (gridDim.y > 1) atomicAdd(o, v);
-                        else if (d.accum) *o += v;
-                        else *o = v;
-                    }
-                }
-            }
+                for (int t = 0; t < TPW; ++t) plain_store(d, acc[mt][t][r], ev[mt][t][r], pixel(mt, r), nblk * BN + (wn * TPW + t) * 32 + l31, ncols);
         return;
     }
     BF_STAMP(3);
     // ---- epilogue: gates, state update, optional gate activations and LayerNorm partial ----------------------------------
-    // Accumulator row r of a lane is one anchor; its column is (gate t * GPT + grp, channel): the 4 gates of an (anchor, channel)
-    // sit in the GPT lanes lane ^ (x * CPW) and the TPW tiles.  Lane grp takes rows r = k * GPT + grp: it keeps its own gate of
-    // that row and receives the others from its partners in GPT - 1 xor-shuffles per tile, each partner sending the row its
-    // receiver owns.  Every lane then updates one (anchor, channel) per k: no idle lanes, 2 (NCH 32) or 3 (NCH 16) shuffles per
-    // cell instead of 8 or 16.  Register arrays are only indexed statically; per-lane choices are select chains.
-    auto pick = [&](const float (&v)[GPT], int idx) -> float {
-        if constexpr (GPT == 2) {
-            return idx ? v[1] : v[0];
-        } else {
-            const float lo = (idx & 1) ? v[1] : v[0], hi = (idx & 1) ? v[3] : v[2];
-            return (idx & 2) ? hi : lo;
-        }
-    };
-    float sv[2][OWN];
+    // (which accumulator row, lane and tile hold which gate of a cell: lstm_gate_epilogue.h; lane grp updates rows r = k * GPT + grp, one
+    // (anchor, channel) per k, with 2 (NCH 32) or 3 (NCH 16) shuffles per cell)
+    float sv[2 * OWN];
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
@@ -527,76 +471,28 @@ __global__ __launch_bounds__(512, 1) void convlstm_bf16_kernel(const IgemmDesc d
             float g4[4];
 #pragma unroll
             for (int t = 0; t < TPW; ++t) {
-                float rows[GPT], val[GPT];
+                float rows[GPT], got[GPT];
 #pragma unroll
                 for (int g = 0; g < GPT; ++g) rows[g] = acc[mt][t][k * GPT + g];
-                val[0] = pick(rows, grp);
+                gate_exchange<GPT, CPW>(rows, grp, got);
 #pragma unroll
-                for (int x = 1; x < GPT; ++x) val[x] = __shfl_xor(pick(rows, grp ^ x), x * CPW, 64);
-#pragma unroll
-                for (int g = 0; g < GPT; ++g) g4[t * GPT + g] = pick(val, g ^ grp);
+                for (int g = 0; g < GPT; ++g) g4[t * GPT + g] = got[g];
             }
             const int r = k * GPT + grp;
             const int i = 64 * wm + 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * half;       // anchor within the block
             const int ti = tw == 16 ? 0 : i >> 6, ay = tw == 16 ? i >> 4 : (i >> 3) & 7, ax = tw == 16 ? i & 15 : i & 7;
             const int m = ((b0 + ti) * H + y0 + ay) * W + x0 + ax;
-            const size_t o = (size_t)m * C + ch;
-            const float aj = b_tanh(g4[0] + bj), ai = b_sigmoid(g4[1] + bi);
-            const float af = b_sigmoid(g4[2] + bf), ao = b_sigmoid(g4[3] + bo);
-            const float cn = cpre[mt][k] * af + ai * aj;
-            d.cstate_out[o] = cn;
-            const float hn = b_tanh(cn) * ao;
-            d.hout[o] = hn;
-            sv[mt][k] = hn;
-            if (d.gates_out) {
-                float* gp = d.gates_out + (size_t)m * 4 * C + ch;
-                gp[0] = aj; gp[C] = ai; gp[2 * C] = af; gp[3 * C] = ao;
-            }
+            const LstmCell cell = lstm_cell<GateActPacked>(g4, bj, bi, bf, bo, cpre[mt][k]);
+            lstm_cell_store(d, cell, m, ch);
+            sv[mt * OWN + k] = cell.h;
         }
     BF_STAMP(4);
 #ifdef PIVP_BF16_STAMPS
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the block's stores have left
     BF_STAMP(5);
 #endif
-    if (d.ln_part) {
-        // (count, mean, M2) of the h values of each image of the tile; with two images wave pair wm owns image wm.
-        float* red = reinterpret_cast<float*>(lds);
-        float s1 = 0.f;
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-            for (int k = 0; k < OWN; ++k) s1 += sv[mt][k];
-        s1 = wave_sum(s1);
-        const float c1 = 64.f * 2 * OWN;
-        __syncthreads();
-        if (lane == 0) { red[wave] = s1; red[4 + wave] = c1; }
-        __syncthreads();
-        float cnt, mean;
-        if (ti_n == 1) {
-            cnt = (red[4] + red[5]) + (red[6] + red[7]);
-            mean = ((red[0] + red[1]) + (red[2] + red[3])) / cnt;
-        } else {
-            cnt = red[4 + wm] + red[6 + wm];
-            mean = (red[wm] + red[2 + wm]) / cnt;
-        }
-        float q = 0.f;
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-            for (int k = 0; k < OWN; ++k) { const float dd = sv[mt][k] - mean; q = fmaf(dd, dd, q); }
-        q = wave_sum(q);
-        if (lane == 0) red[8 + wave] = q;
-        __syncthreads();
-        if (ti_n == 1) {
-            if (tid == 0) {
-                float* p = d.ln_part + ((size_t)b0 * d.ln_nparts + (size_t)trem * n_nblk + nblk) * 4;
-                p[0] = cnt; p[1] = mean; p[2] = (red[8] + red[9]) + (red[10] + red[11]); p[3] = 0.f;
-            }
-        } else if (lane == 0 && wn == 0) {
-            float* p = d.ln_part + ((size_t)(b0 + wm) * d.ln_nparts + (size_t)trem * n_nblk + nblk) * 4;
-            p[0] = cnt; p[1] = mean; p[2] = red[8 + wm] + red[10 + wm]; p[3] = 0.f;
-        }
-    }
+    // with two images per tile wave pair wm owns image wm
+    if (d.ln_part) ln_tile_partial<2, 2>(d, sv, reinterpret_cast<float*>(lds), ti_n == 2, wm, wn, lane, b0, (size_t)trem * n_nblk + nblk);
 }
 
 template <int NCH, bool LSTM, int PL = 1>
@@ -607,14 +503,10 @@ static int launch_bf16(const IgemmDesc& d, const unsigned short* wb, hipStream_t
     IgemmDesc dd = d;
     const int tw = d.Win % 16 == 0 ? 16 : 8, ti_n = tw == 16 ? 1 : 2;
     const int tpi = (d.Hin / TH) * (d.Win / tw);
-    const int np = tpi * nb;
-    dd.ln_nparts = (LSTM && d.ln_part && np <= d.ln_cap) ? np : 0;
-    if (!dd.ln_nparts) dd.ln_part = nullptr;
-    if (ln_nparts) *ln_nparts = dd.ln_nparts;
+    if (!LSTM) dd.ln_part = nullptr;
+    packed_ln_slots(dd, tpi * nb, ln_nparts);
     const int blocks = (d.B / ti_n) * tpi * nb;
-    pivp_fastdiv((unsigned)((d.B / ti_n) * tpi), &dd.fd_mb_mul, &dd.fd_mb_sh);      // tiles, tiles per image, tiles per row: the block's decode
-    pivp_fastdiv((unsigned)tpi, &dd.fd_hw_mul, &dd.fd_hw_sh);
-    pivp_fastdiv((unsigned)(d.Win / tw), &dd.fd_w_mul, &dd.fd_w_sh);
+    packed_decode_divisors(dd, (d.B / ti_n) * tpi, tpi, d.Win / tw);
     hipLaunchKernelGGL((convlstm_bf16_kernel<NCH, LSTM, PL>), dim3(blocks, ksplit), dim3(512), lds_bytes, stream, dd, wb, tw, ncols);
     return PIVP_LAUNCH_STATUS();
 }

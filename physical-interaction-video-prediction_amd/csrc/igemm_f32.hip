@@ -38,7 +38,7 @@
 #include <stdio.h>
 #include <type_traits>
 
-#include "pivp_kernels.h"
+#include "lstm_gate_epilogue.h"
 
 namespace pivp {
 
@@ -46,34 +46,6 @@ constexpr int IG_P = 36;  // LDS row pitch in floats (A and B tiles)
 
 template <int WM, int NTB, int KG = 1>
 constexpr int ig_lds_bytes() { return KG * 2 * (32 * WM + 32 * NTB) * IG_P * 4; }
-
-// sigmoid / tanh of the gate epilogue through v_exp_f32 / v_rcp_f32: |error| <= ~2e-7 absolute, an order
-// below the fp32 accumulation noise of the K = 1600..4800 dot products in front of them.
-// 1 / d as v_rcp_f32 plus one Newton step (3 instructions, error well under 1 ulp) instead of an IEEE division: __frcp_rn expands to
-// ~10 instructions (div_scale x2, rcp, 4 fma, div_fmas, div_fixup), 5 times per cell.  The bare 1-ulp v_rcp_f32 is not enough for the
-// parity path: through 9 recurrent steps and the STP warp of white-noise frames it moved tests/test_gpu_model.py's STP case past its gate.
-__device__ __forceinline__ float fast_rcp(float d) {
-    const float r = __builtin_amdgcn_rcpf(d);
-    return fmaf(fmaf(-d, r, 1.0f), r, r);
-}
-// (x is clamped at -87: below that exp(-x) is +inf, v_rcp_f32 returns 0 and the Newton step's inf * 0 is a NaN -- found in round 4 by a range test
-// of the split-precision kernels with pre-activations of -150, where this kernel wrote NaN cells; sigmoid(-87) = 1.6e-38)
-__device__ __forceinline__ float fast_sigmoid(float x) { return fast_rcp(1.0f + __expf(-fmaxf(x, -87.0f))); }
-// tanh: 2 / (1 + exp(-2x)) - 1 carries ~1.2e-7 of ABSOLUTE error at every x (the rounding of a value near 1), i.e. many ulps of a small
-// tanh; behind a LayerNorm that divides by the ~0.2 spread of h this was a third of the whole path's error against the float64 oracle
-// (scripts/gate_math_study.py: hidden1 3.7e-7 rms with libm's tanh, 4.7e-7 with that formula) and what put the STP fixture over 1e-4.
-// Here: |x| < 0.55: x + x^3 P(x^2), a degree-4 least-squares fit (3.3e-8 absolute, < 1 ulp relative); beyond: 1 - 2 / (1 + exp(2|x|)).
-__device__ __forceinline__ float fast_tanh(float x) {
-    const float a = fminf(fabsf(x), 15.0f);   // tanh(15) rounds to 1; keeps exp finite for the Newton step of fast_rcp
-    const float p = a * a;
-    float q = fmaf(p, -0.006149096414446831f, 0.02097311243414879f);
-    q = fmaf(p, q, -0.053824927657842636f);
-    q = fmaf(p, q, 0.13332274556159973f);
-    q = fmaf(p, q, -0.3333330452442169f);
-    const float small = fmaf(a * p, q, a);
-    const float big = fmaf(-2.0f, fast_rcp(1.0f + __expf(2.0f * a)), 1.0f);
-    return copysignf(a < 0.55f ? small : big, x);
-}
 
 #ifdef PIVP_F32_STAMPS   // per-block phase stamps (constant-rate 100 MHz counter) of the kernel: scripts/f32_stamps.py
 // second half of the array: the shader-cycle counter (s_memtime) at the same points; cycles / wall = the clock the chip holds in that phase
@@ -507,24 +479,10 @@ __global__ __launch_bounds__(256 * KG, (KG == 1 && LSTM && WM < 4) ? 2 : 1) void
         }
     };
     if constexpr (LSTM) {
-        // Accumulator row r of a lane is one anchor, its column (gate t * GPT + grp, channel): the 4 gates of a cell sit in the GPT
-        // lanes lane ^ (x * CPW) and the 4 / GPT tiles.  Lane grp takes rows r = k * GPT + grp: it keeps its own gate of that row
-        // and receives the others from its partners in GPT - 1 xor-shuffles per tile, each partner sending the row its receiver
-        // owns.  Every lane updates one cell per k (no idle lanes; GPT = 1 needs no exchange).  Register arrays are indexed
-        // statically; per-lane choices are select chains.
+        // (which accumulator row, lane and tile hold which gate of a cell: lstm_gate_epilogue.h; lane grp updates rows k * GPT + grp)
         const int C = d.C;
         const int ch = nblk * CB + wn * CPW + (l31 % CPW);
         const int grp = l31 / CPW;
-        auto pick = [&](const float (&v)[GPT], int idx) -> float {
-            if constexpr (GPT == 1) {
-                return v[0];
-            } else if constexpr (GPT == 2) {
-                return idx ? v[1] : v[0];
-            } else {
-                const float lo = (idx & 1) ? v[1] : v[0], hi = (idx & 1) ? v[3] : v[2];
-                return (idx & 2) ? hi : lo;
-            }
-        };
         // Stores go through buffer descriptors: the lane-dependent part of a cell's address (row mlane, channel) is ONE 32-bit offset,
         // the cell-dependent part (row k * GPT + grp -> srow(k) rows further) a scalar offset, and rows past M fall outside the
         // descriptor and are dropped by the hardware -- no 64-bit address arithmetic and no exec-mask region per cell.
@@ -541,33 +499,28 @@ __global__ __launch_bounds__(256 * KG, (KG == 1 && LSTM && WM < 4) ? 2 : 1) void
             float g4[4];
 #pragma unroll
             for (int t = 0; t < 4 / GPT; ++t) {
-                float rows[GPT], val[GPT];
+                float rows[GPT], got[GPT];
 #pragma unroll
                 for (int g = 0; g < GPT; ++g) rows[g] = acc[t][k * GPT + g];
-                val[0] = pick(rows, grp);
+                gate_exchange<GPT, CPW>(rows, grp, got);
 #pragma unroll
-                for (int x = 1; x < GPT; ++x) val[x] = __shfl_xor(pick(rows, grp ^ x), x * CPW, 64);
-#pragma unroll
-                for (int g = 0; g < GPT; ++g) g4[t * GPT + g] = pick(val, g ^ grp);
+                for (int g = 0; g < GPT; ++g) g4[t * GPT + g] = got[g];
             }
             // row r = k * GPT + grp of the wave tile is anchor (r & 3) + 8 (r >> 2) (+ 4 half): srow = the part that does not depend on grp
             const int srow = GPT == 1 ? (k & 3) + 8 * (k >> 2) : GPT == 2 ? 2 * (k & 1) + 8 * (k >> 1) : 8 * k;
             const int so = srow * C * 4;                     // scalar
-            const float aj = fast_tanh(g4[0] + bj), ai = fast_sigmoid(g4[1] + bi);
-            const float af = fast_sigmoid(g4[2] + bf), ao = fast_sigmoid(g4[3] + bo);
-            const float cn = cpre[k] * af + ai * aj;
-            const float hn = fast_tanh(cn) * ao;
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, cn), rsc, vo, so, 0);
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, hn), rsh, vo, so, 0);
+            const LstmCell cell = lstm_cell<GateActF32>(g4, bj, bi, bf, bo, cpre[k]);
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, cell.c), rsc, vo, so, 0);
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, cell.h), rsh, vo, so, 0);
             const bool in = mlane + srow < M;
-            sv[k] = in ? hn : 0.f;
+            sv[k] = in ? cell.h : 0.f;
             own |= in ? 1u << k : 0u;
             if (d.gates_out) {   // training: keep the gate activations for BPTT, [pixel][gate][C]
                 const int sog = so * 4;
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, aj), rsg, vog, sog, 0);
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, ai), rsg, vog, sog + C * 4, 0);
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, af), rsg, vog, sog + C * 8, 0);
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, ao), rsg, vog, sog + C * 12, 0);
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, cell.aj), rsg, vog, sog, 0);
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, cell.ai), rsg, vog, sog + C * 4, 0);
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, cell.af), rsg, vog, sog + C * 8, 0);
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, cell.ao), rsg, vog, sog + C * 12, 0);
             }
         }
         if (d.ln_part) {
