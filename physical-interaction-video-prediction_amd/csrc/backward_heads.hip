@@ -3,6 +3,7 @@
 #include <stdlib.h>
 
 #include "pivp_kernels.h"
+#include "frame_transform.h"
 
 namespace pivp {
 
@@ -79,10 +80,7 @@ __global__ __launch_bounds__(CBC_NT) void composite_bwd_cdna_kernel(const float*
     float* kl = prevt + 3 * PR * PW;             // [NM*25]
     const int tid = threadIdx.x;
     const float* lgb = logits + (size_t)b * NP * HW;
-    // exact x / NP for x * NP < 2^32 (see composite_kernel); staging loops without per-element division and with four
-    // independent loads in flight per thread (the flat-index loops of the first version made one L2 round trip per element)
-    const unsigned magic = 0xFFFFFFFFu / (unsigned)NP + 1u;
-    auto div_np = [&](int x) { return (int)__umulhi((unsigned)x, magic); };
+    const FlatSoftmax sx(NP);
     // Staging: EVERY load of the block is requested before the first LDS store, by all 1,024 threads (round 6).  Before, 256 threads walked the
     // logits planes four loads at a time -- plane after plane: 11 serial L2 round trips --, then the go planes (3 more) behind the frame tile.
     const float* pb = prev + (size_t)b * 3 * HW;
@@ -120,31 +118,10 @@ __global__ __launch_bounds__(CBC_NT) void composite_bwd_cdna_kernel(const float*
         }
     if (tid < NM * 25) kl[tid] = kv;
     __syncthreads();
-    for (int i = tid; i < NP * G; i += CBC_NT) {
-        const int m = i / G, gi = i - m * G;
-        const int gfirst = div_np(m * HW + ep0), glast = div_np(m * HW + ep0 + enp - 1);
-        if (gfirst + gi <= glast) {
-            const float* e = lg + m * win + (gfirst + gi) * NP - (m * HW + ep0 - (NP - 1));
-            float ev[12];
-#pragma unroll
-            for (int u = 0; u < 12; ++u) ev[u] = u < NP ? e[u] : -3.0e38f;
-            float mx = ev[0];
-#pragma unroll
-            for (int u = 1; u < 12; ++u) mx = fmaxf(mx, ev[u]);
-            float sum = 0.f;
-#pragma unroll
-            for (int u = 0; u < 12; ++u) sum += u < NP ? __expf(ev[u] - mx) : 0.f;
-            gmx[i] = mx; ginv[i] = 1.0f / sum;
-        }
-    }
+    sx.groups<ExpFast>(lg, win, G, HW, ep0, enp, gmx, ginv, tid, CBC_NT);
     __syncthreads();
-    for (int m = 0; m < NP; ++m) {
-        const int gbase = div_np(m * HW + ep0);
-        for (int pp = tid; pp < enp; pp += CBC_NT) {
-            const int gi = div_np(m * HW + ep0 + pp) - gbase;
-            mkx[m * PR * W + pp] = __expf(lg[m * win + pp + (NP - 1)] - gmx[m * G + gi]) * ginv[m * G + gi];
-        }
-    }
+    for (int m = 0; m < NP; ++m)
+        for (int pp = tid; pp < enp; pp += CBC_NT) mkx[m * PR * W + pp] = sx.at<ExpFast>(lg + m * win, gmx + m * G, ginv + m * G, HW, ep0, m, pp);
     __syncthreads();
     const int toff = (y0 - ey0) * W;             // tile offset inside the extended arrays
     const int np = rows * W;
@@ -331,12 +308,10 @@ __global__ __launch_bounds__(256) void composite_bwd_dna_kernel(const float* __r
             mk[m] = (F == g0 ? ea : ec) / (ea + ec);
         }
         m0x[pp] = mk[0];
-        float kn[25], S = 0.f;
+        float kw[25];
+        dna_weights([&](int i) { return eb[(size_t)i * HW + p]; }, kw);
 #pragma unroll
-        for (int i = 0; i < 25; ++i) { kn[i] = fmaxf(eb[(size_t)i * HW + p] - 1e-12f, 0.f) + 1e-12f; S += kn[i]; }
-        const float inv = 1.0f / S;
-#pragma unroll
-        for (int i = 0; i < 25; ++i) wx[i * PR * W + pp] = kn[i] * inv;
+        for (int i = 0; i < 25; ++i) wx[i * PR * W + pp] = kw[i];
 #pragma unroll
         for (int c = 0; c < 3; ++c) dtx[c * PR * W + pp] = mk[1] * gb[(size_t)c * HW + p];
     }
@@ -791,8 +766,7 @@ __global__ __launch_bounds__(CBS_NT) void composite_bwd_stp_kernel(const float* 
     else if (dprev)
         for (int i = tid; i < 3 * WR * W; i += CBS_NT) dwin[i] = 0.f;
     const float* lgb = logits + (size_t)b * NP * HW;
-    const unsigned magic = 0xFFFFFFFFu / (unsigned)NP + 1u;        // exact x / NP for x * NP < 2^32 (as in composite_bwd_cdna_kernel)
-    auto div_np = [&](int x) { return (int)__umulhi((unsigned)x, magic); };
+    const FlatSoftmax sx(NP);
   for (int tile = blockIdx.x; tile < (whole ? ntiles : (int)blockIdx.x + 1); tile += gridDim.x) {
     const int y0 = tile * CB_TR;
     const int rows = min(CB_TR, H - y0);
@@ -806,18 +780,7 @@ __global__ __launch_bounds__(CBS_NT) void composite_bwd_stp_kernel(const float* 
         lg[i] = (F >= 0 && F < NP * HW) ? lgb[F] : 0.f;
     }
     __syncthreads();
-    for (int i = tid; i < NP * G; i += CBS_NT) {
-        const int m = i / G, gi = i - m * G;
-        const int gfirst = div_np(m * HW + p0), glast = div_np(m * HW + p0 + np - 1);
-        if (gfirst + gi <= glast) {
-            const float* e = lg + m * win + (gfirst + gi) * NP - (m * HW + p0 - (NP - 1));
-            float mx = e[0];
-            for (int u = 1; u < NP; ++u) mx = fmaxf(mx, e[u]);
-            float sum = 0.f;
-            for (int u = 0; u < NP; ++u) sum += expf(e[u] - mx);
-            gmx[i] = mx; ginv[i] = 1.0f / sum;
-        }
-    }
+    sx.groups<ExpLibm>(lg, win, G, HW, p0, np, gmx, ginv, tid, CBS_NT);      // expf here, __expf in the forward kernels: kept as it was
     __syncthreads();
     const float* th = theta + (size_t)b * 6;
     const float* pb = prev + (size_t)b * 3 * HW;
@@ -826,23 +789,12 @@ __global__ __launch_bounds__(CBS_NT) void composite_bwd_stp_kernel(const float* 
         const int p = p0 + pp, y = p / W, x = p - y * W;
         float mk0 = 0.f, mk1 = 0.f, msum = 0.f;
         for (int m = 0; m < NP; ++m) {
-            const int gi = div_np(m * HW + p) - div_np(m * HW + p0);
-            const float v = expf(lg[m * win + pp + (NP - 1)] - gmx[m * G + gi]) * ginv[m * G + gi];
+            const float v = sx.at<ExpLibm>(lg + m * win, gmx + m * G, ginv + m * G, HW, p0, m, pp);
             if (m == 0) mk0 = v; else if (m == 1) mk1 = v; else msum += v;
         }
-        const double xs = -1.0 + 2.0 * (double)x / (double)(W - 1), ys = -1.0 + 2.0 * (double)y / (double)(H - 1);
-        double gu = (double)th[0] * xs + (double)th[1] * ys + (double)th[2];
-        double gv = (double)th[3] * xs + (double)th[4] * ys + (double)th[5];
-        bool live_u = true, live_v = true;
-        if (!stp_zero) {
-            live_u = gu > -1.0 && gu < 1.0; live_v = gv > -1.0 && gv < 1.0;
-            gu = fmin(fmax(gu, -1.0), 1.0); gv = fmin(fmax(gv, -1.0), 1.0);
-        }
-        const double u = (gu + 1.0) * (double)(W - 1) * 0.5, v = (gv + 1.0) * (double)(H - 1) * 0.5;
-        double u0 = floor(u), v0 = floor(v);
-        if (!stp_zero) { u0 = fmin(fmax(u0, 0.0), (double)(W - 2)); v0 = fmin(fmax(v0, 0.0), (double)(H - 2)); }
-        const float wu1 = (float)(u - u0), wv1 = (float)(v - v0);
-        const int iu = (int)u0, iv = (int)v0;
+        const StpSample sp = stp_sample(th, x, y, H, W, stp_zero);
+        const float wu1 = sp.wu1, wv1 = sp.wv1;
+        const int iu = sp.iu, iv = sp.iv;
         float dmq = 0.f, dmk0 = 0.f, dmk1 = 0.f, du = 0.f, dvv = 0.f;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
@@ -901,9 +853,9 @@ __global__ __launch_bounds__(CBS_NT) void composite_bwd_stp_kernel(const float* 
         float* dm = dmk + (size_t)b * NP * HW + p;
         dm[0] = dmk0; dm[(size_t)HW] = dmk1;
         for (int q = 2; q < NP; ++q) dm[(size_t)q * HW] = dmq;
-        const float dgu = live_u ? du * (float)(W - 1) * 0.5f : 0.f, dgv = live_v ? dvv * (float)(H - 1) * 0.5f : 0.f;
-        dth[0] += dgu * (float)xs; dth[1] += dgu * (float)ys; dth[2] += dgu;
-        dth[3] += dgv * (float)xs; dth[4] += dgv * (float)ys; dth[5] += dgv;
+        const float dgu = sp.live_u ? du * (float)(W - 1) * 0.5f : 0.f, dgv = sp.live_v ? dvv * (float)(H - 1) * 0.5f : 0.f;
+        dth[0] += dgu * (float)sp.xs; dth[1] += dgu * (float)sp.ys; dth[2] += dgu;
+        dth[3] += dgv * (float)sp.xs; dth[4] += dgv * (float)sp.ys; dth[5] += dgv;
     }
 #pragma unroll
     for (int j = 0; j < 6; ++j) dth[j] = wave_sum(dth[j]);

@@ -24,13 +24,13 @@
 // are 37 KB instead of 70 and two blocks share a CU.  The blend phase reuses the tiles for the blended CDNA kernels (MFMA outputs back to
 // "lane = pixel"); the group maxima live in the (dead) halo rows.
 #include "pivp_kernels.h"
+#include "frame_transform.h"
 
 namespace pivp {
 
 constexpr int FH_TR = 4;              // image rows per block (composite_kernel: 4 rows 12.2 us, 8 rows 14.3, 2 rows 14.2 at 64 x 64)
 constexpr int FH_XP = 36;             // floats per pixel row of the transposition tile (144 B: conflict-free per-lane ds_read_b128)
 constexpr int FH_TILE = 64 * FH_XP;   // floats per wave tile
-constexpr int FH_KL = 11 * 28;        // CDNA kernel table [11][28]
 constexpr int FH_MAXKS = 128;         // most K slices the in-kernel finisher takes (every block of a sample re-reads its KS x 1 KB of partial sums)
 constexpr int FH_HP = 68;             // floats per halo row (272 B)
 constexpr int FH_WP = 68;             // floats per row of the weight table [32 outputs][64 k]: per-lane rows (MFMA B operand, halo dots) read conflict-free
@@ -72,15 +72,14 @@ __global__ __launch_bounds__(FH_NT, 2) void frame_head_kernel(const FrameHeadArg
     float* lg = bl + 32;                         // [NP][win] mask logits of the band's windows
     float* l0t = lg + ((NP * win + 3) & ~3);     // [3][np] sigmoid(enc7) (CDNA / STP)
     float* kl = l0t + (MODE == 2 ? 0 : 3 * np);  // [11][28] CDNA kernels
-    float* vs = kl + FH_KL;                      // [256] finisher scratch
+    float* vs = kl + CDNA_KL;                      // [256] finisher scratch
     float* th = vs + 256;                        // [8] STP theta
     float* prevt = th + 8;                       // [3][FH_TR + 4][PW] previous-frame tile with its 2-pixel halo
     float* hal = prevt + ((3 * (FH_TR + 4) * PW + 3) & ~3);   // [2 (NP - 1)][FH_HP] normalised enc6 rows of the halo pixels
     float* un = hal + max(24 * FH_HP, (2 * NP * G + 3) & ~3);                // FH_HW wave tiles (transposition of the heads' operands / outputs, the finisher's chain sums, the blended kernels)
     float* gmx = hal;                            // (gmx, ginv) reuse the halo rows, dead behind barrier (2): the wave tiles serve the blend phase once more
     float* ginv = gmx + NP * G;
-    const unsigned magic = 0xFFFFFFFFu / (unsigned)NP + 1u;     // exact x / NP for x * NP < 2^32
-    auto div_np = [&](int x) { return (int)__umulhi((unsigned)x, magic); };
+    const FlatSoftmax sx(NP);
     const float* pb = a.prev + (size_t)b * 3 * HW;
     const int ntile = np / 64;                   // band tiles (the halo pixels are handled by all threads, below)
     FH_STAMP(0);
@@ -117,7 +116,7 @@ __global__ __launch_bounds__(FH_NT, 2) void frame_head_kernel(const FrameHeadArg
         if (MODE == 0) {
 #pragma unroll
             for (int u = 0; u < 2; ++u) {                    // 308 table entries
-                const int i2 = min(tid + FH_NT * u, FH_KL - 1), k = i2 / 28, e = i2 - k * 28;
+                const int i2 = min(tid + FH_NT * u, CDNA_KL - 1), k = i2 / 28, e = i2 - k * 28;
                 kv0[u] = a.aux[((size_t)b * NM + min(k, NM - 1)) * 25 + min(e, 24)];
             }
         } else {
@@ -183,7 +182,7 @@ __global__ __launch_bounds__(FH_NT, 2) void frame_head_kernel(const FrameHeadArg
 #pragma unroll                                                // the blend's MFMAs read all 10 rows)
         for (int u = 0; u < 2; ++u) {
             const int i2 = tid + FH_NT * u, k = i2 / 28, e = i2 - k * 28;
-            if (i2 < FH_KL) kl[i2] = (!a.partials && k < NM && e < 25) ? kv0[u] : 0.f;
+            if (i2 < CDNA_KL) kl[i2] = (!a.partials && k < NM && e < 25) ? kv0[u] : 0.f;
         }
     } else if (MODE == 1 && !a.partials && tid < 6) {
         th[tid] = kv0[0];
@@ -341,26 +340,7 @@ __global__ __launch_bounds__(FH_NT, 2) void frame_head_kernel(const FrameHeadArg
     FH_STAMP(9);
 
     // ---- per-group max and 1 / sum (groups of NP consecutive flat elements, TM:720-722); the transposition tiles are dead -------------
-    for (int i = tid; i < NP * G; i += FH_NT) {
-        const int m = i / G, gi = i - m * G;
-        const int gfirst = div_np(m * HW + p0);
-        const int glast = div_np(m * HW + p0 + np - 1);
-        if (gfirst + gi <= glast) {
-            const int j0 = (gfirst + gi) * NP - (m * HW + p0 - hn);
-            const float* e = lg + m * win + j0;
-            float ev[12];
-#pragma unroll
-            for (int u = 0; u < 12; ++u) { const float t = e[min(u, NP - 1)]; ev[u] = u < NP ? t : -3.0e38f; }   // clamped, not predicated: the 12 LDS reads go out together
-            float mx = ev[0];
-#pragma unroll
-            for (int u = 1; u < 12; ++u) mx = fmaxf(mx, ev[u]);
-            float sum = 0.f;
-#pragma unroll
-            for (int u = 0; u < 12; ++u) sum += u < NP ? __expf(ev[u] - mx) : 0.f;
-            gmx[i] = mx;
-            ginv[i] = 1.0f / sum;
-        }
-    }
+    sx.groups<ExpFast, true>(lg, win, G, HW, p0, np, gmx, ginv, tid, FH_NT);   // clamped, not predicated: the 12 LDS reads go out together
     FH_STAMP(12);
     // finisher, part 2: thread = output; join the four chains, bias, activation
     if (MODE != 2) {
@@ -423,10 +403,7 @@ __global__ __launch_bounds__(FH_NT, 2) void frame_head_kernel(const FrameHeadArg
 #pragma unroll
         for (int m = 0; m < 12; ++m) {                       // plane index clamped, not predicated: a predicate around the LDS reads made twelve
             const int mc = min(m, NP - 1);                   // dependent read -> wait -> exp chains of this loop (1.6 us by the stamps)
-            const int F = mc * HW + p;
-            const int gi = div_np(F) - div_np(mc * HW + p0);
-            const float v = lg[mc * win + pp + hn];
-            const float mv = __expf(v - gmx[mc * G + gi]) * ginv[mc * G + gi];
+            const float mv = sx.at<ExpFast>(lg + mc * win, gmx + mc * G, ginv + mc * G, HW, p0, mc, pp);
             mk[m] = m < NP ? mv : 0.f;
         }
         if (a.masks_out) {
@@ -474,65 +451,28 @@ __global__ __launch_bounds__(FH_NT, 2) void frame_head_kernel(const FrameHeadArg
             FH_STAMP(14);
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                const float* pt = prevt + (c * (FH_TR + 4) + ry) * PW + x;
-                float t = 0.f;
-#pragma unroll
-                for (int i = 0; i < 5; ++i)
-#pragma unroll
-                    for (int j = 0; j < 5; ++j) t = fmaf(keff[i * 5 + j], pt[i * PW + j], t);
-                const float pc = pt[2 * PW + 2];
+                const int at = (c * (FH_TR + 4) + ry) * PW + x;   // the pixel\'s upper-left tap in the tile
+                const float t = taps5x5(keff, prevt, at, PW);
+                const float pc = prevt[at + 2 * PW + 2];
                 o3[c] = mk[0] * pc + mk[1] * l0v[c] + t;
             }
         } else if (MODE == 1) {
-            const double xs = -1.0 + 2.0 * (double)x / (double)(W - 1);
-            const double ys = -1.0 + 2.0 * (double)y / (double)(H - 1);
-            double gu = (double)th[0] * xs + (double)th[1] * ys + (double)th[2];
-            double gv = (double)th[3] * xs + (double)th[4] * ys + (double)th[5];
-            if (!a.stp_zero) { gu = fmin(fmax(gu, -1.0), 1.0); gv = fmin(fmax(gv, -1.0), 1.0); }
-            const double u = (gu + 1.0) * (double)(W - 1) * 0.5;
-            const double v = (gv + 1.0) * (double)(H - 1) * 0.5;
-            double u0 = floor(u), v0 = floor(v);
-            if (!a.stp_zero) { u0 = fmin(fmax(u0, 0.0), (double)(W - 2)); v0 = fmin(fmax(v0, 0.0), (double)(H - 2)); }
-            const float wu1 = (float)(u - u0), wv1 = (float)(v - v0);
-            const int iu = (int)u0, iv = (int)v0;
-            float msum = 0.f;
-#pragma unroll
-            for (int q = 2; q < 12; ++q) msum += mk[q];
+            const StpSample sp = stp_sample(th, x, y, H, W, a.stp_zero);
+            const float msum = stp_mask_sum(mk);
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                float t = 0.f;
-#pragma unroll
-                for (int dv = 0; dv < 2; ++dv)
-#pragma unroll
-                    for (int du = 0; du < 2; ++du) {
-                        const int uu = iu + du, vv = iv + dv;
-                        const float wgt = (dv ? wv1 : 1.f - wv1) * (du ? wu1 : 1.f - wu1);
-                        if ((unsigned)uu < (unsigned)W && (unsigned)vv < (unsigned)H) t = fmaf(wgt, pb[(size_t)c * HW + vv * W + uu], t);
-                    }
+                const float t = stp_gather(pb, (size_t)c * HW, sp, H, W);
                 o3[c] = mk[0] * pb[(size_t)c * HW + p] + mk[1] * l0v[c] + msum * t;
             }
         } else {
             const float* e7 = a.enc7 + (size_t)b * 25 * HW;
-            float kn[25];
-            float sum = 0.f;
-#pragma unroll
-            for (int i = 0; i < 25; ++i) {
-                kn[i] = fmaxf(e7[(size_t)i * HW + p] - 1e-12f, 0.f) + 1e-12f;
-                sum += kn[i];
-            }
-            const float inv = 1.0f / sum;
+            float kw[25];
+            dna_weights([&](int i) { return e7[(size_t)i * HW + p]; }, kw);
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                const float* pt = prevt + (c * (FH_TR + 4) + ry) * PW + x;
-                float t = 0.f;
-#pragma unroll
-                for (int xk = 0; xk < 5; ++xk)
-#pragma unroll
-                    for (int yk = 0; yk < 5; ++yk) {
-                        const bool ok = (y + xk < H) && (x + yk < W);   // TM:400 slice quirk
-                        t = fmaf(kn[xk * 5 + yk] * inv, ok ? pt[xk * PW + yk] : 0.f, t);
-                    }
-                o3[c] = mk[0] * pt[2 * PW + 2] + mk[1] * t;
+                const int at = (c * (FH_TR + 4) + ry) * PW + x;   // the pixel\'s upper-left tap in the tile
+                const float t = dna_apply(kw, prevt, at, PW, y, x, H, W);
+                o3[c] = mk[0] * prevt[at + 2 * PW + 2] + mk[1] * t;
             }
         }
 #pragma unroll
@@ -543,7 +483,7 @@ __global__ __launch_bounds__(FH_NT, 2) void frame_head_kernel(const FrameHeadArg
 
 static size_t frame_head_lds_floats(int mode, int W, int NM) {
     const int NP = NM + 1, np = FH_TR * W, win = np + 2 * (NP - 1), G = np / NP + 2, PW = W + 4;
-    size_t f = (size_t)32 * FH_WP + 32 + ((NP * win + 3) & ~3) + (mode == 2 ? 0 : 3 * np) + FH_KL + 256 + 8;
+    size_t f = (size_t)32 * FH_WP + 32 + ((NP * win + 3) & ~3) + (mode == 2 ? 0 : 3 * np) + CDNA_KL + 256 + 8;
     const size_t halo = 24 * FH_HP, groups = (size_t)(2 * NP * G + 3) & ~(size_t)3;      // the halo rows, then (gmx, ginv), share one region
     f += ((3 * (FH_TR + 4) * PW + 3) & ~3) + (halo > groups ? halo : groups);
     return f + (size_t)FH_HW * FH_TILE;

@@ -2,6 +2,7 @@
 // generator, the STP parameter regressor, and the fused flat-softmax + transform + compositing
 // kernel that produces the next frame.  "TM" = src/models/train_model.py of the reference.
 #include "pivp_kernels.h"
+#include "frame_transform.h"
 #include "skinny_linear.h"
 
 namespace pivp {
@@ -204,12 +205,8 @@ int stp_params(const float* hidden5, const float* wt1, const float* b1, const fl
 // One block = one sample x 8 image rows; the frame tile with its 2-pixel halo, the logit windows
 // (tile +- NP-1 flat elements per plane) and the sample's kernels are staged in LDS.
 // ------------------------------------------------------------------------------------------
-// image rows per block.  Measured at B = 32, 64x64 (scripts/bench_tail_ops.py): 8 rows 14.3 us, 4 rows 12.2, 2 rows 14.2
-#ifndef PIVP_CP_TR
-#define PIVP_CP_TR 4
-#endif
-constexpr int CP_TR = PIVP_CP_TR;
-constexpr int CP_KL = 11 * 28;   // LDS floats of the CDNA kernel table
+// The arithmetic of each piece is frame_transform.h's; this kernel stages the operands and composes them.
+constexpr int CP_TR = BAND_TR;
 
 #ifdef PIVP_CP_STAMPS
 __device__ long long pivp_cp_stamps[8];
@@ -232,17 +229,14 @@ __global__ __launch_bounds__(256) void composite_kernel(const float* __restrict_
     const int win = np + 2 * (NP - 1);
     const int G = np / NP + 2;
     float* kl = sm;                         // [11][28] (CDNA: 25 taps per kernel + 3 pad); 16-B aligned rows
-    float* lg = sm + CP_KL;                 // [NP][win]
+    float* lg = sm + CDNA_KL;                 // [NP][win]
     float* gmx = lg + NP * win;             // [NP][G]
     float* ginv = gmx + NP * G;             // [NP][G]
     float* prevt = ginv + NP * G;           // [3][CP_TR+4][W+4]
     const int PW = W + 4;
     const int tid = threadIdx.x;
     const float* lgb = logits + (size_t)b * NP * HW;
-    // exact x / NP for x * NP < 2^32 (flat plane offsets are < 12 * H * W): one v_mul_hi instead of a ~35-instruction
-    // integer division, of which the first version executed two per mask plane and pixel
-    const unsigned magic = 0xFFFFFFFFu / (unsigned)NP + 1u;
-    auto div_np = [&](int x) { return (int)__umulhi((unsigned)x, magic); };
+    const FlatSoftmax sx(NP);
     CP_STAMP(0);
 
     // ---- staging: EVERY global load of the block is issued before the first LDS store, so the block pays one L2 / MALL
@@ -257,27 +251,11 @@ __global__ __launch_bounds__(256) void composite_kernel(const float* __restrict_
                 const int F = m * HW + p0 - (NP - 1) + jx;
                 tl[m][jj] = (m < NP && jx < win && F >= 0 && F < NP * HW) ? lgb[F] : 0.f;
             }
-        constexpr int PR = (CP_TR + 4 + 2) / 3;      // prev rows per thread when 256 / PW >= 3 (W <= 81), else looped below
-        float tp[3][PR];
+        float tp[3][BAND_PR];
         const float* pb = prev + (size_t)b * 3 * HW;
-        const int x = tid % PW, r0 = tid / PW, rstep = 256 / PW;   // PW <= 256 (checked by the launcher)
-        const bool prow = MODE != 1 && tid < rstep * PW;
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-#pragma unroll
-            for (int u = 0; u < PR; ++u) {
-                const int r = r0 + u * rstep, iy = y0 + r - 2, ix = x - 2;
-                tp[c][u] = (prow && r < CP_TR + 4 && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W)
-                               ? pb[(size_t)c * HW + iy * W + ix] : 0.f;
-            }
+        band_tile_request<3>(tp, pb, 3, MODE != 1, tid, y0, H, W);
         float tk[2] = {0.f, 0.f};
-        if (MODE == 0) {
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                const int i2 = tid + 256 * u, k = i2 / 28, e = i2 - k * 28;
-                tk[u] = (i2 < CP_KL && k < NM && e < 25) ? aux[((size_t)b * NM + k) * 25 + e] : 0.f;
-            }
-        }
+        if (MODE == 0) cdna_table_request(tk, aux, b, NM, tid);
 #pragma unroll
         for (int m = 0; m < 12; ++m)
 #pragma unroll
@@ -285,27 +263,8 @@ __global__ __launch_bounds__(256) void composite_kernel(const float* __restrict_
                 const int jx = tid + 256 * jj;
                 if (m < NP && jx < win) lg[m * win + jx] = tl[m][jj];
             }
-        if (prow) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c)
-#pragma unroll
-                for (int u = 0; u < PR; ++u) {
-                    const int r = r0 + u * rstep;
-                    if (r < CP_TR + 4) prevt[(c * (CP_TR + 4) + r) * PW + x] = tp[c][u];
-                }
-            for (int r = r0 + PR * rstep; r < CP_TR + 4; r += rstep) {   // wide frames: remaining rows
-                const int iy = y0 + r - 2, ix = x - 2;
-#pragma unroll
-                for (int c = 0; c < 3; ++c)
-                    prevt[(c * (CP_TR + 4) + r) * PW + x] =
-                        ((unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W) ? pb[(size_t)c * HW + iy * W + ix] : 0.f;
-            }
-        }
-        if (MODE == 0) {
-#pragma unroll
-            for (int u = 0; u < 2; ++u)
-                if (tid + 256 * u < CP_KL) kl[tid + 256 * u] = tk[u];
-        }
+        band_tile_file<3>(tp, prevt, pb, 3, MODE != 1, tid, y0, H, W);
+        if (MODE == 0) cdna_table_file(tk, kl, tid);
         for (int m = 0; m < NP; ++m)                              // rows wider than 3 x 256 window elements (W > 93)
             for (int jx = tid + 768; jx < win; jx += 256) {
                 const int F = m * HW + p0 - (NP - 1) + jx;
@@ -314,27 +273,7 @@ __global__ __launch_bounds__(256) void composite_kernel(const float* __restrict_
     }
     __syncthreads();
     CP_STAMP(1);
-    // ---- per-group max and 1/sum (groups of NP consecutive flat elements, TM:720-722) ---------------------------------
-    for (int i = tid; i < NP * G; i += 256) {
-        const int m = i / G, gi = i - m * G;
-        const int gfirst = div_np(m * HW + p0);
-        const int glast = div_np(m * HW + p0 + np - 1);
-        if (gfirst + gi <= glast) {
-            const int j0 = (gfirst + gi) * NP - (m * HW + p0 - (NP - 1));
-            const float* e = lg + m * win + j0;
-            float ev[12];
-#pragma unroll
-            for (int u = 0; u < 12; ++u) ev[u] = u < NP ? e[u] : -3.0e38f;   // all reads in flight together
-            float mx = ev[0];
-#pragma unroll
-            for (int u = 1; u < 12; ++u) mx = fmaxf(mx, ev[u]);
-            float sum = 0.f;
-#pragma unroll
-            for (int u = 0; u < 12; ++u) sum += u < NP ? __expf(ev[u] - mx) : 0.f;
-            gmx[i] = mx;
-            ginv[i] = 1.0f / sum;
-        }
-    }
+    sx.groups<ExpFast>(lg, win, G, HW, p0, np, gmx, ginv, tid, 256);
     __syncthreads();
 
     CP_STAMP(2);
@@ -351,10 +290,7 @@ __global__ __launch_bounds__(256) void composite_kernel(const float* __restrict_
 #pragma unroll
         for (int m = 0; m < 12; ++m) {
             if (m < NP) {
-                const int F = m * HW + p;
-                const int gi = div_np(F) - div_np(m * HW + p0);
-                const float v = lg[m * win + pp + (NP - 1)];
-                mk[m] = __expf(v - gmx[m * G + gi]) * ginv[m * G + gi];
+                mk[m] = sx.at<ExpFast>(lg + m * win, gmx + m * G, ginv + m * G, HW, p0, m, pp);
                 if (masks_out) masks_out[((size_t)b * NP + m) * HW + p] = mk[m];
             } else {
                 mk[m] = 0.f;
@@ -366,82 +302,33 @@ __global__ __launch_bounds__(256) void composite_kernel(const float* __restrict_
 #pragma unroll
             for (int i = 0; i < 25; ++i) keff[i] = 0.f;
 #pragma unroll
-            for (int k = 0; k < 10; ++k) {   // static indices keep mk[] in registers
-                if (k < NM - 1) {
-                    const float mq = mk[k + 2];
-                    float kv[28];   // kernel k's taps: 7 wave-uniform ds_read_b128
-#pragma unroll
-                    for (int q = 0; q < 7; ++q) {
-                        const f32x4 t4 = *reinterpret_cast<const f32x4*>(kl + k * 28 + q * 4);
-                        kv[q * 4] = t4[0]; kv[q * 4 + 1] = t4[1]; kv[q * 4 + 2] = t4[2]; kv[q * 4 + 3] = t4[3];
-                    }
-#pragma unroll
-                    for (int i = 0; i < 25; ++i) keff[i] = fmaf(mq, kv[i], keff[i]);
-                }
-            }
+            for (int k = 0; k < 10; ++k)
+                if (cdna_kernel_paired(k, NM)) cdna_blend_add(mk[k + 2], kl + k * 28, keff);
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                const float* pt = prevt + (c * (CP_TR + 4) + ry) * PW + x;
-                float t = 0.f;
-#pragma unroll
-                for (int i = 0; i < 5; ++i)
-#pragma unroll
-                    for (int j = 0; j < 5; ++j) t = fmaf(keff[i * 5 + j], pt[i * PW + j], t);
+                const int at = (c * (CP_TR + 4) + ry) * PW + x;
+                const float* pt = prevt + at;   // (the centre tap through the pointer: with prevt[at + ..] composite_kernel<2> takes 143 registers for 120)
+                const float t = taps5x5(keff, prevt, at, PW);
                 const float pc = pt[2 * PW + 2];
                 o3[c] = mk[0] * pc + mk[1] * l0v[c] + t;
             }
         } else if (MODE == 1) {
-            const float* th = aux + (size_t)b * 6;
-            // coordinates in fp64 (two dozen flops per pixel): a 1e-5 pixel error is visible at 1e-4 parity
-            const double xs = -1.0 + 2.0 * (double)x / (double)(W - 1);
-            const double ys = -1.0 + 2.0 * (double)y / (double)(H - 1);
-            double gu = (double)th[0] * xs + (double)th[1] * ys + (double)th[2];
-            double gv = (double)th[3] * xs + (double)th[4] * ys + (double)th[5];
-            if (!stp_zero) { gu = fmin(fmax(gu, -1.0), 1.0); gv = fmin(fmax(gv, -1.0), 1.0); }
-            const double u = (gu + 1.0) * (double)(W - 1) * 0.5;
-            const double v = (gv + 1.0) * (double)(H - 1) * 0.5;
-            double u0 = floor(u), v0 = floor(v);
-            if (!stp_zero) { u0 = fmin(fmax(u0, 0.0), (double)(W - 2)); v0 = fmin(fmax(v0, 0.0), (double)(H - 2)); }
-            const float wu1 = (float)(u - u0), wv1 = (float)(v - v0);
-            const int iu = (int)u0, iv = (int)v0;
-            float msum = 0.f;
-#pragma unroll
-            for (int q = 2; q < 12; ++q) msum += mk[q];   // mk[q >= NP] is 0
+            const StpSample sp = stp_sample(aux + (size_t)b * 6, x, y, H, W, stp_zero);
+            const float msum = stp_mask_sum(mk);
             const float* pb = prev + (size_t)b * 3 * HW;
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                float t = 0.f;
-#pragma unroll
-                for (int dv = 0; dv < 2; ++dv)
-#pragma unroll
-                    for (int du = 0; du < 2; ++du) {
-                        const int uu = iu + du, vv = iv + dv;
-                        const float wgt = (dv ? wv1 : 1.f - wv1) * (du ? wu1 : 1.f - wu1);
-                        if ((unsigned)uu < (unsigned)W && (unsigned)vv < (unsigned)H)
-                            t = fmaf(wgt, pb[(size_t)c * HW + vv * W + uu], t);
-                    }
+                const float t = stp_gather(pb, (size_t)c * HW, sp, H, W);
                 o3[c] = mk[0] * pb[(size_t)c * HW + p] + mk[1] * l0v[c] + msum * t;
             }
         } else {
-            float kn[25];
-            float sum = 0.f;
-#pragma unroll
-            for (int i = 0; i < 25; ++i) {
-                kn[i] = fmaxf(aux[((size_t)b * 25 + i) * HW + p] - 1e-12f, 0.f) + 1e-12f;
-                sum += kn[i];
-            }
-            const float inv = 1.0f / sum;
+            float kw[25];
+            dna_weights([&](int i) { return aux[((size_t)b * 25 + i) * HW + p]; }, kw);
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                const float* pt = prevt + (c * (CP_TR + 4) + ry) * PW + x;
-                float t = 0.f;
-#pragma unroll
-                for (int xk = 0; xk < 5; ++xk)
-#pragma unroll
-                    for (int yk = 0; yk < 5; ++yk) {
-                        const bool ok = (y + xk < H) && (x + yk < W);   // TM:400 slice quirk
-                        t = fmaf(kn[xk * 5 + yk] * inv, ok ? pt[xk * PW + yk] : 0.f, t);
-                    }
+                const int at = (c * (CP_TR + 4) + ry) * PW + x;
+                const float* pt = prevt + at;   // (the centre tap through the pointer: with prevt[at + ..] composite_kernel<2> takes 143 registers for 120)
+                const float t = dna_apply(kw, prevt, at, PW, y, x, H, W);
                 o3[c] = mk[0] * pt[2 * PW + 2] + mk[1] * t;
             }
         }
@@ -459,14 +346,6 @@ extern "C" int pivp_debug_cp_stamps(long long* out) {
 namespace pivp {
 #endif
 
-// bytes of LDS a composite block stages for a W-wide frame with num_masks masks
-static size_t composite_lds_bytes(int W, int num_masks) {
-    const int NP = num_masks + 1;
-    const int np = CP_TR * W;
-    const int win = np + 2 * (NP - 1);
-    const int G = np / NP + 2;
-    return sizeof(float) * ((size_t)NP * win + 2 * NP * G + 3 * (CP_TR + 4) * (W + 4) + CP_KL);
-}
 // the frames and mask counts composite() takes (what pivp_plan_create asks before it accepts a configuration: plan_serves_forward, plan.h)
 bool composite_serves(int H, int W, int num_masks, int mode) {
     if (H <= 1 || W <= 1 || num_masks < 1 || num_masks > 11 || mode < 0 || mode > 2) return false;
