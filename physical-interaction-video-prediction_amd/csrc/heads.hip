@@ -202,7 +202,7 @@ int stp_params(const float* hidden5, const float* wt1, const float* b1, const fl
 //   STP (TM:465-471): all NM-1 warps are the same affine warp -> (sum_{q>=2} m_q) * warp(prev).
 //   DNA (TM:392-415): per-pixel 25-tap kernel from enc7, with the reference's slice quirk
 //     (shifted copies are cut at H-xk / W-yk).
-// One block = one sample x 8 image rows; the frame tile with its 2-pixel halo, the logit windows
+// One block = one sample x CP_TR (4) image rows; the frame tile with its 2-pixel halo, the logit windows
 // (tile +- NP-1 flat elements per plane) and the sample's kernels are staged in LDS.
 // ------------------------------------------------------------------------------------------
 // The arithmetic of each piece is frame_transform.h's; this kernel stages the operands and composes them.
@@ -265,7 +265,7 @@ __global__ __launch_bounds__(256) void composite_kernel(const float* __restrict_
             }
         band_tile_file<3>(tp, prevt, pb, 3, MODE != 1, tid, y0, H, W);
         if (MODE == 0) cdna_table_file(tk, kl, tid);
-        for (int m = 0; m < NP; ++m)                              // rows wider than 3 x 256 window elements (W > 93)
+        for (int m = 0; m < NP; ++m)                              // windows longer than 3 x 256 elements (4 W + 2 (NP - 1) > 768: W >= 187 at 12 planes, 192 at 2)
             for (int jx = tid + 768; jx < win; jx += 256) {
                 const int F = m * HW + p0 - (NP - 1) + jx;
                 lg[m * win + jx] = (F >= 0 && F < NP * HW) ? lgb[F] : 0.f;

@@ -238,12 +238,19 @@ def heads(e6, Wm, bm, We, be, num_masks, model_type):
     return logits.cpu().numpy(), enc7.cpu().numpy(), layer0.cpu().numpy()
 
 
-def cdna_kernels(hidden5, W, b, num_masks):
-    lib = _lib.load()
+def _skinny_operands(key, hidden5, W, internal):
+    """-> B, K, device x, device wt.  internal: hidden5 is already the NHWC-flat [B][K] and W the K-major [K][256] operand (any K > 0)."""
+    if internal:
+        assert W.shape == (hidden5.shape[1], 256)
+        return hidden5.shape[0], hidden5.shape[1], _t(hidden5), _t(W)
     B, C, H, Wd = hidden5.shape
-    K = C * H * Wd
-    hd = nhwc(hidden5)
-    wd, bd = _t(pivp_amd.to_internal('model/cdna_kerns/W', W)), _t(b)
+    return B, C * H * Wd, nhwc(hidden5), _t(pivp_amd.to_internal(key, W))
+
+
+def cdna_kernels(hidden5, W, b, num_masks, internal=False):
+    lib = _lib.load()
+    B, K, hd, wd = _skinny_operands('model/cdna_kerns/W', hidden5, W, internal)
+    bd = _t(b)
     scratch = torch.empty(lib.pivp_linear_scratch_floats(B, K), dtype=torch.float32, device=DEV)
     kern = torch.empty((B, num_masks, 5, 5), dtype=torch.float32, device=DEV)
     _lib.check(lib.pivp_cdna_kernels(hd.data_ptr(), wd.data_ptr(), bd.data_ptr(), scratch.data_ptr(), kern.data_ptr(),
@@ -252,12 +259,10 @@ def cdna_kernels(hidden5, W, b, num_masks):
     return kern.cpu().numpy()
 
 
-def stp_params(hidden5, W1, b1, W2, b2):
+def stp_params(hidden5, W1, b1, W2, b2, internal=False):
     lib = _lib.load()
-    B, C, H, Wd = hidden5.shape
-    K = C * H * Wd
-    hd = nhwc(hidden5)
-    args = [_t(pivp_amd.to_internal('model/stp_input/W', W1)), _t(b1), _t(W2), _t(b2)]
+    B, K, hd, w1d = _skinny_operands('model/stp_input/W', hidden5, W1, internal)
+    args = [w1d, _t(b1), _t(W2), _t(b2)]
     scratch = torch.empty(lib.pivp_linear_scratch_floats(B, K), dtype=torch.float32, device=DEV)
     theta = torch.empty((B, 6), dtype=torch.float32, device=DEV)
     _lib.check(lib.pivp_stp_params(hd.data_ptr(), *[a.data_ptr() for a in args], scratch.data_ptr(), theta.data_ptr(),
