@@ -29,8 +29,7 @@ __device__ long long pivp_wg_stamps[2048 * 8];
 
 namespace pivp {
 
-constexpr int WG_PIX = 32;     // pixels (GEMM K) per chunk
-constexpr int WG_CI = 64;      // input channels per block
+// (WG_PIX = 32 pixels (GEMM K) per chunk, WG_CI = 64 input channels per block: wgrad_form.h, with the grid)
 constexpr int WG_XP = WG_CI + 4;   // LDS pitches (floats); +4 keeps 16-B alignment of rows
 
 // NT: 32-column MFMA tiles per wave; the block covers 64 input channels x 64*NT output columns.  NT = 1 for layers with at most
@@ -484,107 +483,58 @@ __global__ __launch_bounds__(256, 2) void wgrad5x5_kernel(const WgradDesc d) {
 }
 
 template <int SW>
-static int launch_wgrad5x5(const WgradDesc& d, hipStream_t s) {
-    constexpr int NTW = 1, OCC = 2;      // 32-column tiles per wave, resident blocks per CU (the kernel's launch bounds)
-    constexpr int R = 32 / SW, SP = R * (SW + 4);
-    constexpr int WBUF = SP * 32 + 32 * 32 * NTW;
-    constexpr int IMG = 5 * NTW * 32 * 33;
-    constexpr int NBUF = 2;
-    constexpr int lds_floats = (4 * NBUF * WBUF > 2 * IMG) ? 4 * NBUF * WBUF : 2 * IMG;
-    constexpr int lds_bytes = lds_floats * 4;
+static int launch_wgrad5x5(const WgradDesc& d, const WgradLaunch& L, hipStream_t s) {
+    constexpr int NTW = 1, NBUF = 2;      // as in wgrad5x5_kernel<SW>: 32-column tiles per wave, LDS buffers per wave
+    constexpr int R = 32 / SW, SP = R * (SW + 4), WBUF = SP * 32 + 32 * 32 * NTW, IMG = 5 * NTW * 32 * 33;
+    static_assert(row5x5_lds_bytes(SW) == ((4 * NBUF * WBUF > 2 * IMG) ? 4 * NBUF * WBUF : 2 * IMG) * 4, "wgrad_form.h states the kernel's staging buffers and reduction images");
     static PerDeviceOnce once;
-    if (pivp_ensure_dyn_lds(once, reinterpret_cast<const void*>(&wgrad5x5_kernel<SW>), lds_bytes) != PIVP_OK) return PIVP_ERR_LAUNCH;
-    const int tiles = 5 * (d.cin / 32) * (d.N / (32 * NTW));
-    const int chunks = d.M / 32 * (d.tcount > 1 ? d.tcount : 1);
-    // One block per CU is resident (~100 KB of LDS), so the grid is sized to whole rounds of the chip's CUs: the first
-    // version asked for "about 512" blocks and got 520-600, i.e. a third round that ran 8-88 blocks on 256 CUs (lstm7: 264 us
-    // for 171 us of MFMA work).  Take the fewest rounds (1..3) whose last round is at least 90 % full.
-    const int cus = pivp_cu_count() * OCC;   // resident blocks
-    int nsplit = 1;
-    double best = 0.0;
-    for (int r = 1; r <= 3; ++r) {
-        int ns = (cus * r) / tiles;
-        if (ns > chunks / 16) ns = chunks / 16;          // >= 4 chunks per wave
-        if (ns < 1) ns = 1;
-        const long blocks = (long)tiles * ns;
-        const double fill = (double)blocks / (double)(((blocks + cus - 1) / cus) * cus);
-        if (fill > best + 0.02) { best = fill; nsplit = ns; }
-        if (best >= 0.9) break;
-    }
-    hipLaunchKernelGGL((wgrad5x5_kernel<SW>), dim3(tiles, nsplit), dim3(256), lds_bytes, s, d);
+    if (pivp_ensure_dyn_lds(once, reinterpret_cast<const void*>(&wgrad5x5_kernel<SW>), L.lds_bytes) != PIVP_OK) return PIVP_ERR_LAUNCH;
+    hipLaunchKernelGGL((wgrad5x5_kernel<SW>), dim3(L.gx, L.gy), dim3(L.threads), L.lds_bytes, s, d);
+    return PIVP_LAUNCH_STATUS();
+}
+template <int NT>
+static int launch_generic(const WgradDesc& d, const WgradLaunch& L, hipStream_t s) {
+    WgradDesc dd = d;
+    if (!L.bias_rides) dd.db = nullptr;      // (the tap set does not qualify: run_wgrad launches bias_grad)
+    hipLaunchKernelGGL(igemm_wgrad_kernel<NT>, dim3(L.gx, L.gy), dim3(L.threads), 0, s, dd);
     return PIVP_LAUNCH_STATUS();
 }
 
-// wgrad5x5_kernel<SW> walks chunks of 32 consecutive pixels = 32 / SW whole image rows and takes the sample and the rows' bounds from a chunk's first pixel:
-// a map narrower than a chunk must be whole chunks deep (Hg % (32 / Wg) == 0), or a chunk would run over the end of a sample and pair the next sample's dY
-// rows with this one's X rows (6 x 8, 9 x 8, 9 x 16 maps: the generic kernel takes them).  The model's power-of-two maps all pass.
-static bool takes_fast_path(const WgradDesc& d) {
-    return !d.deconv && d.ksize == 5 && d.pad == 2 && d.stride == 1 && d.M % 32 == 0 && d.N % 64 == 0 &&
-           (d.Wg == 8 || d.Wg == 16 || d.Wg % 32 == 0) && (d.Wg >= 32 || d.Hg % (32 / d.Wg) == 0) && d.Hx == d.Hy && d.Wx == d.Wy;
-}
-// grid of the generic kernel: a function of the descriptor alone, so a launch, its partial buffer and its reduction agree
-static void generic_grid(const WgradDesc& d, int& wg_n, int& tiles, int& nsplit) {
-    wg_n = d.N <= 64 ? 64 : 128;
-    const int ncb = (d.cin + WG_CI - 1) / WG_CI, nnb = (d.N + wg_n - 1) / wg_n;
-    tiles = d.ksize * d.ksize * ncb * nnb;
-    const int chunks = (d.M + WG_PIX - 1) / WG_PIX;      // of ONE timestep: a batched launch, a single one and the reduction must agree on the planes
-    // direct path: every block ends with a tile of atomics (64 x 128), so no more pixel splits than fill the chip twice (3 blocks fit a
-    // CU) and >= 8 chunks (256 pixels) per block (enc4 with 4: 63 -> 94 us, atomics); kept for the partial-sum path, where a split
-    // costs 16-32 KB of traffic instead
-    // (round 5, call 15: a target of 256 / 384 / 1024 blocks instead of 512 gives config 3 11.50 / 11.27 / 11.27 ms against 11.18-11.22,
-    // fp32 train 28.02 against 27.85 with 256: 512 stays)
-    nsplit = (512 + tiles - 1) / tiles;
-    if (nsplit > chunks / 8) nsplit = chunks / 8;
-    if (nsplit < 1) nsplit = 1;
-}
-
-int igemm_wgrad(const WgradDesc& d, hipStream_t s, int* bias_done) {
-    if (bias_done) *bias_done = 0;
+// the fp32 forms' operands and sizes (the packed forms: wgrad5x5_packed_ok, wgrad_form.h, and wgrad5x5_bf16's pointer checks); asked in front of wgrad_launch,
+// whose grid rules divide by the tile counts
+int igemm_wgrad_check(const WgradDesc& d) {
     PIVP_CHECK_ARG(d.x0 && d.dy && d.dw && d.c0 > 0 && d.c0 % 32 == 0 && d.c1 >= 0 && d.c1 % 32 == 0 && (d.c1 == 0 || d.x1));
     PIVP_CHECK_ARG(d.cin == d.c0 + d.c1 && d.wcin >= d.cin && d.wcin % 32 == 0 && d.N > 0 && d.N % 32 == 0);
     PIVP_CHECK_ARG(d.M == d.B * d.Hg * d.Wg && d.M > 0 && d.ksize >= 1 && d.ksize <= 7);
     PIVP_CHECK_ARG(d.bytes0 > 0 && d.bytesy > 0 && (d.c1 == 0 || d.bytes1 > 0));
-    if (d.part && wgrad5x5p_ok(d)) {        // ConvLSTM 5x5, partial-slot form (round 6): no atomics; the column sums ride along
-        if (bias_done) *bias_done = d.db ? 1 : 0;
-        return wgrad5x5p(d, s);
-    }
-    if (takes_fast_path(d)) {
-        if (bias_done) *bias_done = d.db ? 1 : 0;
-        return d.Wg == 8 ? launch_wgrad5x5<8>(d, s) : d.Wg == 16 ? launch_wgrad5x5<16>(d, s) : launch_wgrad5x5<32>(d, s);
-    }
-    if (d.part && wgrad3x3s2_ok(d)) {      // stride-2 3x3: all nine taps from one staging (wgrad3x3s2.hip); the column sums ride along
-        if (bias_done) *bias_done = d.db ? 1 : 0;
-        return wgrad3x3s2(d, s);
-    }
-    int wg_n, tiles, nsplit;
-    generic_grid(d, wg_n, tiles, nsplit);
-    // the column sums ride along when the tap set qualifies: a 3x3 conv, or the transposed 3x3 s2 conv (see the kernel)
-    const bool bias_here = d.db && d.ksize == 3 && (!d.deconv || (d.Hy == 2 * d.Hx && d.Wy == 2 * d.Wx));
-    WgradDesc dd = d;
-    if (!bias_here) dd.db = nullptr;
-    if (bias_done) *bias_done = bias_here ? 1 : 0;
-    if (wg_n == 64) hipLaunchKernelGGL(igemm_wgrad_kernel<1>, dim3(tiles, nsplit), dim3(256), 0, s, dd);
-    else hipLaunchKernelGGL(igemm_wgrad_kernel<2>, dim3(tiles, nsplit), dim3(256), 0, s, dd);
-    return PIVP_LAUNCH_STATUS();
+    return PIVP_OK;
 }
 
-long long igemm_wgrad_part_floats(const WgradDesc& d) {
-    if (wgrad5x5p_ok(d)) return wgrad5x5p_part_floats(d);
-    if (takes_fast_path(d)) return 0;
-    if (wgrad3x3s2_ok(d)) return wgrad3x3s2_part_floats(d);
-    int wg_n, tiles, nsplit;
-    generic_grid(d, wg_n, tiles, nsplit);
-    return (long long)tiles * nsplit * 64 * wg_n;
+// Every weight gradient's launch: the form and the grid are L's (wgrad_form.h), here is the kernel instance each form names.
+int igemm_wgrad(const WgradDesc& d, const WgradLaunch& L, hipStream_t s) {
+    switch (L.form) {
+        case WgradForm::PackedRow_8: case WgradForm::PackedRow_16: case WgradForm::Packed25x4_8: case WgradForm::Packed25x4_16:
+        case WgradForm::Packed25x8_1_8: case WgradForm::Packed25x8_1_16: case WgradForm::Packed25x8_2_8: case WgradForm::Packed25x8_2_16:
+        case WgradForm::Packed25x8_3_8: case WgradForm::Packed25x8_3_16: return wgrad5x5_bf16(d, L, s);
+        case WgradForm::Slot5x5_8x1: case WgradForm::Slot5x5_8x2: case WgradForm::Slot5x5_16x1: case WgradForm::Slot5x5_16x2: return wgrad5x5p(d, L, s);
+        case WgradForm::Tile3x3s2_D2x2: case WgradForm::Tile3x3s2_D3x3: case WgradForm::Tile3x3s2_C1x1: return wgrad3x3s2(d, L, s);
+        case WgradForm::Row5x5_8: return launch_wgrad5x5<8>(d, L, s);
+        case WgradForm::Row5x5_16: return launch_wgrad5x5<16>(d, L, s);
+        case WgradForm::Row5x5_32: return launch_wgrad5x5<32>(d, L, s);
+        case WgradForm::Generic64: case WgradForm::Generic64Part: return launch_generic<1>(d, L, s);
+        case WgradForm::Generic128: case WgradForm::Generic128Part: return launch_generic<2>(d, L, s);
+        case WgradForm::None: return PIVP_ERR_BADARG;
+    }
+    return PIVP_ERR_BADARG;
 }
 
 int igemm_wgrad_reduce(const WgradDesc& d, hipStream_t s) {
     PIVP_CHECK_ARG(d.part && d.dw);
-    if (wgrad5x5p_ok(d)) return wgrad5x5p_reduce(d, s);
-    PIVP_CHECK_ARG(!takes_fast_path(d));
-    if (wgrad3x3s2_ok(d)) return wgrad3x3s2_reduce(d, s);
-    int wg_n, tiles, nsplit;
-    generic_grid(d, wg_n, tiles, nsplit);
-    hipLaunchKernelGGL(igemm_wgrad_reduce_kernel, dim3((64 * wg_n + 255) / 256, tiles), dim3(256), 0, s, d, wg_n, nsplit);
+    const WgradLaunch L = wgrad_launch(d, true);
+    if (wgrad_is_slot(L.form)) return wgrad5x5p_reduce(d, L, s);
+    if (wgrad_is_tile(L.form)) return wgrad3x3s2_reduce(d, L, s);
+    PIVP_CHECK_ARG(L.form == WgradForm::Generic64Part || L.form == WgradForm::Generic128Part);      // (the kernel-row form has no partial planes)
+    hipLaunchKernelGGL(igemm_wgrad_reduce_kernel, dim3(L.rgx, L.rgy), dim3(256), 0, s, d, L.form == WgradForm::Generic64Part ? 64 : 128, L.gy);
     return PIVP_LAUNCH_STATUS();
 }
 

@@ -276,7 +276,7 @@ void conv3x3s2_wgrad_geom(WgradDesc& d, int mode, int cin, int cout, int B, int 
     d.deconv = mode; d.ksize = 3; d.pad = 1; d.stride = 2;
     d.Hg = mode ? Hin : Hout; d.Wg = mode ? Win : Wout; d.M = B * d.Hg * d.Wg;
 }
-int run_wgrad(WgradDesc& d, hipStream_t s, int* bias_done, Operand form) {
+int run_wgrad(WgradDesc& d, hipStream_t s, Operand form, bool fixed_order) {
     if (!d.x1) d.c1 = 0;      // (the sweep's t = 0 has no h operand: its launch differentiates the x rows only)
     d.cin = d.c0 + d.c1;
     if (d.tcount < 1) d.tcount = 1;
@@ -284,32 +284,45 @@ int run_wgrad(WgradDesc& d, hipStream_t s, int* bias_done, Operand form) {
     if (!fits31(b0) || (d.x1 && !fits31(b1)) || !fits31(by)) return PIVP_ERR_BADARG;
     d.bytes0 = (int)b0; d.bytes1 = (int)b1; d.bytesy = (int)by;
     d.operand = form;
-    if (form != Operand::F32) {   // 5x5 ConvLSTM case only: operands as bf16 or as pieces, fp32 accumulation; db summed on the side in fp32
-        if (bias_done) *bias_done = d.db != nullptr;
-        return wgrad5x5_bf16(d, s);
+    if (form == Operand::F32) { const int rc = igemm_wgrad_check(d); if (rc != PIVP_OK) return rc; }
+    const WgradLaunch L = wgrad_launch(d, d.part != nullptr);
+    // a deterministic sweep's launch: pivp_plan_set_deterministic (det_supported, plan_setup.hip) asked wgrad_launch the same question through
+    // lstm_wgrad_part_floats and conv_backward_fixed_order below, so this does not happen
+    if (fixed_order && !wgrad_fixed_order(L.form)) return PIVP_ERR_STATE;
+    int rc = igemm_wgrad(d, L, s);
+    if (rc != PIVP_OK || !d.db || L.bias_rides) return rc;
+    for (int j = 0; j < d.tcount; ++j) {      // the kernel that ran does not sum dy's columns: one bias_grad launch per timestep
+        rc = bias_grad(reinterpret_cast<const float*>(reinterpret_cast<const char*>(d.dy) + j * d.ts_dy), d.ldy, d.N, d.B * d.Hy * d.Wy, d.db, s);
+        if (rc != PIVP_OK) return rc;
     }
-    return igemm_wgrad(d, s, bias_done);
+    return PIVP_OK;
+}
+// the shape's launch with a partial buffer, as the launch itself will ask for it
+static WgradLaunch lstm_wgrad_launch(int cx, int C, int has_h, int B, int H, int W, int slot_ntw, int slot_j) {
+    WgradDesc d;
+    lstm_wgrad_geom(d, cx, C, B, H, W);
+    d.slot_ntw = slot_ntw; d.slot_j = slot_j;
+    if (!has_h) { d.c1 = 0; d.cin = cx; }
+    return wgrad_launch(d, true);
 }
 long long conv_backward_part_floats(int mode, int cin, int cout, int B, int Hin, int Win) {
     WgradDesc d;
     conv3x3s2_wgrad_geom(d, mode, cin, cout, B, Hin, Win);
-    return igemm_wgrad_part_floats(d);
+    return wgrad_launch(d, true).part_floats;
 }
 bool conv_backward_fixed_order(int mode, int cin, int cout, int B, int Hin, int Win) {
     WgradDesc d;
     conv3x3s2_wgrad_geom(d, mode, cin, cout, B, Hin, Win);
-    return wgrad3x3s2_ok(d);
+    return wgrad_fixed_order(wgrad_launch(d, true).form);
 }
 // (the sweep's t = 0 has no h operand: its launch differentiates the x rows only -- fewer tiles, another partition of the same buffer, reduced on its own)
 long long lstm_wgrad_part_floats(int cx, int C, int B, int H, int W, int slot_ntw, int slot_j) {
     WgradDesc d;
     lstm_wgrad_geom(d, cx, C, B, H, W);
-    d.slot_ntw = slot_ntw; d.slot_j = slot_j;
-    if (!wgrad5x5p_ok(d)) return 0;
-    const long long full = wgrad5x5p_part_floats(d);
-    d.c1 = 0; d.cin = cx;
-    const long long xonly = wgrad5x5p_part_floats(d);
-    return full > xonly ? full : xonly;
+    if (!wp_ok_shape(wgrad_shape(d))) return 0;      // in front of wgrad_launch: the entries that size by this hand it unchecked widths, and the other forms' grid rules divide by them
+    const WgradLaunch full = lstm_wgrad_launch(cx, C, 1, B, H, W, slot_ntw, slot_j);
+    const WgradLaunch xonly = lstm_wgrad_launch(cx, C, 0, B, H, W, slot_ntw, slot_j);
+    return full.part_floats > xonly.part_floats ? full.part_floats : xonly.part_floats;
 }
 int lstm_wgrad_reduce(int cx, int C, int has_h, float* part, float* dW, float* db, int B, int H, int W, hipStream_t s, int slot_ntw, int slot_j) {
     WgradDesc d;
@@ -364,14 +377,12 @@ int run_convlstm_backward(const ConvLstmBwdArgs& a, hipStream_t s) {
     }
     if (rc != PIVP_OK) return rc;
     if (!a.dW) return PIVP_OK;   // the caller batches this layer's weight gradient over several timesteps itself (plan_backward.hip)
-    int bias_done = 0;   // the 5x5 weight-gradient kernel sums dG's columns on the side
     // (a single timestep's weight gradient: bf16 operands in that form, the fp32 kernel in every other)
     WgradDesc d;
     lstm_wgrad_geom(d, cx, C, B, H, W);
     d.x0 = a.x; d.ld0 = a.ldx; d.x1 = a.h_prev; d.dy = a.dG; d.dw = a.dW; d.db = a.db;
-    rc = run_wgrad(d, sw, &bias_done, a.operand == Operand::BF16 ? Operand::BF16 : Operand::F32);
+    rc = run_wgrad(d, sw, a.operand == Operand::BF16 ? Operand::BF16 : Operand::F32);
     if (rc != PIVP_OK) return rc;
-    if (!bias_done) { rc = bias_grad(a.dG, N, N, M, a.db, sw); if (rc != PIVP_OK) return rc; }
     return fork_end(a.fork);
 }
 
@@ -421,13 +432,11 @@ int run_conv_backward(const ConvBwdArgs& a, hipStream_t s) {
         if (rc != PIVP_OK) return rc;
     }
     if (!a.dW) return PIVP_OK;     // the caller batches this layer's weight gradient over several timesteps itself (plan_backward.hip); the fork's `ready` is recorded
-    int bias_done = 0;     // the weight-gradient kernel sums dY's columns on the side when it can
     WgradDesc d;
     conv3x3s2_wgrad_geom(d, mode, a.cin, a.cout, B, Hin, Win);
     d.x0 = a.x; d.ld0 = a.ldx; d.dy = a.dy; d.ldy = a.ldy; d.dw = a.dW; d.db = a.db; d.part = a.part;
-    rc = run_wgrad(d, sw, &bias_done, Operand::F32);
+    rc = run_wgrad(d, sw, Operand::F32);
     if (rc != PIVP_OK) return rc;
-    if (!bias_done) { rc = bias_grad(a.dy, a.ldy, a.cout, B * Hout * Wout, a.db, sw); if (rc != PIVP_OK) return rc; }
     return fork_end(a.fork);
 }
 
@@ -510,15 +519,12 @@ extern "C" long long pivp_conv_backward_part_floats(int mode, int cin, int cout,
 extern "C" int pivp_conv_wgrad_partial(int mode, const float* x, int cin, int ldx, const float* dy, int cout, int ldy, float* part,
                                        float* dW, float* db, int B, int Hin, int Win, int repeats, void* stream) {
     if (!x || !dy || !part || !dW || !db || mode < 0 || mode > 1 || repeats < 1) return PIVP_ERR_BADARG;
-    const int Hout = mode ? 2 * Hin : Hin / 2, Wout = mode ? 2 * Win : Win / 2;
     WgradDesc desc;
     conv3x3s2_wgrad_geom(desc, mode, cin, cout, B, Hin, Win);
     desc.x0 = x; desc.ld0 = ldx; desc.dy = dy; desc.ldy = ldy; desc.dw = dW; desc.db = db; desc.part = part;
     for (int r = 0; r < repeats; ++r) {
-        int bias_done = 0;
-        int rc = run_wgrad(desc, (hipStream_t)stream, &bias_done, Operand::F32);
+        const int rc = run_wgrad(desc, (hipStream_t)stream, Operand::F32);
         if (rc != PIVP_OK) return rc;
-        if (!bias_done) { rc = bias_grad(dy, ldy, cout, B * Hout * Wout, db, (hipStream_t)stream); if (rc != PIVP_OK) return rc; }
     }
     return igemm_wgrad_reduce(desc, (hipStream_t)stream);
 }
@@ -529,21 +535,12 @@ extern "C" int pivp_conv_wgrad_partial_batch(int mode, const float* x, int cin, 
                                              long long dy_step_bytes, int tcount, int overwrite, float* part, float* dW, float* db, int B, int Hin, int Win,
                                              void* stream) {
     if (!x || !dy || !part || !dW || !db || mode < 0 || mode > 1 || tcount < 1) return PIVP_ERR_BADARG;
-    const int Hout = mode ? 2 * Hin : Hin / 2, Wout = mode ? 2 * Win : Win / 2;
-    int bias_done = 0;
     WgradDesc d;
     conv3x3s2_wgrad_geom(d, mode, cin, cout, B, Hin, Win);
     d.x0 = x; d.ld0 = ldx; d.dy = dy; d.ldy = ldy; d.dw = dW; d.db = db;
     d.tcount = tcount; d.ts_x0 = x_step_bytes; d.ts_dy = dy_step_bytes;
     d.part = part; d.part_overwrite = overwrite ? 1 : 0;
-    int rc = run_wgrad(d, (hipStream_t)stream, &bias_done, Operand::F32);
-    if (rc != PIVP_OK) return rc;
-    if (!bias_done)
-        for (int j = 0; j < tcount; ++j) {
-            rc = bias_grad(reinterpret_cast<const float*>(reinterpret_cast<const char*>(dy) + j * dy_step_bytes), ldy, cout, B * Hout * Wout, db, (hipStream_t)stream);
-            if (rc != PIVP_OK) return rc;
-        }
-    return PIVP_OK;
+    return run_wgrad(d, (hipStream_t)stream, Operand::F32);
 }
 extern "C" int pivp_conv_wgrad_partial_reduce(int mode, int cin, int cout, float* part, float* dW, float* db, int B, int Hin, int Win, void* stream) {
     if (!part || !dW || !db || mode < 0 || mode > 1) return PIVP_ERR_BADARG;
@@ -570,19 +567,11 @@ extern "C" int pivp_wgrad5x5_f32_batch(const float* x, int cx, int ldx, const fl
                                        float* dW, float* db, int B, int H, int W, int tcount, long long ts_x, long long ts_h, long long ts_dG, int form,
                                        void* stream) {
     if (!x || !dG || !dW || tcount < 1 || form < 0 || form > 2 || (part && lstm_wgrad_part_floats(cx, C, B, H, W, form, 0) <= 0)) return PIVP_ERR_BADARG;
-    int bias_done = 0;
     WgradDesc d;
     lstm_wgrad_op(d, x, cx, ldx, h_prev, C, dG, dW, db, B, H, W, tcount, ts_x, ts_h, ts_dG);
     d.part = part; d.part_overwrite = overwrite ? 1 : 0;
     d.form = form; d.slot_ntw = form;      // (form: the wave form without part, the slot form's columns per wave with it)
-    int rc = run_wgrad(d, (hipStream_t)stream, &bias_done, Operand::F32);
-    if (rc != PIVP_OK) return rc;
-    if (db && !bias_done)
-        for (int j = 0; j < tcount; ++j) {
-            rc = bias_grad(reinterpret_cast<const float*>(reinterpret_cast<const char*>(dG) + j * ts_dG), 4 * C, 4 * C, B * H * W, db, (hipStream_t)stream);
-            if (rc != PIVP_OK) return rc;
-        }
-    return PIVP_OK;
+    return run_wgrad(d, (hipStream_t)stream, Operand::F32);
 }
 extern "C" int pivp_wgrad5x5_f32_reduce(int cx, int C, int has_h, float* part, float* dW, float* db, int B, int H, int W, int form, void* stream) {
     if (!part || !dW || form < 0 || form > 2 || lstm_wgrad_part_floats(cx, C, B, H, W, form, 0) <= 0) return PIVP_ERR_BADARG;
@@ -599,7 +588,6 @@ extern "C" int pivp_wgrad5x5_f32_partition(int cx, int C, int has_h, int B, int 
     lstm_wgrad_geom(d, cx, C, B, H, W);
     d.slot_ntw = form;
     if (!has_h) { d.c1 = 0; d.cin = cx; }
-    if (!wgrad5x5p_ok(d)) return PIVP_ERR_BADARG;
     return wgrad5x5p_partition(d, geom8, segs, seg_cap, nsegs, slots, slot_cap, nslots);
 }
 // The fp32 ConvLSTM data gradient on its own: a plain 5x5 stride-1 pad-2 convolution of x [B*H*W][cin] with wt (packed [25][cin/32][cout][32]: for the data
@@ -798,12 +786,19 @@ extern "C" int pivp_conv5x5_ep_ksplit(int precision, int cin, int cout, int ldo,
     return conv5x5_bf16_ksplit(d, (Operand)precision);
 }
 // ConvLSTM weight gradient with bf16 operands: dW (K-inner packed like the weight, [25][(cx+C)/32][4C][32]) += x|h^T . dG per tap.
+// (one body behind the five entries; each keeps its own argument checks: what an entry refuses is part of its contract)
+static int lstm_wgrad_packed_op(Operand operand, const float* x, int cx, int ldx, const float* h_prev, int C, const float* dG, float* dW, float* db, int B, int H,
+                                int W, int tcount, long long ts_x, long long ts_h, long long ts_dG, int form, const float* dy_absmax, void* stream) {
+    WgradDesc d;
+    lstm_wgrad_op(d, x, cx, ldx, h_prev, C, dG, dW, db, B, H, W, tcount, ts_x, ts_h, ts_dG);
+    d.form = form;
+    if (dy_absmax) { d.dy_absmax = dy_absmax; d.dy_absmax_stride = 72; }
+    return run_wgrad(d, (hipStream_t)stream, operand);
+}
 extern "C" int pivp_wgrad5x5_bf16(const float* x, int cx, int ldx, const float* h_prev, int C, const float* dG, float* dW, float* db,
                                   int B, int H, int W, void* stream) {
     if (!x || !dG || !dW || C <= 0 || cx <= 0) return PIVP_ERR_BADARG;
-    WgradDesc d;
-    lstm_wgrad_op(d, x, cx, ldx, h_prev, C, dG, dW, db, B, H, W, 1, 0, 0, 0);
-    return run_wgrad(d, (hipStream_t)stream, nullptr, Operand::BF16);
+    return lstm_wgrad_packed_op(Operand::BF16, x, cx, ldx, h_prev, C, dG, dW, db, B, H, W, 1, 0, 0, 0, 0, nullptr, stream);
 }
 // ... with two fp16 pieces per operand and three MFMAs per product (fp32-grade; the fp16x3 mode's weight gradient), a batch of timesteps as below:
 // scratch: 72 * tcount floats (the partial maxima of every timestep's dG: it is staged times a power of two from the largest of the batch)
@@ -816,37 +811,27 @@ extern "C" int pivp_wgrad5x5_fp16x3_batch(const float* x, int cx, int ldx, const
                                        scratch + (size_t)j * 72, (hipStream_t)stream);
         if (rc != PIVP_OK) return rc;
     }
-    WgradDesc d;
-    lstm_wgrad_op(d, x, cx, ldx, h_prev, C, dG, dW, db, B, H, W, tcount, ts_x, ts_h, ts_dG);
-    d.dy_absmax = scratch; d.dy_absmax_stride = 72;
-    return run_wgrad(d, (hipStream_t)stream, nullptr, Operand::FP16X3);
+    return lstm_wgrad_packed_op(Operand::FP16X3, x, cx, ldx, h_prev, C, dG, dW, db, B, H, W, tcount, ts_x, ts_h, ts_dG, 0, scratch, stream);
 }
 // ... with three bf16 pieces per operand and six MFMAs per product (fp32-grade, fp32's exponent range; the bf16x6 mode's weight gradient)
 extern "C" int pivp_wgrad5x5_bf16x6_batch(const float* x, int cx, int ldx, const float* h_prev, int C, const float* dG, float* dW, float* db,
                                           int B, int H, int W, int tcount, long long ts_x, long long ts_h, long long ts_dG, void* stream) {
     if (!x || !dG || !dW || C <= 0 || cx <= 0 || tcount < 1) return PIVP_ERR_BADARG;
-    WgradDesc d;
-    lstm_wgrad_op(d, x, cx, ldx, h_prev, C, dG, dW, db, B, H, W, tcount, ts_x, ts_h, ts_dG);
-    return run_wgrad(d, (hipStream_t)stream, nullptr, Operand::BF16X6);
+    return lstm_wgrad_packed_op(Operand::BF16X6, x, cx, ldx, h_prev, C, dG, dW, db, B, H, W, tcount, ts_x, ts_h, ts_dG, 0, nullptr, stream);
 }
 // ... of a BATCH of timesteps in one launch (the sum over pixels runs over timesteps too): timestep j reads x + j * ts_x, h_prev + j * ts_h,
 // dG + j * ts_dG (byte strides, multiples of 16, may be negative: the backward sweep walks time downwards)
 extern "C" int pivp_wgrad5x5_bf16_batch(const float* x, int cx, int ldx, const float* h_prev, int C, const float* dG, float* dW, float* db,
                                         int B, int H, int W, int tcount, long long ts_x, long long ts_h, long long ts_dG, void* stream) {
     if (!x || !dG || !dW || C <= 0 || cx <= 0 || tcount < 1) return PIVP_ERR_BADARG;
-    WgradDesc d;
-    lstm_wgrad_op(d, x, cx, ldx, h_prev, C, dG, dW, db, B, H, W, tcount, ts_x, ts_h, ts_dG);
-    return run_wgrad(d, (hipStream_t)stream, nullptr, Operand::BF16);
+    return lstm_wgrad_packed_op(Operand::BF16, x, cx, ldx, h_prev, C, dG, dW, db, B, H, W, tcount, ts_x, ts_h, ts_dG, 0, nullptr, stream);
 }
 // ... with the block form chosen by the caller: 1 = four-wave blocks (32 channels x 32 columns, about one per CU: they co-reside with the backward sweep's
 // small kernels), 2 = eight-wave blocks (32 x 64: half the patch traffic per multiply-add), 0 = by size as pivp_wgrad5x5_bf16_batch does
 extern "C" int pivp_wgrad5x5_bf16_batch_form(const float* x, int cx, int ldx, const float* h_prev, int C, const float* dG, float* dW, float* db,
                                              int B, int H, int W, int tcount, long long ts_x, long long ts_h, long long ts_dG, int form, void* stream) {
     if (!x || !dG || !dW || C <= 0 || cx <= 0 || tcount < 1 || form < 0 || form > 2) return PIVP_ERR_BADARG;
-    WgradDesc d;
-    lstm_wgrad_op(d, x, cx, ldx, h_prev, C, dG, dW, db, B, H, W, tcount, ts_x, ts_h, ts_dG);
-    d.form = form;
-    return run_wgrad(d, (hipStream_t)stream, nullptr, Operand::BF16);
+    return lstm_wgrad_packed_op(Operand::BF16, x, cx, ldx, h_prev, C, dG, dW, db, B, H, W, tcount, ts_x, ts_h, ts_dG, form, nullptr, stream);
 }
 static int convlstm_ln_cap(int H, int W, int C) {
     const int tiles = ((H * W + 31) / 32) * (C / 32), slices = ln_stats_slices(H * W * C);

@@ -103,9 +103,11 @@ int run_layernorm(const float* x, const float* g, const float* b, float* out, fl
 // ldy, dw, db) and the options it wants (tcount / ts_*, part / part_overwrite, dy_absmax, form, slot_*) by name; WgradDesc::operand is run_wgrad's to fill.
 void lstm_wgrad_geom(WgradDesc& d, int cx, int C, int B, int H, int W);                                 // 5x5 ConvLSTM: x0 = x [cx], x1 = h_prev [C], dy = dG [4C]
 void conv3x3s2_wgrad_geom(WgradDesc& d, int mode, int cin, int cout, int B, int Hin, int Win);      // conv3x3s2 (mode 0) / deconv3x3s2 (mode 1)
-// completes d (x1 == null: no h operand; a single timestep; the byte extents), checks them and launches in the given form.  Other than F32, 5x5 ConvLSTM case only:
-// BF16, BF16X6, FP16X3 (needs d.dy_absmax); BF16X3 has no weight-gradient form and is refused.  *bias_done: the launch sums dy's columns into d.db itself.
-int run_wgrad(WgradDesc& d, hipStream_t s, int* bias_done, Operand form);
+// The single host entry of every weight gradient.  Completes d (x1 == null: no h operand; a single timestep; the byte extents), asks wgrad_launch (wgrad_form.h)
+// for the form and the grid, launches, and where the kernel that ran does not sum dy's columns into d.db itself runs one bias_grad per timestep (dy + j * ts_dy).
+// Other than F32, 5x5 ConvLSTM case only: BF16, BF16X6, FP16X3 (needs d.dy_absmax); BF16X3 has no weight-gradient form and is refused.  fixed_order (deterministic
+// sweeps): PIVP_ERR_STATE in front of the launch unless the form sums in an order fixed by the shape (wgrad_fixed_order).
+int run_wgrad(WgradDesc& d, hipStream_t s, Operand form, bool fixed_order = false);
 // floats of WgradDesc::part a conv3x3s2 / deconv3x3s2 weight gradient of these sizes needs
 long long conv_backward_part_floats(int mode, int cin, int cout, int B, int Hin, int Win);
 bool conv_backward_fixed_order(int mode, int cin, int cout, int B, int Hin, int Win);      // the partial-plane form with its column sums (wgrad3x3s2) serves it

@@ -11,6 +11,7 @@
 #pragma once
 #include "pivp_common.h"
 #include "conv_form.h"
+#include "wgrad_form.h"
 
 namespace pivp {
 
@@ -35,10 +36,7 @@ constexpr int operand_pieces(Operand o) {
 constexpr bool operand_l2_direct(Operand o) { return o == Operand::BF16X6 || o == Operand::FP16X3; }
 // the operand is staged times a power of two taken from its absmax_partials
 constexpr bool operand_needs_scale(Operand o) { return o == Operand::FP16X3; }
-// The maps the packed-operand kernels' tiles serve (convlstm_bf16.hip, conv5x5_bf16.hip, wgrad_bf16.hip): 8 rows deep, and 16 wide or 8 wide with two images
-// to a tile (an even batch).  The one predicate of the kernels' own checks (bf16_geometry_ok, wgrad5x5_bf16_ok), of the forward's per-layer fall-back to fp32,
-// of the sweep's choice of a cell's data- and weight-gradient form (Modes, plan.h) and of the op entries' refusals: they must agree on every map.
-constexpr bool packed_tiles_serve(int H, int W, int B) { return H % 8 == 0 && (W % 16 == 0 || (W % 8 == 0 && B % 2 == 0)); }
+// (packed_tiles_serve, the maps the packed-operand kernels' tiles serve: wgrad_form.h)
 
 struct IgemmDesc {
     const float* x0; const float* x1;   // input sources (channel-concatenated: x0 then x1)
@@ -130,15 +128,15 @@ struct WgradDesc {
     int Hg, Wg, M;                       // anchor grid (conv: output pixels, deconv: input pixels), M = B*Hg*Wg
     int deconv, ksize, pad, stride;
     int bytes0, bytes1, bytesy;
-    float* db;                           // optional bias gradient [N] (column sums of dy), accumulated with atomics when the
-                                         // kernel that runs can do it on the side (*bias_done = 1), else left to bias_grad
+    float* db;                           // optional bias gradient [N] (column sums of dy): summed by the kernel that runs when it can do it on the
+                                         // side (WgradLaunch::bias_rides), else by the bias_grad launches run_wgrad adds
     // A batch of timesteps in one launch (the reduction of a weight gradient runs over pixels AND timesteps): operand j = 0..tcount-1
     // lives at x0 + j*ts_x0, x1 + j*ts_x1, dy + j*ts_dy (byte strides, may be negative); M, B, bytes* describe ONE timestep.
     // 0 / 1 = a single timestep.  Fewer, longer launches: one block epilogue (LDS reduction + atomics) per batch instead of per step.
     int tcount;
     long long ts_x0, ts_x1, ts_dy;
     // Generic kernel only: per-block partial sums instead of atomics.  Every (tile, pixel-split) block owns one [64][64 or 128] slot of
-    // `part` (igemm_wgrad_part_floats(d) floats, zeroed by the caller before the first launch) and adds its tile into it with plain
+    // `part` (WgradLaunch::part_floats floats, zeroed by the caller before the first launch) and adds its tile into it with plain
     // loads and stores; igemm_wgrad_reduce(d) then sums the splits into dw.  The scattered atomics of the direct path cost 54 of the
     // 85 us of an enc5 / enc6 launch (64 adds per address from 500 blocks).  The launches that share a slot must be stream-ordered.
     float* part;
@@ -147,33 +145,37 @@ struct WgradDesc {
     // timestep j's dy at dy_absmax + j * dy_absmax_stride floats (64 partial maxima at [2..65]): dy is staged times the power of two that puts the largest
     // |value| of the whole batch into [2^14, 2^15) -- gradients lie far below fp16's normal range -- and the sums are scaled back exactly.  Read by that form only.
     const float* dy_absmax; int dy_absmax_stride;
-    Operand operand;                     // filled by run_wgrad (host side only): F32 = the fp32 kernels; wgrad5x5_bf16 serves BF16, BF16X6 (three bf16 pieces, six MFMAs
-                                         // per product) and FP16X3 (needs dy_absmax); BF16X3 has no weight-gradient form
-    int form;                            // wgrad5x5_bf16, plain bf16 operands, a batch of timesteps: 0 = by size (four-wave blocks that co-reside with the main stream's
+    Operand operand;                     // filled by run_wgrad (host side only): F32 = the fp32 kernels; BF16, BF16X6 (three bf16 pieces, six MFMAs per product) and
+                                         // FP16X3 (needs dy_absmax) = the packed forms of wgrad_bf16.hip; BF16X3 has no weight-gradient form
+    // The hints of wgrad_launch (wgrad_form.h), which decides the form and the grid from this descriptor's geometry and them:
+    int form;                            // plain bf16 operands, a batch of timesteps: 0 = by size (four-wave blocks that co-reside with the main stream's
                                          // kernels for maps of up to 32 x 32 x 32 pixels per timestep, else eight-wave blocks), 1 = four-wave, 2 = eight-wave
-    // wgrad5x5p (the fp32 slot form) only -- its partition, which the batch launches, the slot buffer's size and the reduction must agree on:
+    // the fp32 slot form only -- its partition, which the batch launches, the slot buffer's size and the reduction must agree on:
     int slot_ntw;                        // 32-column MFMA tiles per wave: 0 = by shape (1), 1, 2 (needs N % 64 == 0)
     int slot_j;                          // blocks per XCD: 0 = two per CU of this device (the CU count decides the order of the sums), > 0 = this many
 };
-int igemm_wgrad(const WgradDesc& d, hipStream_t s, int* bias_done = nullptr);
-long long igemm_wgrad_part_floats(const WgradDesc& d);    // 0 when the ConvLSTM fast path would take this descriptor
-int igemm_wgrad_reduce(const WgradDesc& d, hipStream_t s);   // dw += sum over the splits of d.part
-// the stride-2 3x3 convs / transposed convs with all nine taps from one staging of the operands (csrc/wgrad3x3s2.hip): partial-sum path only;
-// igemm_wgrad / igemm_wgrad_part_floats / igemm_wgrad_reduce route to it when wgrad3x3s2_ok(d) and d.part is given
-bool wgrad3x3s2_ok(const WgradDesc& d);
-long long wgrad3x3s2_part_floats(const WgradDesc& d);
-int wgrad3x3s2(const WgradDesc& d, hipStream_t s);
-int wgrad3x3s2_reduce(const WgradDesc& d, hipStream_t s);
-// the fp32 ConvLSTM weight gradient with LDS-DMA staging, an XCD-aware balanced partition and per-segment partial slots (csrc/wgrad5x5p.hip): partial-sum
-// path only; igemm_wgrad / igemm_wgrad_part_floats / igemm_wgrad_reduce route to it when wgrad5x5p_ok(d) and d.part is given (db: column sums in the slots)
-bool wgrad5x5p_ok(const WgradDesc& d);
-long long wgrad5x5p_part_floats(const WgradDesc& d);
-int wgrad5x5p(const WgradDesc& d, hipStream_t s);
-int wgrad5x5p_reduce(const WgradDesc& d, hipStream_t s);
+// The descriptor's one-timestep geometry as wgrad_form.h takes it, and its answer for this descriptor on the current device.  with_part: the launch form
+// when a partial buffer is given (d.part != null for a launch; true for the buffer's size and the reduction, whatever d.part is).
+inline WgradShape wgrad_shape(const WgradDesc& d) {
+    return {d.c0, d.ld0, d.c1, d.ld1, d.cin, d.wcin, d.ldy, d.N, d.B, d.Hx, d.Wx, d.Hy, d.Wy, d.Hg, d.Wg, d.M, d.deconv, d.ksize, d.pad, d.stride,
+            !(d.ts_x0 % 16 || d.ts_x1 % 16 || d.ts_dy % 16)};
+}
+inline WgradLaunch wgrad_launch(const WgradDesc& d, bool with_part) {
+    return wgrad_launch(wgrad_shape(d), (int)d.operand, d.tcount, d.form, d.slot_ntw, d.slot_j, with_part, pivp_cu_count());
+}
+// Launches d in the form L = wgrad_launch(d, d.part != null) names (igemm_wgrad.hip; run_wgrad, pivp_c_api.hip, is the host's entry and runs the bias_grad
+// launches of a form whose bias does not ride).  igemm_wgrad_reduce: dw (and db) += the sums of d.part, for the forms that have a reduction.
+int igemm_wgrad_check(const WgradDesc& d);      // the fp32 forms' argument checks: in front of wgrad_launch
+int igemm_wgrad(const WgradDesc& d, const WgradLaunch& L, hipStream_t s);
+int igemm_wgrad_reduce(const WgradDesc& d, hipStream_t s);
+// the launchers of the forms whose kernels live in files of their own: the stride-2 3x3 tile form (wgrad3x3s2.hip), the fp32 slot form with LDS-DMA staging, an
+// XCD-aware balanced partition and per-segment partial slots (wgrad5x5p.hip), the packed-operand forms (wgrad_bf16.hip)
+int wgrad3x3s2(const WgradDesc& d, const WgradLaunch& L, hipStream_t s);
+int wgrad3x3s2_reduce(const WgradDesc& d, const WgradLaunch& L, hipStream_t s);
+int wgrad5x5p(const WgradDesc& d, const WgradLaunch& L, hipStream_t s);
+int wgrad5x5p_reduce(const WgradDesc& d, const WgradLaunch& L, hipStream_t s);
 int wgrad5x5p_partition(const WgradDesc& d, int* geom8, int* segs, int seg_cap, int* nsegs, int* slots, int slot_cap, int* nslots);   // host walk of the partition (tests)
-// bf16-operand form of the ConvLSTM weight gradient (csrc/wgrad_bf16.hip); the bias gradient is left to bias_grad
-bool wgrad5x5_bf16_ok(const WgradDesc& d);
-int wgrad5x5_bf16(const WgradDesc& d, hipStream_t s);
+int wgrad5x5_bf16(const WgradDesc& d, const WgradLaunch& L, hipStream_t s);
 int repack_transpose(const float* w, float* wt, int taps, int cin, int N, int flip, hipStream_t s);
 // Several weight preparations in ONE launch (the weights change once per optimizer step, so every train step rebuilds its packs: 7 + 12 + 7 launches
 // of a few microseconds each in the bf16 mode before round 5).  kind 0: repack_transpose(src, dst, taps = p0, cin = p1, N = p2, flip = p3);

@@ -169,7 +169,6 @@ struct Sweep {
         // starts as soon as this step's dG exists, next to this step's own data gradient
         hipStream_t sw = lane ? lane->stream : s;
         const int cnt = ss.wg_slot + 1;
-        int bias_done = 0;
         WgradDesc d;
         lstm_wgrad_geom(d, L.cx, L.C, B, m.H, m.W);
         d.x0 = wg_x[i]; d.ld0 = ldx; d.x1 = wg_h[i]; d.dy = ring; d.dw = G(&p, p.i_lstm_w[i]); d.db = G(&p, p.i_lstm_b[i]);
@@ -178,14 +177,14 @@ struct Sweep {
             // deterministic sweeps: the fp32 slot form (wgrad5x5p) in every precision mode -- each launch adds into the cell's slots (the sweep's first
             // stores), the slots are summed in a fixed order once: a t = 0 without h operand cuts the slots another way, so the batches with h are
             // reduced in front of it and its own launch behind it.  After a start from a state t = 0 has the K of the other batches and simply joins them.
-            // (the slot form takes every shape pivp_plan_set_deterministic admits, and it sums the columns of dG itself: bias_done is always set)
+            // (the slot form takes every shape pivp_plan_set_deterministic admits, and it sums the columns of dG itself: run_wgrad holds the launch to that)
             float* part = ws + g.lstm_part[i];
             const bool cut = t == 0 && !wg_h[i];
             if (cut && lstm_started[i])
                 RC(lstm_wgrad_reduce(L.cx, L.C, 1, part, G(&p, p.i_lstm_w[i]), G(&p, p.i_lstm_b[i]), B, m.H, m.W, sw, 0, DET_SLOT_J));
             d.part = part; d.part_overwrite = (cut || !lstm_started[i]) ? 1 : 0;
             d.slot_j = DET_SLOT_J;
-            RC(run_wgrad(d, sw, &bias_done, Operand::F32));
+            RC(run_wgrad(d, sw, Operand::F32, true));
             if (t == 0)
                 RC(lstm_wgrad_reduce(L.cx, L.C, wg_h[i] ? 1 : 0, part, G(&p, p.i_lstm_w[i]), G(&p, p.i_lstm_b[i]), B, m.H, m.W, sw, 0, DET_SLOT_J));
             else lstm_started[i] = true;
@@ -193,12 +192,9 @@ struct Sweep {
             const Operand wform = md.wgrad(m.H, m.W, B);
             if (operand_needs_scale(wform)) d.dy_absmax = absmax_ring;      // dG's partial maxima of the batch (run_convlstm_backward left them there)
             d.dy_absmax_stride = 72;
-            d.form = (long)B * c.height * c.width > 32L * 64 * 64 ? 2 : 0;      // (frames above 64 x 64 x 32: the eight-wave weight gradient on every layer)
-            RC(run_wgrad(d, sw, &bias_done, wform));
+            d.form = packed_form_hint(B, c.height, c.width);
+            RC(run_wgrad(d, sw, wform));
         }
-        if (!bias_done && p.det) return PIVP_ERR_STATE;      // (unreachable: see above)
-        if (!bias_done)
-            for (int j = 0; j < cnt; ++j) RC(bias_grad(ring + (size_t)j * dG1, N, N, B * m.H * m.W, G(&p, p.i_lstm_b[i]), sw));
         return lane ? lane->record_done(SLOT_LSTM + i, ss.wg_ring) : PIVP_OK;
     }
     // The side stream's weight gradients read dY buffers that a later step rewrites (enc0 / the motion head: the buffer of two timesteps ago; the stride-2
@@ -224,16 +220,12 @@ struct Sweep {
             if (forked) sw = f.side; else RC(fork_begin(&f, s, &sw));
         }
         const MapSize m = level_map(c, E.level);
-        int bias_done = 0;
         WgradDesc& d = enc_desc[k];      // kept: the sweep's last step reduces the partial planes by it
         conv3x3s2_wgrad_geom(d, E.mode, E.c, E.c, B, m.H, m.W);
         d.x0 = enc_x0[k]; d.ld0 = E.ldx; d.dy = dy0; d.ldy = E.ldy; d.dw = G(&p, p.i_enc_w[E.layer]); d.db = G(&p, p.i_enc_b[E.layer]);
         d.tcount = cnt; d.ts_x0 = -slab_bytes; d.ts_dy = dy_step;
         d.part = ws + g.wg_part[k]; d.part_overwrite = enc_started[k] ? 0 : 1;
-        RC(run_wgrad(d, sw, &bias_done, Operand::F32));
-        if (!bias_done && p.det) return PIVP_ERR_STATE;      // (unreachable: set_deterministic admits only shapes wgrad3x3s2 serves, column sums included)
-        if (!bias_done)
-            for (int j = 0; j < cnt; ++j) RC(bias_grad(dy0 + (size_t)j * (dy_step / 4), E.ldy, E.c, B * d.Hy * d.Wy, G(&p, p.i_enc_b[E.layer]), sw));
+        RC(run_wgrad(d, sw, Operand::F32, p.det != 0));      // (set_deterministic admits only shapes the tile form serves, column sums included)
         if (lane) RC(lane->record_done(SLOT_ENC + k, ss.eg_ring));
         enc_started[k] = true; enc_desc_valid[k] = true; enc_cnt[k] = 0;
         return PIVP_OK;

@@ -260,7 +260,8 @@ extern "C" int pivp_plan_set_precision(pivp_plan_t* plan, int precision_code) {
 }
 // Deterministic training (include/pivp_hip.h): every sum of the forward and the backward sweep in an order fixed by the problem shape.  Served:
 // precision F32, BF16 and BF16X3 (the ConvLSTM weight gradients then take the fp32 slot form, wgrad5x5p), models CDNA, STP and DNA, and shapes whose
-// cells fit wgrad5x5p and whose stride-2 3x3 layers fit wgrad3x3s2 (both with their column sums: no bias_grad launch is needed).
+// cells fit wgrad5x5p and whose stride-2 3x3 layers fit wgrad3x3s2 (both with their column sums: no bias_grad launch is needed) -- wgrad_fixed_order of the
+// form wgrad_launch (wgrad_form.h) names, the question run_wgrad asks again in front of each of the sweep's launches.
 static bool det_supported(const pivp_plan* p, Operand precision) {
     if (operand_l2_direct(precision)) return false;
     const int B = p->cfg.batch;

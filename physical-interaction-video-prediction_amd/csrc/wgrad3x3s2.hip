@@ -19,38 +19,7 @@ namespace pivp {
 namespace {
 __device__ float g_w3_zero[4];      // what out-of-map patch pixels (row -1 / column -1 of the big map) and the image's padding lanes load
 
-constexpr int W3_PW = 17, W3_PH = 9, W3_PPIX = W3_PW * W3_PH;     // patch of a 4 x 8 anchor chunk
-constexpr int W3_TARGET_BLOCKS = 256;
-constexpr int W3_BIAS_TAIL = 128;      // floats behind a block's [unit][16][64] accumulators: its column sums of dY (bias gradient), <= 96 used
-
-struct W3Shape { int deconv, TI, TJ, NW; };
-// which instance takes a layer (0 = none): transposed 96 -> 96 (enc5) as one 3 x 3-tile block of twelve waves (seven units each, six for the last three),
-// transposed convs on multiples of 64 channels (enc6, enc4) as 2 x 2-tile blocks of twelve waves (one kernel row of one tile each), convs (enc1, enc2) as
-// one-tile blocks of three waves (tiny layers: parallelism first).  Waves per block at B = 32, nine timesteps per launch (r05_c17 .. r05_c19): enc6 4 / 8 / 12
-// waves 265 / 244 / 235 us, enc4 76 / 69 / 67, enc5 8 / 12 waves 159 / 152, enc1 and enc2 3 / 9 waves 30 / 29.
-inline int w3_instance(const WgradDesc& d) {
-    if (d.ksize != 3 || d.stride != 2 || d.pad != 1 || d.c1 != 0 || d.cin != d.c0 || d.wcin != d.cin) return 0;
-    if (d.Hg % 4 || d.Wg % 8 || d.cin % 32 || d.N % 32 || d.ld0 % 4 || d.ldy % 4) return 0;
-    if (d.deconv) {
-        if (d.Hy != 2 * d.Hx || d.Wy != 2 * d.Wx || d.Hg != d.Hx || d.Wg != d.Wx) return 0;
-        if (d.cin == 96 && d.N == 96) return 2;
-        if (d.cin % 64 == 0 && d.N % 64 == 0) return 1;
-        return 0;
-    }
-    if (d.Hx != 2 * d.Hy || d.Wx != 2 * d.Wy || d.Hg != d.Hy || d.Wg != d.Wy) return 0;
-    return 3;
-}
-inline W3Shape w3_shape(int inst) {
-    return inst == 1 ? W3Shape{1, 2, 2, 12} : inst == 2 ? W3Shape{1, 3, 3, 12} : W3Shape{0, 1, 1, 3};
-}
-// grid: a function of the descriptor's ONE-timestep geometry alone, so every launch of a sweep, the partial buffer and the reduction agree
-inline void w3_grid(const WgradDesc& d, const W3Shape& sh, int& nblk, int& nsplit) {
-    nblk = (d.cin / (32 * sh.TI)) * (d.N / (32 * sh.TJ));
-    const int cpt = d.B * (d.Hg / 4) * (d.Wg / 8);
-    nsplit = W3_TARGET_BLOCKS / nblk;
-    if (nsplit > cpt) nsplit = cpt;
-    if (nsplit < 1) nsplit = 1;
-}
+// (the patch W3_PW x W3_PH of a chunk, the slots' bias tail W3_BIAS_TAIL, which instance takes a layer and its grid -- w3_instance, w3_shape, w3_grid: wgrad_form.h)
 }  // namespace
 
 template <bool DECONV, int TI, int TJ, int NW>
@@ -244,47 +213,32 @@ __global__ __launch_bounds__(256) void wgrad3x3s2_reduce_kernel(const WgradDesc 
     d.dw[(((size_t)tap * (d.wcin >> 5) + (ci >> 5)) * d.N + n) * 32 + (ci & 31)] += v;
 }
 
-bool wgrad3x3s2_ok(const WgradDesc& d) { return w3_instance(d) != 0; }
-
-long long wgrad3x3s2_part_floats(const WgradDesc& d) {
-    const int inst = w3_instance(d);
-    if (!inst) return 0;
-    const W3Shape sh = w3_shape(inst);
-    int nblk, nsplit;
-    w3_grid(d, sh, nblk, nsplit);
-    return (long long)nblk * nsplit * (sh.TI * sh.TJ * 9 * 1024 + W3_BIAS_TAIL);
-}
-
-template <bool DECONV, int TI, int TJ, int NW>
-static int launch_w3(const WgradDesc& d, int nblk, int nsplit, hipStream_t s) {
-    constexpr int CS = (DECONV ? TI : TJ) * 32, CB = (DECONV ? TJ : TI) * 32;
-    constexpr int TOT4 = W3_PPIX * CB / 4 + 32 * CS / 4, KL = (TOT4 + NW * 64 - 1) / (NW * 64);
-    constexpr int lds_bytes = 2 * KL * NW * 64 * 16;
+template <WgradForm F>
+static int launch_w3(const WgradDesc& d, const WgradLaunch& L, hipStream_t s) {
+    constexpr W3Shape sh = w3_shape(F);
+    constexpr int lds_bytes = w3_lds_bytes(sh);
     static_assert(lds_bytes <= 160 * 1024, "two chunk images must fit the CU's LDS");
     static PerDeviceOnce once;
-    const int rc = pivp_ensure_dyn_lds(once, reinterpret_cast<const void*>(&wgrad3x3s2_kernel<DECONV, TI, TJ, NW>), lds_bytes);
+    const int rc = pivp_ensure_dyn_lds(once, reinterpret_cast<const void*>(&wgrad3x3s2_kernel<sh.deconv != 0, sh.TI, sh.TJ, sh.NW>), lds_bytes);
     if (rc != PIVP_OK) return rc;
-    hipLaunchKernelGGL((wgrad3x3s2_kernel<DECONV, TI, TJ, NW>), dim3(nblk, nsplit), dim3(NW * 64), lds_bytes, s, d);
+    hipLaunchKernelGGL((wgrad3x3s2_kernel<sh.deconv != 0, sh.TI, sh.TJ, sh.NW>), dim3(L.gx, L.gy), dim3(L.threads), L.lds_bytes, s, d);
     return PIVP_LAUNCH_STATUS();
 }
 
-int wgrad3x3s2(const WgradDesc& d, hipStream_t s) {
-    const int inst = w3_instance(d);
-    PIVP_CHECK_ARG(inst && d.x0 && d.dy && d.part);
-    const W3Shape sh = w3_shape(inst);
-    int nblk, nsplit;
-    w3_grid(d, sh, nblk, nsplit);
-    return inst == 1 ? launch_w3<true, 2, 2, 12>(d, nblk, nsplit, s) : inst == 2 ? launch_w3<true, 3, 3, 12>(d, nblk, nsplit, s)
-                                                                                 : launch_w3<false, 1, 1, 3>(d, nblk, nsplit, s);
+int wgrad3x3s2(const WgradDesc& d, const WgradLaunch& L, hipStream_t s) {
+    PIVP_CHECK_ARG(d.x0 && d.dy && d.part);
+    switch (L.form) {
+        case WgradForm::Tile3x3s2_D2x2: return launch_w3<WgradForm::Tile3x3s2_D2x2>(d, L, s);
+        case WgradForm::Tile3x3s2_D3x3: return launch_w3<WgradForm::Tile3x3s2_D3x3>(d, L, s);
+        case WgradForm::Tile3x3s2_C1x1: return launch_w3<WgradForm::Tile3x3s2_C1x1>(d, L, s);
+        default: return PIVP_ERR_BADARG;
+    }
 }
 
-int wgrad3x3s2_reduce(const WgradDesc& d, hipStream_t s) {
-    const int inst = w3_instance(d);
-    PIVP_CHECK_ARG(inst && d.part && d.dw);
-    const W3Shape sh = w3_shape(inst);
-    int nblk, nsplit;
-    w3_grid(d, sh, nblk, nsplit);
-    hipLaunchKernelGGL(wgrad3x3s2_reduce_kernel, dim3(sh.TI * sh.TJ * 9 * 32 + sh.TJ, nblk), dim3(256), 0, s, d, sh.TI, sh.TJ, nblk, nsplit);
+int wgrad3x3s2_reduce(const WgradDesc& d, const WgradLaunch& L, hipStream_t s) {
+    PIVP_CHECK_ARG(wgrad_is_tile(L.form) && d.part && d.dw);
+    const W3Shape sh = w3_shape(L.form);
+    hipLaunchKernelGGL(wgrad3x3s2_reduce_kernel, dim3(L.rgx, L.rgy), dim3(256), 0, s, d, sh.TI, sh.TJ, L.gx, L.gy);
     return PIVP_LAUNCH_STATUS();
 }
 

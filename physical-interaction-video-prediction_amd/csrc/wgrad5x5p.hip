@@ -46,37 +46,12 @@ namespace pivp {
 namespace {
 __device__ float g_wgp_zero[4];      // what out-of-image strip pixels and the strip image's padding lanes load
 
-constexpr int WP_CH = 16;                  // pixels per chunk
 constexpr int WP_IT = 32 * 33;             // one 32 x 32 tile image of the block reduction (rows of 33: see wgrad5x5_kernel)
 constexpr int WP_IMG = 5 * WP_IT;
-constexpr int wp_nbuf(int ntw) { return ntw == 1 ? 3 : 2; }                       // LDS buffers per wave
-constexpr int wp_buf(int ntw) { return (2 * ntw + 3) * 256; }                      // floats per buffer: the dG tile's 2 NTW pieces, then the strip's three
-constexpr int wp_lds_floats(int ntw) { return 4 * wp_nbuf(ntw) * wp_buf(ntw); }   // 60 KiB / 56 KiB: two blocks per CU
-constexpr int wp_slot(int ntw) { return 5 * ntw * 1024 + 64; }                    // floats per segment slot: [t][kx][n][ci] + the bias tail (32 NTW used)
+// (WP_CH = 16 pixels per chunk, the buffers' and the slots' sizes wp_nbuf / wp_buf / wp_lds_floats / wp_slot, the partition WpPartition with wp_range and
+// wp_geom: wgrad_form.h, where the host decides the launch.  The kernels' argument keeps its name.)
 static_assert(2 * WP_IMG + 4 * 64 <= wp_lds_floats(1) && 2 * WP_IMG + 4 * 64 <= wp_lds_floats(2), "the block reduction's images live in the staging buffers");
-
-// The partition: shared by the kernel, the reduction and the host (slot count).  All quantities describe ONE timestep.
-struct WpGeom {
-    int J;              // blocks per XCD (grid = 8 J)
-    int PP, TP;         // pixel parts x tile parts = 8 (one pair per XCD)
-    int NTW;            // 32-column MFMA tiles per wave
-    int T;              // tiles = 5 * (cin / 32) * (N / (32 NTW)), ordered (nb, cb, ky)
-    int cpt;            // 16-pixel chunks per timestep
-    int maxseg;         // slots per block
-    int logW, logHW;    // the map is a power of two wide and high
-};
-struct WpRange { int t_lo, nt, c_lo, len; long long i0, i1; };
-__host__ __device__ inline WpRange wp_range(const WpGeom& g, int x, int j) {
-    WpRange r;
-    const int px = x % g.PP, tx = x / g.PP;
-    r.t_lo = (int)((long long)g.T * tx / g.TP);
-    r.nt = (int)((long long)g.T * (tx + 1) / g.TP) - r.t_lo;
-    r.c_lo = (int)((long long)g.cpt * px / g.PP);
-    r.len = (int)((long long)g.cpt * (px + 1) / g.PP) - r.c_lo;
-    const long long tot = (long long)r.nt * r.len;
-    r.i0 = tot * j / g.J; r.i1 = tot * (j + 1) / g.J;
-    return r;
-}
+struct WpGeom : WpPartition {};
 
 // the next segment of a block's item range [i, i1): tile (local index tl) and chunk range [k0, k1) of the part; advances i
 __host__ __device__ inline void wp_next_segment(const WpRange& r, long long& i, int& tl, int& k0, int& k1) {
@@ -108,46 +83,6 @@ __host__ __device__ inline int wp_for_each_slot(const WpGeom& g, int tile, F f) 
     return n;
 }
 
-inline bool wp_ok_shape(const WgradDesc& d) {
-    if (d.deconv || d.ksize != 5 || d.pad != 2 || d.stride != 1 || d.Hx != d.Hy || d.Wx != d.Wy) return false;
-    if (d.Wg < 8 || (d.Wg & (d.Wg - 1)) || (d.Hg & (d.Hg - 1)) || d.Hg < 2) return false;
-    if (d.M % WP_CH || d.N % 32 || d.cin % 32 || d.c0 % 32 || d.c1 % 32 || d.ld0 % 4 || d.ldy % 4 || (d.c1 && d.ld1 % 4)) return false;
-    return true;
-}
-inline int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
-// d.slot_ntw: 0 = by shape, 1 / 2 = 32 / 64 columns per wave (64 needs N % 64 == 0)
-inline int wp_ntw(const WgradDesc& d) {
-    if (d.N % 64) return 1;
-    if (d.slot_ntw == 1 || d.slot_ntw == 2) return d.slot_ntw;
-    return 1;
-}
-inline WpGeom wp_geom(const WgradDesc& d) {
-    WpGeom g;
-    g.J = d.slot_j > 0 ? d.slot_j : (2 * pivp_cu_count()) / 8;
-    if (g.J < 1) g.J = 1;
-    g.NTW = wp_ntw(d);
-    g.T = 5 * (d.cin / 32) * (d.N / (32 * g.NTW));
-    g.cpt = d.M / WP_CH;
-    // pixel parts: as many as keep the segment count near the block count (every tile of a part is cut once more per part) and a part's chunk
-    // range long enough for four waves
-    int pp = 8;
-    while (pp > 1 && ((long long)g.T * pp > 8LL * g.J || g.cpt / pp < 16)) pp >>= 1;
-    // (r06_c05, all six shapes at B = 32: one part against this rule within +-2 % -- lstm7 222.5 against 218.1 us --, eight parts on the small maps
-    // 5-25 % slower: lstm5 112.4 against 90.1)
-    while (8 / pp > g.T) pp <<= 1;               // (fewer tiles than tile parts: never with this model's layers)
-    g.PP = pp; g.TP = 8 / pp;
-    g.logW = ilog2(d.Wg); g.logHW = ilog2(d.Hg * d.Wg);
-    int ms = 1;
-    for (int x = 0; x < 8; ++x)
-        for (int j = 0; j < g.J; ++j) {
-            const WpRange r = wp_range(g, x, j);
-            if (r.i1 <= r.i0) continue;
-            const int segs = (int)((r.i1 - 1) / r.len - r.i0 / r.len) + 1;
-            if (segs > ms) ms = segs;
-        }
-    g.maxseg = ms;
-    return g;
-}
 template <int N> __device__ __forceinline__ void wp_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 }  // namespace
 
@@ -449,13 +384,12 @@ __global__ __launch_bounds__(256) void wgrad5x5p_reduce_kernel(const WgradDesc d
     if (bias) d.db[(nb * NTW + t) * 32 + tid] += sb;
 }
 
-bool wgrad5x5p_ok(const WgradDesc& d) { return wp_ok_shape(d); }
-
 // The partition as the kernel and the reduction see it, walked on the host (tests/test_host.py: no GPU).  segs: one (block, segment, tile, first chunk, end chunk)
 // quintuple per segment in the kernel's order; slots: per tile, the reduction's list as (tile, slot) pairs.  Returns the counts; nothing is written past the caps.
 int wgrad5x5p_partition(const WgradDesc& d, int* geom8, int* segs, int seg_cap, int* nsegs, int* slots, int slot_cap, int* nslots) {
-    PIVP_CHECK_ARG(wp_ok_shape(d) && geom8 && nsegs && nslots);
-    const WpGeom g = wp_geom(d);
+    const WgradLaunch L = wgrad_launch(d, true);
+    PIVP_CHECK_ARG(wgrad_is_slot(L.form) && geom8 && nsegs && nslots);
+    const WpGeom g{L.wp};
     geom8[0] = g.J; geom8[1] = g.PP; geom8[2] = g.TP; geom8[3] = g.NTW; geom8[4] = g.T; geom8[5] = g.cpt; geom8[6] = g.maxseg; geom8[7] = wp_slot(g.NTW);
     int ns = 0;
     for (int L = 0; L < 8 * g.J; ++L) {
@@ -476,32 +410,28 @@ int wgrad5x5p_partition(const WgradDesc& d, int* geom8, int* segs, int seg_cap, 
     return PIVP_OK;
 }
 
-long long wgrad5x5p_part_floats(const WgradDesc& d) {
-    if (!wp_ok_shape(d)) return 0;
-    const WpGeom g = wp_geom(d);
-    return (long long)8 * g.J * g.maxseg * wp_slot(g.NTW);
-}
-
 template <int SW, int NTW>
-static int launch_wp(const WgradDesc& d, const WpGeom& g, hipStream_t s) {
-    constexpr int lds_bytes = wp_lds_floats(NTW) * 4;
+static int launch_wp(const WgradDesc& d, const WgradLaunch& L, hipStream_t s) {
     static PerDeviceOnce once;
-    if (pivp_ensure_dyn_lds(once, reinterpret_cast<const void*>(&wgrad5x5p_kernel<SW, NTW>), lds_bytes) != PIVP_OK) return PIVP_ERR_LAUNCH;
-    hipLaunchKernelGGL((wgrad5x5p_kernel<SW, NTW>), dim3(8 * g.J), dim3(256), lds_bytes, s, d, g);
+    if (pivp_ensure_dyn_lds(once, reinterpret_cast<const void*>(&wgrad5x5p_kernel<SW, NTW>), L.lds_bytes) != PIVP_OK) return PIVP_ERR_LAUNCH;
+    hipLaunchKernelGGL((wgrad5x5p_kernel<SW, NTW>), dim3(L.gx), dim3(L.threads), L.lds_bytes, s, d, WpGeom{L.wp});
     return PIVP_LAUNCH_STATUS();
 }
 
-int wgrad5x5p(const WgradDesc& d, hipStream_t s) {
-    PIVP_CHECK_ARG(wp_ok_shape(d) && d.x0 && d.dy && d.part && (d.c1 == 0 || d.x1) && d.cin == d.c0 + d.c1 && d.M == d.B * d.Hg * d.Wg);
-    const WpGeom g = wp_geom(d);
-    if (g.NTW == 2) return d.Wg >= 16 ? launch_wp<16, 2>(d, g, s) : launch_wp<8, 2>(d, g, s);
-    return d.Wg >= 16 ? launch_wp<16, 1>(d, g, s) : launch_wp<8, 1>(d, g, s);
+int wgrad5x5p(const WgradDesc& d, const WgradLaunch& L, hipStream_t s) {
+    PIVP_CHECK_ARG(d.x0 && d.dy && d.part && (d.c1 == 0 || d.x1) && d.cin == d.c0 + d.c1 && d.M == d.B * d.Hg * d.Wg);
+    switch (L.form) {
+        case WgradForm::Slot5x5_8x1: return launch_wp<8, 1>(d, L, s);
+        case WgradForm::Slot5x5_8x2: return launch_wp<8, 2>(d, L, s);
+        case WgradForm::Slot5x5_16x1: return launch_wp<16, 1>(d, L, s);
+        case WgradForm::Slot5x5_16x2: return launch_wp<16, 2>(d, L, s);
+        default: return PIVP_ERR_BADARG;
+    }
 }
 
-int wgrad5x5p_reduce(const WgradDesc& d, hipStream_t s) {
-    PIVP_CHECK_ARG(wp_ok_shape(d) && d.part && d.dw && d.wcin >= d.cin && d.wcin % 32 == 0);
-    const WpGeom g = wp_geom(d);
-    hipLaunchKernelGGL(wgrad5x5p_reduce_kernel, dim3(g.T * 5 * g.NTW), dim3(256), 0, s, d, g);
+int wgrad5x5p_reduce(const WgradDesc& d, const WgradLaunch& L, hipStream_t s) {
+    PIVP_CHECK_ARG(wgrad_is_slot(L.form) && d.part && d.dw && d.wcin >= d.cin && d.wcin % 32 == 0);
+    hipLaunchKernelGGL(wgrad5x5p_reduce_kernel, dim3(L.rgx), dim3(256), 0, s, d, WpGeom{L.wp});
     return PIVP_LAUNCH_STATUS();
 }
 

@@ -505,95 +505,34 @@ __global__ __launch_bounds__(64 * NW, 1) void wgrad25_bf16_kernel(const WgradDes
     }
 }
 
-bool wgrad5x5_bf16_ok(const WgradDesc& d) {
-    if (d.deconv || d.ksize != 5 || d.pad != 2 || d.stride != 1 || d.Hx != d.Hy || d.Wx != d.Wy) return false;
-    if (d.N % 128 || d.cin % 32 || d.c0 % 32 || d.c1 % 32 || d.ld0 % 4 || d.ld1 % 4 || d.ldy % 4) return false;
-    if (d.tcount > 1 && (d.ts_x0 % 16 || d.ts_x1 % 16 || d.ts_dy % 16)) return false;
-    return packed_tiles_serve(d.Hx, d.Wx, d.B);
-}
+static_assert(PACKED_ROW_LDS == G_BYTES + X_BYTES && PACKED25_GH == W25_GH && PACKED25_X == W25_X_BYTES, "wgrad_form.h states the kernels' LDS images");
 
-// the 25-tap kernel: grid = (cin / 32) x (N / 64) output slices x pixel splits over the tiles of ALL timesteps of the batch
-// four-wave blocks (the bf16 mode's batched launches): about one per CU, beside the main stream's kernels
-static int launch_wgrad25_nw4(const WgradDesc& d, hipStream_t s) {
-    constexpr int lds_bytes = W25_GH + W25_X_BYTES;
-    const int tw = d.Wx % 16 == 0 ? 16 : 8, ti_n = tw == 16 ? 1 : 2;
-    const int n_tiles = (d.B / ti_n) * (d.Hx / 8) * (d.Wx / tw) * (d.tcount > 1 ? d.tcount : 1);
-    const int gx = (d.cin / 32) * (d.N / 32);
-    int ns = (pivp_cu_count() + gx - 1) / gx;      // about one block per CU (config 3's step against the block target: 128: 11.84 ms, 256: 11.28, 384: 11.25, 512: 11.60)
-    if (ns > n_tiles / 2) ns = n_tiles / 2;
-    if (ns < 1) ns = 1;
-    const int tps = (n_tiles + ns - 1) / ns;
-    ns = (n_tiles + tps - 1) / tps;
-    if (tw == 16) hipLaunchKernelGGL((wgrad25_bf16_kernel<16, 1, 4>), dim3(gx, ns), dim3(256), lds_bytes, s, d, tps);
-    else hipLaunchKernelGGL((wgrad25_bf16_kernel<8, 1, 4>), dim3(gx, ns), dim3(256), lds_bytes, s, d, tps);
-    return PIVP_LAUNCH_STATUS();
-}
-template <int PCS>
-static int launch_wgrad25(const WgradDesc& d, hipStream_t s) {
-    constexpr int lds_bytes = PCS * (W25_G_BYTES + W25_X_BYTES);
-    static PerDeviceOnce once16, once8;
-    if (pivp_ensure_dyn_lds(once16, reinterpret_cast<const void*>(&wgrad25_bf16_kernel<16, PCS>), lds_bytes) != PIVP_OK ||
-        pivp_ensure_dyn_lds(once8, reinterpret_cast<const void*>(&wgrad25_bf16_kernel<8, PCS>), lds_bytes) != PIVP_OK)
-        return PIVP_ERR_LAUNCH;
-    const int tw = d.Wx % 16 == 0 ? 16 : 8, ti_n = tw == 16 ? 1 : 2;
-    const int n_tiles = (d.B / ti_n) * (d.Hx / 8) * (d.Wx / tw) * (d.tcount > 1 ? d.tcount : 1);
-    const int gx = (d.cin / 32) * (d.N / 64);
-    // Pixel splits: one block per CU (8 waves, ~70 KB of LDS), at least 2 tiles per block; every split ends with 25 x 32 x 64 atomic adds
-    // (205 KB: the batch of timesteps is what amortises them).
-    // (fp16 pieces: its 8-wave blocks hold a CU's whole register file, and the sweep's small kernels need CUs without one: half the CUs)
-    // bf16: three quarters (train step 11.86 -> 11.66 ms, profiles/r04/bf16_train_wgrad_batch_slots.txt)
-    const int target = PCS >= 2 ? pivp_cu_count() / 2 : pivp_cu_count() * 3 / 4;
-    int ns = (target + gx - 1) / gx;
-    if (ns > n_tiles / 2) ns = n_tiles / 2;
-    if (ns < 1) ns = 1;
-    const int tps = (n_tiles + ns - 1) / ns;
-    ns = (n_tiles + tps - 1) / tps;
-    if (tw == 16) hipLaunchKernelGGL((wgrad25_bf16_kernel<16, PCS>), dim3(gx, ns), dim3(512), lds_bytes, s, d, tps);
-    else hipLaunchKernelGGL((wgrad25_bf16_kernel<8, PCS>), dim3(gx, ns), dim3(512), lds_bytes, s, d, tps);
+template <void (*K)(const WgradDesc, int)>
+static int launch_packed(const WgradDesc& d, const WgradLaunch& L, hipStream_t s) {
+    static PerDeviceOnce once;
+    if (pivp_ensure_dyn_lds(once, reinterpret_cast<const void*>(K), L.lds_bytes) != PIVP_OK) return PIVP_ERR_LAUNCH;
+    hipLaunchKernelGGL(K, dim3(L.gx, L.gy), dim3(L.threads), L.lds_bytes, s, d, L.tiles_per_split);
     return PIVP_LAUNCH_STATUS();
 }
 
-// d as for igemm_wgrad (ConvLSTM case: 5x5, stride 1, pad 2); dW and, when d.db is set, the bias gradient accumulated with atomics.
-int wgrad5x5_bf16(const WgradDesc& d, hipStream_t s) {
-    PIVP_CHECK_ARG(d.x0 && d.dy && d.dw && wgrad5x5_bf16_ok(d) && (d.c1 == 0 || d.x1) && d.wcin >= d.cin && d.wcin % 32 == 0);
-    // A batch of timesteps goes to the 25-tap kernel (per timestep at B = 32, all seven layers: 168 us at 8 per launch, 225 us at 4); ONE
-    // timestep to the kernel-row kernel below, whose 5 x cin/32 blocks per tile are then the better use of the chip (389 us against 580:
-    // the sweep's t = 0 launches, sequences too short to batch).
-    switch (d.operand) {
-        case Operand::F32: case Operand::BF16X3: return PIVP_ERR_BADARG;      // (the fp32 kernels' / no weight-gradient form)
-        case Operand::FP16X3:       // two fp16 pieces per operand: the 25-tap kernel, whatever the batch
+// d as for igemm_wgrad (ConvLSTM case: 5x5, stride 1, pad 2); dW and, when d.db is set, the bias gradient accumulated with atomics.  Which of the kernel-row
+// kernel, the four-wave and the eight-wave 25-tap kernel runs, and on what pixel split: wgrad_launch (wgrad_form.h).
+int wgrad5x5_bf16(const WgradDesc& d, const WgradLaunch& L, hipStream_t s) {
+    PIVP_CHECK_ARG(d.x0 && d.dy && d.dw && (d.c1 == 0 || d.x1));
+    switch (L.form) {
+        case WgradForm::PackedRow_8: return launch_packed<wgrad5x5_bf16_kernel<8>>(d, L, s);
+        case WgradForm::PackedRow_16: return launch_packed<wgrad5x5_bf16_kernel<16>>(d, L, s);
+        case WgradForm::Packed25x4_8: return launch_packed<wgrad25_bf16_kernel<8, 1, 4>>(d, L, s);
+        case WgradForm::Packed25x4_16: return launch_packed<wgrad25_bf16_kernel<16, 1, 4>>(d, L, s);
+        case WgradForm::Packed25x8_1_8: return launch_packed<wgrad25_bf16_kernel<8, 1>>(d, L, s);
+        case WgradForm::Packed25x8_1_16: return launch_packed<wgrad25_bf16_kernel<16, 1>>(d, L, s);
+        case WgradForm::Packed25x8_2_8: case WgradForm::Packed25x8_2_16:      // two fp16 pieces: dy's power-of-two scale from its partial maxima
             PIVP_CHECK_ARG(d.dy_absmax && (d.dy_absmax_stride >= 66 || d.tcount <= 1));
-            return launch_wgrad25<2>(d, s);
-        case Operand::BF16X6: return launch_wgrad25<3>(d, s);      // three bf16 pieces per operand, likewise
-        case Operand::BF16: break;
+            return L.form == WgradForm::Packed25x8_2_8 ? launch_packed<wgrad25_bf16_kernel<8, 2>>(d, L, s) : launch_packed<wgrad25_bf16_kernel<16, 2>>(d, L, s);
+        case WgradForm::Packed25x8_3_8: return launch_packed<wgrad25_bf16_kernel<8, 3>>(d, L, s);
+        case WgradForm::Packed25x8_3_16: return launch_packed<wgrad25_bf16_kernel<16, 3>>(d, L, s);
+        default: return PIVP_ERR_BADARG;
     }
-    // A batch of timesteps (WgradDesc::form): the four-wave form (co-resident with the main stream's small kernels) on maps of up to 32 x 32 x 32 pixels per
-    // timestep, the eight-wave form (half the patch traffic per multiply-add) on larger ones; the plan asks for the eight-wave form on every layer of frames
-    // above 64 x 64 x 32 -- config 5, whose main-stream kernels fill the chip by themselves: 68.2 ms with the four-wave form everywhere against 66.3.
-    // (One timestep on the four-wave form: config 3 11.36 against 11.29 ms: the kernel-row kernel below stays.)
-    if (d.tcount > 1) return (d.form == 1 || (d.form == 0 && (long)d.B * d.Hx * d.Wx <= 32L * 32 * 32)) ? launch_wgrad25_nw4(d, s) : launch_wgrad25<1>(d, s);
-    constexpr int lds_bytes = G_BYTES + X_BYTES;
-    static PerDeviceOnce once16, once8;
-    if (pivp_ensure_dyn_lds(once16, reinterpret_cast<const void*>(&wgrad5x5_bf16_kernel<16>), lds_bytes) != PIVP_OK ||
-        pivp_ensure_dyn_lds(once8, reinterpret_cast<const void*>(&wgrad5x5_bf16_kernel<8>), lds_bytes) != PIVP_OK)
-        return PIVP_ERR_LAUNCH;
-    const int tw = d.Wx % 16 == 0 ? 16 : 8, ti_n = tw == 16 ? 1 : 2;
-    const int n_tiles = (d.B / ti_n) * (d.Hx / 8) * (d.Wx / tw);
-    const int gx = 5 * (d.cin / 32) * (d.N / 128);
-    // Pixel splits: about one block per TWO CUs, at least 2 tiles per block.  Two blocks per CU could be resident, but the kernel is not
-    // short of parallelism: it is short of tiles per block -- every block ends with 20,480 atomic adds into the same 80 KB of dW as the
-    // other splits of its tile (timing-only build without them: 72 -> 43 us on lstm1 at 52 splits) -- and it runs on the side stream, where
-    // a grid that fills every CU's registers starves the main stream's small kernels (a 5 us add_strided took 34 us beside it).
-    // Train step in the bf16 mode against the block target: 512: 13.93 ms, 256: 13.00, 192: 12.73, 128: 12.54, 96: 13.08, 64: 14.57.
-    const int target = pivp_cu_count() / 2;
-    int ns = (target + gx - 1) / gx;
-    if (ns > n_tiles / 2) ns = n_tiles / 2;
-    if (ns < 1) ns = 1;
-    const int tps = (n_tiles + ns - 1) / ns;
-    ns = (n_tiles + tps - 1) / tps;
-    if (tw == 16) hipLaunchKernelGGL(wgrad5x5_bf16_kernel<16>, dim3(gx, ns), dim3(256), lds_bytes, s, d, tps);
-    else hipLaunchKernelGGL(wgrad5x5_bf16_kernel<8>, dim3(gx, ns), dim3(256), lds_bytes, s, d, tps);
-    return PIVP_LAUNCH_STATUS();
 }
 
 }  // namespace pivp
