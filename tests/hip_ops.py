@@ -50,7 +50,8 @@ def convlstm_bf16(x, h, c, W, b, nch=0, h_is_zero=False, want_gates=False, want_
     _lib.check(lib.pivp_pack_lstm_bf16(wd.data_ptr(), wb.data_ptr(), cx + C, C, stream()), 'pack_lstm_bf16')
     c_out = torch.empty_like(cd); h_out = torch.empty_like(hd)
     gates = torch.empty((B * H * Wd, 4 * C), dtype=torch.float32, device=DEV) if want_gates else None
-    cap = (H * Wd // 128 + 1) * (C // 16)
+    # slots per image: a tile (128 anchors of one image, or 64 of each of two on a map that is no multiple of 16 wide) per 16-channel block
+    cap = max(H * Wd // 128 + 1, (H // 8) * (Wd // 8)) * (C // 16)
     part = torch.zeros((B, cap, 4), dtype=torch.float32, device=DEV) if want_ln else None
     npart = ctypes.c_int(-1)
     _lib.check(lib.pivp_convlstm_bf16(xd.data_ptr(), cx, cx, None if h_is_zero else hd.data_ptr(), C, wb.data_ptr(), bd.data_ptr(),

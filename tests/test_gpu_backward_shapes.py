@@ -12,7 +12,7 @@ Which backward kernel each test reaches on such a map:
   wgrad3x3s2 instances                   test_conv_weight_gradient_in_partial_planes: the conv instance on a 4 x 24 anchor grid, the 96-channel and the
                                          64-channel transposed ones on 4 x 24
   wgrad5x5p                              test_convlstm_weight_gradient_in_partial_slots (4 x 16, 16 x 8, 2 x 8); it refuses 12 x 20 and 9 x 8
-  split-precision data gradients         test_cell_backward_in_every_form, test_conv5x5_forms (8 x 48, 16 x 8, 24 x 8)
+  split-precision data gradients         test_cell_backward_in_every_form, test_conv5x5_forms (8 x 48, 16 x 8, 24 x 8; 8 x 24 and 16 x 40: two-image tiles, three and five to a row)
   split-precision weight gradients       test_wgrad5x5_forms (the same maps)
   lstm_gates_bwd, ln_bwd_*               test_convlstm_backward, test_layernorm_backward, test_layernorm_plus_gate_backward_pair (n = C*H*W no multiple of
                                          the 1024-element slice, and below one slice)"""
@@ -115,8 +115,10 @@ def test_partial_slots_refuse_maps_that_are_no_powers_of_two(env):
 
 
 # ---- the packed-operand forms -------------------------------------------------------------------------------------------------------------------------------
-SERVED = [(2, 32, 64, 8, 48), (2, 64, 128, 16, 8), (4, 32, 32, 24, 8)]       # (B, cx, C, H, W): 16-wide tiles, and 8-wide maps whose tiles hold two images
-NOT_SERVED = [(2, 32, 32, 12, 20), (2, 32, 32, 36, 32)]                      # a width that is no multiple of 8; a height that is none
+# (B, cx, C, H, W): 16-wide tiles; 8-wide maps whose tiles hold two images; maps 24 and 40 wide, which take the two-image tiles too, several to a row
+SERVED = [(2, 32, 64, 8, 48), (2, 64, 128, 16, 8), (4, 32, 32, 24, 8), (2, 32, 32, 8, 24), (2, 32, 32, 16, 40)]
+# a width that is no multiple of 8; a height that is none; two-image tiles with an odd batch
+NOT_SERVED = [(2, 32, 32, 12, 20), (2, 32, 32, 36, 32), (1, 32, 32, 8, 24)]
 
 
 @pytest.mark.parametrize('prec', [1, 2, 3, 4])

@@ -381,6 +381,25 @@ def test_no_form_that_neither_a_layer_nor_a_gpu_case_reaches(exe):
     assert FORM['None'] in LAYER_FORMS and {FORM['Slot5x5_8x2'], FORM['Slot5x5_16x2']} <= LAYER_FORMS      # (the grid test asks with the hints)
 
 
+@pytest.mark.parametrize('B,cx,C,H,W', [(2, 32, 32, 8, 24), (2, 32, 32, 16, 40)])
+def test_two_image_tiles_several_to_a_row_get_a_packed_form_that_covers_every_tile(exe, B, cx, C, H, W):
+    """Maps 24 and 40 wide (lstm5 of a 64 x 192 frame, lstm1 of 128 x 80) are no multiple of 16 wide and take the 8-wide tiles of two images, three and five to
+    a row -- the geometry tests/test_gpu_backward_shapes.py's SERVED runs on the GPU.  Every packed operand form must answer with an 8-wide Packed form whose
+    pixel splits cover the (B / 2) (H / 8) (W / 8) T tiles of the launch, none of them empty."""
+    for operand in (BF16, BF16X6, FP16X3):
+        for T in (1, 2, 4):
+            for hint in ((0, 1, 2) if operand == BF16 else (0,)):
+                for has_h in (1, 0):
+                    got = ask(exe, 256, operand, T, hint, 0, 0, ('cell', cx, C, has_h, 1), [B], [(H, W)])[0][0]
+                    assert got == ref_launch(cell_shape(cx, C, has_h, B, H, W), operand, T, hint, hint, 0, 0, 256), (operand, T, hint, has_h, got)
+                    form, gy, tps = NAME[got[0]], got[2], got[5]
+                    n_tiles = (B // 2) * (H // 8) * (W // 8) * T
+                    assert form.startswith('Packed') and form.endswith('_8'), (operand, T, hint, form)
+                    assert gy * tps >= n_tiles > (gy - 1) * tps, (operand, T, hint, form, gy, tps, n_tiles)
+        # ... and an odd batch cannot pair its images: refused, whatever the form
+        assert ask(exe, 256, operand, 2, 0, 0, 0, ('cell', cx, C, 1, 1), [B + 1], [(H, W)])[0][0] == NONE
+
+
 def test_the_restatement_agrees_with_the_built_library():
     """part_floats of the slot form against pivp_wgrad5x5_f32_part_floats (the larger of the launch with and without the h operand), of the 3x3 layers against
     pivp_conv_backward_part_floats: the library asks the header, the restatement is the parent's arithmetic"""
