@@ -27,7 +27,13 @@ optimisers on that one cost: CEM chooses a plan, gradient descent polishes it, t
 The closed loop: `MPC` plans once per control step from the model's belief, executes the first action and observes; the next plan starts from this
 one moved on by one action (`PlanResult.warm_start`, pivp_cem_shift of include/pivp_mpc.h) and the designated pixels travel as the planes `imagine`
 advected (`cem_plan(designated_planes=)`).  `cem_plan(keep_elites=, add_mean=, noise_beta=)` are the population options of iCEM (Pinneri et al. 2020)
-in pivp_cem_update_ex; all default to off, and then `cem_plan` launches what it always did."""
+in pivp_cem_update_ex; all default to off, and then `cem_plan` launches what it always did.
+
+Gradient refinement from a belief: `refine_actions(belief=)` starts the rollout of every iteration from a `RecurrentState` instead of re-encoding context
+frames from zeros -- in a closed loop those frames exist as the belief only -- and takes d cost / d actions from the sweep through that carried start,
+the state a constant (`Model(carry_state=True, keep_activations=True, state_backward=True)`, include/pivp_state_grad.h).  `cem_refine(belief=)` composes
+it with `cem_plan(belief=)`, and `MPC(refine_steps=)` runs that composition inside every `act()`, the polished plan entering the next step's warm start.
+No new kernel and no new entry point: the existing rollout, sweep, cost and state-copy launches, in a new order.  All off by default."""
 import contextlib
 import ctypes
 import inspect
@@ -789,12 +795,49 @@ def _adam_launch(model, p, g, m, v, lr_t):
                                           1.0, model._stream()), 'pivp_adam_step')
 
 
-def _check_refine_args(model, context_images, state, actions, goal_image, cost_fn, steps, lr, past_actions, bounds):
+REFINE_BELIEF_FLAGS = ('carry_state', 'keep_activations', 'state_backward')      # what a model needs to back-propagate a rollout from a belief
+
+
+def _check_refine_model(model, what):
+    """The complaints about the model that refines from a belief: the three flags, each by its name, and one context frame."""
+    for flag in REFINE_BELIEF_FLAGS:
+        if not getattr(model, flag, False):
+            raise ValueError('%s: the sweep runs through a rollout that started from a carried recurrent state, the model must be built with '
+                             'carry_state=True, keep_activations=True, state_backward=True; %s=True is missing' % (what, flag))
+    if int(model.num_frame_before_prediction) != 1:
+        raise ValueError('%s: the model must be built with num_frame_before_prediction=1, not %d (the belief stands for every frame before the '
+                         'newest one, and the training rollout feeds ground truth for its own context frames only)'
+                         % (what, int(model.num_frame_before_prediction)))
+
+
+def _check_refine_belief(model, belief, ctx_shape, past_actions):
+    """The complaints of `refine_actions(belief=)`: a `RecurrentState` of batch 1 or B at the frames' size (or `_BELIEF_TO_COME`, which stands for a
+    batch-1 one), a model that can sweep from it, the newest frame alone as context and no past actions."""
+    if belief is not _BELIEF_TO_COME and not isinstance(belief, RecurrentState):
+        raise ValueError('belief must be a RecurrentState (Model.recurrent_state()), not %r' % (type(belief).__name__,))
+    _check_refine_model(model, 'refining from a belief')
+    if ctx_shape[0] != 1:
+        raise ValueError('with a belief, context_images is (1, B, 3, H, W): the newest frame only (the belief holds the frames before it), got shape %s'
+                         % (ctx_shape,))
+    if past_actions is not None:
+        raise ValueError('past_actions given with a belief: the belief has consumed the past steps, there is none between context frames')
+    if belief is _BELIEF_TO_COME:
+        return
+    if belief.batch not in (1, ctx_shape[1]):
+        raise ValueError('belief must be a state of batch 1 (shared by every sample) or %d (one per sample), this one holds %d samples'
+                         % (ctx_shape[1], belief.batch))
+    if belief.hw != tuple(ctx_shape[3:]):
+        raise ValueError('belief is of %dx%d frames, context_images of %dx%d' % (belief.hw + tuple(ctx_shape[3:])))
+
+
+def _check_refine_args(model, context_images, state, actions, goal_image, cost_fn, steps, lr, past_actions, bounds, belief=None):
     """Every complaint of `refine_actions` is a ValueError raised here, before the GPU or the library is needed.  -> the checked host-side values."""
     ctx = int(model.num_frame_before_prediction)
     si = Model._host_shape(context_images)
     if len(si) != 5 or si[2] != 3 or si[1] < 1:
         raise ValueError('context_images must be (ctx, B, 3, H, W), got shape %s' % (si,))
+    if belief is not None:
+        _check_refine_belief(model, belief, si, past_actions)
     if ctx < 1 or si[0] != ctx:
         raise ValueError('context_images holds %d frames, the model was built with num_frame_before_prediction=%d' % (si[0], ctx))
     B, H, W = si[1], si[3], si[4]
@@ -834,10 +877,11 @@ def _check_refine_args(model, context_images, state, actions, goal_image, cost_f
         if not isinstance(bounds, (tuple, list)) or len(bounds) != 2:
             raise ValueError('bounds must be a pair (low, high)')
         low, high = _action_box(bounds[0], bounds[1], 'bounds[0]', 'bounds[1]', dim=A)
-    return SimpleNamespace(ctx=ctx, B=B, H=H, W=W, steps_T=sa[0], n_past=n_past, iters=steps, lr=lr, low=low, high=high)
+    return SimpleNamespace(ctx=ctx, B=B, H=H, W=W, steps_T=sa[0], n_past=n_past, iters=steps, lr=lr, low=low, high=high, belief=belief)
 
 
-def refine_actions(model, context_images, state, actions, goal_image=None, cost_fn=None, steps=10, lr=0.05, past_actions=None, bounds=None):
+def refine_actions(model, context_images, state, actions, goal_image=None, cost_fn=None, steps=10, lr=0.05, past_actions=None, bounds=None,
+                   belief=None):
     """Gradient descent (Adam) on an action sequence, with the gradient from the model's own backward sweep.
 
     context_images (ctx, B, 3, H, W), state (B, 5): what each of B robots sees now; actions (T-1, B, 5): the sequence to start from, one action per
@@ -865,8 +909,18 @@ def refine_actions(model, context_images, state, actions, goal_image=None, cost_
         refined, costs = refine_actions(model, context, state, seq, goal_image=spec, past_actions=past)
 
     (`model`: built with keep_activations=True.)  Side effect: the model holds the last rollout; its parameter gradients are
-    unspecified afterwards (`cleargrads()` before training on)."""
-    a = _check_refine_args(model, context_images, state, actions, goal_image, cost_fn, steps, lr, past_actions, bounds)
+    unspecified afterwards (`cleargrads()` before training on).
+
+    belief: a `RecurrentState` of batch 1 or B at the frames' size -- what a carrying model holds after the frames observed so far
+    (`model.recurrent_state()`), the closed-loop case, where those frames exist as the belief only.  The model must be built with carry_state=True,
+    keep_activations=True, state_backward=True and num_frame_before_prediction=1; context_images is then (1, B, 3, H, W), the newest frame alone,
+    `state` its robot state, actions (horizon, B, 5) with every row free, and past_actions must be None: the belief has consumed the past.  A
+    batch-1 belief is expanded to B ONCE, in front of the loop (`RecurrentState.expand`, one pivp_state_copy); the rollout of every iteration starts
+    from it -- a buffer hand-over, no copy -- and the sweep takes it as a constant (the truncated form of include/pivp_state_grad.h), so d cost /
+    d actions is that of `horizon` steps from the belief instead of ctx-1 + horizon from zeros.  The belief is never written, and the model's own
+    carried state is, bit for bit, what it was on entry: on return, and when an exception leaves the loop (`imagine(advance=False)`'s manners).
+    None: the path, the launches and the bits of a call without the argument."""
+    a = _check_refine_args(model, context_images, state, actions, goal_image, cost_fn, steps, lr, past_actions, bounds, belief)
     with torch.cuda.device(model.device) if torch.cuda.is_available() else contextlib.nullcontext():
         return _refine_iterate(model, a, _refine_upload(model, a, context_images, state, actions, goal_image, past_actions), cost_fn)
 
@@ -894,21 +948,56 @@ def _refine_upload(model, a, context_images, state, actions, goal_image, past_ac
         b.goal = model._as_device(goal_image, ())
     to_dev = lambda v: None if v is None else torch.from_numpy(np.asarray(v, dtype=np.float32)).to(dev)
     b.low, b.high = to_dev(a.low), to_dev(a.high)
+    b.belief = b.landing = None
+    if getattr(a, 'belief', None) is not None:      # ONE expansion to the batch (pivp_state_copy); every rollout of the loop starts from it and leaves it untouched
+        model._ensure_params(a.H, a.W)
+        model._checked_state(a.belief)
+        b.belief = a.belief.expand(a.B) if a.belief.batch != a.B else a.belief
+        b.landing = RecurrentState.empty(a.B, (a.H, a.W), dev)      # where those rollouts leave their final state: nobody reads it
     return b
+
+
+@contextlib.contextmanager
+def _rollouts_from(model, start, landing):
+    """Inside: calling what this yields in front of a training rollout makes that rollout start from `start` -- handed over, not copied -- and leave
+    its final state in `landing`, so `start` is never written (a state_backward model writes the final state into its spare buffer, the sweep reads
+    the start again).  Behind it, an exception included: the model's carried state and its spare are the objects they were, untouched.  The model
+    keeps `start` alive for the sweep of the last rollout.  start None: what is yielded does nothing and the model is not touched."""
+    if start is None:
+        yield lambda: None
+        return
+    kept = model._state, model._spare_state
+
+    def put_back():
+        model._adopt_state(start)
+        model._spare_state = landing
+    try:
+        yield put_back
+    finally:
+        model._state, model._spare_state = kept
+        model._swept_start = start
 
 
 def _refine_iterate(model, a, b, cost_fn=None, adam=_adam_launch):
     """The loop of `refine_actions` on its device buffers: rollout, cost, sweep, Adam -- stream-ordered work only (tests/test_gpu_input_grad.py runs it
-    under torch's sync debug mode)."""
+    under torch's sync debug mode).  b.belief (when `_refine_upload` made one): the state every rollout starts from, a constant of every sweep.
+    b.moments / b.costs (when the caller made them, as `MPC.reset` does): Adam's moments and the cost table, instead of fresh ones."""
     T1, t0 = a.steps_T, a.n_past
     p = b.actions[:T1]                    # the optimised buffer: a contiguous prefix
-    m, v = torch.zeros_like(p), torch.zeros_like(p)
-    costs = torch.empty((a.iters + 1, a.B), dtype=torch.float32, device=p.device)
+    if getattr(b, 'moments', None) is not None:
+        m, v = b.moments
+        m.zero_()
+        v.zero_()
+        costs = b.costs
+    else:
+        m, v = torch.zeros_like(p), torch.zeros_like(p)
+        costs = torch.empty((a.iters + 1, a.B), dtype=torch.float32, device=p.device)
     nf = T1 + 1 - a.ctx
 
     def rollout_cost(want_grad):
         k = model.scheduled_sampling_k
         model.scheduled_sampling_k = -1
+        put_start_back()
         try:
             with using_config('train', True):
                 model([b.images, b.actions, b.states])
@@ -936,30 +1025,36 @@ def _refine_iterate(model, a, b, cost_fn=None, adam=_adam_launch):
         grad, = torch.autograd.grad(c.sum(), leaf)
         return c.detach(), grad
 
-    for it in range(a.iters):
-        c, grad = rollout_cost(True)
-        costs[it].copy_(c)
-        model.backward(frame_grad=grad.to(torch.float32).contiguous(), input_grad=True, params=False, builtin_loss=False)
-        g = model.action_grad
-        if t0:
-            g[:t0].zero_()
-        adam(model, p, g, m, v, _adam_lr_t(a.lr, it + 1))
-        if b.low is not None:
-            free = p[t0:]
-            torch.maximum(free, b.low, out=free)
-            torch.minimum(free, b.high, out=free)
-    costs[a.iters].copy_(rollout_cost(False)[0])
-    return p, costs
+    with _rollouts_from(model, getattr(b, 'belief', None), getattr(b, 'landing', None)) as put_start_back:
+        for it in range(a.iters):
+            c, grad = rollout_cost(True)
+            costs[it].copy_(c)
+            model.backward(frame_grad=grad.to(torch.float32).contiguous(), input_grad=True, params=False, builtin_loss=False)
+            g = model.action_grad
+            if t0:
+                g[:t0].zero_()
+            adam(model, p, g, m, v, _adam_lr_t(a.lr, it + 1))
+            if b.low is not None:
+                free = p[t0:]
+                torch.maximum(free, b.low, out=free)
+                torch.minimum(free, b.high, out=free)
+        costs[a.iters].copy_(rollout_cost(False)[0])
+        return p, costs
 
 
-def cem_refine(model, context_images, state, horizon, goal_image, past_actions=None, refine_steps=10, lr=0.05, **cem_arguments):
+def cem_refine(model, context_images, state, horizon, goal_image, past_actions=None, refine_steps=10, lr=0.05, belief=None, **cem_arguments):
     """CEM on a goal image, then gradient refinement of its plan on the SAME cost: `cem_plan(goal_image=)` and `refine_actions(goal_image=)` share one
     `GoalImageCost`, so the polish descends the objective that chose the plan.
 
     model: built with keep_activations=True (the rollouts of CEM run on its inference plan, refinement on its training plan); context_images
     (ctx, 1, 3, H, W), state (1, 5), past_actions (ctx-1, 5) as `cem_plan` takes them; goal_image: a `GoalImageCost` or a bare (3, H, W) array.
     cem_arguments: `cem_plan`'s keywords (iterations, samples, elites, init_mean, init_std, min_std, alpha, action_low, action_high, chunk, seed,
-    trace).  The pixel goals and a belief are not served here.
+    trace).  The pixel goals and the closed-loop options are not served here.
+
+    belief: a batch-1 `RecurrentState`, the closed-loop case -- CEM runs as `cem_plan(belief=)` does and the refinement as `refine_actions(belief=)`
+    does, both from this one belief and on the one cost.  The model must then be built with carry_state=True, keep_activations=True,
+    state_backward=True and num_frame_before_prediction=1; context_images is (1, 1, 3, H, W), the newest frame, and past_actions must be None.
+    The model's own carried state is what it was afterwards.  None: the path and the bits of a call without the argument.
 
     After CEM, `refine_actions` runs `refine_steps` Adam steps of size `lr` at batch 2, from CEM's best sequence and from its final mean, the past
     actions held fixed and CEM's action bounds passed as `bounds`.  The cheapest of the three sequences -- CEM's best (0), the refined best (1), the
@@ -968,12 +1063,12 @@ def cem_refine(model, context_images, state, horizon, goal_image, past_actions=N
     -> an object with `actions` (horizon, 5), `cost`, `source` (0 / 1 / 2, an int64 scalar tensor), `cem` (what `cem_plan` returned) and
     `refine_costs` (refine_steps + 1, 2).  `cost` is never above `cem.cost`.  (The refined costs come from training-plan rollouts, CEM's from
     inference-plan rollouts of the same weights: the two agree to rounding, so does `score_actions(goal_image=)` on the returned actions.)"""
-    a = _check_cem_refine_args(model, context_images, state, horizon, goal_image, past_actions, refine_steps, lr, cem_arguments)
+    a = _check_cem_refine_args(model, context_images, state, horizon, goal_image, past_actions, refine_steps, lr, cem_arguments, belief)
     with torch.cuda.device(model.device) if torch.cuda.is_available() else contextlib.nullcontext():
         return _cem_refine_iterate(model, a, _cem_refine_upload(model, a, context_images, state))
 
 
-def _check_cem_refine_args(model, context_images, state, horizon, goal_image, past_actions, refine_steps, lr, cem_arguments):
+def _check_cem_refine_args(model, context_images, state, horizon, goal_image, past_actions, refine_steps, lr, cem_arguments, belief=None):
     """Every complaint of `cem_refine` is a ValueError (an unknown keyword: a TypeError) raised here, before the GPU or the library is needed.
     -> the checked values of its two stages: `cem` (`_check_cem_args`) and `refine` (`_check_refine_args` at batch 2)."""
     if not getattr(model, 'keep_activations', False):
@@ -981,8 +1076,11 @@ def _check_cem_refine_args(model, context_images, state, horizon, goal_image, pa
     for name in ('designated_rc', 'goal_rc', 'step_weights', 'plane_weights', 'miss_cost'):
         if cem_arguments.get(name) is not None:
             raise ValueError('cem_refine plans and refines on the goal image alone: %s is not served' % name)
-    if cem_arguments.get('belief') is not None:
-        raise ValueError('cem_refine does not plan from a belief: refinement re-encodes the context frames')
+    if belief is not None:
+        if not isinstance(belief, RecurrentState):
+            raise ValueError('belief must be a RecurrentState (Model.recurrent_state()), not %r' % (type(belief).__name__,))
+        if past_actions is not None:
+            raise ValueError('past_actions given with a belief: the belief has consumed the past steps, past_actions must be None')
     for name in ('keep_elites', 'add_mean', 'noise_beta', 'warm', 'designated_planes'):
         v = cem_arguments.get(name)
         if v is not None and not (isinstance(v, (bool, int, float, np.bool_, np.integer, np.floating)) and not v):
@@ -990,13 +1088,13 @@ def _check_cem_refine_args(model, context_images, state, horizon, goal_image, pa
     if goal_image is None:
         raise ValueError('cem_refine needs a goal_image')
     spec = _as_goal_cost(goal_image)      # (one goal per sample is `_check_cem_args`' complaint)
-    kw = dict(cem_arguments, designated_rc=None, goal_rc=None, horizon=horizon, past_actions=past_actions, goal_image=spec)
+    kw = dict(cem_arguments, designated_rc=None, goal_rc=None, horizon=horizon, past_actions=past_actions, goal_image=spec, belief=belief)
     trace = kw.pop('trace', False)
     cem = _check_cem_args(model, context_images, state, **kw)      # (what was refused above is None or off, as the checker's defaults are)
     shaped = lambda *shape: np.broadcast_to(np.float32(0), shape)      # the refinement's arguments exist on the device only: their shapes are checked
     low, high = kw.get('action_low'), kw.get('action_high')
     refine = _check_refine_args(model, shaped(cem.ctx, 2, 3, cem.H, cem.W), shaped(2, 5), shaped(cem.ctx - 1 + cem.horizon, 2, 5), spec, None, refine_steps,
-                                lr, cem.past if cem.ctx > 1 else None, None if low is None and high is None else (low, high))
+                                lr, cem.past if cem.ctx > 1 else None, None if low is None and high is None else (low, high), belief)
     return SimpleNamespace(cem=cem, refine=refine, spec=spec, trace=bool(trace))
 
 
@@ -1049,6 +1147,16 @@ class MPC(object):
     renormalize: the designated planes are divided by their mass after every observed step (a plane that lost all mass stays zero).  The plan of
     control step i uses seed + i.
 
+    refine_steps > 0 (with goal_image, and without goal_rc: the pixel cost has no backward, and descending one part of the ranked cost could raise the
+    total): behind CEM, every `act()` polishes the plan by gradient descent, as `cem_refine(belief=)` does -- the belief is expanded to batch 2 into
+    `refiner` (one pivp_state_copy), `refine_steps` Adam steps of size `refine_lr` run from the plan's best sequence and from its mean under the
+    controller's action bounds (`refine_actions(belief=)`'s loop), and the cheapest of the three sequences -- CEM's best (0), the refined best (1),
+    the refined mean (2) -- is picked on the device.  It becomes the plan's `actions` / `cost`, and, with keep_elites >= 1, kept sequence 0 when it is
+    a refined one: the next control step's warm start carries the polish on.  `last_plan` then also holds `source` and `refine_costs`
+    (refine_steps + 1, 2).  refiner (default: model) must be built with carry_state=True, keep_activations=True, state_backward=True and
+    num_frame_before_prediction=1; a second model serves, as for `planner`, and has to be loaded from the same checkpoint as `model`: the belief
+    it starts from was encoded by `model`'s weights.  refine_steps=0, the default: the launches and the bits of a controller without the keyword.
+
     After `reset()`, `act()` and `observe()` enqueue launches and device-to-device copies only -- given device tensors, they never synchronise
     with the host (`reset()` does the uploads, once)."""
 
@@ -1056,8 +1164,19 @@ class MPC(object):
                      'plane_weights', 'miss_cost', 'chunk', 'keep_elites', 'add_mean', 'noise_beta')      # `cem_plan`'s, with its defaults
 
     def __init__(self, model, horizon, goal_image=None, goal_rc=None, warm_iterations=1, tail_mean=None, tail_std=None, std_floor=None,
-                 renormalize=True, seed=0, planner=None, **cem_arguments):
+                 renormalize=True, seed=0, planner=None, refine_steps=0, refine_lr=0.05, refiner=None, **cem_arguments):
         planner = model if planner is None else planner
+        refine_steps, refine_lr = _whole_number(refine_steps, 'refine_steps', 0), _finite_number(refine_lr, 'refine_lr', 0.0)
+        if refine_steps:
+            if goal_image is None:
+                raise ValueError('MPC: refine_steps > 0 descends the goal-image cost: give goal_image')
+            if goal_rc is not None:
+                raise ValueError('MPC: refine_steps > 0 is not served with goal_rc: the pixel cost has no backward, and descending only the image '
+                                 'part of the ranked cost could raise the total')
+            refiner = model if refiner is None else refiner
+            _check_refine_model(refiner, 'MPC: refiner (refine_steps > 0)')
+            if getattr(refiner, '_extra_loss', False):
+                raise ValueError('MPC: refiner differentiates the goal-image cost alone: it must not carry an image loss')
         for name, m in (('model', model), ('planner', planner)):
             if not getattr(m, 'carry_state', False):
                 raise ValueError('MPC: %s must be a Model built with carry_state=True (the belief is its carried recurrent state)' % name)
@@ -1078,6 +1197,7 @@ class MPC(object):
             raise ValueError('tail_std and std_floor must be non-negative')
         self.model, self.planner, self.horizon, self.goal_image, self.goal_rc = model, planner, horizon, goal_image, goal_rc
         self.warm_iterations, self.renormalize, self.seed = warm_iterations, bool(renormalize), seed
+        self.refine_steps, self.refine_lr, self.refiner = refine_steps, refine_lr, refiner if refine_steps else None
         # what every plan of this controller is checked with, by `cem_plan`'s keywords; `reset` adds the planes, the belief stands for the one to come
         self._plan_arguments = dict(cem_arguments, designated_rc=None, goal_rc=goal_rc, horizon=horizon, goal_image=goal_image, seed=seed,
                                     belief=_BELIEF_TO_COME)
@@ -1105,7 +1225,13 @@ class MPC(object):
             planes = one_hot_planes(_pixel_coords(designated_rc, 'designated_rc', H, W, whole=True)[None], H, W)      # (1, P, H, W), on the host
         frame = np.empty((1, 1, 3, H, W), np.float32)      # (the checks below look at the newest frame's shape alone)
         a = _check_cem_args(self.planner, frame, state, designated_planes=planes[0] if planes is not None else None, **self._plan_arguments)
-        return SimpleNamespace(n=n, H=H, W=W, past=past, planes=planes, cem=a)
+        refine = None
+        if self.refine_steps:      # the polish at batch 2: its arguments exist on the device only, their shapes are checked (as `cem_refine` does)
+            shaped = lambda *shape: np.broadcast_to(np.float32(0), shape)
+            low, high = self._plan_arguments.get('action_low'), self._plan_arguments.get('action_high')
+            refine = _check_refine_args(self.refiner, shaped(1, 2, 3, H, W), shaped(2, 5), shaped(a.horizon, 2, 5), a.image, None, self.refine_steps,
+                                        self.refine_lr, None, None if low is None and high is None else (low, high), _BELIEF_TO_COME)
+        return SimpleNamespace(n=n, H=H, W=W, past=past, planes=planes, cem=a, refine=refine)
 
 
     def reset(self, context_images, state, past_actions=None, designated_rc=None):
@@ -1140,6 +1266,17 @@ class MPC(object):
             b.tails = torch.from_numpy(np.stack([self.tail_mean, self.tail_std, self.std_floor]).astype(np.float32)).to(dev)
             b.state_config = _state_config(H, W)
             self._b = b
+            self._ra = self._rb = None
+            if r.refine is not None:      # the polish: `_refine_upload`'s buffers at batch 2, Adam's moments, the cost table and the training plan
+                ra, rf = r.refine, self.refiner
+                ra.belief = a.belief
+                rb = _refine_upload(rf, ra, self._frame.expand(-1, 2, -1, -1, -1), st.expand(2, -1),
+                                    torch.zeros((a.horizon, 2, 5), dtype=torch.float32, device=dev), a.image, None)
+                rb.moments = (torch.zeros_like(rb.actions[:a.horizon]), torch.zeros_like(rb.actions[:a.horizon]))
+                rb.costs = torch.empty((ra.iters + 1, 2), dtype=torch.float32, device=dev)
+                rb.expand_index = torch.zeros((2,), dtype=torch.int32, device=dev)
+                rf._plan_for(2, a.horizon + 1, H, W)      # sized and bound here, not inside the loop
+                self._ra, self._rb = ra, rb
         self._warm, self._action = None, None
         self.step, self.last_plan = 0, None
 
@@ -1171,8 +1308,35 @@ class MPC(object):
             b.per_iter = b.per_iter_cold if warm is None else b.per_iter_warm
             how = {} if warm is None else dict(iterations=self.warm_iterations, ex=True)
             self.last_plan = _cem_iterate(self.planner, a, b, seed=self.seed + self.step, **how)
+            if self._rb is not None:
+                self._polish(self.last_plan)
             self._action = b.best_actions[0].clone()
         return self._action
+
+    def _polish(self, plan):
+        """Gradient refinement of `plan` inside `act()`: `cem_refine(belief=)`'s second stage on the buffers `reset` made.  The belief goes to batch 2
+        into the refiner's start state, the two starting sequences are copied in, `_refine_iterate` runs, and the cheapest of the three sequences is
+        written into the loop's best_actions / best_cost (which `plan.actions` / `plan.cost` are) and, when it is a refined one, into kept sequence
+        0 -- stream-ordered work only."""
+        m, b, ra, rb = self.model, self._b, self._ra, self._rb
+        Hh = ra.steps_T
+        rb.images[0].copy_(self._frame[0].expand_as(rb.images[0]))
+        rb.states[0].copy_(self._state.expand_as(rb.states[0]))
+        _lib.check(_lib.load().pivp_state_copy(ctypes.byref(b.state_config), m._state.data.data_ptr(), 1, rb.belief.data.data_ptr(), 2,
+                                               rb.expand_index.data_ptr(), m._stream()), 'pivp_state_copy')
+        rb.actions[:Hh, 0].copy_(plan.actions)
+        rb.actions[:Hh, 1].copy_(plan.mean)
+        refined, costs = _refine_iterate(self.refiner, ra, rb)
+        three_costs = torch.cat((plan.cost.view(1), costs[-1]))
+        three = torch.cat((plan.actions.unsqueeze(0), refined.transpose(0, 1)))      # (3, horizon, 5): copies, not views of the loop's buffers
+        source = torch.argmin(three_costs)
+        pick = source.view(1)
+        chosen = three.index_select(0, pick)[0]
+        if plan.kept is not None:      # CEM's best ever need not be kept sequence 0: only a refined sequence replaces it
+            plan.kept[:, 0].copy_(torch.where(source > 0, chosen, plan.kept[:, 0]))
+        b.best_actions.copy_(chosen)
+        b.best_cost.copy_(three_costs.index_select(0, pick))
+        plan.source, plan.refine_costs = source, costs
 
 
     def observe(self, frame, state, action=None):
